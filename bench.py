@@ -21,11 +21,12 @@ as that launcher's rank.  Either way the world size must equal ``--gpus`` or the
   --scaling weak: every rank runs its own |K| x restarts-per-k restarts per step (per-GPU work fixed).
 Every rank holds a replica of X; there is no collective inside the restart loop.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with extra objects:
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step), with extra objects:
   roofline     -- the dominant kernel (MFMA GEMM passes): algorithmic flops / launch duration measured
-                  with HIP events inside the library (every --event-stride-th iteration, default 64), vs the roofline of
-                  the scheme the pass runs (f16 / bf16 dense MFMA peak / MFMAs per f32-class product: 2 on the default
-                  count path, 3 or 6 on the others; f32 MFMA peak on the exact-f32 pipe)
+                  with HIP events inside the library (every --event-stride-th iteration, default 64) during the timed
+                  steps, vs the roofline of the scheme the pass runs (f16 / bf16 dense MFMA peak / MFMAs per f32-class
+                  product: 2 on the default count path, 3 or 6 on the others; f32 MFMA peak on the exact-f32 pipe)
+A plain run stops there.  ``--full`` (N = 1) adds the measurements that take runs of their own:
   cpu_baseline -- scikit-learn's non_negative_factorization (the call the reference makes,
                   cnmf.py:672) timed on this box's host cores on a bounded sample.
   consensus    -- BASELINE config 5 (consensus-only stress) wall-clock, GPU next to the sklearn/pandas calls; with the
@@ -38,7 +39,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with extra obje
                   extrapolation from the measured restart-iterations/s; no total, no speed-up)
   kl_non_zero_path -- Kullback-Leibler restarts (beta_loss != 'frobenius') on a 50 000 x 2 000 count matrix with a real matrix's
                   sparsity (9 % non-zero): the non-zero kernels beside the dense matrix-pipe kernels, us per restart-iteration
-(the last six at N = 1 only).
+``--dump-outputs DIR`` writes what the last timed step computed as .npy files (dump_outputs); the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -84,8 +86,15 @@ def parse():
     ap.add_argument("--kmax", type=int, default=13)
     ap.add_argument("--event-stride", type=int, default=64,
                     help="HIP events around the two GEMM passes of every n-th iteration (the roofline's launch durations)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip general_path, e2e and kl_non_zero_path (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline also measure with_queue_hints, cpu_baseline, consensus, general_path, e2e "
+                         "and kl_non_zero_path (off by default: a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (the spectra of its restarts, "
+                         "per K; n_iter; violation) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and consensus")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip with_queue_hints, general_path, e2e and "
+                                                             "kl_non_zero_path (profiling runs)")
     ap.add_argument("--emulate-rank", default=None, metavar="R/W",
                     help="single GPU: run only the shard rank R of a world of W would run in --scaling strong "
                          "(tools/shard_scaling.py: the projected strong-scaling curve from one GPU)")
@@ -723,6 +732,36 @@ FALLBACK_METRIC = "NMF restarts/sec over torch.distributed (TRANSPORT FALLBACK: 
 
 
 # ------------------------------------------------------------------------------------------ main
+DUMP_SPECTRA_BYTES = 60_000_000        # --dump-outputs: the spectra files stay under this; the rest is a few kB
+
+
+def dump_outputs(out_dir, spectra, restarts, n_iter, violation):
+    """--dump-outputs: what the last timed step handed its caller.  ``spectra`` maps (k, restart index in the step's job)
+    to the k x G float32 spectra; ``restarts`` / ``n_iter`` / ``violation`` cover the same restarts, in order.
+    Writes, all float32 / float64:
+      spectra_kNN.npy          [m, k, G] float32 -- the spectra of every restart with k components; when all
+                                of them would pass DUMP_SPECTRA_BYTES, a fixed sample (numpy default_rng(k)) of each k
+      spectra_kNN_restart.npy  [m] float64        -- which restarts of the step's job those are
+      restart.npy, n_iter.npy, violation.npy  [n] float64 -- every restart of the step (all ranks), its outer
+                                iterations and its final violation"""
+    os.makedirs(out_dir, exist_ok=True)
+    by_k = {}
+    for (k, j) in sorted(spectra):
+        by_k.setdefault(int(k), []).append(j)
+    G = next(iter(spectra.values())).shape[1] if spectra else 0
+    total = sum(k * G * 4 * len(js) for k, js in by_k.items())
+    for k, js in sorted(by_k.items()):
+        if total > DUMP_SPECTRA_BYTES:
+            m = max(1, len(js) * DUMP_SPECTRA_BYTES // total)
+            js = [js[i] for i in np.sort(np.random.default_rng(k).choice(len(js), m, replace=False))]
+        np.save(os.path.join(out_dir, "spectra_k%02d.npy" % k),
+                np.stack([np.asarray(spectra[(k, j)], dtype=np.float32) for j in js]))
+        np.save(os.path.join(out_dir, "spectra_k%02d_restart.npy" % k), np.asarray(js, dtype=np.float64))
+    np.save(os.path.join(out_dir, "restart.npy"), np.asarray(restarts, dtype=np.float64))
+    np.save(os.path.join(out_dir, "n_iter.npy"), np.asarray(n_iter, dtype=np.float64))
+    np.save(os.path.join(out_dir, "violation.npy"), np.asarray(violation, dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.cpu_baseline_child:
@@ -890,36 +929,40 @@ def main():
         return v[None, :]
 
     def gather(H_list, ks, step):
-        """The one data-path collective: all-gather of the packed per-restart spectra.  Returns the restart count
-        every rank now holds."""
+        """The one data-path collective: all-gather of the packed per-restart spectra.  Returns what every rank now
+        holds, ``{(k, restart index in the step's job): spectra}``; None when there is nothing to gather (N = 1)."""
         if gather_mode == "none":
-            return len(ks)
+            return None
         from cnmf_amd import dist as cd
         if gather_mode == "rccl":
             hdr = np.array([(i, int(k), rank + world * i) for i, k in enumerate(ks)], dtype=np.int32).reshape(-1, 3)
-            merged = cd.allgather_spectra_rccl(eng, hdr, None, G)      # blk=None: the device-resident spectra store
-            return len(merged)
+            return cd.allgather_spectra_rccl(eng, hdr, None, G)        # blk=None: the device-resident spectra store
         import torch
         rows = [(i, int(H.shape[0]), rank + world * i) for i, H in enumerate(H_list)]
         hdr, blk = cd.pack_local(rows, H_list, G)
         merged = cd.allgather_spectra(hdr, blk, G, device=None if tdev == "cpu" else "cuda:%d" % local_rank)
         torch.cuda.synchronize()
-        return len(merged)
+        return merged
+
+    last = {}                                                    # what the latest step computed (--dump-outputs)
 
     def run_step(step, profile):
         ks, seeds, job_restarts = step_jobs(step)
         if gather_mode == "rccl":
             eng.spectra_reset()
-            _, _, n_it, _ = eng.nmf_batch(ks, seeds=seeds, warn=False, profile=args.event_stride if profile else 0, resident=True)
+            _, _, n_it, viol = eng.nmf_batch(ks, seeds=seeds, warn=False, profile=args.event_stride if profile else 0,
+                                             resident=True)
             st = dict(eng.last_stats)
+            H = None
             got = gather(None, ks, step)
         else:
-            H, _, n_it, _ = eng.nmf_batch(ks, seeds=seeds, warn=False, profile=args.event_stride if profile else 0)
+            H, _, n_it, viol = eng.nmf_batch(ks, seeds=seeds, warn=False, profile=args.event_stride if profile else 0)
             st = dict(eng.last_stats)
             got = gather(H, ks, step)
         st["n_iter"] = np.asarray(n_it, dtype=np.int64)
         if multi and world > 1:
-            assert got == job_restarts, "gather returned %d restarts, the step's job has %d" % (got, job_restarts)
+            assert len(got) == job_restarts, "gather returned %d restarts, the step's job has %d" % (len(got), job_restarts)
+        last.update(ks=ks, H=H, merged=got, n_iter=n_it, violation=viol)
         return ks, st, job_restarts
 
     agg = dict(restarts=0, restart_iters=0, rc_iters=0, outer=0, col_iters=0, passA_ms=0.0,
@@ -951,6 +994,21 @@ def main():
     elapsed = float(per_rank[:, 0].max())                      # MAX over ranks
     total_restarts = float(per_rank[:, 1].sum())
     total_riters = float(per_rank[:, 2].sum())
+    if args.dump_outputs and args.steps > 0:
+        # restart i of this rank is row (shard_rank + shard_world * i) of the step's job (worker_filter), as in gather()
+        ids = [(shard_rank + shard_world * i) if strong else (rank + world * i) for i in range(len(last["ks"]))]
+        # every rank's (restart, n_iter, violation), padded to the longest shard, so that the per-restart files cover the
+        # same restarts as the gathered spectra at any world size (a collective: every rank takes part)
+        width = -(-len(ks_all) * args.restarts_per_k // world) if strong and world > 1 else len(ids)
+        mine = np.full((3, width), -1.0)
+        mine[0, :len(ids)], mine[1, :len(ids)], mine[2, :len(ids)] = ids, last["n_iter"], last["violation"]
+        rows = over_ranks(mine.ravel()).reshape(-1, 3, width).transpose(1, 0, 2).reshape(3, -1)
+        rows = rows[:, rows[0] >= 0]
+        rows = rows[:, np.argsort(rows[0], kind="stable")]
+        if rank == 0:
+            spectra = last["merged"] if last["merged"] is not None else {
+                (int(k), j): h for k, j, h in zip(last["ks"], ids, last["H"])}
+            dump_outputs(args.dump_outputs, spectra, rows[0], rows[1], rows[2])
 
     if rank == 0:
         # roofline of the dominant kernel (rank 0's launches): the MFMA GEMM pass
@@ -1099,7 +1157,7 @@ def main():
         if emu:
             out["config"]["emulated_shard"] = {"rank": emu[0], "world": emu[1],
                                                "note": "single GPU running only the shard that rank would own"}
-        if world == 1 and not emu and not args.no_extras and gather_mode == "none":
+        if args.full and world == 1 and not emu and not args.no_extras and gather_mode == "none":
             # the same job once more WITH queue hints (what the timed steps learned about the iterations per rank, handed back
             # explicitly: Engine.set_iteration_hints) -- reported beside the headline, never part of it: the headline steps
             # each learn their queue order from scratch
@@ -1115,7 +1173,7 @@ def main():
                                        "column_utilisation": int(st_h["restart_column_iterations"]) / max(int(st_h["column_iterations"]), 1),
                                        "note": "one more step of the same job with cnmf_set_iteration_hints(cnmf_get_iteration_means()); "
                                                "not the headline"}
-        if world == 1 and not emu:
+        if args.full and world == 1 and not emu:
             cpu = None
             if not args.no_cpu_baseline:
                 cpu = cpu_baseline(X, mean_it, args.cpu_iters)

@@ -1,6 +1,7 @@
 """world_size-2 test of the restart sharding + the single all-gather of spectra on CPU
 (gloo backend), as the driver cannot give this round more than one GPU.  The same code path
 runs with backend nccl (= RCCL) and GPU tensors in bench.py --gpus N."""
+import json
 import os
 import subprocess
 import sys
@@ -22,7 +23,7 @@ def test_shard_is_reference_worker_filter():
         assert sorted(seen) == list(range(23))
 
 
-def test_pack_unpack_roundtrip():
+def test_pack_unpack_roundtrip(tmp_path):
     rs = np.random.RandomState(0)
     rows = [(0, 3, 0), (2, 5, 1), (4, 4, 7)]
     spectra = [rs.rand(k, 11).astype(np.float32) for _, k, _ in rows]
@@ -31,9 +32,17 @@ def test_pack_unpack_roundtrip():
     out = cd.unpack([hdr], [blk])
     for (_, k, it), s in zip(rows, spectra):
         assert np.array_equal(out[(k, it)], s)
-    # single process, no process group: allgather degenerates to unpack
-    out2 = cd.allgather_spectra(hdr, blk, 11)
-    assert set(out2) == set(out)
+    # single process, no process group: allgather degenerates to unpack.  Checked in a child process: allgather_spectra
+    # imports torch, whose bundled HIP runtime and RCCL must not be loaded into the pytest process ahead of the GPU tests
+    # (libcnmf_hip.so would then bind to them instead of the system ROCm's)
+    code = ("import sys, numpy as np; from cnmf_amd import dist as cd; "
+            "d = np.load(sys.argv[1]); out2 = cd.allgather_spectra(d['hdr'], d['blk'], 11); "
+            "import json; print(json.dumps(sorted((int(k), int(i)) for k, i in out2)))")
+    np.savez(str(tmp_path / "packed.npz"), hdr=hdr, blk=blk)
+    p = subprocess.run([sys.executable, "-c", code, str(tmp_path / "packed.npz")], env=dict(os.environ, PYTHONPATH=ROOT),
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert json.loads(p.stdout.strip().splitlines()[-1]) == [list(key) for key in sorted(set(out))]
 
 
 def test_allgather_two_ranks_gloo():

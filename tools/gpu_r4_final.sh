@@ -6,10 +6,11 @@ mkdir -p gpurun_out; export TMPDIR=/tmp
 timeout 1800 python -m pytest tests -m gpu -x -q > gpurun_out/r4_pytest.log 2>&1; echo "pytest rc=$?" | tee gpurun_out/r4_final.status
 tail -3 gpurun_out/r4_pytest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/r4_smoke.log 2>&1; echo "smoke rc=$?" | tee -a gpurun_out/r4_final.status
-timeout 900 python bench.py > gpurun_out/r4_bench_default.json 2> gpurun_out/r4_bench_default.err; echo "bench rc=$?" | tee -a gpurun_out/r4_final.status
+OUT=${OUT:-$TMPDIR}     # the line below reads the bench's --full measurements
+timeout 900 python bench.py --full > $OUT/r4_bench_default.json 2> $OUT/r4_bench_default.err; echo "bench rc=$?" | tee -a $OUT/r4_final.status
 python - <<P
 import json
-d = json.loads(open("gpurun_out/r4_bench_default.json").read().strip().splitlines()[-1])
+d = json.loads(open("$OUT/r4_bench_default.json").read().strip().splitlines()[-1])
 print("bench:", round(d["value"], 1), "restarts/s; roofline", round(d["roofline"]["frac"], 3), "passA/B TF", round(d["roofline"]["achieved_passA"]), round(d["roofline"]["achieved_passB"]), "e2e", round(d["roofline"]["end_to_end"]["frac"], 3), "gemm share", round(d["roofline"]["gemm_share_of_gpu_time"], 3), "tail", round(d["config"]["tail"]["share_of_gpu_time"], 3))
 print("hints:", d.get("with_queue_hints"))
 print("general:", d["general_path"].get("restarts_per_s"), "consensus:", d["consensus"]["gpu_ms"], d["consensus"].get("gpu_ms_spectra_resident"))

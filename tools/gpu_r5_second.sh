@@ -10,10 +10,11 @@ tail -3 gpurun_out/r5_iters_c4.log
 timeout 300 python tools/probe_gemm2h_ablate.py > gpurun_out/r5_gemm2h_ablation.txt 2>&1; echo "ablate rc=$?" | tee -a gpurun_out/r5_second.status
 cat gpurun_out/r5_gemm2h_ablation.txt | tail -24
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/mfma_stream_probe.hip -o /tmp/mfma_stream_probe && /tmp/mfma_stream_probe > gpurun_out/r5_mfma_stream.txt 2>&1; cat gpurun_out/r5_mfma_stream.txt | tail -8
-timeout 900 python bench.py > gpurun_out/r5_bench_default.json 2> gpurun_out/r5_bench_default.err; echo "bench rc=$?" | tee -a gpurun_out/r5_second.status
+OUT=${OUT:-$TMPDIR}     # the line below reads the bench's --full measurements
+timeout 900 python bench.py --full > $OUT/r5_bench_default.json 2> $OUT/r5_bench_default.err; echo "bench rc=$?" | tee -a $OUT/r5_second.status
 python - <<P
 import json
-d = json.loads(open("gpurun_out/r5_bench_default.json").read().strip().splitlines()[-1])
+d = json.loads(open("$OUT/r5_bench_default.json").read().strip().splitlines()[-1])
 print("bench:", round(d["value"], 1), "restarts/s; roofline", round(d["roofline"]["frac"], 3), "passA/B TF", round(d["roofline"]["achieved_passA"]), round(d["roofline"]["achieved_passB"]), "e2e", round(d["roofline"]["end_to_end"]["frac"], 3), "gemm share", round(d["roofline"]["gemm_share_of_gpu_time"], 3), "tail", round(d["config"]["tail"]["share_of_gpu_time"], 3))
 print("hints:", d.get("with_queue_hints"))
 print("kl:", json.dumps(d.get("kl_non_zero_path"))[:900])

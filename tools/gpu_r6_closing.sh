@@ -35,10 +35,11 @@ d = json.loads(open("gpurun_out/r6_shard8.json").read().strip().splitlines()[-1]
 print("shard 0/8:", round(d["value"], 1), "restarts/s of the shard; tail share", round(d["config"]["tail"]["share_of_gpu_time"], 3))
 P
 # the default bench line, last
-timeout 900 python bench.py > gpurun_out/r6_bench_default.json 2> gpurun_out/r6_bench_default.err; echo "bench rc=$?" | tee -a $S
+OUT=${OUT:-$TMPDIR}     # the lines below read the bench's --full measurements
+timeout 900 python bench.py --full > $OUT/r6_bench_default.json 2> $OUT/r6_bench_default.err; echo "bench rc=$?" | tee -a $S
 python - <<P
 import json
-d = json.loads(open("gpurun_out/r6_bench_default.json").read().strip().splitlines()[-1])
+d = json.loads(open("$OUT/r6_bench_default.json").read().strip().splitlines()[-1])
 print("bench:", round(d["value"], 1), "restarts/s; roofline", round(d["roofline"]["frac"], 3), "passA/B TF", round(d["roofline"]["achieved_passA"]), round(d["roofline"]["achieved_passB"]), "e2e", round(d["roofline"]["end_to_end"]["frac"], 3), "gemm share", round(d["roofline"]["gemm_share_of_gpu_time"], 3), "tail", round(d["config"]["tail"]["share_of_gpu_time"], 3), "traffic", d["roofline"].get("traffic"))
 print("regime:", d["config"].get("regime"))
 print("hints:", d.get("with_queue_hints"))
