@@ -19,6 +19,8 @@ SYMBOLS = [
     "cnmf_device_count", "cnmf_create", "cnmf_destroy", "cnmf_last_error", "cnmf_reload_env", "cnmf_version",
     "cnmf_set_matrix", "cnmf_set_matrix_csr", "cnmf_set_count_detection", "cnmf_get_shape", "cnmf_matrix_images", "cnmf_get_matrix",
     "cnmf_col_moments", "cnmf_scale_columns", "cnmf_row_sums",
+    "cnmf_prepare_upload_csr", "cnmf_prepare_tpm_stats", "cnmf_prepare_select", "cnmf_prepare_fetch",
+    "cnmf_prepare_release",
     "cnmf_nmf_cd_batch", "cnmf_nmf_cd_batch_resident", "cnmf_get_iteration_means", "cnmf_set_iteration_hints", "cnmf_nnls",
     "cnmf_consensus", "cnmf_pairwise_distances", "cnmf_prediction_error", "cnmf_nmf_mu_batch", "cnmf_mu_refit_f64", "cnmf_x_matmul",
     "cnmf_xt_matmul_f64", "cnmf_nnls_spectra", "cnmf_nnls_f64", "cnmf_nnls_gram", "cnmf_nnls_batch", "cnmf_kselect_stats",
@@ -143,6 +145,17 @@ def load():
     lib.cnmf_scale_columns.argtypes = [vp, dblp]
     lib.cnmf_row_sums.restype = i32
     lib.cnmf_row_sums.argtypes = [vp, dblp]
+    i64p_ = C.POINTER(C.c_int64)
+    lib.cnmf_prepare_upload_csr.restype = i32
+    lib.cnmf_prepare_upload_csr.argtypes = [vp, i64p_, i32p, vp, i32, i64, i64]
+    lib.cnmf_prepare_tpm_stats.restype = i32
+    lib.cnmf_prepare_tpm_stats.argtypes = [vp, C.c_double, dblp, dblp, dblp, dblp]
+    lib.cnmf_prepare_select.restype = i32
+    lib.cnmf_prepare_select.argtypes = [vp, i32, i32p, i32, dblp, dblp, i64p_]
+    lib.cnmf_prepare_fetch.restype = i32
+    lib.cnmf_prepare_fetch.argtypes = [vp, i64p_, i32p, dblp]
+    lib.cnmf_prepare_release.restype = i32
+    lib.cnmf_prepare_release.argtypes = [vp]
     lib.cnmf_nmf_cd_batch.restype = i32
     lib.cnmf_nmf_cd_batch.argtypes = [vp, i32, i32p, i32, u32p, dblp, f32p, f32p,
                                       C.POINTER(CdParams), f32p, f32p, i32p, dblp,

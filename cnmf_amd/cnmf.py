@@ -14,11 +14,15 @@ What is different by design
   ``combine`` becomes a gather instead of n_iter file reads; the per-restart
   ``.df.npz`` files are still written (``write_iter_files=True``) so that the reference's
   ``completed`` ledger / ``skip_completed_runs`` / ``skip_missing_files`` semantics survive;
-* ``prepare`` (HVG selection, TPM, scanpy I/O) is out of scope:
-  ``prepare_from_matrix`` takes the normalised cells x genes matrix the reference's
-  ``prepare`` would have written and produces the same ledger / yaml.  The matrix itself is
-  stored as ``.df.npz`` (the reference's own DataFrame container, cnmf.py:31-40) because
-  scanpy/anndata do not exist in this image.
+* ``prepare`` (cnmf.py:333-459) starts from raw counts over all genes: TPM, the per-gene TPM
+  moments, the column subset and the unit-variance scaling run on the device
+  (csrc/prepare_host.hip.h); the high-variance-gene model runs on the host over those moments
+  (``select_highvar_genes``); the scaled matrix stays resident for ``factorize``.  Inputs are
+  ``.df.npz`` / tab-text paths or in-memory frames and sparse matrices: ``.h5ad`` / ``.mtx``
+  need scanpy/anndata, which this package does not use.  ``prepare_from_matrix`` (an already
+  normalised matrix) and ``prepare_from_counts`` (raw counts of chosen genes) remain.  The
+  normalised matrix is stored as ``.df.npz`` (the reference's own DataFrame container,
+  cnmf.py:31-40) or as a CSR container instead of the reference's h5ad.
 """
 import errno
 import itertools
@@ -192,6 +196,87 @@ def ledger_seeds(ks, n_iter, random_state_seed):
     return [(k, r, nmf_seeds[i]) for i, (k, r) in enumerate(itertools.product(k_list, range(n_iter)))]
 
 
+def _check_zero_cells(zerocells, cell_names):
+    """The reference's check for cells without counts of the chosen genes (cnmf.py:550-554), with its exception text."""
+    zerocells = np.ravel(zerocells)
+    if zerocells.sum() > 0:
+        examples = pd.Index(cell_names)[zerocells]
+        raise Exception("Error: %d cells have zero counts of overdispersed genes. E.g. %s. Filter those cells "
+                        "and re-run or adjust the number of overdispersed genes. Quitting!"
+                        % (zerocells.sum(), ", ".join(map(str, examples[:4]))))
+
+
+# ---------------------------------------------------------------- prepare: inputs and the high-variance-gene model
+def read_counts_file(path):
+    """A counts (or TPM) file as the reference's ``prepare`` reads it (cnmf.py:382-393): ``.npz`` -> the reference's
+    DataFrame container, anything else -> tab-delimited text with the cell names in the first column.  ``.h5ad`` and
+    10x ``.mtx`` directories need scanpy / anndata, which this package does not use."""
+    p = os.fspath(path)
+    if p.endswith(".h5ad") or p.endswith(".mtx") or p.endswith(".mtx.gz"):
+        raise NotImplementedError("cannot read %r: .h5ad / .mtx need scanpy, which this package does not use -- load the "
+                                  "matrix yourself and pass it in memory: a DataFrame, or a tuple (scipy.sparse matrix, "
+                                  "cell names, gene names)" % p)
+    if p.endswith(".npz"):
+        return load_df_from_npz(p)
+    return pd.read_csv(p, sep="\t", index_col=0)
+
+
+def counts_to_csr(obj, like=None):
+    """``(CSR matrix, cell names, gene names)`` from any input form ``cNMF.prepare`` accepts: a file path
+    (read_counts_file), a DataFrame, an ndarray or a tuple (scipy.sparse matrix, cell names, gene names).  An ndarray or
+    a bare sparse matrix takes the names of ``like`` (a tuple of the same kind) when the shapes agree, else
+    ``cell%d`` / ``gene%d`` (prepare_from_matrix's convention).  Names become str, as in the files the reference writes."""
+    import scipy.sparse as sp
+    if isinstance(obj, (str, bytes, os.PathLike)):
+        obj = read_counts_file(obj)
+    if isinstance(obj, tuple) and len(obj) == 3:
+        mat, cells, genes = obj
+    elif isinstance(obj, pd.DataFrame):
+        mat, cells, genes = obj.values, obj.index, obj.columns
+    else:
+        mat = obj if sp.issparse(obj) else np.asarray(obj)
+        n, g = mat.shape
+        if like is not None and (len(like[1]), len(like[2])) == (n, g):
+            cells, genes = like[1], like[2]
+        else:
+            cells, genes = ["cell%d" % i for i in range(n)], ["gene%d" % j for j in range(g)]
+    mat = sp.csr_matrix(mat)
+    if mat.shape != (len(cells), len(genes)):
+        raise ValueError("matrix of shape %s with %d cell and %d gene names" % (mat.shape, len(cells), len(genes)))
+    return mat, pd.Index([str(c) for c in cells]), pd.Index([str(x) for x in genes])
+
+
+def select_highvar_genes(mean, var, numgenes=None, expected_fano_threshold=None, minimal_mean=0.5):
+    """The over-dispersion model of the reference's ``get_highvar_genes`` / ``get_highvar_genes_sparse``
+    (cnmf.py:136-243), fed with per-gene moments instead of the matrix: ``mean`` and POPULATION ``var`` (float64, [G]).
+
+    fano = var / mean (0 / 0 = NaN for a gene without counts: it fails every comparison below and sorts last,
+    cnmf.py:141, 195); A = min of sqrt(var) / mean over the 20 genes of largest mean (:144-145, 198-199); the winsor box
+    = fano and mean strictly inside their own 10 % / 90 % quantiles (:147-152, 201-206); B^2 = median fano in the box
+    (:153-154, 207-208); fano_ratio = fano / (A^2 mean + B^2) (:156-157, 210-212).  With ``numgenes``: the genes whose
+    ratio is among the ``numgenes`` largest (a descending pandas sort, :160-163, 215-218); otherwise ratio > T and
+    mean > ``minimal_mean``, T = 1 + the ddof=1 std of the fano in the box unless given (:166-172, 221-227).
+
+    Returns ``(mask, params)``: a boolean mask in the input's gene order and {A, B, T, minimal_mean, fano_ratio}."""
+    m = pd.Series(np.asarray(mean, dtype=np.float64))
+    v = pd.Series(np.asarray(var, dtype=np.float64))
+    fano = v / m
+    largest = m.sort_values(ascending=False).index[:20]
+    A = (np.sqrt(v) / m)[largest].min()
+    m_lo, m_hi = m.quantile([0.10, 0.90])
+    f_lo, f_hi = fano.quantile([0.10, 0.90])
+    box = (fano > f_lo) & (fano < f_hi) & (m > m_lo) & (m < m_hi)
+    B = np.sqrt(fano[box].median())
+    ratio = fano / ((A ** 2) * m + B ** 2)
+    if numgenes is not None:
+        mask = ratio.index.isin(ratio.sort_values(ascending=False).index[:numgenes])
+        T = None
+    else:
+        T = expected_fano_threshold if expected_fano_threshold else 1.0 + fano[box].std()
+        mask = ((ratio > T) & (m > minimal_mean)).values
+    return np.asarray(mask, dtype=bool), dict(A=A, B=B, T=T, minimal_mean=minimal_mean, fano_ratio=ratio.values)
+
+
 class SparseFrame:
     """A cells x genes scipy CSR matrix with its labels -- what the reference holds in ``norm_counts`` (an AnnData with a
     sparse ``.X``, cnmf.py:537-556 sparse branch) when the counts were stored sparse and not densified.  Only what the
@@ -233,6 +318,7 @@ class cNMF:
                                          # while we hold it CPython cannot hand its id() to another object)
         self.compress_merged = compress_merged
         self.last_factorize_stats = None
+        self.last_prepare_seconds = None  # the steps of the last prepare() (wall seconds; tools/prepare_probe.py)
         self.last_factorize_jobs = []
         self.learned_iterations = {}     # rank -> mean outer iterations the last factorize saw (queue hints for the next one)
 
@@ -374,7 +460,7 @@ class cNMF:
 
     def prepare_from_matrix(self, norm_counts, components, n_iter=100, seed=None, beta_loss="frobenius",
                             alpha_usage=0.0, alpha_spectra=0.0, init="random", max_NMF_iter=1000,
-                            tpm=None, _zero_cells_checked=False):
+                            tpm=None, _zero_cells_checked=False, _tpm_stats=None):
         """Stand-in for the tail of ``prepare`` (cnmf.py:452-459): persist the already
         normalised cells x HVG matrix (DataFrame or ndarray) and write the restart ledger +
         run parameters exactly as the reference does.  Raises the reference's zero-count
@@ -401,7 +487,8 @@ class cNMF:
                 mat = mat.copy()
                 mat.sum_duplicates()
             norm_counts = SparseFrame(mat, [str(c) for c in sparse_in[1]], [str(g) for g in sparse_in[2]])
-            zerocells = np.asarray(mat.sum(axis=1)).ravel() == 0
+            zerocells = (np.zeros(mat.shape[0], dtype=bool) if _zero_cells_checked
+                         else np.asarray(mat.sum(axis=1)).ravel() == 0)
         else:
             if not isinstance(norm_counts, pd.DataFrame):
                 norm_counts = pd.DataFrame(np.asarray(norm_counts),
@@ -410,11 +497,7 @@ class cNMF:
             # (prepare_from_counts has the row sums from the device already: no second pass over 8 N G bytes on the host)
             zerocells = (np.zeros(norm_counts.shape[0], dtype=bool) if _zero_cells_checked
                          else np.array(norm_counts.values.sum(axis=1) == 0).reshape(-1))
-        if zerocells.sum() > 0:
-            examples = norm_counts.index[np.ravel(zerocells)]
-            raise Exception("Error: %d cells have zero counts of overdispersed genes. E.g. %s. Filter those cells "
-                            "and re-run or adjust the number of overdispersed genes. Quitting!"
-                            % (zerocells.sum(), ", ".join(map(str, examples[:4]))))
+        _check_zero_cells(zerocells, norm_counts.index)
         self._initialize_dirs()
         self._forget_results()
         sp_path = self.paths["normalized_counts_sparse"]
@@ -434,11 +517,21 @@ class cNMF:
         self._norm_counts_cache = ((self._nc_path(), os.path.getmtime(self._nc_path())), norm_counts)
         with open(self.paths["nmf_genes_list"], "w") as F:
             F.write("\n".join(map(str, norm_counts.columns)))
+        if tpm is not None:
+            self._save_tpm(tpm, _tpm_stats)
+        replicate_params, run_params = self.get_nmf_iter_params(
+            ks=components, n_iter=n_iter, random_state_seed=seed, beta_loss=beta_loss,
+            alpha_usage=alpha_usage, alpha_spectra=alpha_spectra, init=init, max_iter=max_NMF_iter)
+        self.save_nmf_iter_params(replicate_params, run_params)
+
+    def _save_tpm(self, tpm, stats=None):
+        """The TPM files and ``tpm_stats`` (cnmf.py:407-447): ``tpm`` a DataFrame (dense ``tpm``) or (scipy.sparse matrix,
+        gene names) (``tpm_sparse``); ``stats`` -- the __mean / __std frame -- when it was computed elsewhere (the device)."""
         for stale in (self.paths["tpm"], self.paths["tpm_sparse"], self.paths["tpm_sparse_genes"]) + tuple(
                 "%s.%s.npy" % (self.paths["tpm_sparse"], part) for part in ("data", "indices", "indptr")):
-            if tpm is not None and os.path.exists(stale):
+            if os.path.exists(stale):
                 os.remove(stale)
-        if tpm is not None and isinstance(tpm, tuple):
+        if isinstance(tpm, tuple):
             # (scipy sparse cells x ALL genes, gene names): the reference keeps a sparse tpm.h5ad (cnmf.py:423-447);
             # statistics as get_mean_var does for sparse input (cnmf.py:126-134: population variance)
             import scipy.sparse as sp
@@ -453,23 +546,21 @@ class cNMF:
             # (this process holds what it just wrote: consensus() need not read and CRC-check it back)
             self._tpm_sparse_cache = ((self.paths["tpm_sparse"], os.path.getmtime(self.paths["tpm_sparse"])),
                                       mat, pd.Index([str(g) for g in genes]))
-            # column mean and E[x^2] in float64 as two weighted bin counts over the stored entries (row-major order, like
-            # the sparse sums of get_mean_var; 3-10 x faster than .mean() / .multiply().mean() on a 50 000 x 2 000 matrix)
-            d64 = mat.data.astype(np.float64)
-            n_rows, n_cols = mat.shape
-            mean = np.bincount(mat.indices, weights=d64, minlength=n_cols) / n_rows
-            var = np.bincount(mat.indices, weights=d64 * d64, minlength=n_cols) / n_rows - mean ** 2
-            stats = pd.DataFrame([mean, np.sqrt(np.maximum(var, 0.0))], index=["__mean", "__std"], columns=list(genes)).T
+            if stats is None:
+                # column mean and E[x^2] in float64 as two weighted bin counts over the stored entries (row-major order,
+                # like the sparse sums of get_mean_var; 3-10 x faster than .mean() / .multiply().mean() on 50 000 x 2 000)
+                d64 = mat.data.astype(np.float64)
+                n_rows, n_cols = mat.shape
+                mean = np.bincount(mat.indices, weights=d64, minlength=n_cols) / n_rows
+                var = np.bincount(mat.indices, weights=d64 * d64, minlength=n_cols) / n_rows - mean ** 2
+                stats = pd.DataFrame([mean, np.sqrt(np.maximum(var, 0.0))], index=["__mean", "__std"], columns=list(genes)).T
             save_df_to_npz(stats, self.paths["tpm_stats"])
-        elif tpm is not None:
+        else:
             save_df_to_npz(tpm, self.paths["tpm"])
-            stats = pd.DataFrame([tpm.values.mean(axis=0), tpm.values.std(axis=0, ddof=0)],
-                                 index=["__mean", "__std"], columns=tpm.columns).T
+            if stats is None:
+                stats = pd.DataFrame([tpm.values.mean(axis=0), tpm.values.std(axis=0, ddof=0)],
+                                     index=["__mean", "__std"], columns=tpm.columns).T
             save_df_to_npz(stats, self.paths["tpm_stats"])
-        replicate_params, run_params = self.get_nmf_iter_params(
-            ks=components, n_iter=n_iter, random_state_seed=seed, beta_loss=beta_loss,
-            alpha_usage=alpha_usage, alpha_spectra=alpha_spectra, init=init, max_iter=max_NMF_iter)
-        self.save_nmf_iter_params(replicate_params, run_params)
 
     def prepare_from_counts(self, counts, components, n_iter=100, seed=None, beta_loss="frobenius",
                             alpha_usage=0.0, alpha_spectra=0.0, init="random", max_NMF_iter=1000, tpm=None):
@@ -488,12 +579,7 @@ class cNMF:
         self._engine_key = None
         self._resident_obj = None
         _, row_sums = eng.scale_genes_unit_variance()
-        zerocells = row_sums == 0
-        if zerocells.sum() > 0:
-            examples = counts.index[np.ravel(zerocells)]
-            raise Exception("Error: %d cells have zero counts of overdispersed genes. E.g. %s. Filter those cells "
-                            "and re-run or adjust the number of overdispersed genes. Quitting!"
-                            % (zerocells.sum(), ", ".join(map(str, examples[:4]))))
+        _check_zero_cells(row_sums == 0, counts.index)
         norm_counts = pd.DataFrame(eng.get_matrix().astype(np.float64), index=counts.index, columns=counts.columns)
         # the init scale must be the one every OTHER worker derives from the file (set_matrix: X.mean() of the
         # float64 matrix), bit for bit -- not the device's own row-sum total
@@ -505,6 +591,85 @@ class cNMF:
         self._engine_key = ("norm_counts", self._nc_path(), os.path.getmtime(self._nc_path()))
         eng.x_mean, eng.x_dtype = x_mean, x_dtype
         return norm_counts
+
+    def prepare(self, counts, components, n_iter=100, densify=False, tpm=None, seed=None, beta_loss="frobenius",
+                num_highvar_genes=2000, genes_file=None, alpha_usage=0.0, alpha_spectra=0.0, init="random",
+                max_NMF_iter=1000):
+        """The reference's ``prepare`` (cnmf.py:333-459) from RAW counts over all genes, its O(nnz) passes on the device.
+
+        ``counts`` / ``tpm`` (the reference's ``counts_fn`` / ``tpm_fn``): a ``.df.npz`` or tab-delimited text path, a
+        DataFrame, an ndarray or a tuple (scipy.sparse matrix, cell names, gene names); ``.h5ad`` / ``.mtx`` paths raise
+        NotImplementedError.  Without ``tpm`` the device computes the TPM (x * 1e6 / cell total, cnmf.py:245-251);
+        either way the per-gene mean and population std of the TPM (cnmf.py:436-447) come from the device.  The genes:
+        ``genes_file`` (its list, in its order, cnmf.py:449-452) or the over-dispersion model on those moments
+        (select_highvar_genes: the top ``num_highvar_genes``, or the threshold route with ``num_highvar_genes=None``),
+        in the input's gene order.  Their raw counts are divided by their ddof=1 std on the device (cnmf.py:522-548:
+        ``densify=False`` -> sc.pp.scale(zero_center=False), a CSR with zero-std columns left as they are;
+        ``densify=True`` -> X /= X.std(ddof=1), a dense float64 frame) and STAY resident for ``factorize``.  The files
+        and the zero-cell check are prepare_from_matrix's."""
+        import time
+        import scipy.sparse as sp
+        t = [time.perf_counter()]
+        mat, cells, genes = counts_to_csr(counts)
+        eng = self.engine
+        # prepare_select replaces the resident matrix: from here until this call has written the files of the new one,
+        # nothing may take it for the matrix of an earlier prepare (factorize would skip its upload)
+        self._engine_key = None
+        self._resident_obj = None
+        try:
+            if tpm is None:
+                staged = eng.prepare_upload(mat)
+                t.append(time.perf_counter())
+                _, t_mean, t_var, t_data = eng.prepare_tpm_stats(1e6, want_tpm=True)
+                tpm_mat = sp.csr_matrix((t_data, staged.indices, staged.indptr), shape=staged.shape)
+                tpm_cells, tpm_genes = cells, genes
+            else:
+                tpm_mat, tpm_cells, tpm_genes = counts_to_csr(tpm, like=(mat, cells, genes))
+                tpm_mat = eng.prepare_upload(tpm_mat)
+                t.append(time.perf_counter())
+                _, t_mean, t_var, _ = eng.prepare_tpm_stats(0.0)
+                eng.prepare_upload(mat)
+            t.append(time.perf_counter())
+            tpm_stats = pd.DataFrame([t_mean, np.sqrt(t_var)], index=["__mean", "__std"], columns=tpm_genes).T
+            if genes_file is not None:
+                hvgs = pd.Index(open(genes_file).read().rstrip().split("\n"))
+            else:
+                mask, _ = select_highvar_genes(t_mean, t_var, numgenes=num_highvar_genes)
+                hvgs = tpm_genes[mask]
+            cols = genes.get_indexer(hvgs)
+            if (cols < 0).any():
+                raise KeyError("genes not in the counts matrix: %s" % list(hvgs[cols < 0][:4]))
+            t.append(time.perf_counter())
+            if len(cols):
+                _, row_sums, Y = eng.prepare_select(cols, densify)
+            else:
+                row_sums = np.zeros(len(cells))          # no gene chosen: every cell fails the check below
+        finally:
+            eng.prepare_release()                        # (the staging, also when a step above raised)
+        t.append(time.perf_counter())
+        if densify:
+            tpm_arg = pd.DataFrame(tpm_mat.toarray(), index=tpm_cells, columns=tpm_genes)
+        else:
+            tpm_arg = (tpm_mat, tpm_genes)
+        if (row_sums == 0).any():
+            # the reference has written the TPM, its statistics and the gene list when it reaches this check
+            # (cnmf.py:407-447, 545-554)
+            self._initialize_dirs()
+            self._save_tpm(tpm_arg, tpm_stats)
+            with open(self.paths["nmf_genes_list"], "w") as F:
+                F.write("\n".join(hvgs))
+            _check_zero_cells(row_sums == 0, cells)
+        norm_counts = pd.DataFrame(Y, index=cells, columns=hvgs) if densify else (Y, cells, hvgs)
+        t.append(time.perf_counter())
+        self.prepare_from_matrix(norm_counts, components, n_iter=n_iter, seed=seed, beta_loss=beta_loss,
+                                 alpha_usage=alpha_usage, alpha_spectra=alpha_spectra, init=init,
+                                 max_NMF_iter=max_NMF_iter, tpm=tpm_arg, _zero_cells_checked=True, _tpm_stats=tpm_stats)
+        # the matrix just written is the one already resident (eng.x_mean / x_dtype follow set_matrix's rules on it)
+        self._engine_key = ("norm_counts", self._nc_path(), os.path.getmtime(self._nc_path()))
+        self._resident_obj = None
+        t.append(time.perf_counter())
+        self.last_prepare_seconds = dict(zip(("inputs_and_upload", "device_tpm_stats", "hvg_model", "device_select",
+                                              "host_frames", "write_files"), np.diff(t).tolist()))
 
     # ------------------------------------------------------------------ the NMF call-site
     def _check_kwargs(self, kw):

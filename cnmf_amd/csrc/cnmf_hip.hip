@@ -143,6 +143,7 @@ extern "C" void cnmf_destroy(cnmf_ctx* ctx)
     hipFree(ctx->C1h); hipFree(ctx->Ct1h); hipFree(ctx->hiA); hipFree(ctx->hiB);
     hipFree(ctx->stageW); hipFree(ctx->stageH); hipFree(ctx->spectra);
     ctx->cons_ws.release();
+    ctx->prep.release();
     if (ctx->cons_pinned) hipHostFree(ctx->cons_pinned);
     hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -332,6 +333,7 @@ extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
 #include "mu_refit_host.hip.h"
 #include "comm_host.hip.h"
 #include "normalize_host.hip.h"
+#include "prepare_host.hip.h"
 #include "tail_host.hip.h"
 
 #include "debug_host.hip.h"

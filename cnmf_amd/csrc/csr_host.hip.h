@@ -56,15 +56,22 @@ __global__ __launch_bounds__(256) void csr_widen_ptr_kernel(const int* __restric
     if (i < n) p64[i] = p32[i];
 }
 
-// ---- transpose.  Pass 1: entries per (row chunk, column)
+// ---- transpose.  Pass 1: entries per (row chunk, column).  sel != nullptr: row r of the input is the segment of row sel[r]
+// (the transpose of a gathered, re-ordered subset of rows: the chosen columns of prepare_host.hip.h)
 __global__ __launch_bounds__(256) void csr_tr_hist_kernel(const long long* __restrict__ ptr, const int* __restrict__ idx,
-                                                          int R, int C, int rows_per_chunk, int* __restrict__ cnt)
+                                                          const int* __restrict__ sel, int R, int C, int rows_per_chunk,
+                                                          int* __restrict__ cnt)
 {
     const int t = blockIdx.x;
     const int r0 = t * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
     if (r0 >= r1) return;
     int* c = cnt + (size_t)t * C;
-    for (long long p = ptr[r0] + threadIdx.x; p < ptr[r1]; p += 256) atomicAdd(&c[idx[p]], 1);
+    if (!sel) {
+        for (long long p = ptr[r0] + threadIdx.x; p < ptr[r1]; p += 256) atomicAdd(&c[idx[p]], 1);
+        return;
+    }
+    for (int r = r0; r < r1; ++r)
+        for (long long p = ptr[sel[r]] + threadIdx.x; p < ptr[sel[r] + 1]; p += 256) atomicAdd(&c[idx[p]], 1);
 }
 
 // Pass 2a: entries per column
@@ -88,21 +95,27 @@ __global__ __launch_bounds__(256) void csr_tr_offsets_kernel(int* __restrict__ c
 
 // Pass 3: ONE wavefront per chunk walks its rows in order; the entries of a row name distinct columns, so the 64 lanes
 // never meet on a counter, and the counters of a chunk belong to this wavefront alone (the atomic is only there to go
-// through L2: a plain load could see the line as it was before the previous row's store)
+// through L2: a plain load could see the line as it was before the previous row's store).  sel as in pass 1; div != nullptr:
+// the values of row r are divided by div[r] in float64 on the way (prepare's unit-variance scaling)
+template <typename T>
 __global__ __launch_bounds__(64) void csr_tr_fill_kernel(const long long* __restrict__ ptr, const int* __restrict__ idx,
-                                                         const float* __restrict__ val, int R, int C, int rows_per_chunk,
+                                                         const T* __restrict__ val, const int* __restrict__ sel,
+                                                         const double* __restrict__ div, int R, int C, int rows_per_chunk,
                                                          int* __restrict__ cnt, const long long* __restrict__ tptr,
-                                                         int* __restrict__ tidx, float* __restrict__ tval)
+                                                         int* __restrict__ tidx, T* __restrict__ tval)
 {
     const int t = blockIdx.x, lane = threadIdx.x;
     const int r0 = t * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk);
     int* c = cnt + (size_t)t * C;
     for (int r = r0; r < r1; ++r) {
-        const long long b = ptr[r], e = ptr[r + 1];
+        const int s = sel ? sel[r] : r;
+        const long long b = ptr[s], e = ptr[s + 1];
+        const double d = div ? div[r] : 1.0;
         for (long long p = b + lane; p < e; p += 64) {
             const int col = idx[p];
             const long long q = tptr[col] + atomicAdd(&c[col], 1);
-            tidx[q] = r; tval[q] = val[p];
+            tidx[q] = r;
+            tval[q] = div ? (T)((double)val[p] / d) : val[p];
         }
         __builtin_amdgcn_s_waitcnt(0);            // the counters of this row are back before the next row asks for them
     }
@@ -280,7 +293,7 @@ static int ensure_csc(cnmf_ctx* ctx)
     int* tidx = nullptr;
     float* tval = nullptr;
     HIP_TRY(ctx, hipMalloc((void**)&tptr, ((size_t)G + 1) * sizeof(long long)));
-    csr_tr_hist_kernel<<<T, 256, 0, st>>>(ctx->csr_ptr, ctx->csr_idx, N, G, rpc, cnt);
+    csr_tr_hist_kernel<<<T, 256, 0, st>>>(ctx->csr_ptr, ctx->csr_idx, nullptr, N, G, rpc, cnt);
     csr_tr_total_kernel<<<(G + 255) / 256, 256, 0, st>>>(cnt, T, G, tptr);
     csr_tr_offsets_kernel<<<(G + 255) / 256, 256, 0, st>>>(cnt, T, G);
     long long total = 0;
@@ -290,7 +303,8 @@ static int ensure_csc(cnmf_ctx* ctx)
     if (!rc) e = hipMalloc((void**)&tidx, (size_t)std::max<long long>(nnz, 1) * sizeof(int));
     if (!rc && e == hipSuccess) e = hipMalloc((void**)&tval, (size_t)std::max<long long>(nnz, 1) * sizeof(float));
     if (!rc && e == hipSuccess) {
-        csr_tr_fill_kernel<<<T, 64, 0, st>>>(ctx->csr_ptr, ctx->csr_idx, ctx->csr_val, N, G, rpc, cnt, tptr, tidx, tval);
+        csr_tr_fill_kernel<float><<<T, 64, 0, st>>>(ctx->csr_ptr, ctx->csr_idx, ctx->csr_val, nullptr, nullptr, N, G, rpc, cnt,
+                                                    tptr, tidx, tval);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(st);
     }

@@ -44,6 +44,26 @@ struct SpImage {
     void release() { hipFree(perm); hipFree(off); hipFree(len); hipFree(ent); *this = SpImage{}; }
 };
 
+// staging of the cnmf_prepare_* entry points (prepare_host.hip.h): the raw cells x all-genes counts as CSR (float64
+// values), their transpose (built on first use), and the float64 result of cnmf_prepare_select until it is fetched
+struct PrepStage {
+    int64_t N = 0, G = 0, nnz = -1;                 // nnz = -1: nothing uploaded
+    long long* ptr = nullptr; int* idx = nullptr; double* val = nullptr;
+    long long* cptr = nullptr; int* crow = nullptr; double* cval = nullptr;
+    int64_t out_n = 0, out_nnz = -1; int out_dense = 0;   // out_nnz = -1: no selection to fetch
+    long long* optr = nullptr; int* oidx = nullptr; double* oval = nullptr;
+    double* odense = nullptr;
+    void release_counts() {
+        hipFree(ptr); hipFree(idx); hipFree(val); hipFree(cptr); hipFree(crow); hipFree(cval);
+        ptr = cptr = nullptr; idx = crow = nullptr; val = cval = nullptr; nnz = -1;
+    }
+    void release_out() {
+        hipFree(optr); hipFree(oidx); hipFree(oval); hipFree(odense);
+        optr = nullptr; oidx = nullptr; oval = odense = nullptr; out_nnz = -1;
+    }
+    void release() { release_counts(); release_out(); }
+};
+
 struct cnmf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -119,6 +139,8 @@ struct cnmf_ctx {
     size_t cons_pinned_bytes = 0;
 
     cnmf_comm* comm = nullptr;        // RCCL communicator (comm_host.hip.h); NULL = single GPU
+
+    PrepStage prep;                   // cnmf_prepare_* staging (prepare_host.hip.h), apart from the resident matrix
 };
 
 extern char** environ;

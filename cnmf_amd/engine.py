@@ -93,6 +93,7 @@ class Engine:
         self.x_dtype = None
         self.x_has_zero = False            # (scikit-learn refuses beta_loss <= 0 on a matrix that contains a zero)
         self.last_stats = None
+        self._prep = None                  # (shape, nnz) of the counts staged by prepare_upload
         self.store_gen = 0                 # generation of the resident spectra store (bumped by spectra_reset)
         self.last_store_offsets = None     # first store row of every restart of the last resident batch
         self.last_store_gen = -1
@@ -252,6 +253,83 @@ class Engine:
         self.x_dtype = np.dtype(np.float64)
         self.x_mean = np.float64(rs.sum() / (float(N) * float(G)))
         return std, rs
+
+    # ------------------------------------------------------------------ prepare (cnmf_prepare_*, prepare_host.hip.h)
+    def prepare_upload(self, counts):
+        """Stage the raw cells x all-genes counts (scipy.sparse) on the device, apart from the resident matrix.  Stored
+        zeros are dropped and duplicates summed (on a copy); integer data below 2^24 and float32 data travel as float32,
+        anything else as float64 -- the device keeps float64 either way."""
+        import scipy.sparse as sp
+        X = sp.csr_matrix(counts)
+        if not X.has_canonical_format or (X.nnz and not X.data.all()):
+            X = X.copy()
+            X.sum_duplicates()
+            X.eliminate_zeros()
+        data = X.data
+        if data.dtype == np.float32 or (data.dtype.kind in "iub" and (data.size == 0 or np.abs(data).max() < (1 << 24))):
+            vals, f64 = np.ascontiguousarray(data, dtype=np.float32), 0
+        else:
+            vals, f64 = np.ascontiguousarray(data, dtype=np.float64), 1
+        indptr = np.ascontiguousarray(X.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(X.indices, dtype=np.int32)
+        self._check(self._lib.cnmf_prepare_upload_csr(self._ctx, indptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      indices.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      vals.ctypes.data_as(C.c_void_p), f64, X.shape[0], X.shape[1]))
+        self._prep = (X.shape, X.nnz)
+        return X
+
+    def prepare_tpm_stats(self, target_sum=1e6, want_tpm=False):
+        """Row sums of the staged counts, and the per-gene mean and POPULATION variance of their TPM
+        (``x * target_sum / row_sum``; ``target_sum <= 0``: of the matrix as staged).  ``want_tpm``: also the TPM values in
+        the staged CSR order.  Returns ``(row_sums, mean, var, tpm_data or None)``."""
+        (N, G), nnz = self._prep
+        dblp = C.POINTER(C.c_double)
+        rs, mean, var = np.empty(N), np.empty(G), np.empty(G)
+        tpm = np.empty(max(nnz, 1)) if want_tpm else None
+        self._check(self._lib.cnmf_prepare_tpm_stats(self._ctx, float(target_sum), rs.ctypes.data_as(dblp),
+                                                     mean.ctypes.data_as(dblp), var.ctypes.data_as(dblp),
+                                                     tpm.ctypes.data_as(dblp) if want_tpm else None))
+        return rs, mean, var, (tpm[:nnz] if want_tpm else None)
+
+    def prepare_select(self, genes, densify):
+        """The columns ``genes`` of the staged counts, in list order, divided by their ddof=1 std (float64), become the
+        RESIDENT matrix (dense image when ``densify``, CSR otherwise -- what set_matrix makes of the float64 result); the
+        staging is released.  Returns ``(std, row_sums, Y)``: Y the float64 result, an ndarray (densify) or a scipy CSR."""
+        import scipy.sparse as sp
+        (N, G), _ = self._prep
+        genes = np.ascontiguousarray(genes, dtype=np.int32)
+        n = int(genes.size)
+        dblp = C.POINTER(C.c_double)
+        std, rs, nnz = np.empty(max(n, 1)), np.empty(N), C.c_int64(0)
+        self._check(self._lib.cnmf_prepare_select(self._ctx, n, genes.ctypes.data_as(C.POINTER(C.c_int32)), int(bool(densify)),
+                                                  std.ctypes.data_as(dblp), rs.ctypes.data_as(dblp), C.byref(nnz)))
+        self.shape = (int(N), n)
+        self.x_dtype = np.dtype(np.float64)
+        if densify:
+            Y = np.empty((N, n))
+            self._check(self._lib.cnmf_prepare_fetch(self._ctx, None, None, Y.ctypes.data_as(dblp)))
+            self.x_has_zero = bool(Y.size and Y.min() == 0)
+            self.x_mean = Y.mean()                  # (set_matrix's rule for a float64 array)
+        else:
+            nz = int(nnz.value)
+            indptr, indices, data = np.empty(N + 1, dtype=np.int64), np.empty(max(nz, 1), dtype=np.int32), np.empty(max(nz, 1))
+            self._check(self._lib.cnmf_prepare_fetch(self._ctx, indptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                     indices.ctypes.data_as(C.POINTER(C.c_int32)), data.ctypes.data_as(dblp)))
+            if indptr[-1] < (1 << 31):
+                indptr = indptr.astype(np.int32)    # (scipy's own index type for a matrix of this size)
+                Y = sp.csr_matrix((data[:nz], indices[:nz], indptr), shape=(N, n))
+            else:
+                Y = sp.csr_matrix((data[:nz], indices[:nz].astype(np.int64), indptr), shape=(N, n))
+            Y.has_canonical_format = True           # (the device lists every row's columns ascending, without duplicates)
+            self.x_has_zero = bool(nz < N * n)
+            self._x_mean, self._x_mean_src = None, Y     # (set_matrix's rule for a sparse matrix: X.mean() when asked)
+        self._prep = None
+        return std[:n], rs, Y
+
+    def prepare_release(self):
+        """Free the staged counts and any selection not fetched (a prepare that stopped half way)."""
+        self._check(self._lib.cnmf_prepare_release(self._ctx))
+        self._prep = None
 
     @property
     def x_mean(self):

@@ -73,3 +73,21 @@ def consensus_stress(R=5000, G=2000, k=20, n_outliers=100, seed=0):
     S = np.vstack([S, out])
     perm = rs.permutation(R)
     return np.ascontiguousarray(S[perm]), np.concatenate([lab, -np.ones(n_outliers, int)])[perm]
+
+
+def sparse_counts(n_cells, n_genes, density=0.07, seed=0):
+    """Seeded scRNA-like raw counts as a scipy CSR (float32 integers) at roughly ``density`` non-zero, built without the
+    dense matrix (atlas shapes): per cell ~Binomial(G, density) draws of genes with a skewed popularity (duplicates
+    merge), count = 1 + Poisson(gene rate x cell depth)."""
+    import scipy.sparse as sp
+    rs = np.random.RandomState(seed)
+    per_row = rs.binomial(n_genes, density, size=n_cells)
+    rows = np.repeat(np.arange(n_cells, dtype=np.int64), per_row)
+    u = rs.random_sample(rows.size)
+    cols = np.minimum((u ** 1.3 * n_genes).astype(np.int64), n_genes - 1)
+    rate = rs.gamma(0.6, 2.0, n_genes)
+    depth = rs.lognormal(0.0, 0.3, n_cells)
+    vals = (1 + rs.poisson(rate[cols] * depth[rows])).astype(np.float32)
+    M = sp.csr_matrix((vals, (rows, cols)), shape=(n_cells, n_genes))
+    M.sum_duplicates()
+    return M

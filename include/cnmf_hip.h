@@ -136,6 +136,42 @@ int cnmf_col_moments(cnmf_ctx* ctx, double* mean_out /* [G] */, double* ssd_out 
 int cnmf_scale_columns(cnmf_ctx* ctx, const double* divisor /* [G] */);
 int cnmf_row_sums(cnmf_ctx* ctx, double* out /* [N] */);
 
+/* ---- prepare: TPM, gene statistics and the high-variance-gene matrix -----------------------
+ * The O(nnz) passes of the reference's prepare (cnmf.py:333-459, get_norm_counts :487-556) on a STAGING matrix: the
+ * raw cells x all-genes counts as CSR, held apart from the resident matrix and released by cnmf_prepare_fetch (or by
+ * the next upload / cnmf_destroy).  Everything is accumulated in float64 in a fixed order (no float atomics): two
+ * calls on the same input give the same bits.
+ *   cnmf_prepare_upload_csr  indptr int64 [n_cells + 1], indices int32, data float32 (data_is_f64 = 0: counts up to
+ *                            2^24 are exact) or float64 (data_is_f64 = 1: values that float32 would round keep their
+ *                            bits).  Rows must list strictly increasing columns with finite values > 0 (scipy's
+ *                            canonical format after eliminate_zeros()); a column index outside [0, n_genes), a bad
+ *                            row pointer, a non-canonical row or a value <= 0: CNMF_EINVAL.
+ *   cnmf_prepare_tpm_stats   row_sums[i] = sum_g x_ig; with target_sum > 0 the TPM is tpm_ig = x_ig * (target_sum /
+ *                            row_sums[i]) (0 for a cell without counts; cnmf.py:245-251 / sc.pp.normalize_total), with
+ *                            target_sum <= 0 the matrix as given (the tpm_fn route, cnmf.py:406-433).  mean / var: the
+ *                            per-gene mean and POPULATION variance of that matrix (cnmf.py:436-447, two passes).
+ *                            tpm_data (may be NULL): the TPM values in the uploaded CSR order [nnz].
+ *   cnmf_prepare_select      gathers the columns genes[0..n_sel) (in list order) of the raw counts, std_out[j] = their
+ *                            ddof=1 standard deviation, and divides: y = x / s in float64 with s = std, or 1 where
+ *                            std == 0 and densify == 0 (sc.pp.scale(zero_center=False)); densify != 0 refuses a zero
+ *                            std (CNMF_EINVAL: x /= std would leave NaN / inf, cnmf.py:544).  The result REPLACES the
+ *                            resident matrix, as cnmf_set_matrix (densify) or cnmf_set_matrix_csr would build it from
+ *                            float32(y): the same images, bit for bit.  row_sums_out[i] = float64 sum of row i of y
+ *                            (the zero-cell check, cnmf.py:550-554); nnz_out = stored entries of y.  The staging counts
+ *                            are released.
+ *   cnmf_prepare_fetch       y in float64 for the normalised-counts file: densify == 0 -> CSR (indptr [n_cells + 1],
+ *                            indices [nnz], values [nnz]; columns ascending in every row), densify != 0 -> values
+ *                            [n_cells][n_sel] row-major (indptr / indices may be NULL).  Releases what select kept. */
+int cnmf_prepare_upload_csr(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data,
+                            int data_is_f64, int64_t n_cells, int64_t n_genes);
+int cnmf_prepare_tpm_stats(cnmf_ctx* ctx, double target_sum, double* row_sums /* [N] */, double* mean /* [G] */,
+                           double* var /* [G] */, double* tpm_data /* [nnz] or NULL */);
+int cnmf_prepare_select(cnmf_ctx* ctx, int32_t n_sel, const int32_t* genes, int32_t densify, double* std_out /* [n_sel] */,
+                        double* row_sums_out /* [N] */, int64_t* nnz_out);
+int cnmf_prepare_fetch(cnmf_ctx* ctx, int64_t* indptr, int32_t* indices, double* values);
+/* releases the staging and any result not fetched (a prepare that stops between upload and fetch); harmless otherwise */
+int cnmf_prepare_release(cnmf_ctx* ctx);
+
 /* ---- the restart hot loop ---------------------------------------------------------
  * Replaces the loop body of cNMF.factorize (cnmf.py:735-741): for every restart r,
  *   (usages, spectra, n_iter) = non_negative_factorization(X, n_components=k[r],
