@@ -21,6 +21,9 @@ SYMBOLS = [
     "cnmf_col_moments", "cnmf_scale_columns", "cnmf_row_sums",
     "cnmf_prepare_upload_csr", "cnmf_prepare_tpm_stats", "cnmf_prepare_select", "cnmf_prepare_fetch",
     "cnmf_prepare_release",
+    "cnmf_preprocess_upload_csr", "cnmf_preprocess_set_dense", "cnmf_preprocess_select", "cnmf_preprocess_order_stats",
+    "cnmf_preprocess_ceiling", "cnmf_preprocess_densify", "cnmf_preprocess_fetch", "cnmf_preprocess_scatter",
+    "cnmf_preprocess_project", "cnmf_preprocess_ridge_moments", "cnmf_preprocess_ridge_apply", "cnmf_preprocess_release",
     "cnmf_nmf_cd_batch", "cnmf_nmf_cd_batch_resident", "cnmf_get_iteration_means", "cnmf_set_iteration_hints", "cnmf_nnls",
     "cnmf_consensus", "cnmf_pairwise_distances", "cnmf_prediction_error", "cnmf_nmf_mu_batch", "cnmf_mu_refit_f64", "cnmf_x_matmul",
     "cnmf_xt_matmul_f64", "cnmf_nnls_spectra", "cnmf_nnls_f64", "cnmf_nnls_gram", "cnmf_nnls_batch", "cnmf_kselect_stats",
@@ -39,6 +42,7 @@ COMM_ID_BYTES = 128
 
 CNMF_KMAX = 128
 CNMF_MU_KMAX = 64
+CNMF_RIDGE_MAX = 4096
 
 
 class CdParams(C.Structure):
@@ -154,6 +158,30 @@ def load():
     lib.cnmf_prepare_select.argtypes = [vp, i32, i32p, i32, dblp, dblp, i64p_]
     lib.cnmf_prepare_fetch.restype = i32
     lib.cnmf_prepare_fetch.argtypes = [vp, i64p_, i32p, dblp]
+    lib.cnmf_preprocess_upload_csr.restype = i32
+    lib.cnmf_preprocess_upload_csr.argtypes = [vp, i64p_, i32p, vp, i32, i64, i64]
+    lib.cnmf_preprocess_set_dense.restype = i32
+    lib.cnmf_preprocess_set_dense.argtypes = [vp, i32, dblp, i64, i64]
+    lib.cnmf_preprocess_select.restype = i32
+    lib.cnmf_preprocess_select.argtypes = [vp, i32, i32, i32p, C.c_double, C.c_double, dblp, i64p_]
+    lib.cnmf_preprocess_order_stats.restype = i32
+    lib.cnmf_preprocess_order_stats.argtypes = [vp, i32, i64, dblp, dblp]
+    lib.cnmf_preprocess_ceiling.restype = i32
+    lib.cnmf_preprocess_ceiling.argtypes = [vp, i32, C.c_double]
+    lib.cnmf_preprocess_densify.restype = i32
+    lib.cnmf_preprocess_densify.argtypes = [vp, i32]
+    lib.cnmf_preprocess_fetch.restype = i32
+    lib.cnmf_preprocess_fetch.argtypes = [vp, i32, i64p_, i32p, dblp]
+    lib.cnmf_preprocess_scatter.restype = i32
+    lib.cnmf_preprocess_scatter.argtypes = [vp, i32, dblp, dblp]
+    lib.cnmf_preprocess_project.restype = i32
+    lib.cnmf_preprocess_project.argtypes = [vp, i32, i32, dblp, dblp, dblp]
+    lib.cnmf_preprocess_ridge_moments.restype = i32
+    lib.cnmf_preprocess_ridge_moments.argtypes = [vp, i32, i32, i32, dblp, dblp, dblp, dblp]
+    lib.cnmf_preprocess_ridge_apply.restype = i32
+    lib.cnmf_preprocess_ridge_apply.argtypes = [vp, i32, dblp]
+    lib.cnmf_preprocess_release.restype = i32
+    lib.cnmf_preprocess_release.argtypes = [vp]
     lib.cnmf_prepare_release.restype = i32
     lib.cnmf_prepare_release.argtypes = [vp]
     lib.cnmf_nmf_cd_batch.restype = i32

@@ -144,6 +144,7 @@ extern "C" void cnmf_destroy(cnmf_ctx* ctx)
     hipFree(ctx->stageW); hipFree(ctx->stageH); hipFree(ctx->spectra);
     ctx->cons_ws.release();
     ctx->prep.release();
+    ctx->pre.release();
     if (ctx->cons_pinned) hipHostFree(ctx->cons_pinned);
     hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -334,6 +335,7 @@ extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
 #include "comm_host.hip.h"
 #include "normalize_host.hip.h"
 #include "prepare_host.hip.h"
+#include "preprocess_host.hip.h"
 #include "tail_host.hip.h"
 
 #include "debug_host.hip.h"

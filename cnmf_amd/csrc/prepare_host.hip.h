@@ -177,10 +177,10 @@ static int prep_ensure_columns(cnmf_ctx* ctx)
     return prep_transpose(ctx, P.ptr, P.idx, P.val, nullptr, nullptr, (int)P.N, (int)P.G, P.nnz, &P.cptr, &P.crow, &P.cval);
 }
 
-extern "C" int cnmf_prepare_upload_csr(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data,
-                                       int data_is_f64, int64_t n_cells, int64_t n_genes)
+// the host-side checks of a CSR upload (shape, row pointers, null arrays)
+static int prep_csr_args(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data, int64_t n_cells,
+                         int64_t n_genes)
 {
-    using namespace cnmf;
     if (!ctx || !indptr) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     if (n_cells <= 0 || n_genes <= 0 || n_cells > (1ll << 30) || n_genes > (1ll << 24)) {
         SET_ERR(ctx, "bad matrix shape %lld x %lld", (long long)n_cells, (long long)n_genes);
@@ -191,46 +191,69 @@ extern "C" int cnmf_prepare_upload_csr(cnmf_ctx* ctx, const int64_t* indptr, con
         if (indptr[i + 1] < indptr[i]) { SET_ERR(ctx, "indptr decreases at row %lld", (long long)i); return CNMF_EINVAL; }
     const int64_t nnz = indptr[n_cells];
     if (nnz > 0 && (!indices || !data)) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
+    return CNMF_OK;
+}
+
+// stages raw counts (checked by prep_csr_args) as CSR with float64 values into freshly allocated (*ptr_out, *idx_out,
+// *val_out); frees them again on any failure.  Shared by cnmf_prepare_upload_csr and cnmf_preprocess_upload_csr.
+static int prep_stage_csr(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data, int data_is_f64,
+                          int64_t n_cells, int64_t n_genes, long long** ptr_out, int** idx_out, double** val_out)
+{
+    using namespace cnmf;
+    const int64_t nnz = indptr[n_cells];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    PrepStage& P = ctx->prep;
-    hipStreamSynchronize(st);
-    P.release();
     const size_t n1 = (size_t)std::max<int64_t>(nnz, 1);
     DevPool pool;
     int* d_bad = pool.get<int>(1, true, st);
     float* tmp32 = data_is_f64 ? nullptr : pool.get<float>(n1);
     POOL_TRY(ctx, pool);
-    hipError_t e = hipMalloc((void**)&P.ptr, (size_t)(n_cells + 1) * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&P.idx, n1 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&P.val, n1 * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(P.ptr, indptr, (size_t)(n_cells + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(P.idx, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, st);
+    long long* ptr = nullptr;
+    int* idx = nullptr;
+    double* val = nullptr;
+    hipError_t e = hipMalloc((void**)&ptr, (size_t)(n_cells + 1) * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc((void**)&idx, n1 * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&val, n1 * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpyAsync(ptr, indptr, (size_t)(n_cells + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(idx, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && nnz > 0) {
         if (data_is_f64) {
-            e = hipMemcpyAsync(P.val, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st);
+            e = hipMemcpyAsync(val, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st);
         } else {
             e = hipMemcpyAsync(tmp32, data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, st);
             if (e == hipSuccess) {
                 const long long blocks = std::min<long long>((nnz + 255) / 256, 8192);
-                prep_widen_kernel<<<(unsigned)blocks, 256, 0, st>>>(tmp32, nnz, P.val);
+                prep_widen_kernel<<<(unsigned)blocks, 256, 0, st>>>(tmp32, nnz, val);
                 e = hipGetLastError();
             }
         }
     }
     int bad = 0;
     if (e == hipSuccess) {
-        prep_check_kernel<<<(unsigned)((n_cells + 3) / 4), 256, 0, st>>>(P.ptr, P.idx, P.val, (int)n_cells, (int)n_genes, d_bad);
+        prep_check_kernel<<<(unsigned)((n_cells + 3) / 4), 256, 0, st>>>(ptr, idx, val, (int)n_cells, (int)n_genes, d_bad);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
     }
-    if (e != hipSuccess || bad) P.release();
+    if (e != hipSuccess || bad) { hipFree(ptr); hipFree(idx); hipFree(val); }
     HIP_TRY(ctx, e);
     if (bad & 2) { SET_ERR(ctx, "column index out of range in the CSR arrays"); return CNMF_EINVAL; }
     if (bad & 1) { SET_ERR(ctx, "every row must list strictly increasing columns (canonical CSR)"); return CNMF_EINVAL; }
     if (bad & 4) { SET_ERR(ctx, "stored values must be finite and > 0 (counts without stored zeros)"); return CNMF_EINVAL; }
-    P.N = n_cells; P.G = n_genes; P.nnz = nnz;
+    *ptr_out = ptr; *idx_out = idx; *val_out = val;
+    return CNMF_OK;
+}
+
+extern "C" int cnmf_prepare_upload_csr(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data,
+                                       int data_is_f64, int64_t n_cells, int64_t n_genes)
+{
+    if (int rc = prep_csr_args(ctx, indptr, indices, data, n_cells, n_genes)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PrepStage& P = ctx->prep;
+    hipStreamSynchronize(ctx->stream);
+    P.release();
+    if (int rc = prep_stage_csr(ctx, indptr, indices, data, data_is_f64, n_cells, n_genes, &P.ptr, &P.idx, &P.val)) return rc;
+    P.N = n_cells; P.G = n_genes; P.nnz = indptr[n_cells];
     return CNMF_OK;
 }
 

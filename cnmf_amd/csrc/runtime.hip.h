@@ -64,6 +64,31 @@ struct PrepStage {
     void release() { release_counts(); release_out(); }
 };
 
+// staging of the cnmf_preprocess_* entry points (preprocess_host.hip.h), apart from both the resident matrix and the
+// prepare staging: the raw counts (CSR, float64 values) and their transpose, two result slots (cells x selected genes,
+// CSR or dense float64) and the ridge factors R^T / Phi^T of the last moments pass
+struct PreSlot {
+    int64_t n = 0, nnz = -1;                         // columns; nnz = -1: empty, -2: dense
+    long long* ptr = nullptr; int* idx = nullptr; double* val = nullptr;
+    double* dense = nullptr;                         // [N][n] row-major
+    void release() { hipFree(ptr); hipFree(idx); hipFree(val); hipFree(dense); *this = PreSlot{}; }
+};
+
+struct PreStage {
+    int64_t N = 0, G = 0, nnz = -1;                  // the staged counts; nnz = -1: none
+    long long* ptr = nullptr; int* idx = nullptr; double* val = nullptr;
+    long long* cptr = nullptr; int* crow = nullptr; double* cval = nullptr;
+    PreSlot slot[2];
+    double *Rt = nullptr, *Pt = nullptr;             // [N][K], [N][B1]
+    int K = 0, B1 = 0;
+    void release_counts() {
+        hipFree(ptr); hipFree(idx); hipFree(val); hipFree(cptr); hipFree(crow); hipFree(cval);
+        ptr = cptr = nullptr; idx = crow = nullptr; val = cval = nullptr; nnz = -1; G = 0;
+    }
+    void release_ridge() { hipFree(Rt); hipFree(Pt); Rt = Pt = nullptr; K = B1 = 0; }
+    void release() { release_counts(); release_ridge(); slot[0].release(); slot[1].release(); N = 0; }
+};
+
 struct cnmf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -141,6 +166,7 @@ struct cnmf_ctx {
     cnmf_comm* comm = nullptr;        // RCCL communicator (comm_host.hip.h); NULL = single GPU
 
     PrepStage prep;                   // cnmf_prepare_* staging (prepare_host.hip.h), apart from the resident matrix
+    PreStage pre;                     // cnmf_preprocess_* staging (preprocess_host.hip.h)
 };
 
 extern char** environ;

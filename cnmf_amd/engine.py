@@ -331,6 +331,123 @@ class Engine:
         self._check(self._lib.cnmf_prepare_release(self._ctx))
         self._prep = None
 
+    # ------------------------------------------------------------------ preprocess (cnmf_preprocess_*, preprocess_host.hip.h)
+    # A staging of its own with two result slots: the resident matrix, the spectra store and the prepare staging stay as
+    # they are.
+    def preprocess_upload(self, counts):
+        """Stage raw counts (scipy.sparse, values > 0 once stored zeros are dropped) for preprocess_select; releases the
+        previous preprocess staging.  Returns the canonical CSR that was staged."""
+        import scipy.sparse as sp
+        X = sp.csr_matrix(counts)
+        if not X.has_canonical_format or (X.nnz and not X.data.all()):
+            X = X.copy()
+            X.sum_duplicates()
+            X.eliminate_zeros()
+        vals = np.ascontiguousarray(X.data, dtype=np.float64)
+        indptr = np.ascontiguousarray(X.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(X.indices, dtype=np.int32)
+        self._check(self._lib.cnmf_preprocess_upload_csr(self._ctx, indptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                         indices.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                         vals.ctypes.data_as(C.c_void_p), 1, X.shape[0], X.shape[1]))
+        self._pre = {"N": X.shape[0], 0: None, 1: None}
+        return X
+
+    def preprocess_set_dense(self, slot, X):
+        """A dense float64 matrix (cells x genes) into ``slot``."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        self._check(self._lib.cnmf_preprocess_set_dense(self._ctx, int(slot), X.ctypes.data_as(C.POINTER(C.c_double)),
+                                                        X.shape[0], X.shape[1]))
+        pre = getattr(self, "_pre", None) or {"N": X.shape[0], 0: None, 1: None}
+        pre["N"], pre[int(slot)] = X.shape[0], (X.shape[1], -2)
+        self._pre = pre
+
+    def preprocess_select(self, slot, genes, target_sum=0.0, max_value=None):
+        """``slot`` := the columns ``genes`` of the staged counts (rows scaled to ``target_sum`` when > 0), each divided by
+        its ddof=1 std (1 for a zero std), clipped at ``max_value``.  Returns the std."""
+        genes = np.ascontiguousarray(genes, dtype=np.int32)
+        n = int(genes.size)
+        std, nnz = np.empty(max(n, 1)), C.c_int64(0)
+        mv = np.inf if max_value is None else float(max_value)
+        self._check(self._lib.cnmf_preprocess_select(self._ctx, int(slot), n, genes.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                     float(target_sum), mv, std.ctypes.data_as(C.POINTER(C.c_double)),
+                                                     C.byref(nnz)))
+        self._pre[int(slot)] = (n, int(nnz.value))
+        return std[:n]
+
+    def preprocess_order_stats(self, slot, k):
+        """The k-th and (k+1)-th smallest of all entries of ``slot`` (implicit zeros included), as float64."""
+        lo, hi = C.c_double(0), C.c_double(0)
+        self._check(self._lib.cnmf_preprocess_order_stats(self._ctx, int(slot), int(k), C.byref(lo), C.byref(hi)))
+        return np.float64(lo.value), np.float64(hi.value)
+
+    def preprocess_ceiling(self, slot, thresh):
+        self._check(self._lib.cnmf_preprocess_ceiling(self._ctx, int(slot), float(thresh)))
+
+    def preprocess_densify(self, slot):
+        self._check(self._lib.cnmf_preprocess_densify(self._ctx, int(slot)))
+        self._pre[int(slot)] = (self._pre[int(slot)][0], -2)
+
+    def preprocess_fetch(self, slot):
+        """The slot's matrix: an ndarray (dense slot) or a canonical scipy CSR."""
+        import scipy.sparse as sp
+        N = self._pre["N"]
+        n, nnz = self._pre[int(slot)]
+        dblp = C.POINTER(C.c_double)
+        if nnz == -2:
+            Y = np.empty((N, n))
+            self._check(self._lib.cnmf_preprocess_fetch(self._ctx, int(slot), None, None, Y.ctypes.data_as(dblp)))
+            return Y
+        indptr, indices, data = np.empty(N + 1, dtype=np.int64), np.empty(max(nnz, 1), dtype=np.int32), np.empty(max(nnz, 1))
+        self._check(self._lib.cnmf_preprocess_fetch(self._ctx, int(slot), indptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    indices.ctypes.data_as(C.POINTER(C.c_int32)), data.ctypes.data_as(dblp)))
+        if indptr[-1] < (1 << 31):
+            indptr = indptr.astype(np.int32)
+        Y = sp.csr_matrix((data[:nnz], indices[:nnz].astype(indptr.dtype), indptr), shape=(N, n))
+        Y.has_canonical_format = True
+        return Y
+
+    def preprocess_scatter(self, slot):
+        """Column means and the scatter matrix sum_i (x_i - mean)(x_i - mean)^T of a dense slot (float64)."""
+        n = self._pre[int(slot)][0]
+        mean, S = np.empty(n), np.empty((n, n))
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_preprocess_scatter(self._ctx, int(slot), mean.ctypes.data_as(dblp), S.ctypes.data_as(dblp)))
+        return mean, S
+
+    def preprocess_project(self, slot, mean, V):
+        """(X - mean) V over a dense slot."""
+        mean = np.ascontiguousarray(mean, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        out = np.empty((self._pre["N"], V.shape[1]))
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_preprocess_project(self._ctx, int(slot), V.shape[1], mean.ctypes.data_as(dblp),
+                                                      V.ctypes.data_as(dblp), out.ctypes.data_as(dblp)))
+        return out
+
+    def preprocess_ridge_moments(self, slot, R, Phi):
+        """R [K][N], Phi [B1][N] (harmonypy's old layout) over the dense slot X [N][n]: M [K][B1][n] with
+        M[k, b] = sum_i R[k,i] Phi[b,i] X[i] and gram [K][B1][B1] = sum_i R[k,i] Phi[b,i] Phi[c,i]."""
+        K, B1, n = R.shape[0], Phi.shape[0], self._pre[int(slot)][0]
+        if K * B1 > _lib.CNMF_RIDGE_MAX:
+            raise NotImplementedError("K * (B + 1) = %d is above the device limit %d" % (K * B1, _lib.CNMF_RIDGE_MAX))
+        Rt = np.ascontiguousarray(np.asarray(R, dtype=np.float64).T)
+        Pt = np.ascontiguousarray(np.asarray(Phi, dtype=np.float64).T)
+        M, G = np.empty((K, B1, n)), np.empty((K, B1, B1))
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_preprocess_ridge_moments(self._ctx, int(slot), K, B1, Rt.ctypes.data_as(dblp),
+                                                            Pt.ctypes.data_as(dblp), M.ctypes.data_as(dblp),
+                                                            G.ctypes.data_as(dblp)))
+        return M, G
+
+    def preprocess_ridge_apply(self, slot, W):
+        """Dense slot X := max(X - sum_k sum_b (R[k] Phi[b])^T W[k, b], 0), W [K][B1][n], factors of the last moments."""
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        self._check(self._lib.cnmf_preprocess_ridge_apply(self._ctx, int(slot), W.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def preprocess_release(self):
+        self._check(self._lib.cnmf_preprocess_release(self._ctx))
+        self._pre = None
+
     @property
     def x_mean(self):
         if self._x_mean is None and self._x_mean_src is not None:

@@ -1,0 +1,310 @@
+"""Host-side mirror of the reference's ``Preprocess`` (src/cnmf/preprocess.py) for the batch-corrected input of
+``cNMF.prepare``: ``stdscale_quantile_celing`` (:21-29), ``Preprocess.normalize_batchcorrect`` (:246-360) and
+``Preprocess.harmony_correct_X`` (:362-422 with ``moe_correct_ridge``, :9-18).  Same names, argument meanings,
+defaults and error texts; every O(N G) step runs on the device (csrc/preprocess_host.hip.h) in float64:
+
+* library-size normalisation, the high-variance-gene subset and ``sc.pp.scale(zero_center=False, max_value)``: one
+  upload of the raw counts serves both the normalised copy (for the PCA) and the raw copy (for the correction);
+* the global quantile ceiling: the two order statistics around ``h = (N G - 1) q`` come from a radix select over all
+  N G entries (implicit zeros of sparse input counted), and numpy interpolates between them
+  (``np.quantile([lo, hi], frac)``), so the ceiling is the one ``np.quantile`` gives for the same matrix, bit for bit;
+* the PCA of ``sc.pp.pca(zero_center=True)``: min(50, min(N, G) - 1) components; the column means, the G x G covariance
+  and the scores ``(X - mean) V`` on the device, ``np.linalg.eigh`` on the host.  Sign rule: the loading of largest
+  magnitude of every component is positive (scanpy's sign depends on its solver; Harmony's result does not depend on it);
+* Harmony's mixture-of-experts ridge correction: every cluster's ``W_k`` is formed from the uncorrected X (as in the
+  reference), so the moments ``M_k = (R_k Phi) X`` and ``Gram_k = (R_k Phi) Phi^T`` of all K clusters come from one
+  device pass, ``W_k = inv(Gram_k + lamb) @ M_k`` (``W_k[0] = 0``) runs in numpy, so that ``lamb`` broadcasts exactly as
+  in the reference, and ``X - sum_k W_k^T (R_k Phi)`` clipped at 0 is a second device pass.  K (B + 1) is limited to
+  4096 (``NotImplementedError`` above).
+
+There is no AnnData here: data moves in the forms ``cNMF.prepare`` accepts (``counts_to_csr``): a DataFrame, an ndarray
+or a tuple (scipy.sparse matrix, cell names, gene names); cell metadata is an ``obs`` DataFrame indexed by cell.
+``highly_variable`` (a boolean mask or a list of gene names) plays the role of ``var['highly_variable']``; the genes keep
+the data's order, as the reference's boolean subset does.  ``harmony_correct_X`` also takes a dense ``X`` (the
+reference's ``.todense()`` needs a sparse one) and an optional ``harmony_res`` (any object with ``Z_corr``, ``R``,
+``Phi_moe``, ``K`` and ``lamb``) instead of running harmonypy.
+
+Out of scope: ``preprocess_for_cnmf``, ``filter_adata``, ``select_features_MI``, the seurat_v3 HVG selection
+(``n_top_genes``: it needs skmisc's loess), plots (``makeplots`` is accepted and nothing is drawn) and ``.h5ad`` writing.
+"""
+import numpy as np
+import pandas as pd
+
+HARMONY_IMPORT_ERROR = "harmonypy is not installed. Please install it using 'pip install harmonypy' before proceeding."
+HVG_REQUIRED_ERROR = ("If a numeric value for n_top_genes is not provided, you must include a highly_variable column "
+                      "in _adata")
+
+
+class PreprocessResult:
+    """What the reference's ``normalize_batchcorrect`` returns as an AnnData: ``X`` (cells x HVGs; a dense ndarray after
+    Harmony or for dense input, a scipy CSR for sparse input without Harmony), ``obs_names``, ``var_names``, ``obs``
+    and ``obsm`` ({'X_pca', 'X_pca_harmony'} when Harmony ran)."""
+
+    def __init__(self, X, obs_names, var_names, obs=None, obsm=None):
+        self.X, self.obs_names, self.var_names = X, obs_names, var_names
+        self.obs = obs
+        self.obsm = obsm if obsm is not None else {}
+
+    @property
+    def shape(self):
+        return self.X.shape
+
+
+def _data_parts(data):
+    """(matrix, cell names, gene names, dense?) of a DataFrame, an ndarray or a (matrix, cells, genes) tuple."""
+    import scipy.sparse as sp
+    if isinstance(data, tuple) and len(data) == 3:
+        mat, cells, genes = data
+    elif isinstance(data, pd.DataFrame):
+        mat, cells, genes = data.values, data.index, data.columns
+    else:
+        mat = data
+        n, g = mat.shape
+        cells, genes = ["cell%d" % i for i in range(n)], ["gene%d" % j for j in range(g)]
+    dense = not sp.issparse(mat)
+    if dense:
+        mat = np.asarray(mat)
+    if mat.ndim != 2 or mat.shape != (len(cells), len(genes)):
+        raise ValueError("matrix of shape %s with %d cell and %d gene names" % (mat.shape, len(cells), len(genes)))
+    return mat, pd.Index([str(c) for c in cells]), pd.Index([str(x) for x in genes]), dense
+
+
+def _to_csr(mat):
+    import scipy.sparse as sp
+    X = sp.csr_matrix(mat, dtype=np.float64)
+    if X.nnz and not (np.isfinite(X.data).all() and (X.data >= 0).all()):
+        raise ValueError("Preprocess expects finite non-negative values")
+    return X
+
+
+def quantile_from_order_stats(lo, hi, n, q):
+    """``np.quantile`` (method 'linear') of n values whose order statistics floor(h) and floor(h) + 1 are lo and hi,
+    h = (n - 1) q: numpy's own interpolation between the two, so the result has the bits np.quantile gives."""
+    h = (n - 1) * q
+    frac = h - np.floor(h)
+    return np.quantile(np.array([lo, hi], dtype=np.float64), frac)
+
+
+def _check_quantile(q):
+    if q is not None and not 0.0 <= q <= 1.0:
+        raise ValueError("Quantiles must be in the range [0, 1]")
+
+
+def _ceiling(eng, slot, n_rows, n_cols, quantile_thresh):
+    """the reference's quantile ceiling over all n_rows x n_cols entries of a device slot; returns the threshold"""
+    if quantile_thresh is None:
+        return None
+    total = int(n_rows) * int(n_cols)
+    k = int(np.floor((total - 1) * quantile_thresh))
+    lo, hi = eng.preprocess_order_stats(slot, min(k, total - 1))
+    thresh = quantile_from_order_stats(lo, hi, total, quantile_thresh)
+    eng.preprocess_ceiling(slot, thresh)
+    return thresh
+
+
+def _pca(eng, slot, n_rows, n_cols, n_comps=None):
+    """sc.pp.pca(zero_center=True) of a dense device slot: scores [n_rows][n_comps] (see the module docstring)."""
+    if n_comps is None:
+        n_comps = 50 if 50 < min(n_rows, n_cols) else min(n_rows, n_cols) - 1
+    mean, scatter = eng.preprocess_scatter(slot)
+    w, V = np.linalg.eigh(scatter / (n_rows - 1))
+    order = np.argsort(-w, kind="stable")[:n_comps]
+    V = V[:, order]
+    lead = V[np.argmax(np.abs(V), axis=0), np.arange(V.shape[1])]
+    V = V * np.where(lead < 0, -1.0, 1.0)
+    return eng.preprocess_project(slot, mean, V)
+
+
+def stdscale_quantile_celing(data, max_value=None, quantile_thresh=None, engine=None, device=0):
+    """preprocess.py:21-29 on the device: every column divided by its ddof=1 std (a zero-std column as it is), clipped
+    at ``max_value``, then every entry above ``np.quantile(all entries, quantile_thresh)`` (zeros counted) set to that
+    value.  ``data``: a dense array (dense result) or a scipy.sparse matrix (CSR result) of non-negative values; the
+    reference changes its AnnData in place, this returns the new matrix."""
+    import scipy.sparse as sp
+    _check_quantile(quantile_thresh)
+    dense = not sp.issparse(data)
+    X = _to_csr(data)
+    N, G = X.shape
+    from .engine import Engine
+    eng = engine if engine is not None else Engine(device)
+    try:
+        eng.preprocess_upload(X)
+        eng.preprocess_select(0, np.arange(G), 0.0, max_value)
+        _ceiling(eng, 0, N, G, quantile_thresh)
+        if dense:
+            eng.preprocess_densify(0)
+        return eng.preprocess_fetch(0)
+    finally:
+        eng.preprocess_release()
+        if engine is None:
+            eng.close()
+
+
+def _harmony_vars_list(harmony_vars):
+    return [harmony_vars] if isinstance(harmony_vars, str) else list(harmony_vars)
+
+
+def _check_harmony_vars(obs, harmony_vars):
+    if obs is None:
+        raise KeyError("obs is required for harmony_vars %s" % (_harmony_vars_list(harmony_vars),))
+    missing = [v for v in _harmony_vars_list(harmony_vars) if v not in obs.columns]
+    if missing:
+        raise KeyError("harmony_vars %s are not columns of obs" % (missing,))
+
+
+def _import_harmonypy():
+    try:
+        import harmonypy
+    except Exception:
+        raise ImportError(HARMONY_IMPORT_ERROR)
+    return harmonypy
+
+
+class Preprocess:
+    def __init__(self, random_seed=None, device=0, engine=None):
+        """preprocess.py:42-56: ``np.random.seed(random_seed)``.  ``device`` / ``engine``: where the device steps run
+        (an engine given here is shared, its resident matrix and spectra store stay as they are); the engine is created
+        on first use, so argument errors raise without a GPU."""
+        np.random.seed(random_seed)
+        self.device = int(device)
+        self._engine = engine
+        self._own_engine = False
+
+    @property
+    def engine(self):
+        if self._engine is None:
+            from .engine import Engine
+            self._engine = Engine(self.device)
+            self._own_engine = True
+        return self._engine
+
+    def close(self):
+        if self._own_engine and self._engine is not None:
+            self._engine.close()
+        self._engine, self._own_engine = None, False
+
+    # ------------------------------------------------------------------ harmony_correct_X (preprocess.py:362-422)
+    def harmony_correct_X(self, X, obs, pca, harmony_vars, theta=1, max_iter_harmony=20, harmony_res=None):
+        """Runs Harmony on ``pca`` (or takes ``harmony_res``) and applies its mixture-of-experts ridge correction to the
+        cells x genes ``X`` (sparse or dense).  Returns ``(X_corr, X_pca_harmony)``: X_corr dense float64, clipped at 0."""
+        import scipy.sparse as sp
+        if harmony_res is None:
+            harmonypy = _import_harmonypy()
+            _check_harmony_vars(obs, harmony_vars)
+            harmony_res = harmonypy.run_harmony(pca, obs, harmony_vars, max_iter_harmony=max_iter_harmony, theta=theta)
+        X = X.toarray() if sp.issparse(X) else np.asarray(X)
+        X_corr, X_pca_harmony = self._ridge(X, None, pca, harmony_res)
+        return X_corr, X_pca_harmony
+
+    def _ridge(self, X, slot, pca, harmony_res):
+        """moe_correct_ridge on the device over X (uploaded to slot 1) or over the dense device slot ``slot``."""
+        Z_corr = np.asarray(harmony_res.Z_corr)
+        R = np.asarray(harmony_res.R, dtype=np.float64)
+        Phi = np.asarray(harmony_res.Phi_moe, dtype=np.float64)
+        new_harmony = Z_corr.shape[0] == np.asarray(pca).shape[0]      # (preprocess.py:405-414)
+        if new_harmony:
+            X_pca_harmony, R, Phi = Z_corr, R.T, Phi.T
+        else:
+            X_pca_harmony = Z_corr.T
+        K = int(harmony_res.K)
+        R = R[:K]                                                     # (the reference's loop reads rows 0..K-1)
+        lamb = harmony_res.lamb
+        eng = self.engine
+        try:
+            if slot is None:
+                slot = 1
+                eng.preprocess_release()
+                eng.preprocess_set_dense(slot, X)
+            N = eng._pre["N"]
+            if R.shape != (K, N) or Phi.ndim != 2 or Phi.shape[1] != N:
+                raise ValueError("Harmony's R %s / Phi_moe %s do not match %d cells" % (R.shape, Phi.shape, N))
+            M, gram = eng.preprocess_ridge_moments(slot, R, Phi)
+            W = np.empty_like(M)
+            for k in range(K):
+                W[k] = np.linalg.inv(gram[k] + lamb) @ M[k]
+                W[k][0, :] = 0                                        # do not remove the intercept
+            eng.preprocess_ridge_apply(slot, W)
+            X_corr = eng.preprocess_fetch(slot)
+        finally:
+            eng.preprocess_release()
+        return X_corr, X_pca_harmony
+
+    # ------------------------------------------------------------------ normalize_batchcorrect (preprocess.py:246-360)
+    def normalize_batchcorrect(self, data, obs=None, highly_variable=None, normalize_librarysize=False, harmony_vars=None,
+                               n_top_genes=None, librarysize_targetsum=1e4, max_scaled_thresh=None, quantile_thresh=.9999,
+                               theta=1, makeplots=True, max_iter_harmony=20, harmony_res=None):
+        """Normalises the high-variance genes of raw counts and optionally corrects them with Harmony.  Returns
+        ``(result, hvgs)``: ``result.X`` goes straight into ``cNMF.prepare(counts=(result.X, result.obs_names, hvgs),
+        ...)``."""
+        if n_top_genes is not None:
+            raise NotImplementedError("n_top_genes (seurat_v3 HVG selection) needs skmisc's loess, which this package does "
+                                      "not use: pass highly_variable instead")
+        if highly_variable is None:
+            raise Exception(HVG_REQUIRED_ERROR)
+        _check_quantile(quantile_thresh)
+        if harmony_vars is not None:
+            if harmony_res is None:
+                _import_harmonypy()
+            _check_harmony_vars(obs, harmony_vars)
+        mat, cells, genes, dense = _data_parts(data)
+        hv = np.asarray(highly_variable)
+        if hv.dtype == bool:
+            if hv.shape != (len(genes),):
+                raise ValueError("highly_variable mask of length %d for %d genes" % (hv.size, len(genes)))
+            mask = hv
+        else:
+            names = pd.Index([str(x) for x in hv])
+            unknown = names.difference(genes)
+            if len(unknown):
+                raise KeyError("highly_variable names not among the genes: %s" % list(unknown[:5]))
+            mask = genes.isin(names)
+        sel = np.flatnonzero(mask)
+        if sel.size == 0:
+            raise ValueError("highly_variable selects no gene")
+        hvgs = list(genes[sel])
+        if obs is not None:
+            obs = _align_obs(obs, cells)
+        X = _to_csr(mat)
+        N, n = X.shape[0], int(sel.size)
+        eng = self.engine
+        obsm = {}
+        try:
+            eng.preprocess_upload(X)
+            if harmony_vars is not None:
+                # anorm: normalize_total(copy=True) -> HVG subset -> scale + ceiling (preprocess.py:316-318)
+                eng.preprocess_select(0, sel, float(librarysize_targetsum), max_scaled_thresh)
+                _ceiling(eng, 0, N, n, quantile_thresh)
+                # _adata: raw counts -> HVG subset -> scale + ceiling (:320-321)
+                if not normalize_librarysize:
+                    eng.preprocess_select(1, sel, 0.0, max_scaled_thresh)
+                    _ceiling(eng, 1, N, n, quantile_thresh)
+                eng.preprocess_densify(0)
+                obsm["X_pca"] = _pca(eng, 0, N, n)                     # (:326)
+                slot = 0 if normalize_librarysize else 1
+                eng.preprocess_densify(slot)
+                if harmony_res is None:
+                    harmony_res = _import_harmonypy().run_harmony(obsm["X_pca"], obs, harmony_vars,
+                                                                  max_iter_harmony=max_iter_harmony, theta=theta)
+                Xout, obsm["X_pca_harmony"] = self._ridge(None, slot, obsm["X_pca"], harmony_res)
+            else:
+                target = float(librarysize_targetsum) if normalize_librarysize else 0.0
+                eng.preprocess_select(0, sel, target, max_scaled_thresh)
+                _ceiling(eng, 0, N, n, quantile_thresh)
+                if dense:
+                    eng.preprocess_densify(0)
+                Xout = eng.preprocess_fetch(0)
+        finally:
+            eng.preprocess_release()
+        return PreprocessResult(Xout, cells, pd.Index(hvgs), obs, obsm), hvgs
+
+
+def _align_obs(obs, cells):
+    """obs in the order of the cells (by name when its index holds them all, else by position)"""
+    idx = pd.Index([str(c) for c in obs.index])
+    if len(idx) == len(cells) and idx.equals(cells):
+        return obs
+    if len(idx) == len(cells) and set(idx) == set(cells):
+        return obs.iloc[idx.get_indexer(cells)]
+    if len(obs) != len(cells):
+        raise ValueError("obs has %d rows for %d cells" % (len(obs), len(cells)))
+    return obs

@@ -35,6 +35,7 @@ extern "C" {
 #define CNMF_EUNSUPPORTED -5   /* e.g. rank > CNMF_KMAX (NotImplementedError)    */
 #define CNMF_ECOMM        -6   /* RCCL failure                                   */
 
+#define CNMF_RIDGE_MAX 4096    /* largest K * (B + 1) of cnmf_preprocess_ridge_moments (CNMF_EUNSUPPORTED above)      */
 #define CNMF_KMAX 128          /* largest rank of the coordinate-descent / NNLS / consensus entry points
                                   (<= 64: register-resident sweep; 65..128: sweep_big_kernel)              */
 
@@ -171,6 +172,47 @@ int cnmf_prepare_select(cnmf_ctx* ctx, int32_t n_sel, const int32_t* genes, int3
 int cnmf_prepare_fetch(cnmf_ctx* ctx, int64_t* indptr, int32_t* indices, double* values);
 /* releases the staging and any result not fetched (a prepare that stops between upload and fetch); harmless otherwise */
 int cnmf_prepare_release(cnmf_ctx* ctx);
+
+/* ---- preprocess: scaling, quantile ceiling, PCA products and Harmony's ridge correction ------------------------
+ * The O(N G) passes of the reference's Preprocess.normalize_batchcorrect (preprocess.py:9-29, 314-422) on a staging of
+ * their own (two result slots, each cells x selected genes, CSR or dense float64), apart from the resident matrix, the
+ * spectra store and the prepare staging.  Float64 throughout, fixed summation orders, no float atomics: two calls on the
+ * same input give the same bits.
+ *   cnmf_preprocess_upload_csr   the raw counts, as cnmf_prepare_upload_csr (same checks); releases the whole staging.
+ *   cnmf_preprocess_set_dense    a dense row-major float64 matrix [n_rows][n_cols] into a slot (n_rows must match the
+ *                                staged cells, if any).
+ *   cnmf_preprocess_select       slot := the columns genes[0..n_sel) (list order) of the staged counts, each row scaled by
+ *                                target_sum / its row sum over ALL genes when target_sum > 0 (sc.pp.normalize_total),
+ *                                each column divided by its ddof=1 std (std_out; 1 where the std is 0), then v > max_value
+ *                                -> max_value (+inf: no clip) -- sc.pp.scale(zero_center=False, max_value).  CSR result.
+ *   cnmf_preprocess_order_stats  the k-th and (k+1)-th smallest (0-based; k+1 clamped to the last) of ALL n_cells x n
+ *                                entries of a slot, implicit zeros of a CSR slot included; values must be >= 0.
+ *   cnmf_preprocess_ceiling      v > thresh -> thresh over the slot, in place.
+ *   cnmf_preprocess_densify      a CSR slot becomes dense (a no-op on a dense slot).
+ *   cnmf_preprocess_fetch        a CSR slot: indptr [n_cells + 1], indices, values; a dense slot: values [n_cells][n].
+ *   cnmf_preprocess_scatter      dense slot: mean [n] of its columns and scatter [n][n] = sum_i (x_i - mean)(x_i - mean)^T.
+ *   cnmf_preprocess_project      dense slot: scores [n_cells][n_comp] = (X - mean) V, V [n][n_comp].
+ *   cnmf_preprocess_ridge_moments  dense slot X [N][n], Rt [N][K] (R^T), Phit [N][B1] (Phi_moe^T), K * B1 <= CNMF_RIDGE_MAX:
+ *                                M [K*B1][n] = A X and gram [K*B1][B1] = A Phi^T with A[k*B1 + b][i] = R[k][i] Phi[b][i].
+ *                                Keeps Rt / Phit for the apply.
+ *   cnmf_preprocess_ridge_apply  dense slot X := max(X - A^T W, 0) in place, W [K*B1][n] (the last moments' K, B1).
+ *   cnmf_preprocess_release      frees the whole staging. */
+int cnmf_preprocess_upload_csr(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data,
+                               int data_is_f64, int64_t n_cells, int64_t n_genes);
+int cnmf_preprocess_set_dense(cnmf_ctx* ctx, int32_t slot, const double* X, int64_t n_rows, int64_t n_cols);
+int cnmf_preprocess_select(cnmf_ctx* ctx, int32_t slot, int32_t n_sel, const int32_t* genes, double target_sum,
+                           double max_value, double* std_out /* [n_sel] */, int64_t* nnz_out);
+int cnmf_preprocess_order_stats(cnmf_ctx* ctx, int32_t slot, int64_t k, double* lo, double* hi);
+int cnmf_preprocess_ceiling(cnmf_ctx* ctx, int32_t slot, double thresh);
+int cnmf_preprocess_densify(cnmf_ctx* ctx, int32_t slot);
+int cnmf_preprocess_fetch(cnmf_ctx* ctx, int32_t slot, int64_t* indptr, int32_t* indices, double* values);
+int cnmf_preprocess_scatter(cnmf_ctx* ctx, int32_t slot, double* mean /* [n] */, double* scatter /* [n][n] */);
+int cnmf_preprocess_project(cnmf_ctx* ctx, int32_t slot, int32_t n_comp, const double* mean, const double* V,
+                            double* scores /* [n_cells][n_comp] */);
+int cnmf_preprocess_ridge_moments(cnmf_ctx* ctx, int32_t slot, int32_t K, int32_t B1, const double* Rt, const double* Phit,
+                                  double* M /* [K*B1][n] */, double* gram /* [K*B1][B1] */);
+int cnmf_preprocess_ridge_apply(cnmf_ctx* ctx, int32_t slot, const double* W /* [K*B1][n] */);
+int cnmf_preprocess_release(cnmf_ctx* ctx);
 
 /* ---- the restart hot loop ---------------------------------------------------------
  * Replaces the loop body of cNMF.factorize (cnmf.py:735-741): for every restart r,
