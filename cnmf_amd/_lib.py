@@ -9,6 +9,8 @@ import ctypes as C
 import os
 import subprocess
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcnmf_hip.so")
 SRC_DIR = os.path.join(_HERE, "csrc")
@@ -24,6 +26,7 @@ SYMBOLS = [
     "cnmf_preprocess_upload_csr", "cnmf_preprocess_set_dense", "cnmf_preprocess_select", "cnmf_preprocess_order_stats",
     "cnmf_preprocess_ceiling", "cnmf_preprocess_densify", "cnmf_preprocess_fetch", "cnmf_preprocess_scatter",
     "cnmf_preprocess_project", "cnmf_preprocess_ridge_moments", "cnmf_preprocess_ridge_apply", "cnmf_preprocess_release",
+    "cnmf_preprocess_row_sums", "cnmf_preprocess_normalize_dense", "cnmf_preprocess_select_mi",
     "cnmf_nmf_cd_batch", "cnmf_nmf_cd_batch_resident", "cnmf_get_iteration_means", "cnmf_set_iteration_hints", "cnmf_nnls",
     "cnmf_consensus", "cnmf_pairwise_distances", "cnmf_prediction_error", "cnmf_nmf_mu_batch", "cnmf_mu_refit_f64", "cnmf_x_matmul",
     "cnmf_xt_matmul_f64", "cnmf_nnls_spectra", "cnmf_nnls_f64", "cnmf_nnls_gram", "cnmf_nnls_batch", "cnmf_kselect_stats",
@@ -36,7 +39,7 @@ SYMBOLS = [
 # test hooks (include/cnmf_hip_debug.h): present only in a library built with -DCNMF_DEBUG_ABI -- the in-tree default,
 # because tests/ call them; CNMF_PRODUCT_BUILD=1 in the environment of build() leaves them out
 DEBUG_SYMBOLS = ["cnmf_debug_stream", "cnmf_debug_gemm", "cnmf_debug_gemm3", "cnmf_debug_gemm3c", "cnmf_debug_gemm2h",
-                 "cnmf_debug_standard_normal"]
+                 "cnmf_debug_standard_normal", "cnmf_debug_mt_normals"]
 
 COMM_ID_BYTES = 128
 
@@ -63,6 +66,24 @@ class BatchStats(C.Structure):
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class MtState(C.Structure):
+    """cnmf_mt_state: numpy's RandomState state"""
+    _fields_ = [("key", C.c_uint32 * 624), ("pos", C.c_int32), ("has_gauss", C.c_int32), ("gauss", C.c_double)]
+
+    @classmethod
+    def from_numpy(cls, state):
+        name, key, pos, has_gauss, gauss = state
+        if name != "MT19937":
+            raise ValueError("not an MT19937 state: %r" % (name,))
+        s = cls()
+        s.key[:] = [int(k) for k in np.asarray(key, dtype=np.uint32)]
+        s.pos, s.has_gauss, s.gauss = int(pos), int(has_gauss), float(gauss)
+        return s
+
+    def to_numpy(self):
+        return ("MT19937", np.array(self.key[:], dtype=np.uint32), int(self.pos), int(self.has_gauss), float(self.gauss))
 
 
 class ConsensusParams(C.Structure):
@@ -180,6 +201,12 @@ def load():
     lib.cnmf_preprocess_ridge_moments.argtypes = [vp, i32, i32, i32, dblp, dblp, dblp, dblp]
     lib.cnmf_preprocess_ridge_apply.restype = i32
     lib.cnmf_preprocess_ridge_apply.argtypes = [vp, i32, dblp]
+    lib.cnmf_preprocess_row_sums.restype = i32
+    lib.cnmf_preprocess_row_sums.argtypes = [vp, dblp]
+    lib.cnmf_preprocess_normalize_dense.restype = i32
+    lib.cnmf_preprocess_normalize_dense.argtypes = [vp, i32, C.c_double, C.c_double, dblp]
+    lib.cnmf_preprocess_select_mi.restype = i32
+    lib.cnmf_preprocess_select_mi.argtypes = [vp, i32, i32p, i32, i32, C.POINTER(MtState), dblp, C.c_double, dblp]
     lib.cnmf_preprocess_release.restype = i32
     lib.cnmf_preprocess_release.argtypes = [vp]
     lib.cnmf_prepare_release.restype = i32
@@ -277,5 +304,7 @@ def load():
         lib.cnmf_debug_gemm2h.argtypes = [vp, f32p, f32p, f32p, i32, i32, i32, i32, i32, dblp, i32]
         lib.cnmf_debug_standard_normal.restype = i32
         lib.cnmf_debug_standard_normal.argtypes = [vp, C.c_uint32, i64, dblp]
+        lib.cnmf_debug_mt_normals.restype = i32
+        lib.cnmf_debug_mt_normals.argtypes = [vp, C.POINTER(MtState), i64, dblp]
     _lib = lib
     return lib

@@ -349,7 +349,7 @@ class Engine:
         self._check(self._lib.cnmf_preprocess_upload_csr(self._ctx, indptr.ctypes.data_as(C.POINTER(C.c_int64)),
                                                          indices.ctypes.data_as(C.POINTER(C.c_int32)),
                                                          vals.ctypes.data_as(C.c_void_p), 1, X.shape[0], X.shape[1]))
-        self._pre = {"N": X.shape[0], 0: None, 1: None}
+        self._pre = {"N": X.shape[0], "G": X.shape[1], 0: None, 1: None}
         return X
 
     def preprocess_set_dense(self, slot, X):
@@ -443,6 +443,41 @@ class Engine:
         """Dense slot X := max(X - sum_k sum_b (R[k] Phi[b])^T W[k, b], 0), W [K][B1][n], factors of the last moments."""
         W = np.ascontiguousarray(W, dtype=np.float64)
         self._check(self._lib.cnmf_preprocess_ridge_apply(self._ctx, int(slot), W.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def preprocess_row_sums(self):
+        """Row sums [N] of the staged counts (the sums normalize_total divides by)."""
+        rs = np.empty(self._pre["N"])
+        self._check(self._lib.cnmf_preprocess_row_sums(self._ctx, rs.ctypes.data_as(C.POINTER(C.c_double))))
+        return rs
+
+    def preprocess_normalize_dense(self, slot, target_sum=0.0, max_value=None):
+        """``slot`` := all genes of the staged counts, dense (rows scaled to ``target_sum`` when > 0), each column divided
+        by its ddof=1 std summed row after row (numpy's order for a C-ordered matrix; 1 for a zero std), clipped at
+        ``max_value``.  Returns the std."""
+        G = self._pre.get("G")
+        std = np.empty(G)
+        mv = np.inf if max_value is None else float(max_value)
+        self._check(self._lib.cnmf_preprocess_normalize_dense(self._ctx, int(slot), float(target_sum), mv,
+                                                              std.ctypes.data_as(C.POINTER(C.c_double))))
+        self._pre[int(slot)] = (G, -2)
+        return std
+
+    def preprocess_select_mi(self, slot, cls, n_classes, n_neighbors, state, psi, cst):
+        """sklearn's mutual_info_classif over the dense ``slot`` (select_mi_host.hip.h): ``cls`` [N] class ids (-1:
+        dropped), ``state`` numpy's RandomState state to draw the noise from, ``psi`` [N + 1] digamma(0..N), ``cst`` the
+        gene-independent terms.  Returns (mi [n], the RandomState state after the draws)."""
+        n = self._pre[int(slot)][0]
+        cls = np.ascontiguousarray(cls, dtype=np.int32)
+        psi = np.ascontiguousarray(psi, dtype=np.float64)
+        if cls.shape != (self._pre["N"],) or psi.shape != (self._pre["N"] + 1,):
+            raise ValueError("cls [%d] / psi [%d] for %d cells" % (cls.size, psi.size, self._pre["N"]))
+        st = _lib.MtState.from_numpy(state)
+        mi = np.empty(n)
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_preprocess_select_mi(self._ctx, int(slot), cls.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        int(n_classes), int(n_neighbors), C.byref(st),
+                                                        psi.ctypes.data_as(dblp), float(cst), mi.ctypes.data_as(dblp)))
+        return mi, st.to_numpy()
 
     def preprocess_release(self):
         self._check(self._lib.cnmf_preprocess_release(self._ctx))
@@ -1303,6 +1338,13 @@ class Engine:
         self._check(self._lib.cnmf_debug_gemm2h(self._ctx, _fp(A), _fp(Bn), _fp(Cout), KC, K, J, int(nsplit),
                                                 int(nsub), C.byref(ms), int(reps)))
         return Cout, ms.value
+
+    def debug_mt_normals(self, state, n):
+        """n draws of numpy's legacy standard_normal continuing the RandomState ``state``: (draws, final state)."""
+        st = _lib.MtState.from_numpy(state)
+        out = np.empty(max(n, 1), dtype=np.float64)
+        self._check(self._lib.cnmf_debug_mt_normals(self._ctx, C.byref(st), n, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out[:n], st.to_numpy()
 
     def debug_standard_normal(self, seed, n):
         out = np.empty(max(n, 1), dtype=np.float64)

@@ -24,8 +24,14 @@ the data's order, as the reference's boolean subset does.  ``harmony_correct_X``
 reference's ``.todense()`` needs a sparse one) and an optional ``harmony_res`` (any object with ``Z_corr``, ``R``,
 ``Phi_moe``, ``K`` and ``lamb``) instead of running harmonypy.
 
-Out of scope: ``preprocess_for_cnmf``, ``filter_adata``, ``select_features_MI``, the seurat_v3 HVG selection
-(``n_top_genes``: it needs skmisc's loess), plots (``makeplots`` is accepted and nothing is drawn) and ``.h5ad`` writing.
+``Preprocess.select_features_MI`` (:425-467) ranks the genes by sklearn's ``mutual_info_classif(X, cluster,
+n_neighbors=3)``: normalize_total with the median of the positive row sums as the target, the scaling and ceiling above,
+then on the device (csrc/select_mi_host.hip.h) sklearn's own scaling and noise -- drawn from numpy's global RandomState,
+whose state the call advances exactly as the reference does -- and Ross's k-NN estimate per gene, bit for bit.  The
+ranking (``MI``, ``MI_Rank``, ``MI_diff``, ``highly_variable``) uses the reference's own pandas expressions.
+
+Out of scope: ``preprocess_for_cnmf``, ``filter_adata``, the seurat_v3 HVG selection (``n_top_genes``: it needs
+skmisc's loess), plots (``makeplots`` is accepted and nothing is drawn) and ``.h5ad`` writing.
 """
 import numpy as np
 import pandas as pd
@@ -38,12 +44,14 @@ HVG_REQUIRED_ERROR = ("If a numeric value for n_top_genes is not provided, you m
 class PreprocessResult:
     """What the reference's ``normalize_batchcorrect`` returns as an AnnData: ``X`` (cells x HVGs; a dense ndarray after
     Harmony or for dense input, a scipy CSR for sparse input without Harmony), ``obs_names``, ``var_names``, ``obs``
-    and ``obsm`` ({'X_pca', 'X_pca_harmony'} when Harmony ran)."""
+    and ``obsm`` ({'X_pca', 'X_pca_harmony'} when Harmony ran); ``var`` (indexed by ``var_names``) when
+    ``select_features_MI`` made it."""
 
-    def __init__(self, X, obs_names, var_names, obs=None, obsm=None):
+    def __init__(self, X, obs_names, var_names, obs=None, obsm=None, var=None):
         self.X, self.obs_names, self.var_names = X, obs_names, var_names
         self.obs = obs
         self.obsm = obsm if obsm is not None else {}
+        self.var = var
 
     @property
     def shape(self):
@@ -296,6 +304,98 @@ class Preprocess:
         finally:
             eng.preprocess_release()
         return PreprocessResult(Xout, cells, pd.Index(hvgs), obs, obsm), hvgs
+
+    # ------------------------------------------------------------------ select_features_MI (preprocess.py:425-467)
+    def select_features_MI(self, data, cluster, max_scaled_thresh=None, quantile_thresh=.9999, n_top_features=70,
+                           makeplots=True):
+        """Ranks the genes by their mutual information with ``cluster`` (an array-like of N labels, or a Series indexed
+        by the cell names).  Returns a PreprocessResult: ``X`` the normalised, scaled and ceilinged matrix (cells x all
+        genes, in the input's sparsity; the noise goes on a copy), ``var`` with ``MI``, ``MI_Rank``, ``MI_diff`` and
+        ``highly_variable`` (MI_Rank < n_top_features) in the data's gene order.  numpy's global RandomState advances as
+        the reference's call advances it."""
+        import scipy.sparse as sp
+        from scipy.special import digamma
+        _check_quantile(quantile_thresh)
+        mat, cells, genes, dense = _data_parts(data)
+        labels = _cluster_labels(cluster, cells)
+        n_neighbors = 3
+        cls, n_cls, cst = mi_classes(labels, n_neighbors)
+        X = _to_csr(mat)
+        N, G = X.shape
+        psi = digamma(np.arange(N + 1, dtype=np.float64))
+        psi[0] = 0.0                                                  # (m >= 1: a cell counts itself)
+        eng = self.engine
+        try:
+            Xc = eng.preprocess_upload(X)
+            rs = eng.preprocess_row_sums()                            # normalize_total(target_sum=None)
+            if not (rs > 0).any():
+                raise ValueError("no cell has counts")
+            target = np.median(rs[rs > 0])
+            # sc.pp.scale over the whole matrix: its std in numpy's order, as the reference's scale computes it
+            eng.preprocess_normalize_dense(0, float(target), max_scaled_thresh)
+            _ceiling(eng, 0, N, G, quantile_thresh)
+            Xout = eng.preprocess_fetch(0)
+            if not dense:                                             # on the staged counts' structure
+                rows = np.repeat(np.arange(N), np.diff(Xc.indptr))
+                Xout = sp.csr_matrix((Xout[rows, Xc.indices], Xc.indices.copy(), Xc.indptr.copy()), shape=(N, G))
+            mi, state = eng.preprocess_select_mi(0, cls, n_cls, n_neighbors, np.random.get_state(), psi, cst)
+            np.random.set_state(state)
+        finally:
+            eng.preprocess_release()
+        return PreprocessResult(Xout, cells, genes, var=mi_ranking(mi, genes, n_top_features))
+
+
+CONTINUOUS_LABELS_ERROR = ("Unknown label type: continuous. Maybe you are trying to fit a classifier, which expects "
+                           "discrete classes on a regression target with continuous values.")
+
+
+def _cluster_labels(cluster, cells):
+    """the labels of the cells, in their order: a Series indexed by the cell names is aligned as _align_obs does;
+    float labels must be integral (sklearn's check_classification_targets)"""
+    if isinstance(cluster, pd.Series):
+        cluster = _align_obs(cluster.to_frame(), cells).iloc[:, 0]
+    y = np.asarray(cluster)
+    if y.ndim != 1 or y.shape[0] != len(cells):
+        raise ValueError("cluster has shape %s for %d cells" % (y.shape, len(cells)))
+    if y.dtype.kind == "c" or (y.dtype.kind == "f" and not (np.isfinite(y).all() and (y == np.round(y)).all())):
+        raise ValueError(CONTINUOUS_LABELS_ERROR)
+    return y
+
+
+def mi_classes(labels, n_neighbors):
+    """what the device needs from the labels (sklearn's _compute_mi_cd): class ids [N] (-1 for a cell of a class with
+    one cell, dropped), the number of kept classes and the gene-independent terms
+    (psi(n_kept) + mean psi(k_all)) - mean psi(label_counts), computed with sklearn's own arrays and expression"""
+    from scipy.special import digamma
+    _, inv = np.unique(labels, return_inverse=True)
+    inv = inv.reshape(-1)
+    counts = np.bincount(inv)
+    keep_cls = np.flatnonzero(counts > 1)
+    if keep_cls.size == 0:
+        raise ValueError("no cluster has two cells")
+    code = np.full(counts.size, -1, dtype=np.int32)
+    code[keep_cls] = np.arange(keep_cls.size, dtype=np.int32)
+    cls = code[inv]
+    label_counts = counts[inv].astype(np.float64)
+    k_all = np.minimum(n_neighbors, label_counts - 1)
+    mask = label_counts > 1
+    n_samples = np.sum(mask)
+    label_counts, k_all = label_counts[mask], k_all[mask]
+    cst = digamma(n_samples) + np.mean(digamma(k_all)) - np.mean(digamma(label_counts))
+    return cls, int(keep_cls.size), float(cst)
+
+
+def mi_ranking(mi, genes, n_top_features):
+    """the reference's var columns from the MI vector (preprocess.py:452-465), in the genes' order"""
+    res = pd.Series(mi, index=genes)
+    res = res.sort_values(ascending=False)
+    resdf = pd.DataFrame([res.values, np.arange(res.shape[0])], columns=res.index, index=['MI', 'MI_Rank']).T
+    resdf['MI_diff'] = resdf['MI'].diff()
+    var = pd.DataFrame(index=genes)
+    for v in resdf.columns:
+        var[v] = resdf[v]
+    var['highly_variable'] = var['MI_Rank'] < n_top_features
+    return var
 
 
 def _align_obs(obs, cells):

@@ -43,6 +43,14 @@ extern "C" {
 
 typedef struct cnmf_ctx cnmf_ctx;
 
+/* numpy's RandomState state (get_state()): the MT19937 key, pos in [0, 624], the cached Gaussian */
+typedef struct cnmf_mt_state {
+    uint32_t key[624];
+    int32_t pos;
+    int32_t has_gauss;
+    double gauss;
+} cnmf_mt_state;
+
 /* Solver parameters = the yaml kwargs the reference persists (cnmf.py:618-631)
  * after sklearn's scaling of the regularisers (sklearn:decomposition/_nmf.py:1254-1265):
  *   l1_reg_W = G*alpha_W*l1_ratio   l2_reg_W = G*alpha_W*(1-l1_ratio)
@@ -196,6 +204,20 @@ int cnmf_prepare_release(cnmf_ctx* ctx);
  *                                M [K*B1][n] = A X and gram [K*B1][B1] = A Phi^T with A[k*B1 + b][i] = R[k][i] Phi[b][i].
  *                                Keeps Rt / Phit for the apply.
  *   cnmf_preprocess_ridge_apply  dense slot X := max(X - A^T W, 0) in place, W [K*B1][n] (the last moments' K, B1).
+ *   cnmf_preprocess_row_sums     row_sums [n_cells] of the staged counts (the sums normalize_total divides by).
+ *   cnmf_preprocess_normalize_dense  slot := ALL genes of the staged counts as a dense [n_cells][n_genes] matrix, rows
+ *                                scaled as cnmf_preprocess_select scales them (target_sum > 0), each column divided by its
+ *                                ddof=1 std summed row after row as numpy's std(axis=0) of a C-ordered matrix sums (std_out;
+ *                                1 where the std is 0), then v > max_value -> max_value (+inf: no clip).
+ *   cnmf_preprocess_select_mi    sklearn's mutual_info_classif(X, cluster, n_neighbors) over a dense slot X [N][n]
+ *                                (Preprocess.select_features_MI, preprocess.py:425-467): X / nanstd(X, 0) plus
+ *                                1e-10 max(1, mean|X|) standard_normal((N, n)) drawn from *state (numpy's RandomState
+ *                                state: any pos, with or without a cached Gaussian; the final state is written back),
+ *                                then Ross's k-NN estimate per gene.  cls [N]: class id in [0, n_classes) of every cell,
+ *                                -1 for a cell of a class with one cell (dropped); every class in [0, n_classes) has
+ *                                >= 2 cells.  n_neighbors in [1, 8], psi [N + 1]: digamma(m) for m = 0..N, cst =
+ *                                (psi(n_kept) + mean psi(k_all)) - mean psi(label_counts) computed by the caller.
+ *                                mi [n]: the estimates, clipped at 0.  The slot itself is left as it is.
  *   cnmf_preprocess_release      frees the whole staging. */
 int cnmf_preprocess_upload_csr(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data,
                                int data_is_f64, int64_t n_cells, int64_t n_genes);
@@ -212,6 +234,11 @@ int cnmf_preprocess_project(cnmf_ctx* ctx, int32_t slot, int32_t n_comp, const d
 int cnmf_preprocess_ridge_moments(cnmf_ctx* ctx, int32_t slot, int32_t K, int32_t B1, const double* Rt, const double* Phit,
                                   double* M /* [K*B1][n] */, double* gram /* [K*B1][B1] */);
 int cnmf_preprocess_ridge_apply(cnmf_ctx* ctx, int32_t slot, const double* W /* [K*B1][n] */);
+int cnmf_preprocess_row_sums(cnmf_ctx* ctx, double* row_sums /* [n_cells] */);
+int cnmf_preprocess_normalize_dense(cnmf_ctx* ctx, int32_t slot, double target_sum, double max_value,
+                                    double* std_out /* [n_genes] */);
+int cnmf_preprocess_select_mi(cnmf_ctx* ctx, int32_t slot, const int32_t* cls, int32_t n_classes, int32_t n_neighbors,
+                              cnmf_mt_state* state, const double* psi, double cst, double* mi /* [n] */);
 int cnmf_preprocess_release(cnmf_ctx* ctx);
 
 /* ---- the restart hot loop ---------------------------------------------------------

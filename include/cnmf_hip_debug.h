@@ -32,6 +32,9 @@ int cnmf_debug_gemm2h(cnmf_ctx* ctx, const float* A, const float* Bn, float* C, 
 int cnmf_debug_stream(cnmf_ctx* ctx, int width, long long n_floats, int reps);
 /* numpy RandomState(seed).standard_normal(n) reproduced on the device. */
 int cnmf_debug_standard_normal(cnmf_ctx* ctx, uint32_t seed, int64_t n, double* out);
+/* n draws of numpy's legacy standard_normal continuing *state (the noise stream of cnmf_preprocess_select_mi); *state
+ * := the state after them. */
+int cnmf_debug_mt_normals(cnmf_ctx* ctx, cnmf_mt_state* state, int64_t n, double* out);
 
 #ifdef __cplusplus
 }
