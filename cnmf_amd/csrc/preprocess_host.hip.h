@@ -7,7 +7,7 @@
 //   * sc.pp.scale(zero_center=False, max_value) + the global quantile ceiling (stdscale_quantile_celing, :21-29): the
 //     column moments and the gather are prepare_host.hip.h's (fixed-order float64 sums, counting-sort transposes); the
 //     ceiling's order statistics come from a radix select over the float64 bit patterns (all values >= 0, so the bit
-//     order is the value order) with integer counters only, the implicit zeros of a CSR slot counted analytically;
+//     order is the value order; -0.0 is taken as +0.0) with integer counters only, the implicit zeros of a CSR slot counted analytically;
 //   * PCA (sc.pp.pca(zero_center=True)): column means and the G x G scatter matrix, then the scores (X - mean) V, on the
 //     float64 MFMA pipe; the eigendecomposition runs on the host;
 //   * Harmony's ridge correction (moe_correct_ridge, :9-18): every cluster's W_k = (Phi_Rk Phi^T + lamb)^-1 Phi_Rk X is
@@ -22,7 +22,8 @@
 namespace cnmf {
 
 // ---------------------------------------------------------------- order statistics and ceilings on a value array
-// histogram of digit (key >> shift) & 255 over the keys whose bits above shift + 8 equal those of prefix
+// histogram of digit (key >> shift) & 255 over the keys whose bits above shift + 8 equal those of prefix; -0.0 counts
+// as +0.0 (numpy orders them as equal), so only values < 0 (and NaNs with the sign bit) reach the digits 128..255
 __global__ __launch_bounds__(256) void pre_radix_hist_kernel(const double* __restrict__ v, long long n,
                                                              unsigned long long prefix, int shift,
                                                              unsigned long long* __restrict__ hist)
@@ -33,7 +34,8 @@ __global__ __launch_bounds__(256) void pre_radix_hist_kernel(const double* __res
     __syncthreads();
     const unsigned long long mask = shift + 8 >= 64 ? 0ull : (~0ull << (shift + 8));
     for (long long i = (long long)blockIdx.x * 256 + t; i < n; i += (long long)gridDim.x * 256) {
-        const unsigned long long key = (unsigned long long)__double_as_longlong(v[i]);
+        unsigned long long key = (unsigned long long)__double_as_longlong(v[i]);
+        if (key == 0x8000000000000000ull) key = 0ull;
         if ((key & mask) == prefix) atomicAdd(&h[(key >> shift) & 255], 1u);
     }
     __syncthreads();

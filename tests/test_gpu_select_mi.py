@@ -12,6 +12,7 @@ import scipy.sparse as sp
 from cnmf_amd import synth
 from cnmf_amd.engine import Engine
 from cnmf_amd.preprocess import Preprocess, mi_classes
+from tests._mi_ref import assert_state_equal, host_noise
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -46,12 +47,6 @@ def engine():
 def state_of(gold, prefix):
     return ("MT19937", gold[prefix + "_key"], int(gold[prefix + "_pos"]), int(gold[prefix + "_has_gauss"]),
             float(gold[prefix + "_gauss"]))
-
-
-def assert_state_equal(a, b):
-    assert a[0] == b[0] and np.array_equal(np.asarray(a[1]), np.asarray(b[1]))
-    assert (int(a[2]), int(a[3])) == (int(b[2]), int(b[3]))
-    assert np.float64(a[4]).view(np.uint64) == np.float64(b[4]).view(np.uint64)
 
 
 def run_fixture(tag, gold, inputs, engine):
@@ -121,20 +116,6 @@ def test_noise_stream_from_any_state(pos, cached, engine):
 
 
 # ---------------------------------------------------------------- full size against sklearn's _compute_mi_cd
-def host_noise(X, state):
-    """sklearn's _estimate_mi scaling and noise on the host from ``state``, as it writes them (X[:, mask] is a
-    column-major copy, which sets numpy's summation order)"""
-    from sklearn.preprocessing import scale
-    rs = np.random.RandomState()
-    rs.set_state(state)
-    X = X.astype(np.float64, copy=True)
-    mask = np.ones(X.shape[1], dtype=bool)
-    X[:, mask] = scale(X[:, mask], with_mean=False, copy=False)
-    means = np.maximum(1, np.mean(np.abs(X[:, mask]), axis=0))
-    X[:, mask] += 1e-10 * means * rs.standard_normal(size=X.shape)
-    return X, rs.get_state()
-
-
 def test_full_size_against_sklearn(engine):
     from scipy.special import digamma
     from sklearn.feature_selection._mutual_info import _compute_mi_cd
