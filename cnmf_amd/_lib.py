@@ -27,6 +27,8 @@ SYMBOLS = [
     "cnmf_preprocess_ceiling", "cnmf_preprocess_densify", "cnmf_preprocess_fetch", "cnmf_preprocess_scatter",
     "cnmf_preprocess_project", "cnmf_preprocess_ridge_moments", "cnmf_preprocess_ridge_apply", "cnmf_preprocess_release",
     "cnmf_preprocess_row_sums", "cnmf_preprocess_normalize_dense", "cnmf_preprocess_select_mi",
+    "cnmf_preprocess_upload_csr_as_stored", "cnmf_preprocess_gene_detect", "cnmf_preprocess_cell_sums",
+    "cnmf_preprocess_subset", "cnmf_preprocess_fetch_counts",
     "cnmf_nmf_cd_batch", "cnmf_nmf_cd_batch_resident", "cnmf_get_iteration_means", "cnmf_set_iteration_hints", "cnmf_nnls",
     "cnmf_consensus", "cnmf_pairwise_distances", "cnmf_prediction_error", "cnmf_nmf_mu_batch", "cnmf_mu_refit_f64", "cnmf_x_matmul",
     "cnmf_xt_matmul_f64", "cnmf_nnls_spectra", "cnmf_nnls_f64", "cnmf_nnls_gram", "cnmf_nnls_batch", "cnmf_kselect_stats",
@@ -209,6 +211,17 @@ def load():
     lib.cnmf_preprocess_select_mi.argtypes = [vp, i32, i32p, i32, i32, C.POINTER(MtState), dblp, C.c_double, dblp]
     lib.cnmf_preprocess_release.restype = i32
     lib.cnmf_preprocess_release.argtypes = [vp]
+    u8p = C.POINTER(C.c_uint8)
+    lib.cnmf_preprocess_upload_csr_as_stored.restype = i32
+    lib.cnmf_preprocess_upload_csr_as_stored.argtypes = [vp, i64p_, i32p, dblp, i64, i64]
+    lib.cnmf_preprocess_gene_detect.restype = i32
+    lib.cnmf_preprocess_gene_detect.argtypes = [vp, u8p, i64p_, dblp]
+    lib.cnmf_preprocess_cell_sums.restype = i32
+    lib.cnmf_preprocess_cell_sums.argtypes = [vp, u8p, dblp]
+    lib.cnmf_preprocess_subset.restype = i32
+    lib.cnmf_preprocess_subset.argtypes = [vp, u8p, u8p, i64p_, i64p_, i64p_]
+    lib.cnmf_preprocess_fetch_counts.restype = i32
+    lib.cnmf_preprocess_fetch_counts.argtypes = [vp, C.c_double, i64p_, i32p, dblp]
     lib.cnmf_prepare_release.restype = i32
     lib.cnmf_prepare_release.argtypes = [vp]
     lib.cnmf_nmf_cd_batch.restype = i32

@@ -20,7 +20,8 @@ __global__ __launch_bounds__(256) void prep_widen_kernel(const float* __restrict
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) out[i] = (double)in[i];
 }
 
-// one wavefront per row: *bad |= 1 (columns not strictly increasing), 2 (column outside [0, C)), 4 (value not finite > 0)
+// one wavefront per row: *bad |= 1 (columns not strictly increasing), 2 (column outside [0, C)), 4 (value not finite > 0),
+// 8 (value not finite >= 0)
 __global__ __launch_bounds__(256) void prep_check_kernel(const long long* __restrict__ ptr, const int* __restrict__ idx,
                                                          const double* __restrict__ val, int R, int C, int* __restrict__ bad)
 {
@@ -34,6 +35,7 @@ __global__ __launch_bounds__(256) void prep_check_kernel(const long long* __rest
         if (p > b && idx[p - 1] >= c) flag |= 1;
         const double v = val[p];
         if (!(v > 0.0) || !isfinite(v)) flag |= 4;
+        if (!(v >= 0.0) || !isfinite(v)) flag |= 8;
     }
     if (flag) atomicOr(bad, flag);
 }
@@ -196,8 +198,11 @@ static int prep_csr_args(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* in
 
 // stages raw counts (checked by prep_csr_args) as CSR with float64 values into freshly allocated (*ptr_out, *idx_out,
 // *val_out); frees them again on any failure.  Shared by cnmf_prepare_upload_csr and cnmf_preprocess_upload_csr.
+// as_stored: the rows may list their (distinct) columns in any order and zeros may be stored
+// (cnmf_preprocess_upload_csr_as_stored).
 static int prep_stage_csr(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data, int data_is_f64,
-                          int64_t n_cells, int64_t n_genes, long long** ptr_out, int** idx_out, double** val_out)
+                          int64_t n_cells, int64_t n_genes, long long** ptr_out, int** idx_out, double** val_out,
+                          bool as_stored = false)
 {
     using namespace cnmf;
     const int64_t nnz = indptr[n_cells];
@@ -235,11 +240,13 @@ static int prep_stage_csr(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* i
         if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
     }
+    if (as_stored) bad &= 2 | 8;
     if (e != hipSuccess || bad) { hipFree(ptr); hipFree(idx); hipFree(val); }
     HIP_TRY(ctx, e);
     if (bad & 2) { SET_ERR(ctx, "column index out of range in the CSR arrays"); return CNMF_EINVAL; }
     if (bad & 1) { SET_ERR(ctx, "every row must list strictly increasing columns (canonical CSR)"); return CNMF_EINVAL; }
     if (bad & 4) { SET_ERR(ctx, "stored values must be finite and > 0 (counts without stored zeros)"); return CNMF_EINVAL; }
+    if (bad & 8) { SET_ERR(ctx, "stored values must be finite and >= 0"); return CNMF_EINVAL; }
     *ptr_out = ptr; *idx_out = idx; *val_out = val;
     return CNMF_OK;
 }

@@ -479,6 +479,80 @@ class Engine:
                                                         psi.ctypes.data_as(dblp), float(cst), mi.ctypes.data_as(dblp)))
         return mi, st.to_numpy()
 
+    # ---- filters over the staged counts (filter_host.hip.h): Preprocess.filter_adata / preprocess_for_cnmf
+    def preprocess_upload_as_stored(self, counts):
+        """Stage a scipy CSR exactly as it is stored: rows may list their (distinct) columns in any order and zeros may
+        be stored.  Returns the CSR that was staged."""
+        import scipy.sparse as sp
+        X = sp.csr_matrix(counts)
+        vals = np.ascontiguousarray(X.data, dtype=np.float64)
+        indptr = np.ascontiguousarray(X.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(X.indices, dtype=np.int32)
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_preprocess_upload_csr_as_stored(self._ctx, indptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                                   indices.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                                   vals.ctypes.data_as(dblp), X.shape[0], X.shape[1]))
+        self._pre = {"N": X.shape[0], "G": X.shape[1], 0: None, 1: None}
+        return X
+
+    def _pre_mask(self, mask, axis, name):
+        """(the bytes of a boolean mask over the staged cells 'N' / genes 'G', their pointer); None: (None, None)"""
+        if getattr(self, "_pre", None) is None or self._pre.get("G") is None:
+            raise RuntimeError("preprocess_upload has not been called")
+        if mask is None:
+            return None, None
+        m = np.asarray(mask)
+        if m.dtype != bool or m.shape != (self._pre[axis],):
+            raise ValueError("%s must be a boolean mask of length %d (got %s of shape %s)"
+                             % (name, self._pre[axis], m.dtype, m.shape))
+        m = np.ascontiguousarray(m, dtype=np.uint8)
+        return m, m.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    def preprocess_gene_detect(self, cell_mask=None):
+        """Per staged gene, over the cells of ``cell_mask`` (None: all): the number of stored entries > 0 (int64) and the
+        sum of its entries.  Returns ``(n_cells, totals)``."""
+        m, mp = self._pre_mask(cell_mask, "N", "cell_mask")
+        G = self._pre["G"]
+        n_cells, totals = np.empty(G, dtype=np.int64), np.empty(G)
+        self._check(self._lib.cnmf_preprocess_gene_detect(self._ctx, mp, n_cells.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                          totals.ctypes.data_as(C.POINTER(C.c_double))))
+        return n_cells, totals
+
+    def preprocess_cell_sums(self, gene_mask=None):
+        """Per staged cell, the sum of its entries over the genes of ``gene_mask`` (None: all -- preprocess_row_sums)."""
+        m, mp = self._pre_mask(gene_mask, "G", "gene_mask")
+        sums = np.empty(self._pre["N"])
+        self._check(self._lib.cnmf_preprocess_cell_sums(self._ctx, mp, sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return sums
+
+    def preprocess_subset(self, keep_cells=None, keep_genes=None):
+        """The staged counts := their restriction to the kept cells and genes (on the device; stored order kept); both
+        result slots are released.  Returns the new ``(n_cells, n_genes, nnz)``."""
+        mc, mcp = self._pre_mask(keep_cells, "N", "keep_cells")
+        mg, mgp = self._pre_mask(keep_genes, "G", "keep_genes")
+        n, g, nnz = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.cnmf_preprocess_subset(self._ctx, mcp, mgp, C.byref(n), C.byref(g), C.byref(nnz)))
+        self._pre = {"N": int(n.value), "G": int(g.value), 0: None, 1: None}
+        return int(n.value), int(g.value), int(nnz.value)
+
+    def preprocess_fetch_counts(self, target_sum=0.0):
+        """The staged counts as a scipy CSR, as stored; ``target_sum > 0``: every cell scaled to that total
+        (sc.pp.normalize_total over all staged genes; a cell without counts stays 0)."""
+        import scipy.sparse as sp
+        self._pre_mask(None, "N", "")
+        N, G = self._pre["N"], self._pre["G"]
+        i64p = C.POINTER(C.c_int64)
+        indptr = np.empty(N + 1, dtype=np.int64)
+        self._check(self._lib.cnmf_preprocess_fetch_counts(self._ctx, 0.0, indptr.ctypes.data_as(i64p), None, None))
+        nnz = int(indptr[-1])
+        indices, data = np.empty(max(nnz, 1), dtype=np.int32), np.empty(max(nnz, 1))
+        self._check(self._lib.cnmf_preprocess_fetch_counts(self._ctx, float(target_sum), None,
+                                                           indices.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                           data.ctypes.data_as(C.POINTER(C.c_double))))
+        if nnz < (1 << 31):
+            indptr = indptr.astype(np.int32)
+        return sp.csr_matrix((data[:nnz], indices[:nnz].astype(indptr.dtype), indptr), shape=(N, G))
+
     def preprocess_release(self):
         self._check(self._lib.cnmf_preprocess_release(self._ctx))
         self._pre = None

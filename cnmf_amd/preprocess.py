@@ -30,8 +30,15 @@ then on the device (csrc/select_mi_host.hip.h) sklearn's own scaling and noise -
 whose state the call advances exactly as the reference does -- and Ross's k-NN estimate per gene, bit for bit.  The
 ranking (``MI``, ``MI_Rank``, ``MI_diff``, ``highly_variable``) uses the reference's own pandas expressions.
 
-Out of scope: ``preprocess_for_cnmf``, ``filter_adata``, the seurat_v3 HVG selection (``n_top_genes``: it needs
-skmisc's loess), plots (``makeplots`` is accepted and nothing is drawn) and ``.h5ad`` writing.
+``Preprocess.filter_adata`` (:60-132) and ``Preprocess.preprocess_for_cnmf`` (:135-267) stage the counts once and work on
+that staging (csrc/filter_host.hip.h): the per-gene detection counts, the per-cell sums over a gene mask (``n_counts``, the
+mitochondrial totals), the restriction of the staging to the kept cells and genes (one device pass, the stored order kept)
+and the library-size-normalised matrix over all genes (``tp10k``); ``normalize_batchcorrect``'s body then runs on the
+staging that is already there.  Counts are integers, so every sum is exact; ``pct_mito`` and the normalised values are one
+rounding each: all of it equals the reference bit for bit.
+
+Out of scope: the seurat_v3 HVG selection (``n_top_genes`` / ``n_top_rna_genes``: it needs skmisc's loess), plots
+(``makeplots`` is accepted and nothing is drawn) and ``.h5ad`` writing.
 """
 import numpy as np
 import pandas as pd
@@ -39,6 +46,11 @@ import pandas as pd
 HARMONY_IMPORT_ERROR = "harmonypy is not installed. Please install it using 'pip install harmonypy' before proceeding."
 HVG_REQUIRED_ERROR = ("If a numeric value for n_top_genes is not provided, you must include a highly_variable column "
                       "in _adata")
+N_TOP_GENES_ERROR = ("n_top_genes (seurat_v3 HVG selection) needs skmisc's loess, which this package does not use: pass "
+                     "highly_variable instead")
+ADT_CELL_COUNT_ERROR = "ADT and RNA AnnDatas don't have the same number of cells"
+ADT_CELL_INDEX_ERROR = "Inconsistency of the index for the ADT and RNA AnnDatas"
+DATA_FORM_ERROR = 'data should either be an AnnData object or a list of 2 AnnData objects'
 
 
 class PreprocessResult:
@@ -83,6 +95,59 @@ def _to_csr(mat):
     if X.nnz and not (np.isfinite(X.data).all() and (X.data >= 0).all()):
         raise ValueError("Preprocess expects finite non-negative values")
     return X
+
+
+def _hv_mask(highly_variable, genes):
+    """the boolean mask over ``genes`` of a highly_variable mask or list of names"""
+    hv = np.asarray(highly_variable)
+    if hv.dtype == bool:
+        if hv.shape != (len(genes),):
+            raise ValueError("highly_variable mask of length %d for %d genes" % (hv.size, len(genes)))
+        return hv
+    names = pd.Index([str(x) for x in hv])
+    unknown = names.difference(genes)
+    if len(unknown):
+        raise KeyError("highly_variable names not among the genes: %s" % list(unknown[:5]))
+    return genes.isin(names)
+
+
+def make_unique_names(names, join="-"):
+    """anndata's ``var_names_make_unique``: the first occurrence of a name keeps it, later ones become ``name-1``,
+    ``name-2``, ..., skipping any name that exists already (among the originals or made earlier)."""
+    names = [str(x) for x in names]
+    out = list(names)
+    taken = set(names)
+    counter = {}
+    seen = set()
+    for i, v in enumerate(names):
+        if v not in seen:
+            seen.add(v)
+            continue
+        k = counter.get(v, 0) + 1
+        new = "%s%s%d" % (v, join, k)
+        while new in taken:
+            k += 1
+            new = "%s%s%d" % (v, join, k)
+        counter[v] = k
+        taken.add(new)
+        out[i] = new
+    return pd.Index(out)
+
+
+def mito_genes_mask(genes):
+    """the reference's ``'MT-' in name`` (preprocess.py:109): a substring test, not a prefix test"""
+    return np.array(['MT-' in str(x) for x in genes], dtype=bool)
+
+
+def dot_genes_mask(genes):
+    return np.array(['.' in str(x) for x in genes], dtype=bool)
+
+
+def _is_single_matrix(data):
+    import scipy.sparse as sp
+    if isinstance(data, tuple):
+        return len(data) == 3
+    return isinstance(data, (pd.DataFrame, np.ndarray)) or sp.issparse(data)
 
 
 def quantile_from_order_stats(lo, hi, n, q):
@@ -245,8 +310,7 @@ class Preprocess:
         ``(result, hvgs)``: ``result.X`` goes straight into ``cNMF.prepare(counts=(result.X, result.obs_names, hvgs),
         ...)``."""
         if n_top_genes is not None:
-            raise NotImplementedError("n_top_genes (seurat_v3 HVG selection) needs skmisc's loess, which this package does "
-                                      "not use: pass highly_variable instead")
+            raise NotImplementedError(N_TOP_GENES_ERROR)
         if highly_variable is None:
             raise Exception(HVG_REQUIRED_ERROR)
         _check_quantile(quantile_thresh)
@@ -255,55 +319,234 @@ class Preprocess:
                 _import_harmonypy()
             _check_harmony_vars(obs, harmony_vars)
         mat, cells, genes, dense = _data_parts(data)
-        hv = np.asarray(highly_variable)
-        if hv.dtype == bool:
-            if hv.shape != (len(genes),):
-                raise ValueError("highly_variable mask of length %d for %d genes" % (hv.size, len(genes)))
-            mask = hv
-        else:
-            names = pd.Index([str(x) for x in hv])
-            unknown = names.difference(genes)
-            if len(unknown):
-                raise KeyError("highly_variable names not among the genes: %s" % list(unknown[:5]))
-            mask = genes.isin(names)
-        sel = np.flatnonzero(mask)
+        sel = np.flatnonzero(_hv_mask(highly_variable, genes))
         if sel.size == 0:
             raise ValueError("highly_variable selects no gene")
         hvgs = list(genes[sel])
         if obs is not None:
             obs = _align_obs(obs, cells)
         X = _to_csr(mat)
-        N, n = X.shape[0], int(sel.size)
         eng = self.engine
-        obsm = {}
         try:
             eng.preprocess_upload(X)
-            if harmony_vars is not None:
-                # anorm: normalize_total(copy=True) -> HVG subset -> scale + ceiling (preprocess.py:316-318)
-                eng.preprocess_select(0, sel, float(librarysize_targetsum), max_scaled_thresh)
-                _ceiling(eng, 0, N, n, quantile_thresh)
-                # _adata: raw counts -> HVG subset -> scale + ceiling (:320-321)
-                if not normalize_librarysize:
-                    eng.preprocess_select(1, sel, 0.0, max_scaled_thresh)
-                    _ceiling(eng, 1, N, n, quantile_thresh)
-                eng.preprocess_densify(0)
-                obsm["X_pca"] = _pca(eng, 0, N, n)                     # (:326)
-                slot = 0 if normalize_librarysize else 1
-                eng.preprocess_densify(slot)
-                if harmony_res is None:
-                    harmony_res = _import_harmonypy().run_harmony(obsm["X_pca"], obs, harmony_vars,
-                                                                  max_iter_harmony=max_iter_harmony, theta=theta)
-                Xout, obsm["X_pca_harmony"] = self._ridge(None, slot, obsm["X_pca"], harmony_res)
-            else:
-                target = float(librarysize_targetsum) if normalize_librarysize else 0.0
-                eng.preprocess_select(0, sel, target, max_scaled_thresh)
-                _ceiling(eng, 0, N, n, quantile_thresh)
-                if dense:
-                    eng.preprocess_densify(0)
-                Xout = eng.preprocess_fetch(0)
+            Xout, obsm = self._batchcorrect_staged(eng, X.shape[0], sel, dense, obs, normalize_librarysize, harmony_vars,
+                                                   librarysize_targetsum, max_scaled_thresh, quantile_thresh, theta,
+                                                   max_iter_harmony, harmony_res)
         finally:
             eng.preprocess_release()
         return PreprocessResult(Xout, cells, pd.Index(hvgs), obs, obsm), hvgs
+
+    def _batchcorrect_staged(self, eng, N, sel, dense, obs, normalize_librarysize, harmony_vars, librarysize_targetsum,
+                             max_scaled_thresh, quantile_thresh, theta, max_iter_harmony, harmony_res):
+        """normalize_batchcorrect (preprocess.py:314-358) over the counts ``eng`` has staged (N cells), for the staged
+        genes ``sel``: returns ``(X, obsm)``.  The caller uploads and releases."""
+        n = int(sel.size)
+        obsm = {}
+        if harmony_vars is not None:
+            # anorm: normalize_total(copy=True) -> HVG subset -> scale + ceiling (preprocess.py:316-318)
+            eng.preprocess_select(0, sel, float(librarysize_targetsum), max_scaled_thresh)
+            _ceiling(eng, 0, N, n, quantile_thresh)
+            # _adata: raw counts -> HVG subset -> scale + ceiling (:320-321)
+            if not normalize_librarysize:
+                eng.preprocess_select(1, sel, 0.0, max_scaled_thresh)
+                _ceiling(eng, 1, N, n, quantile_thresh)
+            eng.preprocess_densify(0)
+            obsm["X_pca"] = _pca(eng, 0, N, n)                     # (:326)
+            slot = 0 if normalize_librarysize else 1
+            eng.preprocess_densify(slot)
+            if harmony_res is None:
+                harmony_res = _import_harmonypy().run_harmony(obsm["X_pca"], obs, harmony_vars,
+                                                              max_iter_harmony=max_iter_harmony, theta=theta)
+            Xout, obsm["X_pca_harmony"] = self._ridge(None, slot, obsm["X_pca"], harmony_res)
+        else:
+            target = float(librarysize_targetsum) if normalize_librarysize else 0.0
+            eng.preprocess_select(0, sel, target, max_scaled_thresh)
+            _ceiling(eng, 0, N, n, quantile_thresh)
+            if dense:
+                eng.preprocess_densify(0)
+            Xout = eng.preprocess_fetch(0)
+        return Xout, obsm
+
+    # ------------------------------------------------------------------ filter_adata (preprocess.py:60-132)
+    def filter_adata(self, data, obs=None, filter_mito_thresh=None, min_cells_per_gene=10, min_counts_per_cell=500,
+                     filter_mito_genes=False, filter_dot_genes=True, makeplots=True):
+        """The reference's optional filter, in its order: genes detected (value > 0) in at least ``min_cells_per_gene``
+        cells; ``n_counts`` = every cell's sum over those genes; cells with ``n_counts >= min_counts_per_cell``;
+        ``pct_mito`` = the share of the genes whose name contains ``'MT-'`` and cells with ``pct_mito <
+        filter_mito_thresh`` (a cell without counts has NaN and goes); then the genes containing ``'.'``
+        (``filter_dot_genes``) and the mitochondrial genes (``filter_mito_genes``) are dropped.  Genes are not filtered
+        again after cells went, as in the reference.  The counts are staged once, the sums and the one restriction to
+        the kept cells and genes run on the device.
+
+        Returns a PreprocessResult: ``X`` the raw filtered counts (float64; CSR for sparse input, dense for dense
+        input), ``obs_names``, ``var_names``, ``obs`` (the given columns plus ``n_counts`` and, with a threshold,
+        ``pct_mito``) and ``var`` with ``n_cells`` (the detection counts over all cells of the input; the reference has
+        this column only when ``min_cells_per_gene`` is given).  A filter that leaves no cell or no gene raises
+        ValueError.  The reference's ``ax.title(...)`` defect (plots with a threshold) is not reproduced."""
+        mat, cells, genes, dense = _data_parts(data)
+        obs = pd.DataFrame(index=cells) if obs is None else _align_obs(obs, cells).copy()
+        X = _to_csr(mat)
+        mt = mito_genes_mask(genes)
+        eng = self.engine
+        try:
+            eng.preprocess_upload(X)
+            n_cells, _ = eng.preprocess_gene_detect()
+            keep_g = n_cells >= min_cells_per_gene if min_cells_per_gene is not None else np.ones(len(genes), dtype=bool)
+            if not keep_g.any():
+                raise ValueError("min_cells_per_gene = %s leaves no gene" % (min_cells_per_gene,))
+            n_counts = eng.preprocess_cell_sums(None if keep_g.all() else keep_g)
+            keep_c = n_counts >= min_counts_per_cell if min_counts_per_cell is not None else np.ones(len(cells), dtype=bool)
+            if not keep_c.any():
+                raise ValueError("min_counts_per_cell = %s leaves no cell" % (min_counts_per_cell,))
+            obs["n_counts"] = n_counts
+            mt_kept = mt & keep_g
+            if filter_mito_thresh is not None:
+                num_mito = eng.preprocess_cell_sums(mt_kept)
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    pct_mito = num_mito / n_counts
+                obs["pct_mito"] = pct_mito
+                keep_c = keep_c & (pct_mito < filter_mito_thresh)
+                if not keep_c.any():
+                    raise ValueError("filter_mito_thresh = %s leaves no cell" % (filter_mito_thresh,))
+            drop = np.zeros(len(genes), dtype=bool)
+            if filter_dot_genes:
+                drop |= dot_genes_mask(genes)
+            if filter_mito_genes:
+                drop |= mt_kept
+            keep_g = keep_g & ~drop
+            if not keep_g.any():
+                raise ValueError("the gene filters leave no gene")
+            eng.preprocess_subset(None if keep_c.all() else keep_c, None if keep_g.all() else keep_g)
+            Xout = eng.preprocess_fetch_counts(0.0)
+        finally:
+            eng.preprocess_release()
+        if dense:
+            Xout = Xout.toarray()
+        var = pd.DataFrame({"n_cells": n_cells[keep_g]}, index=genes[keep_g])
+        return PreprocessResult(Xout, cells[keep_c], genes[keep_g], obs.loc[keep_c], var=var)
+
+    # ------------------------------------------------------------------ preprocess_for_cnmf (preprocess.py:135-267)
+    def preprocess_for_cnmf(self, data, obs=None, highly_variable=None, feature_type=None,
+                            adt_feature_name='Antibody Capture', harmony_vars=None, n_top_rna_genes=None,
+                            librarysize_targetsum=1e4, max_scaled_thresh=None, quantile_thresh=.9999, makeplots=True,
+                            theta=1, save_output_base=None, max_iter_harmony=20, exclude_genes=None, harmony_res=None):
+        """The reference's minimal preprocessing: the HVG-filtered, variance-normalised, optionally Harmony-corrected RNA
+        matrix (the ``counts`` input of cNMF) and the library-size-normalised matrix over all genes, ADT features
+        appended and normalised on their own (the ``tpm`` input).
+
+        ``data``: one matrix (RNA only, or RNA and ADT told apart by ``feature_type``: an array-like over the genes, or
+        a Series indexed by gene, that plays ``var[feature_type_col]``; ``== adt_feature_name`` is ADT) or a list
+        ``[rna, adt]`` over the same cells.  A single-modality input gets anndata's ``var_names_make_unique``.
+
+        Deliberate difference from the reference: ``n_top_rna_genes`` defaults to None (the reference: 2000) and
+        ``highly_variable`` -- a boolean mask or a list of names over the RNA genes -- takes its place, because the
+        seurat_v3 selection needs skmisc's loess; a number raises normalize_batchcorrect's NotImplementedError, None
+        without ``highly_variable`` the reference's "you must include a highly_variable column".
+
+        The RNA counts are uploaded once: ``tp10k`` comes from them over all RNA genes before ``exclude_genes`` are taken
+        out (on the device), then normalize_batchcorrect's body runs on the same staging.
+
+        Returns ``(result_rna, tp10k, hvgs)``, both PreprocessResult.  ``save_output_base``: ``<base>.Corrected.HVGs.txt``
+        as the reference writes it; there is no ``.h5ad`` here: ``<base>.Corrected.HVG.Varnorm`` and ``<base>.TP10K``
+        are ``.df.npz`` files (save_df_to_npz) when dense, ``.npz`` (save_csr_fast) plus ``.cells.txt`` / ``.genes.txt``
+        when sparse."""
+        import scipy.sparse as sp
+        if isinstance(data, list) and len(data) == 2:
+            rna, adt = data
+        elif _is_single_matrix(data):
+            rna, adt = data, None
+        else:
+            raise Exception(DATA_FORM_ERROR)
+        if n_top_rna_genes is not None:
+            raise NotImplementedError(N_TOP_GENES_ERROR)
+        if highly_variable is None:
+            raise Exception(HVG_REQUIRED_ERROR)
+        _check_quantile(quantile_thresh)
+        if harmony_vars is not None:
+            if harmony_res is None:
+                _import_harmonypy()
+            _check_harmony_vars(obs, harmony_vars)
+        mat, cells, genes, dense = _data_parts(rna)
+        types_rna = types_adt = None
+        hv = np.asarray(highly_variable)
+        if adt is not None:
+            amat, acells, agenes, _ = _data_parts(adt)
+            if amat.shape[0] != mat.shape[0]:
+                raise Exception(ADT_CELL_COUNT_ERROR)
+            if np.sum(np.asarray(acells) != np.asarray(cells)) > 0:
+                raise Exception(ADT_CELL_INDEX_ERROR)
+        elif feature_type is not None:
+            if isinstance(feature_type, pd.Series):
+                ft = feature_type.copy()
+                ft.index = [str(x) for x in ft.index]
+                ft = ft.reindex(genes) if not ft.index.equals(genes) and ft.index.is_unique else ft
+            else:
+                ft = pd.Series(np.asarray(feature_type))
+            if len(ft) != len(genes):
+                raise ValueError("feature_type has %d entries for %d genes" % (len(ft), len(genes)))
+            is_adt = np.asarray(ft.values == adt_feature_name)
+            ft = np.asarray(ft.values)
+            X_all = sp.csr_matrix(mat) if not dense else mat
+            amat, agenes, types_adt = X_all[:, np.flatnonzero(is_adt)], genes[is_adt], ft[is_adt]
+            if hv.dtype == bool and hv.shape == (len(genes),) and is_adt.any():
+                hv = hv[~is_adt]                                  # (a var['highly_variable'] column over all features)
+            mat, genes, types_rna = X_all[:, np.flatnonzero(~is_adt)], genes[~is_adt], ft[~is_adt]
+            adt = (amat, cells, agenes)
+        else:
+            genes = make_unique_names(genes)
+        hv_mask = _hv_mask(hv, genes)
+        excluded = np.zeros(len(genes), dtype=bool)
+        if exclude_genes is not None:
+            excluded = np.asarray(genes.isin([str(x) for x in exclude_genes]))
+        sel = np.flatnonzero(hv_mask[~excluded])
+        if sel.size == 0:
+            raise ValueError("highly_variable selects no gene")
+        if excluded.all():
+            raise ValueError("exclude_genes leaves no gene")
+        hvgs = list(genes[~excluded][sel])
+        if obs is not None:
+            obs = _align_obs(obs, cells)
+        X = _to_csr(mat)
+        Xa = _to_csr(adt[0]) if adt is not None else None
+        target = float(librarysize_targetsum)
+        eng = self.engine
+        try:
+            eng.preprocess_upload(X)
+            tp10k = eng.preprocess_fetch_counts(target)             # over ALL RNA genes (preprocess.py:232-233)
+            if exclude_genes is not None:
+                if excluded.any():
+                    print(f"Excluding {excluded.sum()} genes from cNMF input (retained in tp10k):")
+                    print(list(genes[excluded]))
+                    eng.preprocess_subset(keep_genes=~excluded)
+                else:
+                    print("exclude_genes provided but none found in adata_RNA.var_names.")
+            Xout, obsm = self._batchcorrect_staged(eng, X.shape[0], sel, dense, obs, False, harmony_vars, target,
+                                                   max_scaled_thresh, quantile_thresh, theta, max_iter_harmony,
+                                                   harmony_res)
+            tp_genes, tp_types = genes, types_rna
+            if adt is not None:
+                eng.preprocess_upload(Xa)                           # normalised on its own (:254)
+                tp10k = sp.hstack((tp10k, eng.preprocess_fetch_counts(target)), format="csr")
+                tp_genes = pd.Index(list(genes) + list(adt[2]))
+                if types_rna is not None:
+                    tp_types = np.concatenate([types_rna, types_adt])
+        finally:
+            eng.preprocess_release()
+        if dense:
+            tp10k = tp10k.toarray()
+        var = pd.DataFrame(index=tp_genes)
+        if tp_types is not None:
+            var["feature_type"] = tp_types
+        elif adt is None:
+            var["features_renamed"] = tp_genes
+        result = PreprocessResult(Xout, cells, pd.Index(hvgs), obs, obsm)
+        tp = PreprocessResult(tp10k, cells, tp_genes, obs, var=var)
+        if save_output_base is not None:
+            _save_result(save_output_base + '.Corrected.HVG.Varnorm', result)
+            _save_result(save_output_base + '.TP10K', tp)
+            with open(save_output_base + '.Corrected.HVGs.txt', 'w') as F:
+                F.write('\n'.join(hvgs))
+        return result, tp, hvgs
 
     # ------------------------------------------------------------------ select_features_MI (preprocess.py:425-467)
     def select_features_MI(self, data, cluster, max_scaled_thresh=None, quantile_thresh=.9999, n_top_features=70,
@@ -396,6 +639,20 @@ def mi_ranking(mi, genes, n_top_features):
         var[v] = resdf[v]
     var['highly_variable'] = var['MI_Rank'] < n_top_features
     return var
+
+
+def _save_result(base, res):
+    """a PreprocessResult on disk: ``<base>.df.npz`` (save_df_to_npz) when dense, ``<base>.npz`` (save_csr_fast) with
+    ``<base>.cells.txt`` / ``<base>.genes.txt`` when sparse"""
+    import scipy.sparse as sp
+    from .cnmf import save_csr_fast, save_df_to_npz
+    if not sp.issparse(res.X):
+        save_df_to_npz(pd.DataFrame(res.X, index=res.obs_names, columns=res.var_names), base + '.df.npz')
+        return
+    save_csr_fast(base + '.npz', sp.csr_matrix(res.X))
+    for ext, names in (('.cells.txt', res.obs_names), ('.genes.txt', res.var_names)):
+        with open(base + ext, 'w') as F:
+            F.write('\n'.join(str(x) for x in names))
 
 
 def _align_obs(obs, cells):

@@ -218,7 +218,22 @@ int cnmf_prepare_release(cnmf_ctx* ctx);
  *                                >= 2 cells.  n_neighbors in [1, 8], psi [N + 1]: digamma(m) for m = 0..N, cst =
  *                                (psi(n_kept) + mean psi(k_all)) - mean psi(label_counts) computed by the caller.
  *                                mi [n]: the estimates, clipped at 0.  The slot itself is left as it is.
- *   cnmf_preprocess_release      frees the whole staging. */
+ *   cnmf_preprocess_release      frees the whole staging.
+ * Filters over the staged counts (Preprocess.filter_adata, the head of preprocess_for_cnmf; filter_host.hip.h).  A mask is
+ * one byte per cell / gene of the staging, non-zero = in; NULL = all.
+ *   cnmf_preprocess_upload_csr_as_stored  as cnmf_preprocess_upload_csr for float64 values, but the arrays are staged as they
+ *                                are: a row may list its (distinct) columns in any order and zeros (>= 0) may be stored.
+ *   cnmf_preprocess_gene_detect  per gene, over the cells of cell_mask: n_cells = stored entries > 0 (a stored zero is no
+ *                                detection), totals = the sum of its entries.
+ *   cnmf_preprocess_cell_sums    per cell, the sum of its entries whose gene is in gene_mask, in the summation order of
+ *                                cnmf_preprocess_row_sums (NULL mask: the same bits).
+ *   cnmf_preprocess_subset       the staged counts := their restriction to the kept cells and genes, on the device; the kept
+ *                                entries of a row keep their stored order, stored zeros stay.  Both slots and the ridge
+ *                                factors are released (they named the old cells and genes).  CNMF_EINVAL when no cell or no
+ *                                gene is kept; on any error the staging is left as it was.
+ *   cnmf_preprocess_fetch_counts the staged CSR: target_sum > 0: values x * target_sum / row sum (0 for a cell without
+ *                                counts; the bits of the normalised copy inside cnmf_preprocess_select), target_sum == 0:
+ *                                the raw values.  Any of the three arrays may be NULL (skipped). */
 int cnmf_preprocess_upload_csr(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data,
                                int data_is_f64, int64_t n_cells, int64_t n_genes);
 int cnmf_preprocess_set_dense(cnmf_ctx* ctx, int32_t slot, const double* X, int64_t n_rows, int64_t n_cols);
@@ -240,6 +255,15 @@ int cnmf_preprocess_normalize_dense(cnmf_ctx* ctx, int32_t slot, double target_s
 int cnmf_preprocess_select_mi(cnmf_ctx* ctx, int32_t slot, const int32_t* cls, int32_t n_classes, int32_t n_neighbors,
                               cnmf_mt_state* state, const double* psi, double cst, double* mi /* [n] */);
 int cnmf_preprocess_release(cnmf_ctx* ctx);
+int cnmf_preprocess_upload_csr_as_stored(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const double* data,
+                                         int64_t n_cells, int64_t n_genes);
+int cnmf_preprocess_gene_detect(cnmf_ctx* ctx, const uint8_t* cell_mask /* [n_cells] or NULL */,
+                                int64_t* n_cells /* [n_genes] */, double* totals /* [n_genes] */);
+int cnmf_preprocess_cell_sums(cnmf_ctx* ctx, const uint8_t* gene_mask /* [n_genes] or NULL */, double* sums /* [n_cells] */);
+int cnmf_preprocess_subset(cnmf_ctx* ctx, const uint8_t* keep_cells /* [n_cells] or NULL */,
+                           const uint8_t* keep_genes /* [n_genes] or NULL */, int64_t* n_cells_out, int64_t* n_genes_out,
+                           int64_t* nnz_out);
+int cnmf_preprocess_fetch_counts(cnmf_ctx* ctx, double target_sum, int64_t* indptr, int32_t* indices, double* values);
 
 /* ---- the restart hot loop ---------------------------------------------------------
  * Replaces the loop body of cNMF.factorize (cnmf.py:735-741): for every restart r,
