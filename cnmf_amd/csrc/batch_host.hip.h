@@ -3,18 +3,12 @@
 #pragma once
 
 // ------------------------------------------------------------------ batch buffers
-static int sweep_max_parts()
-{
-    static const int v = getenv("CNMF_SWEEP_PARTS") ? atoi(getenv("CNMF_SWEEP_PARTS")) : 64;
-    return std::max(1, v);
-}
-static int sweep_chunks(int L) { const int64_t m = 256ll * sweep_max_parts(); return std::max(1, (int)(((int64_t)L + m - 1) / m)); }
+static int sweep_chunks(const cnmf_ctx* ctx, int L) { const int64_t m = 256ll * ctx->knobs.sweep_parts; return std::max(1, (int)(((int64_t)L + m - 1) / m)); }
 // partials per slot of a half-step: one per sweep workgroup (sweep_chunks 256-row tiles each)
-static int sweep_parts(int L) { const int c = sweep_chunks(L); return (L + 256 * c - 1) / (256 * c); }
+static int sweep_parts(const cnmf_ctx* ctx, int L) { const int c = sweep_chunks(ctx, L); return (L + 256 * c - 1) / (256 * c); }
 
 static int pick_nsplit(const cnmf_ctx* ctx, int KC)
 {
-    if (const char* s = ctx_getenv(ctx, "CNMF_NSPLIT")) { int v = atoi(s); if (v > 0) return v; }
     // pass B grid = ceil(G_pad/128) x (KC/128 or 1) x nsplit ; aim at ~2 workgroups per CU
     const int jt = (ctx->G_pad + 127) / 128;
     const int mg = std::max(1, KC / 128);
@@ -34,7 +28,6 @@ static int effective_splits(int Ktot, int nsplit)
 // that ~2 workgroups per CU are in flight; the planes are summed by reduce_splits_kernel.
 static int pick_nsplit_A(const cnmf_ctx* ctx, int KC)
 {
-    if (const char* s = ctx_getenv(ctx, "CNMF_NSPLIT_A")) { int v = atoi(s); if (v > 0) return effective_splits(ctx->G_pad, v); }
     const int T = (ctx->N_pad / 128) * std::max(1, KC / 128);
     if (T > 256) return 1;                                  // stream-K territory
     int s = std::max(1, 512 / T);
@@ -48,7 +41,7 @@ static int pick_nsplit_A3(const cnmf_ctx* ctx, int KC, int jw)
 {
     const int T = std::max(1, ctx->N_pad / jw) * std::max(1, KC / G3_MW);
     const int Kb = ctx->G_pad / G3_BK;
-    int s = std::max(1, std::min(gemm3_wg_slots() / T, Kb / 8));
+    int s = std::max(1, std::min(gemm3_wg_slots(ctx->knobs) / T, Kb / 8));
     const int kb_per = (Kb + s - 1) / s;
     return (Kb + kb_per - 1) / kb_per;
 }
@@ -60,7 +53,7 @@ static int ensure_batch(cnmf_ctx* ctx, int KC, int max_k = KMAX, int min_k = 1)
                             : pick_nsplit(ctx, KC);
     const int nsplitA = use3 ? std::max(pick_nsplit_A(ctx, KC), std::max(pick_nsplit_A3(ctx, KC, G3_JW), pick_nsplit_A3(ctx, KC, G3C_JW)))
                              : pick_nsplit_A(ctx, KC);
-    const int parts = std::max(sweep_parts((int)ctx->N), sweep_parts((int)ctx->G));
+    const int parts = std::max(sweep_parts(ctx, (int)ctx->N), sweep_parts(ctx, (int)ctx->G));
     const size_t gp_need = (size_t)(KC / std::max(1, min_k) + 1) * parts * max_k * max_k;
     if (ctx->kc_alloc == KC && ctx->nsplit_alloc == nsplit && ctx->nsplitA_alloc == nsplitA &&
         ctx->parts_alloc == parts && ctx->gram_part_floats >= gp_need && (!use3 || ctx->H3)) return CNMF_OK;
@@ -164,7 +157,6 @@ static int wait_snapshot(cnmf_ctx* ctx, const SlotDesc* sp, int n, int stamp)
     // marker behind the last enqueued kernel -- here always the H finalize -- and the GPU then pays ~6 us for that
     // barrier packet in front of every pass A (measured: the finalize -> pass A gap of round 2's kernel traces).
     using clk = std::chrono::steady_clock;
-    static const bool eager_query = getenv("CNMF_SPIN_QUERY") != nullptr;       // A/B: the round-1 behaviour
     for (int s = 0; s < n; ++s) {
         const volatile int* flag = &sp[s].pad_;
         long spins = 0;
@@ -173,7 +165,7 @@ static int wait_snapshot(cnmf_ctx* ctx, const SlotDesc* sp, int n, int stamp)
         while (*flag != stamp) {
             if (++spins % 4096 != 0) continue;
             if (!timing) { t0 = clk::now(); timing = true; continue; }
-            if (!eager_query && std::chrono::duration_cast<std::chrono::milliseconds>(clk::now() - t0).count() < 20) continue;
+            if (std::chrono::duration_cast<std::chrono::milliseconds>(clk::now() - t0).count() < 20) continue;
             t0 = clk::now();
             const hipError_t q = hipStreamQuery(ctx->stream);
             if (q == hipSuccess) {                       // stream drained: the stamp must be there
@@ -196,22 +188,13 @@ static int wait_snapshot(cnmf_ctx* ctx, const SlotDesc* sp, int n, int stamp)
 // pass: both passes then read every X tile once per 1024 columns instead of once per 256, the stream-K partial planes of
 // pass A and the latency-bound H half-step are amortised over four times the columns (169 -> 198 -> 215 restarts/s at
 // 256 / 512 / 1024 columns, 50 000 x 2000); the batch narrows in 256-column steps once the queue is dry (compact()).
-// kc_max: 0 = auto, else an upper bound (multiple of 32; above 256 in steps of 256, up to CNMF_KC_LIMIT).
-constexpr int CNMF_KC_LIMIT_DEFAULT = 1024;
-static int kc_limit(const cnmf_ctx* ctx)   // (CNMF_KC_LIMIT: A/B knob, up to 2048 = the 64 tile bits of the live mask; read from
-{                                          //  the context's snapshot of the environment like every per-call switch)
-    const char* s = ctx_getenv(ctx, "CNMF_KC_LIMIT");
-    const int v = s ? atoi(s) : CNMF_KC_LIMIT_DEFAULT;
-    return std::max(256, std::min(2048, (v / 256) * 256));
-}
-#define CNMF_KC_LIMIT kc_limit(ctx)
+// kc_max: 0 = auto, else an upper bound (multiple of 32; above 256 in steps of 256, up to CNMF_KC_LIMIT, default 1024).
 static int pick_kc(const cnmf_ctx* ctx, int64_t total_k, int max_k, int kc_max, bool wide_ok)
 {
-    bool forced = false;
-    if (const char* s = ctx_getenv(ctx, "CNMF_KC")) { int v = atoi(s); if (v >= 32) { kc_max = v; forced = true; } }
+    if (ctx->knobs.kc >= 32) kc_max = ctx->knobs.kc;
     const bool autosize = kc_max <= 0;
     if (autosize) kc_max = 256;
-    kc_max = std::max(32, std::min(CNMF_KC_LIMIT, (kc_max / 32) * 32));
+    kc_max = std::max(32, std::min(ctx->knobs.kc_limit, (kc_max / 32) * 32));
     if (kc_max > 256) kc_max = wide_ok ? (kc_max / 256) * 256 : 256;
     int kc = 32;
     while (kc < std::min(kc_max, 256) && kc < total_k) kc *= 2;
@@ -220,10 +203,9 @@ static int pick_kc(const cnmf_ctx* ctx, int64_t total_k, int max_k, int kc_max, 
         // as wide as the job, up to the limit: a job that fits entirely starts every restart at once and the batch
         // narrows behind the ones that finish (compact()); measured and simulated on the iteration counts of the
         // north-star job (tools/sim_schedule.py): 113 restarts run 187 / 172 / 145 restarts/s at 1024 / 512 / 256 columns
-        if (autosize && !ctx_getenv(ctx, "CNMF_NO_WIDE")) kc = (int)std::min<int64_t>(CNMF_KC_LIMIT, round_up(total_k, 256));
+        if (autosize) kc = (int)std::min<int64_t>(ctx->knobs.kc_limit, round_up(total_k, 256));
         else if (!autosize && kc_max > 256) kc = (int)std::min<int64_t>(kc_max, round_up(total_k, 256));
     }
-    (void)forced;
     if (kc < max_k) kc = round_up(max_k, 32);
     return kc;
 }
@@ -246,7 +228,8 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
 {
     if (!ctx) { SET_ERR(ctx, "ctx is NULL"); return CNMF_EINVAL; }
     if (int rcd_ = ensure_dense(ctx)) return rcd_;
-    refresh_gemm3_mode(ctx);
+    KnobScope knob_scope(ctx);
+    const CdKnobs& kn = ctx->knobs;
     int rc = validate_params(ctx, prm);
     if (rc) return rc;
     if (n < 0 || (n > 0 && !kk)) { SET_ERR(ctx, "bad restart list"); return CNMF_EINVAL; }
@@ -269,17 +252,16 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
         woff[r + 1] = woff[r] + (size_t)kk[r] * N;
     }
     // (wide batches need the whole-tile matrix-pipe kernels and a matrix large enough to be worth them)
-    const bool wide_can = gemm3_mode() != 0 && gemm3_enabled(ctx, 512);
+    const bool wide_can = kn.gemm3 != 0 && gemm3_enabled(ctx, 512);
     // round 6: a SMALL matrix (BASELINE config 2: 2 700 x 2 000) is launch-latency-bound -- an iteration costs its six
     // launches whatever the width -- so a job of >= 512 columns also runs wide there (C2: 1 000 columns in one batch instead
     // of four 256-column rounds, 17 -> 8 ms per job); CNMF_WIDE_SMALL=0: the round-5 rule (A/B)
-    const char* ws_ = ctx_getenv(ctx, "CNMF_WIDE_SMALL");
-    const bool wide_small = total_k >= 512 && !(ws_ && atoi(ws_) == 0);
+    const bool wide_small = total_k >= 512 && kn.wide_small;
     const bool wide_auto = wide_can && ((int64_t)ctx->N_pad * ctx->G_pad >= (1ll << 24) || wide_small);
-    int KC = pick_kc(ctx, total_k, max_k, prm->kc_max, (prm->kc_max > 256 || ctx_getenv(ctx, "CNMF_KC")) ? wide_can : wide_auto);
+    int KC = pick_kc(ctx, total_k, max_k, prm->kc_max, (prm->kc_max > 256 || kn.kc_set) ? wide_can : wide_auto);
     // 65..128 columns of a count-structured matrix: the 256-column integer-plane kernels (half empty) are still
     // faster than 128 columns on the f32 pipe
-    if (KC == 128 && prm->kc_max <= 0 && !ctx_getenv(ctx, "CNMF_KC") && gemm3_mode() >= 3 && gemm3_enabled(ctx, 256) &&
+    if (KC == 128 && prm->kc_max <= 0 && !kn.kc_set && kn.gemm3 >= 3 && gemm3_enabled(ctx, 256) &&
         (int64_t)ctx->N_pad * ctx->G_pad >= (1ll << 24)) {
         rc = ensure_counts(ctx);
         if (rc) return rc;
@@ -290,21 +272,19 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
     if (rc) return rc;
     rc = ensure_stage(ctx, (size_t)N * KMAX, (size_t)G * KMAX);
     if (rc) return rc;
-    int nsplit = std::min(pick_nsplit(ctx, KC), ctx->nsplit_alloc);
     bool use3 = gemm3_enabled(ctx, KC);            // split-operand bf16 MFMA path (whole 256-column tiles only)
     bool usec = false;                             // ... with X as one integer plane (count-structured data)
-    if (use3 && gemm3_mode() >= 3) {
+    if (use3 && kn.gemm3 >= 3) {
         rc = ensure_counts(ctx);
         if (rc) return rc;
         usec = ctx->count_state == 1;
     }
     // any OTHER matrix in the default mode: X itself as two f16 planes with a per-row exponent, 4 MFMAs per product
-    // (gemm_mode 5; CNMF_G2G=0 keeps the 3 x 3 bf16 planes of rounds 1-2, 6 MFMAs)
-    static const bool g2g_off = getenv("CNMF_G2G") && atoi(getenv("CNMF_G2G")) == 0;
-    bool use2g = use3 && !usec && gemm3_mode() >= 4 && !g2g_off && ctx->G_pad % G3C_JW == 0 && ctx->N_pad % G3C_JW == 0;
+    // (gemm_mode 5; CNMF_GEMM3=1|2 keep the 3 x 3 bf16 planes of rounds 1-2, 6 MFMAs)
+    bool use2g = use3 && !usec && kn.gemm3 >= 4 && ctx->G_pad % G3C_JW == 0 && ctx->N_pad % G3C_JW == 0;
     if (use2g) { rc = ensure_x2planes(ctx); if (rc) return rc; }
     bool use2h = (usec && ctx->count_fmt == 4) || use2g;      // ... on the f16 pipe: two f16 factor planes
-    const int gemm_mode_used = !use3 ? 0 : (use2g ? 5 : (usec ? (use2h ? 4 : 3) : std::min(gemm3_mode(), 2)));
+    const int gemm_mode_used = !use3 ? 0 : (use2g ? 5 : (usec ? (use2h ? 4 : 3) : std::min(kn.gemm3, 2)));
     const int KbA = ctx->G_pad / 16, KbB = ctx->N_pad / 16;
     // the X-side operands of the f16 kernels: the integer count plane(s), or the two planes of a general matrix
     const unsigned char *xA = use2g ? ctx->X2h : ctx->C1, *xAhi = use2g ? ctx->X2m : ctx->C1h;
@@ -314,19 +294,15 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
     const double* dsc = use2g ? nullptr : ctx->d_scale;                                      // per-gene scale of the count path
     const int nsubA = use2h ? gemm2h_nsub(xAhi != nullptr, KbA) : 1, nsubB = use2h ? gemm2h_nsub(xBhi != nullptr, KbB) : 1;
     // W planes written by the W sweep itself (kernels_sweep.hip.h, PLN) instead of a separate pass over W; ranks above
-    // 64 (sweep_big_kernel) keep the separate split for the whole call.  CNMF_FUSE_W=0: the round-2 scheme (A/B).
-    static const bool fuse_off = getenv("CNMF_FUSE_W") && atoi(getenv("CNMF_FUSE_W")) == 0;
-    const bool fuseW = use2h && !fuse_off && max_k <= KSMALL && ctx->shiftW != nullptr;
+    // 64 (sweep_big_kernel) keep the separate split for the whole call.
+    const bool fuseW = use2h && max_k <= KSMALL && ctx->shiftW != nullptr;
     int shgen = 0;                                        // generation of the exponents the NEXT W sweep uses
     int* const shW[2] = {ctx->shiftW, ctx->shiftW ? ctx->shiftW + ctx->kc_alloc : nullptr};
     if (fuseW) HIP_TRY(ctx, hipMemsetAsync(ctx->shiftW, 0, (size_t)3 * ctx->kc_alloc * sizeof(int), ctx->stream));
     if (use3 && !usec && !use2g) { rc = ensure_planes(ctx); if (rc) return rc; }
     const int jwA = (usec || use2g) ? G3C_JW : G3_JW;         // width of a pass-A / pass-B tile
-    int nsplit3 = use3 ? pick_nsplit3(ctx, KC, jwA) : 1;
-    const int nsplit3_first = nsplit3;             // (reported: the tail narrows the batch and re-plans)
     const int fin_y = (max_k * max_k + 255) / 256;       // finalize blocks per slot
-    const int lag_env = ctx_getenv(ctx, "CNMF_LAG") ? atoi(ctx_getenv(ctx, "CNMF_LAG")) : 0;
-    const int lag = std::max(1, std::min(RING - 2, prm->lag > 0 ? prm->lag : (lag_env > 0 ? lag_env : 2)));
+    const int lag = std::max(1, std::min(RING - 2, prm->lag > 0 ? prm->lag : (kn.lag > 0 ? kn.lag : 2)));
     hipStream_t st = ctx->stream;
 
     // device result buffers
@@ -392,9 +368,7 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
     //     rank is sampled within the first fill of the packed columns;
     //   * as restarts retire, the mean iteration count per rank is learned and the pending queue is re-sorted by it,
     //     descending (LPT) -- the short restarts are kept for the end, where they fill the columns the long ones free.
-    // CNMF_QUEUE=rank restores the plain descending-rank order (A/B).
     std::vector<int> order(n);
-    const bool queue_by_rank = ctx_getenv(ctx, "CNMF_QUEUE") && !strcmp(ctx_getenv(ctx, "CNMF_QUEUE"), "rank");
     // round 4: the caller's iteration hints (cnmf_set_iteration_hints: mean iterations per rank, e.g. what an earlier call
     // on this matrix learned -- cnmf_get_iteration_means) order the queue from the start: a second factorize with more
     // restarts, a resumed ledger do not have to re-learn that k = 13 runs 1000 iterations and k = 9 runs 37.  Explicit only:
@@ -402,10 +376,7 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
     // (tests/test_gpu_determinism.py); without hints a call's result depends on its own arguments alone.
     const bool have_prior = ctx->iter_hint.size() == (size_t)KMAX + 1;
     auto prior_of = [&](int k) { return have_prior ? ctx->iter_hint[k] : 0.0; };
-    if (queue_by_rank) {
-        for (int r = 0; r < n; ++r) order[r] = r;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return kk[a] > kk[b]; });
-    } else {
+    {
         std::vector<std::vector<int>> by_k(KMAX + 1);
         for (int r = 0; r < n; ++r) by_k[kk[r]].push_back(r);
         size_t pos = 0;
@@ -419,10 +390,6 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
             });
     }
     std::vector<int64_t> k_iters(KMAX + 1, 0), k_done(KMAX + 1, 0);     // learned per rank: sum of n_iter, restarts retired
-    std::vector<double> rank_expect(KMAX + 1, 1e30);                   // expected iterations per rank (1e30: nothing known yet)
-    static const bool holes_fill = !(getenv("CNMF_HOLES") && !strcmp(getenv("CNMF_HOLES"), "wait"));
-    if (have_prior)
-        for (int k = 1; k <= KMAX; ++k) if (prior_of(k) > 0) rank_expect[k] = prior_of(k);
     int last_resort_done = 0;
     size_t next = 0;                 // first queue position that may still be pending
     int n_pending = n;
@@ -433,13 +400,21 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
     int n_active = 0;
     int64_t it = 0;          // batch iterations enqueued so far
     int snap_nslots[RING] = {0};
-    const bool no_defrag = ctx_getenv(ctx, "CNMF_NO_DEFRAG") != nullptr;
-    const bool no_psum = ctx_getenv(ctx, "CNMF_NO_PSUM") != nullptr;          // (A/B knob: keep the separate split-K reduce)
+    auto live_columns = [&]() { int c = 0; for (int s = 0; s < nslots; ++s) if (hs[s].state) c += hs[s].k; return c; };
+    // bit t: the 32 packed columns 32 t .. 32 t + 31 hold a live restart; *fullest: most live tiles in one 256-column group
+    auto live_tiles = [&](int* fullest) {
+        unsigned long long m = 0ull;
+        for (int s = 0; s < nslots; ++s)
+            if (hs[s].state)
+                for (int t = hs[s].off / 32; t <= (hs[s].off + hs[s].k - 1) / 32 && t < 64; ++t) m |= 1ull << t;
+        *fullest = 0;
+        for (int g = 0; g < KC / 256; ++g) *fullest = std::max(*fullest, __builtin_popcountll((m >> (8 * g)) & 0xffull));
+        return m;
+    };
     // partial-tile passes in the tail (the f16 kernels skip the MFMAs of 32-column tiles without a live restart, the live
     // restarts dealt evenly to the component groups): built and measured in round 3 -- 183.0 vs 182.2 restarts/s on the
     // 113-restart shard, 216.5 vs 215.7 on the full job: within noise (the skipping variant is ~4 % slower with all tiles
-    // live, and a tail pass is bound by streaming the count plane as much as by its MFMAs).  Opt-in: CNMF_PART=1.
-    const bool no_part = ctx_getenv(ctx, "CNMF_PART") == nullptr || ctx_getenv(ctx, "CNMF_NO_PART") != nullptr;
+    // live, and a tail pass is bound by streaming the count plane as much as by its MFMAs).  Opt-in: CNMF_PART=1 (kn.part).
     int64_t last_tail_repack = -1000;
     int64_t last_defrag = -8, n_defrag = 0;
     bool h3_valid = false;           // H3 holds the planes of the current H (split-operand modes)
@@ -450,28 +425,42 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
     HIP_TRY(ctx, hipEventRecord(ev_begin, st));
     // HIP events around the two GEMM passes of every `time_stride`-th iteration (an event record costs
     // ~6 us of queue time: bracketing every launch would take 4 % off the throughput it measures)
-    const int time_stride = !stats ? 0 : (prm->profile > 0 ? prm->profile : (ctx_getenv(ctx, "CNMF_TIME_GEMM") ? 1 : 0));
+    const int time_stride = (stats && prm->profile > 0) ? prm->profile : 0;
     std::vector<hipEvent_t> gev;   // (a0,a1,b0,b1) per iteration when timing is requested
 
-    const int chunksW = sweep_chunks(N), partsW = sweep_parts(N);
-    const int chunksH = sweep_chunks(G), partsH = sweep_parts(G);
+    const int chunksW = sweep_chunks(ctx, N), partsW = sweep_parts(ctx, N);
+    const int chunksH = sweep_chunks(ctx, G), partsH = sweep_parts(ctx, G);
     const float l1W = (float)prm->l1_reg_W, l2W = (float)prm->l2_reg_W;
     const float l1H = (float)prm->l1_reg_H, l2H = (float)prm->l2_reg_H;
-    const int gvarA = ctx_getenv(ctx, "CNMF_GEMM_A") ? atoi(ctx_getenv(ctx, "CNMF_GEMM_A")) : 0;
-    const int gvarB = ctx_getenv(ctx, "CNMF_GEMM_B") ? atoi(ctx_getenv(ctx, "CNMF_GEMM_B")) : 0;
     int64_t restart_iters = 0, column_iters = 0, restart_col_iters = 0;
-    const bool dbg = ctx_getenv(ctx, "CNMF_DEBUG") != nullptr;
+    const bool dbg = kn.debug;
     int64_t dbg_it[65] = {0}, dbg_live[65] = {0};          // by KC / 32 (up to 2048 packed columns)
-    const int wg_slots = ctx_getenv(ctx, "CNMF_SK_WGS") ? atoi(ctx_getenv(ctx, "CNMF_SK_WGS")) : 2 * 256;                    // T-layout pass A: 2 workgroups per CU (73.7 KB LDS each)
-    StreamK sk = plan_streamk(KC, ctx->N_pad, ctx->G_pad, wg_slots);
-    if (sk.on) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_split, sk.split.data(), sk.split.size(), hipMemcpyHostToDevice, st));
-    int nsplitA = (sk.on && gvarA == 0) ? 1 : std::min(pick_nsplit_A(ctx, KC), ctx->nsplitA_alloc);
+    // The plan of the two GEMM passes at the current width KC, on the pipe `use3` names: K splits of pass B (nsplit3 on
+    // the split-operand kernels, nsplit on the f32 pipe), and pass A either as a stream-K plan (sk3 / sk, its cut flags
+    // uploaded to d_split) or, on few tiles, as nsplitA K splits + reduce.  cap / capA: the partial planes the product
+    // buffers hold at this width.  Made before the loop, and again whenever compact() narrows the batch.
+    int nsplit = 1, nsplit3 = 1, nsplitA = 1;
+    StreamK sk;
     StreamK3 sk3;
-    if (use3) {
-        sk3 = plan_streamk3(KC, ctx->N_pad, ctx->G_pad, gemm3_wg_slots(), jwA, nsubA);
-        if (sk3.on) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_split, sk3.flags.data(), sk3.flags.size(), hipMemcpyHostToDevice, st));
-        else nsplitA = std::min(pick_nsplit_A3(ctx, KC, jwA), ctx->nsplitA_alloc);   // few tiles: K split + reduce
-    }
+    auto plan_passes = [&](int cap, int capA) -> int {
+        const std::vector<unsigned char>* flags = nullptr;
+        if (use3) {
+            nsplit3 = std::max(1, std::min(pick_nsplit3(ctx, KC, jwA), cap));
+            sk3 = plan_streamk3(KC, ctx->N_pad, ctx->G_pad, gemm3_wg_slots(ctx->knobs), jwA, nsubA);
+            if (sk3.on) flags = &sk3.flags;
+            else nsplitA = std::max(1, std::min(pick_nsplit_A3(ctx, KC, jwA), capA));
+        } else {
+            nsplit = std::max(1, std::min(pick_nsplit(ctx, KC), cap));
+            sk = plan_streamk(KC, ctx->N_pad, ctx->G_pad, 2 * 256);       // T-layout pass A: 2 workgroups per CU (73.7 KB LDS each)
+            if (sk.on) { flags = &sk.split; nsplitA = 1; }
+            else nsplitA = std::max(1, std::min(pick_nsplit_A(ctx, KC), capA));
+        }
+        // (the flags of the old plan may still be read by an in-flight sweep: same stream -> ordered)
+        if (flags) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_split, flags->data(), flags->size(), hipMemcpyHostToDevice, st));
+        return CNMF_OK;
+    };
+    if ((rc = plan_passes(ctx->nsplit_alloc, ctx->nsplitA_alloc))) return rc;
+    const int nsplit3_first = nsplit3;             // (reported: the tail narrows the batch and re-plans)
     int n_done = 0;
     hipEvent_t ev_tail = nullptr;    // recorded when the queue runs dry
     int64_t tail_its = 0, tail_live = 0;
@@ -579,30 +568,16 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
         // pending restarts are sorted by descending rank; a hole too small for the head of the
         // queue is filled with the largest pending rank that fits (restarts are independent, so
         // the order they run in is free) -> the packed columns stay full in the main phase
-        // round-4 experiment (CNMF_HOLES=wait, not the default).  Filling every freed slot at once with the largest pending
-        // rank that fits keeps the columns full but freezes every rank's share of them at what the first fill gave it: free
-        // columns never accumulate, so a rank-13 restart only ever starts where a rank-13 (or larger) restart ended, and the
-        // longest-expected-first order decides nothing across ranks (debug trace: 13 restarts of rank 13 in flight from start
-        // to end, 31 still running when the queue is dry).  "wait": once the HEAD of the queue does not fit, a later entry may
-        // take a hole only if its rank is known to be short against the head's expectation; otherwise the hole waits until the
-        // free columns add up to the head's rank and a re-packing makes room.  Measured (same box, two alternations): tail
-        // 9.7 -> 7.9 % of the call, but 218 instead of 115 re-packings and idle holes: 221.0 / 220.5 vs 222.4 / 221.7
-        // restarts/s -- not adopted.
+        // (letting a hole wait for the head of the queue instead was measured and not adopted: DESIGN.md section 8)
         for (int attempt = 0; attempt < 2; ++attempt) {
         int failed_k = 1 << 30;                       // smallest rank that did not fit in this pass
-        int head_k = 0; double head_expect = 0.0;     // the first pending entry that did not fit, and what it is expected to run
         for (size_t pi = next; pi < order.size() && n_pending > 0; ++pi) {
             const int r = order[pi];
             if (r < 0) { if (pi == next) ++next; continue; }      // already taken
             const int k = kk[r];
             if (k >= failed_k) continue;
-            if (head_k && !holes_fill && !(rank_expect[k] < 0.3 * head_expect)) continue;     // (unknown = 1e30: not short)
             const int off = cols.alloc(k);
-            if (off < 0) {
-                failed_k = k;
-                if (!head_k) { head_k = k; head_expect = rank_expect[k]; }
-                continue;
-            }
+            if (off < 0) { failed_k = k; continue; }
             order[pi] = -1; --n_pending;
             if (pi == next) ++next;
             int s = 0;
@@ -641,10 +616,8 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
         // Defragmentation: a pending restart did not fit although enough columns are free in total (holes
         // left by retired slots of other ranks).  Repacking costs about one iteration and buys a restart
         // that runs for hundreds -- at most once every 8 iterations.
-        if (attempt == 0 && n_pending > 0 && failed_k < (1 << 30) && !no_defrag && it - last_defrag >= 8) {
-            int live_cols = 0;
-            for (int s2 = 0; s2 < nslots; ++s2) if (hs[s2].state) live_cols += hs[s2].k;
-            if (KC - live_cols >= (holes_fill ? failed_k : head_k)) {
+        if (attempt == 0 && n_pending > 0 && failed_k < (1 << 30) && it - last_defrag >= 8) {
+            if (KC - live_columns() >= failed_k) {
                 int rcd = repack_left(KC);
                 if (rcd) return rcd;
                 cols = ColAlloc(KC);
@@ -671,15 +644,11 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
             if (hs[s2].state) tiers |= hs[s2].k <= 16 ? 1 : (hs[s2].k <= 32 ? 2 : (hs[s2].k <= KSMALL ? 4 : 8));
         // the tail (nothing left to refill with): the f16 kernels skip the 32-column tiles without a live restart
         unsigned long long livemask = ~0ull;
-        if (use2h && n_pending == 0 && !no_part) {
-            livemask = 0ull;
-            for (int s2 = 0; s2 < nslots; ++s2)
-                if (hs[s2].state)
-                    for (int t = hs[s2].off / 32; t <= (hs[s2].off + hs[s2].k - 1) / 32 && t < 64; ++t) livemask |= 1ull << t;
+        if (use2h && n_pending == 0 && kn.part) {
             // the skipping variant of the kernels is ~4 % slower with everything live, and a pass lasts as long as its
             // fullest component group: use it only when EVERY group has at least two dead tiles
             int fullest = 0;
-            for (int g = 0; g < KC / 256; ++g) fullest = std::max(fullest, __builtin_popcountll((livemask >> (8 * g)) & 0xffull));
+            livemask = live_tiles(&fullest);
             if (fullest > 6) livemask = ~0ull;
         }
         const bool time_gemm = time_stride > 0 && it % time_stride == 0;
@@ -721,12 +690,12 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
                 HIP_TRY(ctx, launch_gemm3(st, ctx->H3, ctx->X3, ctx->G_pad / 16, ctx->XHt, ctx->N_pad,
                                           (long long)KC * ctx->N_pad, KC, ctx->N_pad, nsplitA));
             }
-        } else if (sk.on && gvarA == 0) {
+        } else if (sk.on) {
             HIP_TRY(ctx, launch_streamk_passA(st, sk, ctx->H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->XHt,
                                               ctx->XHt1, ctx->N_pad, ctx->N_pad));
             spA = SplitInfo{ctx->XHt1, ctx->d_split, 128, sk.mw, sk.MG};
         } else
-            HIP_TRY(ctx, launch_gemm<false>(st, gvarA, ctx->H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->XHt,
+            HIP_TRY(ctx, launch_gemm<false>(st, 0, ctx->H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->XHt,
                                             ctx->N_pad, (long long)KC * ctx->N_pad, KC, ctx->G_pad, ctx->N_pad, nsplitA));
         if (time_gemm) hipEventRecord(gev[gev.size() - 3], st);
         if (!spA.plane1)
@@ -770,12 +739,12 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
             HIP_TRY(ctx, launch_gemm3(st, ctx->Wt3, ctx->Xt3, ctx->N_pad / 16, ctx->XtW, ctx->G_pad,
                                       (long long)KC * ctx->G_pad, KC, ctx->G_pad, nsplit3));
         else
-            HIP_TRY(ctx, launch_gemm<true>(st, gvarB, ctx->Wt, ctx->N_pad, ctx->X, ctx->G_pad, ctx->XtW,
+            HIP_TRY(ctx, launch_gemm<true>(st, 0, ctx->Wt, ctx->N_pad, ctx->X, ctx->G_pad, ctx->XtW,
                                            ctx->G_pad, (long long)KC * ctx->G_pad, KC, ctx->N_pad,
                                            ctx->G_pad, nsplit));
         if (time_gemm) hipEventRecord(gev[gev.size() - 1], st);
         // H half-step.  On the f16 path the split-K partials are summed (and scaled by d) inside the sweep itself.
-        if (use2h && !no_psum && !(tiers & 8)) {      // (ranks above 64 take the separately reduced product)
+        if (use2h && !kn.no_psum && !(tiers & 8)) {      // (ranks above 64 take the separately reduced product)
             HIP_TRY(ctx, launch_sweep(st, nslots, ctx->H, ctx->G_pad, G, ctx->XtW, ctx->gramW,
                                       ctx->d_slots, l1H, ctx->gram_part, ctx->viol_part, chunksH, partsH, 1, max_k, tiers,
                                       psum_info(nsB, (long long)KC * ctx->G_pad, dsc), ctx->rmaxH, dsc, true));
@@ -812,16 +781,8 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
         HIP_TRY(ctx, hipGetLastError());
         snap_nslots[it % RING] = nslots;
         column_iters += KC;
-        if (n_pending == 0) {
-            int live = 0;
-            for (int s2 = 0; s2 < nslots; ++s2) if (hs[s2].state) live += hs[s2].k;
-            ++tail_its; tail_live += live;
-        }
-        if (dbg) {
-            int live = 0;
-            for (int s2 = 0; s2 < nslots; ++s2) if (hs[s2].state) live += hs[s2].k;
-            dbg_it[KC / 32] += 1; dbg_live[KC / 32] += live;
-        }
+        if (n_pending == 0) { ++tail_its; tail_live += live_columns(); }
+        if (dbg) { dbg_it[KC / 32] += 1; dbg_live[KC / 32] += live_columns(); }
         ++it;
         return CNMF_OK;
     };
@@ -840,7 +801,7 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
             }
         // longest-expected-first: re-sort what is still pending by the mean iteration count learned per rank (ranks
         // without a finished restart yet count as longest: they are sampled first), every 8 retirements
-        if (!queue_by_rank && n_pending > 1 && n_done - last_resort_done >= 8) {
+        if (n_pending > 1 && n_done - last_resort_done >= 8) {
             last_resort_done = n_done;
             std::vector<int> rest;
             rest.reserve(n_pending);
@@ -858,10 +819,6 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
                 if (prior_of(k) > 0) { num += 4.0 * prior_of(k); den += 4.0; }
                 return den > 0 ? num / den : 1e30;
             };
-            for (int k = 1; k <= KMAX; ++k) {
-                const double den = (double)k_done[k] + fly_n[k] + (prior_of(k) > 0 ? 4.0 : 0.0);
-                if (den > 0) rank_expect[k] = ((double)k_iters[k] + fly_age[k] + 4.0 * prior_of(k)) / den;
-            }
             if (dbg && n_done % 64 < 8) {
                 fprintf(stderr, "[cnmf] it %lld done %d pending %d expected per rank:", (long long)it, n_done, n_pending);
                 for (int k = 1; k <= KMAX; ++k)
@@ -883,12 +840,9 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
     // ---- step 4: tail compaction -- nothing left to refill with and at most half of the packed
     // columns still iterate: repack the live slots into a narrower batch so the two GEMM passes
     // shrink with the work (their cost is proportional to KC).
-    const bool no_compact = ctx_getenv(ctx, "CNMF_NO_COMPACT") != nullptr;
-    const bool f32_tail = ctx_getenv(ctx, "CNMF_F32_TAIL") != nullptr;      // (A/B knob: compact the count path at 128 / 64 too)
     auto compact = [&]() -> int {
-        if (n_pending == 0 && n_active > 0 && KC > 32 && !no_compact) {
-            int live_cols = 0;
-            for (int s = 0; s < nslots; ++s) if (hs[s].state) live_cols += hs[s].k;
+        if (n_pending == 0 && n_active > 0 && KC > 32) {
+            const int live_cols = live_columns();
             int KCn = 32;
             while (KCn < live_cols && KCn < 256) KCn *= 2;
             if (live_cols > 256) KCn = round_up(live_cols, 256);
@@ -898,17 +852,13 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
             // columns on the f32 pipe (417 / 2 vs 157 TF of roof per live column), not 64.
             // A WIDE batch (512+) narrows in steps of 256 columns and stays on the same kernels.
             bool stay3 = false;
-            if (use3 && !f32_tail && KCn > (usec ? 32 : 64)) { KCn = round_up(std::max(live_cols, 1), 256); stay3 = true; }
-            if (KCn == KC && use2h && !no_part && it - last_tail_repack >= 16) {
+            if (use3 && KCn > (usec ? 32 : 64)) { KCn = round_up(std::max(live_cols, 1), 256); stay3 = true; }
+            if (KCn == KC && use2h && kn.part && it - last_tail_repack >= 16) {
                 // same width, but the live restarts lie scattered: pack them to the left so that whole 32-column
                 // tiles fall dead (the GEMM passes skip those) -- when that frees at least 2 tiles and an eighth of them
-                unsigned long long m = 0ull;
-                for (int s = 0; s < nslots; ++s)
-                    if (hs[s].state)
-                        for (int t = hs[s].off / 32; t <= (hs[s].off + hs[s].k - 1) / 32 && t < 64; ++t) m |= 1ull << t;
                 const int ng = KC / 256;
                 int fullest = 0;
-                for (int g = 0; g < ng; ++g) fullest = std::max(fullest, __builtin_popcountll((m >> (8 * g)) & 0xffull));
+                live_tiles(&fullest);
                 const int ideal = ((live_cols + 31) / 32 + ng - 1) / ng;       // tiles per group if dealt evenly
                 if (ideal <= 6 && fullest >= ideal + 2) {
                     int rcp = repack_left(KC, true);
@@ -918,28 +868,14 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
             }
             if (KCn < KC) {
                 last_tail_repack = it;
-                int rcp = repack_left(KCn, stay3 && use2h && !no_part);
+                int rcp = repack_left(KCn, stay3 && use2h && kn.part);
                 if (rcp) return rcp;
                 KC = KCn;
                 cols = ColAlloc(KC);
                 for (int s = 0; s < nslots; ++s) if (hs[s].state) cols.alloc(hs[s].k);
-                const int cap = (ctx->nsplit_alloc * KC0) / KC;
-                if (stay3) {
-                    nsplit3 = std::max(1, std::min(pick_nsplit3(ctx, KC, jwA), cap));
-                    sk3 = plan_streamk3(KC, ctx->N_pad, ctx->G_pad, gemm3_wg_slots(), jwA, nsubA);
-                    if (sk3.on) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_split, sk3.flags.data(), sk3.flags.size(), hipMemcpyHostToDevice, st));
-                    else nsplitA = std::max(1, std::min(pick_nsplit_A3(ctx, KC, jwA), (ctx->nsplitA_alloc * KC0) / KC));
-                } else {
-                nsplit = std::max(1, std::min(pick_nsplit(ctx, KC), cap));
-                use3 = usec = use2h = use2g = false; // fewer than 256 packed columns: the f32 pipe takes over
-                sk = plan_streamk(KC, ctx->N_pad, ctx->G_pad, wg_slots);
-                nsplitA = (sk.on && gvarA == 0) ? 1
-                        : std::max(1, std::min(pick_nsplit_A(ctx, KC), (ctx->nsplitA_alloc * KC0) / KC));
-                if (sk.on) {
-                    // the flags of the old plan may still be read by an in-flight sweep: same stream -> ordered
-                    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_split, sk.split.data(), sk.split.size(), hipMemcpyHostToDevice, st));
-                }
-                }
+                if (!stay3) use3 = usec = use2h = use2g = false;     // fewer than 256 packed columns: the f32 pipe takes over
+                // (the buffers were sized for KC0 columns: a narrower batch may keep more partial planes in them)
+                if ((rcp = plan_passes((ctx->nsplit_alloc * KC0) / KC, (ctx->nsplitA_alloc * KC0) / KC))) return rcp;
             }
         }
         return CNMF_OK;
@@ -1045,6 +981,7 @@ extern "C" int cnmf_nnls(cnmf_ctx* ctx, int k, const float* Hin, const cnmf_cd_p
                          float* W_out, int32_t* n_iter_out, double* viol_out)
 {
     if (!ctx) { SET_ERR(ctx, "ctx is NULL"); return CNMF_EINVAL; }
+    KnobScope knob_scope(ctx);
     if (int rcd_ = ensure_dense(ctx)) return rcd_;
     int rc = validate_params(ctx, prm);
     if (rc) return rc;
@@ -1074,7 +1011,7 @@ extern "C" int cnmf_nnls(cnmf_ctx* ctx, int k, const float* Hin, const cnmf_cd_p
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_slot_list, ctx->h_slot_list, sizeof(int), hipMemcpyHostToDevice, st));
     gram_rows_kernel<<<1, 256, 0, st>>>(ctx->H, ctx->G_pad, G, ctx->d_slots, ctx->d_slot_list, ctx->gramH, (float)prm->l2_reg_W);
     HIP_TRY(ctx, launch_gemm<false>(st, 0, ctx->H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->XHt, ctx->N_pad, 0, KC, ctx->G_pad, ctx->N_pad, 1));
-    const int chunksW = sweep_chunks(N), partsW = sweep_parts(N);
+    const int chunksW = sweep_chunks(ctx, N), partsW = sweep_parts(ctx, N);
     DevPool pool;
     EventPool events;
     hipEvent_t ev = events.get(hipEventDisableTiming);

@@ -6,6 +6,7 @@
 extern "C" int cnmf_x_matmul(cnmf_ctx* ctx, int trans, const float* Q, int ncols, float* out)
 {
     if (!ctx || !Q || !out) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
+    KnobScope knob_scope(ctx);
     if (int rcd_ = ensure_dense(ctx)) return rcd_;
     if (ncols < 1 || ncols > 256 || (trans != 0 && trans != 1)) { SET_ERR(ctx, "bad ncols/trans"); return CNMF_EINVAL; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -48,6 +49,7 @@ extern "C" int cnmf_debug_gemm(cnmf_ctx* ctx, int mode, int variant, const float
     if (KC % 32 || K % 32 || J % 32 || nsplit < 1 || (mode != 0 && mode != 1)) {
         SET_ERR(ctx, "debug_gemm needs KC,K,J multiples of 32"); return CNMF_EINVAL;
     }
+    KnobScope knob_scope(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const int Jp = round_up(J, 128);           // J padded like N_pad so any tile shape is addressable
@@ -97,7 +99,7 @@ extern "C" int cnmf_debug_gemm3(cnmf_ctx* ctx, const float* A, const float* B, f
 {
     if (!ctx || !A || !B || !C) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     if (KC % 256 || K % 16 || J < 1 || nsplit < 1) { SET_ERR(ctx, "debug_gemm3 needs KC %% 256 == 0, K %% 16 == 0"); return CNMF_EINVAL; }
-    refresh_gemm3_mode(ctx);
+    KnobScope knob_scope(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const int Jp = round_up(J, gemm3_jw()), Kb = K / 16;
@@ -264,11 +266,9 @@ extern "C" int cnmf_debug_gemm2h(cnmf_ctx* ctx, const float* A, const float* Bn,
         if (i == 1) hipEventRecord(e0, st);
         hipError_t e;
         if (has_hi) e = launch_gemm2h_t<1, true>(st, dA2, dB1, dBh, dFl, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
-        else if (ns == 2 && var == 1) e = launch_gemm2h_t<2, false, 1>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
         else if (ns == 2 && var == 2) e = launch_gemm2h_t<2, false, 2>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
         else if (ns == 2 && var == 3) e = launch_gemm2h_t<2, false, 3>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
         else if (ns == 2 && var == 4) e = launch_gemm2h_t<2, false, 4>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
-        else if (ns == 2 && var == 5) e = launch_gemm2h_t<2, false, 5>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
         else if (ns == 2 && var == 6) e = launch_gemm2h_t<2, false, 6>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
         else if (ns == 2 && var == 7) e = launch_gemm2h_t<2, false, 7>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
         else if (ns == 2) e = launch_gemm2h_t<2, false, 0>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);

@@ -25,10 +25,19 @@ static hipError_t launch_gemm_t(hipStream_t st, const float* A, int lda, const f
     return hipGetLastError();
 }
 
-// A/B knobs of the launch planning, read ONCE per process (they are not part of the per-context snapshot: cnmf_reload_env
-// does not refresh them -- documented as process-lifetime in include/cnmf_hip.h)
-static bool no_streamk_env() { static const bool v = getenv("CNMF_NO_STREAMK") != nullptr; return v; }
-static const bool s_mtw2 = getenv("CNMF_S_MTW2") != nullptr;
+// The launchers and planners below carry no context: they read the switches (CdKnobs, runtime.hip.h) of the context whose
+// call is running on this thread.  Every entry point that reaches one of them holds a KnobScope for the length of the call;
+// between calls the pointer names the built-in defaults, never a context (which may be destroyed from any thread).  Code
+// that has the context in hand reads ctx->knobs and does not depend on this.
+static const CdKnobs k_default_knobs;
+static thread_local const CdKnobs* g_knobs = &k_default_knobs;
+struct KnobScope {
+    const CdKnobs* prev;
+    explicit KnobScope(const cnmf_ctx* ctx) : prev(g_knobs) { g_knobs = &ctx->knobs; }
+    ~KnobScope() { g_knobs = prev; }
+    KnobScope(const KnobScope&) = delete;
+    KnobScope& operator=(const KnobScope&) = delete;
+};
 
 template <bool NN>
 static hipError_t launch_gemm(hipStream_t st, int variant, const float* A, int lda, const float* B,
@@ -42,7 +51,7 @@ static hipError_t launch_gemm(hipStream_t st, int variant, const float* A, int l
     if (variant == 3 && KC < 64) variant = 2;
     switch (variant) {
         case 1:  // S: 4 waves x (MTW tiles of 32 comps), 32 j
-            if (KC % 256 == 0 && KC >= 256 && s_mtw2) GO(2, 4, 1);
+            if (KC % 256 == 0 && KC >= 256 && g_knobs->s_mtw2) GO(2, 4, 1);
             GO(1, 4, 1);
         case 3:  // 2x2
             if (KC % 128 == 0) GO(2, 2, 2);
@@ -150,7 +159,7 @@ struct StreamK {
 static StreamK plan_streamk(int KC, int N_pad, int G_pad, int n_wg_slots)
 {
     StreamK sk;
-    if (KC % 128 != 0 || no_streamk_env()) return sk;
+    if (KC % 128 != 0 || g_knobs->no_streamk) return sk;
     sk.MG = KC / sk.mw;
     sk.T = sk.MG * (N_pad / 128);
     sk.nk = G_pad / BK;                                    // stages per tile, as the kernel counts them
@@ -209,26 +218,15 @@ static hipError_t launch_split3(hipStream_t st, const float* src, int ld, int ro
 // ping-pong workgroup per CU; 3 (default) = 2, plus the count-structured path (one integer plane for X, 3 MFMAs
 // per product on 256 x 256 tiles) whenever the resident matrix has that structure; 4 (default) = 3 on the f16 matrix
 // pipe (kernels_gemm2h.hip.h): counts <= 2048 in one f16 plane, the factor as two f16 planes with a per-row exponent,
-// 2 MFMAs per product.  Read at every call from the context's snapshot (cnmf_reload_env re-reads it): tests switch it.
+// 2 MFMAs per product.  Tests switch it between calls (cnmf_reload_env).
 // (Tried and dropped, all within 3 % of variant 2 at the 50k x 2000 shape: the same ping-pong with register
 //  staging; 256 x 256 tiles with the two wave groups half a block apart (2/3 of the DMA bytes per flop).)
-static thread_local int g_gemm3_mode = CNMF_GEMM3_DEFAULT;
-static thread_local int g_g2_gvar = 4;      // instruction stream of the general-matrix GEMMs (CNMF_G2_GVAR, refreshed below)
-static void refresh_gemm3_mode(const cnmf_ctx* ctx)   // at every API entry that launches GEMMs (not inside the hot loop): from the
-{                                                      // context's snapshot of the environment, like every per-call switch
-    const char* e = ctx_getenv(ctx, "CNMF_GEMM3");
-    const int mode = e ? atoi(e) : CNMF_GEMM3_DEFAULT;
-    g_gemm3_mode = (mode < 0 || mode > 4) ? CNMF_GEMM3_DEFAULT : mode;
-    const char* gv = ctx_getenv(ctx, "CNMF_G2_GVAR");
-    g_g2_gvar = (gv && atoi(gv) == 0) ? 0 : 4;
-}
-static int gemm3_mode() { return g_gemm3_mode; }
+static int gemm3_mode() { return g_knobs->gemm3; }
 // (CNMF_WG_SLOTS: fewer persistent GEMM workgroups than CUs -- leaves whole CUs to the kernels of another stream)
-static int gemm3_wg_slots()
+static int gemm3_wg_slots(const CdKnobs& k)
 {
-    static const int env = getenv("CNMF_WG_SLOTS") ? atoi(getenv("CNMF_WG_SLOTS")) : 0;
-    if (env >= 32 && gemm3_mode() >= 2) return env;
-    return gemm3_mode() >= 2 ? 256 : 512;
+    if (k.wg_slots >= 32 && k.gemm3 >= 2) return k.wg_slots;
+    return k.gemm3 >= 2 ? 256 : 512;
 }
 static int gemm3_jw() { return G3_JW; }     // j extent of a tile = row tile of the B planes
 
@@ -278,7 +276,7 @@ static StreamK3 plan_streamk3(int KC, int N_pad, int G_pad, int n_wg_slots, int 
     sk.T = sk.MG * (N_pad / jw);
     sk.Kb = G_pad / (G3_BK * unit);
     sk.P = n_wg_slots;
-    if (sk.T < sk.P / 2 + sk.P / 4 || sk.P > 2 * sk.T || no_streamk_env()) return sk;   // few tiles: K split + reduce instead
+    if (sk.T < sk.P / 2 + sk.P / 4 || sk.P > 2 * sk.T || g_knobs->no_streamk) return sk;   // few tiles: K split + reduce instead
     sk.on = true;
     sk.flags.assign(sk.T, 0);
     const long long U = (long long)sk.T * sk.Kb;
@@ -400,24 +398,8 @@ static hipError_t launch_gemm3c_streamk(hipStream_t st, const StreamK3& sk, cons
 }
 
 // ---- f16 two-plane count path (kernels_gemm2h.hip.h)
-// 16-k sub-blocks per barrier pair of the production launches (CNMF_G2_NSUB = 1 | 2)
-static int g2_nsub()
-{
-    static const int v = getenv("CNMF_G2_NSUB") ? atoi(getenv("CNMF_G2_NSUB")) : 2;
-    return v == 1 ? 1 : 2;
-}
-// instruction-stream variant of the NSUB = 2 kernels (kernels_gemm2h.hip.h): bit 0 = DMA pieces spread through the
-// MFMA stream, bit 1 = s_setprio around the MFMA halves
-#ifndef CNMF_G2_VAR_DEFAULT
-#define CNMF_G2_VAR_DEFAULT 4
-#endif
-// general matrices (GEN): 4 = the spread instruction stream (round 6, default), 0 = the burst loop (A/B; same bits)
-static int g2_gvar() { return g_g2_gvar; }
-static int g2_var()
-{
-    static const int v = getenv("CNMF_G2_VAR") ? atoi(getenv("CNMF_G2_VAR")) : CNMF_G2_VAR_DEFAULT;
-    return (v >= 0 && v <= 5) ? v : CNMF_G2_VAR_DEFAULT;
-}
+// Instruction streams (the VAR parameter of kernels_gemm2h.hip.h): production launches use 4, the spread stream, and 0,
+// the burst loop, on the two-plane count path; general matrices (GEN) take 0 instead of 4 with CNMF_G2_GVAR=0 (same bits).
 
 static inline unsigned long long g2_full_mask(int KC) { const int t = KC / 32; return t >= 64 ? ~0ull : ((1ull << t) - 1ull); }
 
@@ -446,19 +428,19 @@ static int gemm2h_splits(int Kb, int nsplit, int nsub)
     return (Kb + kb_per - 1) / kb_per;
 }
 
+// 16-k sub-blocks per barrier pair: 2 on the one-plane count path (CNMF_G2_NSUB=1: one), 1 with a second X plane
+static int gemm2h_nsub(bool hi, int Kb) { return (!hi && g_knobs->g2_nsub == 2 && Kb % 2 == 0) ? 2 : 1; }
+
 static hipError_t launch_gemm2h(hipStream_t st, const unsigned char* A2, const unsigned char* B1,
                                 const unsigned char* Bhi, const unsigned int* hiflag, const float* rscale, int Kb,
                                 float* C, int ldc, long long cstride, int KC, int Jpad, int nsplit,
                                 const float* cscale = nullptr, unsigned long long livemask = ~0ull)
 {
     // livemask: bit t = the 32 packed columns 32 t .. 32 t + 31 hold a restart that still iterates (all ones: everything)
-    static const bool nostore = getenv("CNMF_G2_NOSTORE") != nullptr;      // timing ablation: results meaningless
-    if (nostore) C = nullptr;
     const bool part = (livemask & g2_full_mask(KC)) != g2_full_mask(KC);
     // general matrices (cscale != nullptr: X as two f16 planes) multiply three of the four plane pairs (GEN); CNMF_G2_GEN4=1: all four (A/B)
-    static const bool gen4 = getenv("CNMF_G2_GEN4") != nullptr;
-    if (Bhi && cscale && !gen4) {
-        if (g2_gvar() == 0)                 // (A/B: the burst loop of rounds 3-5; bit-identical results)
+    if (Bhi && cscale && !g_knobs->g2_gen4) {
+        if (g_knobs->g2_gvar == 0)                 // (A/B: the burst loop of rounds 3-5; bit-identical results)
             return part ? launch_gemm2h_t<1, true, 0, true, true>(st, A2, B1, Bhi, hiflag, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, cscale, livemask)
                         : launch_gemm2h_t<1, true, 0, false, true>(st, A2, B1, Bhi, hiflag, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, cscale);
         return part ? launch_gemm2h_t<1, true, 4, true, true>(st, A2, B1, Bhi, hiflag, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, cscale, livemask)
@@ -467,22 +449,11 @@ static hipError_t launch_gemm2h(hipStream_t st, const unsigned char* A2, const u
     if (Bhi) return part ? launch_gemm2h_t<1, true, 0, true>(st, A2, B1, Bhi, hiflag, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, cscale, livemask)
                          : launch_gemm2h_t<1, true>(st, A2, B1, Bhi, hiflag, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, cscale);
     if (cscale) return hipErrorInvalidValue;              // a column scale exists only on the two-plane operand path
-    if (g2_nsub() == 2 && Kb % 2 == 0) {
-        if (part && g2_var() == CNMF_G2_VAR_DEFAULT)
-            return launch_gemm2h_t<2, false, CNMF_G2_VAR_DEFAULT, true>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, nullptr, livemask);
-        switch (g2_var()) {
-            case 1: return launch_gemm2h_t<2, false, 1>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit);
-            case 2: return launch_gemm2h_t<2, false, 2>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit);
-            case 3: return launch_gemm2h_t<2, false, 3>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit);
-            case 4: return launch_gemm2h_t<2, false, 4>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit);
-            case 5: return launch_gemm2h_t<2, false, 5>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit);
-            default: return launch_gemm2h_t<2, false, 0>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit);
-        }
-    }
-    if (g2_var() >= 1) return launch_gemm2h_t<1, false, 4>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit);
-    return launch_gemm2h_t<1, false>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit);
+    if (gemm2h_nsub(false, Kb) == 2)
+        return part ? launch_gemm2h_t<2, false, 4, true>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, nullptr, livemask)
+                    : launch_gemm2h_t<2, false, 4>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit);
+    return launch_gemm2h_t<1, false, 4>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit);
 }
-static int gemm2h_nsub(bool hi, int Kb) { return (!hi && g2_nsub() == 2 && Kb % 2 == 0) ? 2 : 1; }
 
 template <int NSUB, bool HI, int VAR = 0, bool NTB = true, bool PART = false, bool GEN = false>
 static hipError_t launch_gemm2h_streamk_t(hipStream_t st, const StreamK3& sk, const unsigned char* A2,
@@ -499,8 +470,7 @@ static hipError_t launch_gemm2h_streamk_t(hipStream_t st, const StreamK3& sk, co
     // path (GEN: both X planes, 410 MB at 50 000 x 2 000, re-streamed per component group): the identity order (0) -- the four
     // groups of a row tile share it in one L2 -- measured +1.3 % (133.7 / 134.1 vs 131.9 / 132.4 restarts/s, round 6); the
     // count path measured -2 % with it (round 3).  CNMF_G2_XMAP=0|1 forces either.
-    static const int xmap_env = getenv("CNMF_G2_XMAP") ? atoi(getenv("CNMF_G2_XMAP")) : -1;
-    const int xmap = xmap_env >= 0 ? xmap_env : (GEN ? 0 : 1);
+    const int xmap = g_knobs->g2_xmap >= 0 ? g_knobs->g2_xmap : (GEN ? 0 : 1);
     gemm2h_streamk_kernel<NSUB, HI, VAR, NTB, PART, GEN><<<sk.P, 512, lds, st>>>(A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, sk.MG, sk.T, xmap, cscale, livemask);
     return hipGetLastError();
 }
@@ -511,15 +481,11 @@ static hipError_t launch_gemm2h_streamk(hipStream_t st, const StreamK3& sk, cons
                                         const float* rscale, int Kb, float* C0, float* C1, float* C2, int ldc,
                                         const float* cscale = nullptr, unsigned long long livemask = ~0ull)
 {
-    static const bool nostore = getenv("CNMF_G2_NOSTORE") != nullptr;      // timing ablation: results meaningless
-    if (nostore) C0 = C1 = C2 = nullptr;
     const bool part = (livemask & g2_full_mask(sk.MG * G3_MW)) != g2_full_mask(sk.MG * G3_MW);
-    // several component groups share every count-plane tile in the L2: no non-temporal loads then (CNMF_G2_NT=1: A/B)
-    static const bool force_nt = getenv("CNMF_G2_NT") != nullptr;
-    const bool shared = sk.MG > 1 && !force_nt;
-    static const bool gen4 = getenv("CNMF_G2_GEN4") != nullptr;
-    if (Bhi && cscale && !gen4) {          // general matrices: three of the four plane pairs (GEN)
-        if (g2_gvar() == 0) {              // (A/B: the burst loop of rounds 3-5; bit-identical results)
+    // several component groups share every count-plane tile in the L2: no non-temporal loads then
+    const bool shared = sk.MG > 1;
+    if (Bhi && cscale && !g_knobs->g2_gen4) {          // general matrices: three of the four plane pairs (GEN)
+        if (g_knobs->g2_gvar == 0) {              // (A/B: the burst loop of rounds 3-5; bit-identical results)
             if (part) return launch_gemm2h_streamk_t<1, true, 0, false, true, true>(st, sk, A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, cscale, livemask);
             return shared ? launch_gemm2h_streamk_t<1, true, 0, false, false, true>(st, sk, A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, cscale)
                           : launch_gemm2h_streamk_t<1, true, 0, true, false, true>(st, sk, A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, cscale);
@@ -535,23 +501,13 @@ static hipError_t launch_gemm2h_streamk(hipStream_t st, const StreamK3& sk, cons
     }
     if (cscale) return hipErrorInvalidValue;
     if (gemm2h_nsub(false, Kb) == 2) {
-        if (part && g2_var() == CNMF_G2_VAR_DEFAULT)
-            return launch_gemm2h_streamk_t<2, false, CNMF_G2_VAR_DEFAULT, false, true>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc, nullptr, livemask);
-        if (shared && g2_var() == CNMF_G2_VAR_DEFAULT)
-            return launch_gemm2h_streamk_t<2, false, CNMF_G2_VAR_DEFAULT, false>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc);
-        switch (g2_var()) {
-            case 1: return launch_gemm2h_streamk_t<2, false, 1>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc);
-            case 2: return launch_gemm2h_streamk_t<2, false, 2>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc);
-            case 3: return launch_gemm2h_streamk_t<2, false, 3>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc);
-            case 4: return launch_gemm2h_streamk_t<2, false, 4>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc);
-            case 5: return launch_gemm2h_streamk_t<2, false, 5>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc);
-            default: return launch_gemm2h_streamk_t<2, false, 0>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc);
-        }
+        if (part) return launch_gemm2h_streamk_t<2, false, 4, false, true>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc, nullptr, livemask);
+        return shared ? launch_gemm2h_streamk_t<2, false, 4, false>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc)
+                      : launch_gemm2h_streamk_t<2, false, 4>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc);
     }
-    if (g2_var() >= 1)                     // (CNMF_G2_NSUB=1 A/B: the one-block spread stream on the count plane)
-        return shared ? launch_gemm2h_streamk_t<1, false, 4, false>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc)
-                      : launch_gemm2h_streamk_t<1, false, 4, true>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc);
-    return launch_gemm2h_streamk_t<1, false>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc);
+    // (CNMF_G2_NSUB=1 A/B: the one-block spread stream on the count plane)
+    return shared ? launch_gemm2h_streamk_t<1, false, 4, false>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc)
+                  : launch_gemm2h_streamk_t<1, false, 4, true>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc);
 }
 
 // geometry of the split launch: tiles of 16 rows x 256 k when K % 256 == 0 (1 KB contiguous per row), else 64 x 64;
@@ -594,7 +550,7 @@ static hipError_t launch_rowmax_part(hipStream_t st, const float* V, int ld, int
 // integer planes of X and X^T and the per-gene scale (kernels_counts.hip.h).
 static int ensure_counts(cnmf_ctx* ctx)
 {
-    const int fmt = gemm3_mode() == 4 ? 4 : 3;      // plane format the current mode multiplies
+    const int fmt = ctx->knobs.gemm3 == 4 ? 4 : 3;      // plane format the current mode multiplies
     if (ctx->count_state == 1 && ctx->count_fmt != fmt) {
         // the mode was switched between two calls on the same matrix (tests, A/B runs): rebuild the planes
         hipStreamSynchronize(ctx->stream);
@@ -607,7 +563,7 @@ static int ensure_counts(cnmf_ctx* ctx)
     ctx->count_state = -1;
     ctx->count_fmt = fmt;
     const int N = (int)ctx->N, G = (int)ctx->G;
-    if (ctx->N_pad % G3C_JW || ctx->G_pad % G3C_JW || getenv("CNMF_NO_COUNTS") || !ctx->count_detect) return CNMF_OK;
+    if (ctx->N_pad % G3C_JW || ctx->G_pad % G3C_JW || ctx->knobs.no_counts || !ctx->count_detect) return CNMF_OK;
     hipStream_t st = ctx->stream;
     const int chunks = (N + CNT_ROWS - 1) / CNT_ROWS;
     DevPool pool;
@@ -689,7 +645,7 @@ static bool gemm3_enabled(const cnmf_ctx* ctx, int KC)
     // (round 6: the plane builders carry the 16-cell blocks on grid.x, so matrices beyond 65 535 x 16 = 1 048 560 cells keep the
     //  matrix-pipe path -- probed at 1 100 000 x 2 000, 2.25e9 padded elements: tools/probe_big_matrix.py; bounded at 2^24 cells
     //  only because nothing larger has been run; the gene side still rides on grid.y of those builders: G_pad / 256 <= 65 535)
-    return gemm3_mode() != 0 && KC % G3_MW == 0 && ctx->G_pad % gemm3_jw() == 0 && ctx->N_pad % gemm3_jw() == 0 &&
+    return ctx->knobs.gemm3 != 0 && KC % G3_MW == 0 && ctx->G_pad % gemm3_jw() == 0 && ctx->N_pad % gemm3_jw() == 0 &&
            ctx->N_pad <= (1 << 24) && ctx->G_pad / 256 <= 65535;
 }
 
@@ -698,7 +654,7 @@ static int pick_nsplit3(const cnmf_ctx* ctx, int KC, int jw)
     // pass B grid = (G_pad/jw) x (KC/256) x nsplit; aim at one (two) workgroups per CU, >= 16 blocks per split
     const int tiles = std::max(1, ctx->G_pad / jw) * std::max(1, KC / G3_MW);
     const int Kb = ctx->N_pad / G3_BK;
-    int s = std::max(1, std::min(gemm3_wg_slots() / std::max(1, tiles), Kb / 16));
+    int s = std::max(1, std::min(gemm3_wg_slots(ctx->knobs) / std::max(1, tiles), Kb / 16));
     const int kb_per = (Kb + s - 1) / s;
     return (Kb + kb_per - 1) / kb_per;
 }

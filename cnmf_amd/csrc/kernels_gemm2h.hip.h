@@ -33,7 +33,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4_g __attribute__((ext_vector_type(4)));
 // (A/B build: -DCNMF_G2_LDS_STORE sends the finished tile through LDS and out with 16-byte stores; measured on one box,
 //  two alternations: 216.8 / 215.6 restarts/s against 217.5 / 216.8 with the four-byte stores straight from the
-//  accumulator registers -- the stores cost 10-13 % of a pass (CNMF_G2_NOSTORE ablation) but not through their issue)
+//  accumulator registers -- the stores cost 10-13 % of a pass (store ablation, profiles/r4_gemm_store_ablation.txt) but not through their issue)
 #ifdef CNMF_G2_LDS_STORE
 constexpr bool G2_LDS_STORE = true;
 #else
@@ -411,22 +411,6 @@ __global__ __launch_bounds__(256) void count_max_base_kernel(const float* __rest
     if (big) atomicOr(any_big, 1u);
 }
 
-// LDS-DMA issued from inline asm (cdna_hip_programming.md section 5.7): hipcc does not see an LDS write, so it neither
-// drains the pending fragment reads in front of it (the builtin makes it wait lgkmcnt(0): a possible alias) nor counts it
-// in vmcnt -- the kernel counts by hand anyway.  M0 is saved and restored inside the statement.
-__device__ __forceinline__ void glds16_asm(const void* gsrc, unsigned lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void glds16_asm_nt(const void* gsrc, unsigned lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
 // ------------------------------------------------------------------------------------------
 // One K segment [kb0, kb0 + nkb) (in 16-k blocks; kb0 and nkb multiples of NSUB) of one 256 x 256 tile.
 //   A2 : f16 planes of the component-major factor (rows m0..), B1 : f16 count plane (rows j0..),
@@ -437,8 +421,7 @@ __device__ __forceinline__ void glds16_asm_nt(const void* gsrc, unsigned lds_dst
 //   bit 0: the six LDS-DMA pieces of a step are spread through the MFMA stream (one after every 4th MFMA of the step's
 //          first 24) instead of issued in one burst behind the X barrier -- a burst of DMA issues in front of 20
 //          ds_read_b128 is the expensive place for them (MI355X_MICROARCH.md, "LDS-DMA piece issue cost");
-//   VAR 4: VAR 1 with the fragment reads in two batches (see G2_READ_A / G2_READ_B);
-//   VAR 5: VAR 4 with the steady-state DMA pieces issued from inline asm (glds16_asm);
+//   VAR 4 (production): that stream with the fragment reads in two batches (see G2_READ_A / G2_READ_B);
 //   VAR 2 / 3 (timing ablations, results meaningless): the spread stream WITHOUT its MFMAs (fill + fragment reads
 //          only) / WITHOUT its steady-state DMA (MFMAs + fragment reads on stale images).  s_setprio around the MFMA
 //          halves was tried and is neutral (profiles/r2_probe_gemm2h_variants.txt).
@@ -514,12 +497,6 @@ __device__ __forceinline__ void gemm2h_segment(const unsigned char* __restrict__
     {                                                                                              \
         unsigned char* d_ = smem + ((s_) % IMGS) * IMG + wave * 1024;                              \
         const unsigned char* a_ = abase + (size_t)(s_) * (NSUB * G2_A);                            \
-        if constexpr (VAR == 5) {                       /* no LDS-DMA builtin anywhere in this variant */ \
-            const unsigned l_ = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)G3_AS3(d_)); \
-            _Pragma("unroll") for (int i = 0; i < NA; ++i) glds16_asm(a_ + i * 8192, l_ + i * 8192); \
-            _Pragma("unroll") for (int i = 0; i < NB; ++i)                                         \
-                glds16_asm_nt(bbase + (size_t)(s_) * (NSUB * G2_B) + i * 8192, l_ + OFF_B + i * 8192); \
-        } else {                                                                                   \
         _Pragma("unroll") for (int i = 0; i < NA; ++i)                                             \
             __builtin_amdgcn_global_load_lds(G3_AS1(a_ + i * 8192), G3_AS3(d_ + i * 8192), 16, 0, 0); \
         /* the count planes are read once per pass: non-temporal */                                \
@@ -531,7 +508,6 @@ __device__ __forceinline__ void gemm2h_segment(const unsigned char* __restrict__
                 if (G2_BLKFLAG((s_) * NSUB + i))                                                   \
                     __builtin_amdgcn_global_load_lds(G3_AS1(hbase + (size_t)(s_) * (NSUB * G2_B) + i * 8192), \
                                                      G3_AS3(d_ + OFF_H + i * 8192), 16, 0, NTB ? 2 : 0); \
-        }                                                                                          \
         }                                                                                          \
     }
 #define G2_FRAG(ptr_) __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(ptr_))
@@ -581,7 +557,8 @@ __device__ __forceinline__ void gemm2h_segment(const unsigned char* __restrict__
     // burst loop below: results are bit-identical (tests/test_gpu_nmf.py).
     constexpr bool SPREADG = VAR >= 1 && NSUB == 1 && ((HI && GEN) || !HI);   // (!HI: the count plane alone, A/B via CNMF_G2_NSUB=1)
     constexpr bool PRIO = false;
-    constexpr bool NOMFMA = VAR == 2, NODMA = VAR == 3 || VAR == 6 || VAR == 7, SPLITRD = VAR >= 4, ASMDMA = VAR == 5;
+    constexpr bool NOMFMA = VAR == 2, NODMA = VAR == 3 || VAR == 6 || VAR == 7, SPLITRD = VAR >= 4;
+    static_assert(VAR != 1 && VAR != 5, "instruction streams 1 and 5 were retired");
     constexpr bool NOREAD = VAR == 6 || VAR == 7;         // timing ablations: fragments read once / ... and no barriers
     constexpr bool NOBAR = VAR == 7;
     G3_WAIT_VM(0);                                          // stores of a previous segment
@@ -681,12 +658,7 @@ __device__ __forceinline__ void gemm2h_segment(const unsigned char* __restrict__
 #define G2_PIECE(s_, i_)                                                                           \
         {                                                                                          \
             unsigned char* d_ = smem + ((s_) % IMGS) * IMG + wave * 1024;                          \
-            if constexpr (ASMDMA) {                                                                \
-                const unsigned l_ = __builtin_amdgcn_readfirstlane(                                \
-                    (unsigned)(unsigned long long)G3_AS3(d_ + ((i_) < NA ? (i_) * 8192 : OFF_B + ((i_) - NA) * 8192))); \
-                if ((i_) < NA) glds16_asm(abase + (size_t)(s_) * (NSUB * G2_A) + (i_) * 8192, l_);  \
-                else glds16_asm_nt(bbase + (size_t)(s_) * (NSUB * G2_B) + ((i_) - NA) * 8192, l_);  \
-            } else if ((i_) < NA)                                                                  \
+            if ((i_) < NA)                                                                         \
                 __builtin_amdgcn_global_load_lds(G3_AS1(abase + (size_t)(s_) * (NSUB * G2_A) + (i_) * 8192), \
                                                  G3_AS3(d_ + (i_) * 8192), 16, 0, 0);              \
             else                                                                                   \
@@ -774,14 +746,14 @@ __device__ __forceinline__ void gemm2h_segment(const unsigned char* __restrict__
         // a tile computed in one piece: the epilogue takes the accumulators (and stores what it does not consume itself)
         if (whole_tile && epi->on) { (*epi)(acc, rscale, C, ldc, m0, j0, smem); return; }
     }
-    if (C == nullptr) return;                                // (timing ablation CNMF_G2_NOSTORE: the pass without its stores)
+    if (C == nullptr) return;                                // (a pass without its stores: timing ablation)
     const int j = j0 + wn * 64 + li;
     // general (not count-structured) X as two f16 planes of x * 2^s_j (x2h_planes_kernel): the per-column exponent is
     // undone here (a power of two: exact); 1 otherwise
     const float cs[2] = {(HI && cscale) ? cscale[j] : 1.0f, (HI && cscale) ? cscale[j + 32] : 1.0f};
     if constexpr (!PART && G2_LDS_STORE && g2_lds_bytes(NSUB, HI) >= 8 * 16384) {
         // round-4 experiment (build flag, not adopted): the tile leaves through LDS with 16-byte stores instead of 128
-        // four-byte stores per lane.  The stores are 10-13 % of a pass (CNMF_G2_NOSTORE ablation: pass A 325 -> 291 us,
+        // four-byte stores per lane.  The stores are 10-13 % of a pass (store ablation: pass A 325 -> 291 us,
         // pass B 197 -> 171 us) but this form measured 0.4 % SLOWER end to end.  The DMA images are dead here (both wave
         // groups are past their last fragment read), every wave transposes its own 128 components x 64 cells in two rounds
         // of 64 x 64 through a private 16 KB strip and writes rows of 256 contiguous bytes.  Same values, same places.

@@ -89,14 +89,43 @@ struct PreStage {
     void release() { release_counts(); release_ridge(); slot[0].release(); slot[1].release(); N = 0; }
 };
 
+static constexpr int RING = 8;
+#ifndef CNMF_GEMM3_DEFAULT
+#define CNMF_GEMM3_DEFAULT 4
+#endif
+
+// The CNMF_* switches of the coordinate-descent batch path (batch_host.hip.h, gemm_host.hip.h): parsed in ONE place,
+// parse_cd_knobs below, whenever the context's snapshot of the environment is taken.  The host code reads these fields.
+struct CdKnobs {
+    int  gemm3 = CNMF_GEMM3_DEFAULT;   // CNMF_GEMM3=0..4: operand scheme of the GEMM passes at >= 256 packed columns (gemm_host.hip.h)
+    int  g2_gvar = 4;                  // CNMF_G2_GVAR=0: general matrices on the burst-issue loop, not the spread stream (same bits)
+    bool g2_gen4 = false;              // CNMF_G2_GEN4: general matrices multiply all four f16 plane pairs instead of three
+    int  g2_nsub = 2;                  // CNMF_G2_NSUB=1|2: 16-k sub-blocks per barrier pair of the one-plane f16 GEMMs
+    int  g2_xmap = -1;                 // CNMF_G2_XMAP=0|1: XCD mapping of the persistent f16 GEMM workgroups (-1: by path)
+    bool part = false;                 // CNMF_PART: the tail's GEMM passes skip 32-column tiles without a live restart
+    bool no_psum = false;              // CNMF_NO_PSUM: a separate split-K reduce in front of the H sweep
+    bool wide_small = true;            // CNMF_WIDE_SMALL=0: a small matrix never runs wider than 256 columns
+    bool kc_set = false;               // CNMF_KC is set ...
+    int  kc = 0;                       // ... and from 32 up it is the batch width (a bound like cnmf_cd_params.kc_max)
+    int  kc_limit = 1024;              // CNMF_KC_LIMIT: widest batch, a multiple of 256 in [256, 2048] (the 64 tile bits of the live mask)
+    int  lag = 0;                      // CNMF_LAG: iterations between the device and the snapshot the host inspects (0: the caller's, or 2)
+    int  sweep_parts = 64;             // CNMF_SWEEP_PARTS >= 1: most workgroups (partials) per slot of a half-step
+    int  wg_slots = 0;                 // CNMF_WG_SLOTS >= 32: persistent GEMM workgroups, leaving CUs to another stream (0: one per CU)
+    bool no_streamk = false;           // CNMF_NO_STREAMK: pass A always as K splits + reduce
+    bool s_mtw2 = false;               // CNMF_S_MTW2: the "S" f32 GEMM layout with two tiles per wave (diagnostic entry point only)
+    bool no_counts = false;            // CNMF_NO_COUNTS: no count-structure detection
+    bool debug = false;                // CNMF_DEBUG: scheduler statistics of the batch path on stderr (consensus and MU read the snapshot themselves)
+};
+
 struct cnmf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
     // the CNMF_* environment variables as they were when the context was created (cnmf_create) or last re-read
-    // (cnmf_reload_env): the host paths of a call consult THIS snapshot (ctx_getenv), not the process environment -- a
-    // knob that steers a numerics-affecting path cannot change between two calls on one context behind the caller's back
+    // (cnmf_reload_env): the host paths of a call consult THIS snapshot (ctx_getenv, knobs), never the process environment
+    // -- a knob that steers a numerics-affecting path cannot change between two calls on one context behind the caller's back
     std::map<std::string, std::string> env;
+    CdKnobs knobs;                                 // ... and the switches of the coordinate-descent batch path, parsed from it
 
     // data matrix
     int64_t N = 0, G = 0;
@@ -169,6 +198,38 @@ struct cnmf_ctx {
     PreStage pre;                     // cnmf_preprocess_* staging (preprocess_host.hip.h)
 };
 
+static const char* ctx_getenv(const cnmf_ctx* ctx, const char* name)
+{
+    if (!ctx) return getenv(name);
+    auto it = ctx->env.find(name);
+    return it == ctx->env.end() ? nullptr : it->second.c_str();
+}
+static void parse_cd_knobs(cnmf_ctx* ctx)
+{
+    CdKnobs k;
+    auto num = [](const char* s, int dflt) { return s ? atoi(s) : dflt; };
+    k.gemm3 = num(ctx_getenv(ctx, "CNMF_GEMM3"), CNMF_GEMM3_DEFAULT);
+    if (k.gemm3 < 0 || k.gemm3 > 4) k.gemm3 = CNMF_GEMM3_DEFAULT;
+    k.g2_gvar = num(ctx_getenv(ctx, "CNMF_G2_GVAR"), 4) == 0 ? 0 : 4;
+    k.g2_gen4 = ctx_getenv(ctx, "CNMF_G2_GEN4") != nullptr;
+    k.g2_nsub = num(ctx_getenv(ctx, "CNMF_G2_NSUB"), 2) == 1 ? 1 : 2;
+    k.g2_xmap = num(ctx_getenv(ctx, "CNMF_G2_XMAP"), -1);
+    k.part = ctx_getenv(ctx, "CNMF_PART") != nullptr;
+    k.no_psum = ctx_getenv(ctx, "CNMF_NO_PSUM") != nullptr;
+    k.wide_small = num(ctx_getenv(ctx, "CNMF_WIDE_SMALL"), 1) != 0;
+    k.kc_set = ctx_getenv(ctx, "CNMF_KC") != nullptr;
+    k.kc = num(ctx_getenv(ctx, "CNMF_KC"), 0);
+    k.kc_limit = std::max(256, std::min(2048, (num(ctx_getenv(ctx, "CNMF_KC_LIMIT"), 1024) / 256) * 256));
+    k.lag = num(ctx_getenv(ctx, "CNMF_LAG"), 0);
+    k.sweep_parts = std::max(1, num(ctx_getenv(ctx, "CNMF_SWEEP_PARTS"), 64));
+    k.wg_slots = num(ctx_getenv(ctx, "CNMF_WG_SLOTS"), 0);
+    k.no_streamk = ctx_getenv(ctx, "CNMF_NO_STREAMK") != nullptr;
+    k.s_mtw2 = ctx_getenv(ctx, "CNMF_S_MTW2") != nullptr;
+    k.no_counts = ctx_getenv(ctx, "CNMF_NO_COUNTS") != nullptr;
+    k.debug = ctx_getenv(ctx, "CNMF_DEBUG") != nullptr;
+    ctx->knobs = k;
+}
+
 extern char** environ;
 static void ctx_snapshot_env(cnmf_ctx* ctx)
 {
@@ -178,18 +239,8 @@ static void ctx_snapshot_env(cnmf_ctx* ctx)
         const char* eq = strchr(*e, '=');
         if (eq) ctx->env[std::string(*e, eq - *e)] = std::string(eq + 1);
     }
+    parse_cd_knobs(ctx);
 }
-static const char* ctx_getenv(const cnmf_ctx* ctx, const char* name)
-{
-    if (!ctx) return getenv(name);
-    auto it = ctx->env.find(name);
-    return it == ctx->env.end() ? nullptr : it->second.c_str();
-}
-
-static constexpr int RING = 8;
-#ifndef CNMF_GEMM3_DEFAULT
-#define CNMF_GEMM3_DEFAULT 4
-#endif
 
 #define SET_ERR(ctx, ...)                                                   \
     do {                                                                    \

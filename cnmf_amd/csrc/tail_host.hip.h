@@ -254,7 +254,7 @@ static int nnls_sweep_loop(cnmf_ctx* ctx, int nslots, float* V, int ldv, int L, 
                            float l1, const cnmf_cd_params* prm, int kmax, int tiers)
 {
     hipStream_t st = ctx->stream;
-    const int chunks = sweep_chunks(L), parts = sweep_parts(L);
+    const int chunks = sweep_chunks(ctx, L), parts = sweep_parts(ctx, L);
     EventPool events;
     hipEvent_t ev = events.get(hipEventDisableTiming);
     POOL_TRY(ctx, events);
@@ -434,6 +434,7 @@ static int nnls_batch_impl(cnmf_ctx* ctx, int n, const int32_t* ks, const float*
 {
     using namespace cnmf;
     if (!ctx || !ks || !Hin || n < 1) { SET_ERR(ctx, "bad argument"); return CNMF_EINVAL; }
+    KnobScope knob_scope(ctx);
     if (int rcd_ = ensure_dense(ctx)) return rcd_;
     int rc = validate_params(ctx, prm);
     if (rc) return rc;

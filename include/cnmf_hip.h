@@ -95,13 +95,10 @@ int         cnmf_device_count(void);
 cnmf_ctx*   cnmf_create(int device);           /* NULL on failure; see cnmf_last_error(NULL) */
 void        cnmf_destroy(cnmf_ctx* ctx);
 const char* cnmf_last_error(const cnmf_ctx* ctx);
-/* The CNMF_* environment variables (INTEGRATION.md "Runtime switches") that steer per-call host decisions are read ONCE,
- * when the context is created, into the context; cnmf_reload_env re-reads them (A/B tools, tests).  A knob therefore
- * cannot change between two calls on one context unless the caller asks for it.  In the snapshot: the GEMM operand
- * scheme (CNMF_GEMM3), the batch width (CNMF_KC, CNMF_KC_LIMIT, CNMF_NO_WIDE, CNMF_WIDE_SMALL), CNMF_LAG, the consensus and
- * multiplicative-update switches.  PROCESS-LIFETIME (read once per process, NOT refreshed by cnmf_reload_env): the A/B
- * knobs of the kernel launch planning and instruction streams -- CNMF_NO_STREAMK, CNMF_S_MTW2, CNMF_G2_*, CNMF_WG_SLOTS,
- * CNMF_FUSE_W, CNMF_G2G, CNMF_SPIN_QUERY, CNMF_NO_COUNTS -- set them before the library is loaded.                    */
+/* The CNMF_* environment variables (INTEGRATION.md "Runtime switches") are read ONCE, when the context is created, into
+ * the context; cnmf_reload_env re-reads all of them (A/B tools, tests).  A knob therefore cannot change between two
+ * calls on one context unless the caller asks for it.  The one exception is CNMF_RCCL_LIB, the path RCCL is loaded
+ * from: read from the process environment the first time a communicator is formed.                                    */
 int cnmf_reload_env(cnmf_ctx* ctx);
 const char* cnmf_version(void);
 

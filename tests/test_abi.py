@@ -31,6 +31,29 @@ def test_header_and_loader_agree():
     assert "#ifdef CNMF_DEBUG_ABI" in open(os.path.join(ROOT, "cnmf_amd", "csrc", "debug_host.hip.h")).read()
 
 
+CSRC = os.path.join(ROOT, "cnmf_amd", "csrc")
+
+
+def test_every_switch_the_library_reads_is_documented():
+    """The CNMF_* names the library passes to ctx_getenv / getenv are exactly those of INTEGRATION.md "Runtime switches"."""
+    read = set()
+    for f in sorted(os.listdir(CSRC)):
+        read |= set(re.findall(r'getenv\(\s*(?:\w+\s*,\s*)?"(CNMF_[A-Z0-9_]+)"', open(os.path.join(CSRC, f)).read()))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc[doc.index("Runtime switches"):]
+    section = section[:section.index("\n**")]                      # up to the next bold paragraph
+    documented = set(re.findall(r"CNMF_[A-Z0-9_]+", section))
+    assert read and read == documented, (sorted(read - documented), sorted(documented - read))
+
+
+def test_batch_path_reads_switches_from_the_context_snapshot_only():
+    """batch_host.hip.h and gemm_host.hip.h read typed fields of the context's knob table: no getenv of their own."""
+    for f in ("batch_host.hip.h", "gemm_host.hip.h"):
+        src = open(os.path.join(CSRC, f)).read()
+        assert "getenv(" not in src, f
+        assert not re.search(r"^[ \t]+static const\b", src, flags=re.M), f      # no function-local once-per-process value
+
+
 def test_every_declared_symbol_is_exported(lib):
     missing = [s for s in header_symbols() if not hasattr(lib, s)]
     assert not missing, missing

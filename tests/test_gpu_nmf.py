@@ -234,7 +234,7 @@ def test_general_matrix_on_the_f16_pipe_matches_oracle(engine):
         _check(H_ref, n_ref, h, n, slack=3)
     H2, _, n2, _ = engine.nmf_batch(ks, seeds=seeds)
     assert list(n2) == list(n_iter) and all(np.array_equal(a, b) for a, b in zip(H, H2))
-    # against the 3 x 3 bf16 planes of rounds 1-2 (CNMF_G2G=0 is read once per process: compared through the oracle only)
+    # (the 3 x 3 bf16 planes of rounds 1-2 stay reachable as CNMF_GEMM3=1|2: test_full_width_batch_matches_oracle_in_every_gemm_mode)
 
 
 def test_general_path_spread_stream_is_bit_identical_to_the_burst_loop(engine, monkeypatch):

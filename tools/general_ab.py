@@ -1,5 +1,5 @@
-"""One timed step of the GENERAL path (count detection off: gemm_mode 5) at the bench's shape, for A/B runs of process-lifetime
-knobs (CNMF_G2_XMAP, CNMF_LIB_PATH ...):   CNMF_G2_XMAP=0 python tools/general_ab.py [restarts_per_k]
+"""One timed step of the GENERAL path (count detection off: gemm_mode 5) at the bench's shape, for A/B runs of a knob or of
+another build (CNMF_G2_XMAP, CNMF_LIB_PATH ...):   CNMF_G2_XMAP=0 python tools/general_ab.py [restarts_per_k]
 Prints one JSON line (bench.py::general_path_step: restarts/s, pass A / pass B launch times, roofline fraction)."""
 import importlib.util
 import json
