@@ -26,6 +26,9 @@ SYMBOLS = [
     "cnmf_preprocess_upload_csr", "cnmf_preprocess_set_dense", "cnmf_preprocess_select", "cnmf_preprocess_order_stats",
     "cnmf_preprocess_ceiling", "cnmf_preprocess_densify", "cnmf_preprocess_fetch", "cnmf_preprocess_scatter",
     "cnmf_preprocess_project", "cnmf_preprocess_ridge_moments", "cnmf_preprocess_ridge_apply", "cnmf_preprocess_release",
+    "cnmf_preprocess_ridge_apply_mode",
+    "cnmf_harmony_begin", "cnmf_harmony_init", "cnmf_harmony_kmeans_step", "cnmf_harmony_ridge_moments",
+    "cnmf_harmony_ridge_apply", "cnmf_harmony_fetch", "cnmf_harmony_release",
     "cnmf_preprocess_row_sums", "cnmf_preprocess_normalize_dense", "cnmf_preprocess_select_mi",
     "cnmf_preprocess_upload_csr_as_stored", "cnmf_preprocess_gene_detect", "cnmf_preprocess_cell_sums",
     "cnmf_preprocess_subset", "cnmf_preprocess_fetch_counts",
@@ -48,6 +51,8 @@ COMM_ID_BYTES = 128
 CNMF_KMAX = 128
 CNMF_MU_KMAX = 64
 CNMF_RIDGE_MAX = 4096
+CNMF_HARMONY_KMAX = 128
+CNMF_HARMONY_DMAX = 64
 
 
 class CdParams(C.Structure):
@@ -203,6 +208,22 @@ def load():
     lib.cnmf_preprocess_ridge_moments.argtypes = [vp, i32, i32, i32, dblp, dblp, dblp, dblp]
     lib.cnmf_preprocess_ridge_apply.restype = i32
     lib.cnmf_preprocess_ridge_apply.argtypes = [vp, i32, dblp]
+    lib.cnmf_preprocess_ridge_apply_mode.restype = i32
+    lib.cnmf_preprocess_ridge_apply_mode.argtypes = [vp, i32, dblp, i32]
+    lib.cnmf_harmony_begin.restype = i32
+    lib.cnmf_harmony_begin.argtypes = [vp, i64, i32, i32, i32, i32, dblp, i32p, i32p, dblp, dblp, dblp]
+    lib.cnmf_harmony_init.restype = i32
+    lib.cnmf_harmony_init.argtypes = [vp, dblp, dblp]
+    lib.cnmf_harmony_kmeans_step.restype = i32
+    lib.cnmf_harmony_kmeans_step.argtypes = [vp, i32p, i32, dblp]
+    lib.cnmf_harmony_ridge_moments.restype = i32
+    lib.cnmf_harmony_ridge_moments.argtypes = [vp, dblp, dblp]
+    lib.cnmf_harmony_ridge_apply.restype = i32
+    lib.cnmf_harmony_ridge_apply.argtypes = [vp, dblp]
+    lib.cnmf_harmony_fetch.restype = i32
+    lib.cnmf_harmony_fetch.argtypes = [vp, dblp, dblp, dblp, dblp]
+    lib.cnmf_harmony_release.restype = i32
+    lib.cnmf_harmony_release.argtypes = [vp]
     lib.cnmf_preprocess_row_sums.restype = i32
     lib.cnmf_preprocess_row_sums.argtypes = [vp, dblp]
     lib.cnmf_preprocess_normalize_dense.restype = i32

@@ -145,6 +145,7 @@ extern "C" void cnmf_destroy(cnmf_ctx* ctx)
     ctx->cons_ws.release();
     ctx->prep.release();
     ctx->pre.release();
+    ctx->har.release();
     if (ctx->cons_pinned) hipHostFree(ctx->cons_pinned);
     hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -336,6 +337,7 @@ extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
 #include "normalize_host.hip.h"
 #include "prepare_host.hip.h"
 #include "preprocess_host.hip.h"
+#include "harmony_host.hip.h"
 #include "filter_host.hip.h"
 #include "select_mi_host.hip.h"
 #include "tail_host.hip.h"

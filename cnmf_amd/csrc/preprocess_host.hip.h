@@ -103,6 +103,7 @@ __global__ __launch_bounds__(256) void pre_splitk_sum_kernel(const double* __res
 //           3  A(m, k) = Rt[m][k / B1] Pt[m][k % B1]   (ridge apply; m = cell, k = (cluster, covariate))
 // B modes:  0  B(k, n) = Bm[k][n]                 1  B(k, n) = X[k][n] - mu[n]
 // Epilogues: 0  C[z][m][n] = acc (split-K partial, z stride cs)     1  X[m][n] = max(X[m][n] - acc, 0) (in place)
+//            2  X[m][n] = X[m][n] - acc (in place, no clip: a matrix with negative entries, Harmony's PCA scores)
 // Workgroup tile 64 x 64, 4 waves (2 x 2) of 32 x 32 = 2 x 2 v_mfma_f64_16x16x4f64 tiles, k steps of 16 through LDS
 // (double-buffered).  Every global access is guarded: the edges of every dimension are zero-filled.
 //   A operand lane l: A[m = l&15][k = l>>4]   B operand lane l: B[k = l>>4][n = l&15]
@@ -201,9 +202,12 @@ __global__ __launch_bounds__(256) void pre_gemm_kernel(const PreGemm g)
                 if (m >= g.M || n >= g.Nn) continue;
                 if (EPI == 0) {
                     g.C[(size_t)blockIdx.z * g.cs + (size_t)m * g.ldc + n] = acc[i][j][r];
-                } else {
+                } else if (EPI == 1) {
                     double* p = g.X + (size_t)m * g.ldx + n;
                     *p = fmax(*p - acc[i][j][r], 0.0);
+                } else {
+                    double* p = g.X + (size_t)m * g.ldx + n;
+                    *p = *p - acc[i][j][r];
                 }
             }
 }
@@ -579,6 +583,11 @@ extern "C" int cnmf_preprocess_ridge_moments(cnmf_ctx* ctx, int32_t slot, int32_
 
 extern "C" int cnmf_preprocess_ridge_apply(cnmf_ctx* ctx, int32_t slot, const double* W)
 {
+    return cnmf_preprocess_ridge_apply_mode(ctx, slot, W, 1);
+}
+
+extern "C" int cnmf_preprocess_ridge_apply_mode(cnmf_ctx* ctx, int32_t slot, const double* W, int32_t clip)
+{
     using namespace cnmf;
     if (int rc = pre_need_dense(ctx, slot)) return rc;
     if (!W) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
@@ -595,7 +604,9 @@ extern "C" int cnmf_preprocess_ridge_apply(cnmf_ctx* ctx, int32_t slot, const do
     PreGemm g{};
     g.M = N; g.Nn = C; g.K = KB; g.kps = KB; g.X = S.dense; g.ldx = C; g.Rt = P.Rt; g.Pt = P.Pt; g.KR = P.K; g.B1 = P.B1;
     g.Bm = dW; g.ldb = C;
-    pre_gemm_kernel<3, 0, 1><<<dim3((C + 63) / 64, (N + 63) / 64, 1), 256, 0, st>>>(g);
+    const dim3 grid((C + 63) / 64, (N + 63) / 64, 1);
+    if (clip) pre_gemm_kernel<3, 0, 1><<<grid, 256, 0, st>>>(g);
+    else pre_gemm_kernel<3, 0, 2><<<grid, 256, 0, st>>>(g);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return CNMF_OK;

@@ -89,6 +89,27 @@ struct PreStage {
     void release() { release_counts(); release_ridge(); slot[0].release(); slot[1].release(); N = 0; }
 };
 
+// state of the cnmf_harmony_* entry points (harmony_host.hip.h): Harmony's soft clustering of N cells over d components
+// into K clusters.  Cell-indexed arrays are component- or cluster-major with rows of N_pad (a multiple of 64) doubles.
+struct HarStage {
+    int N = 0, Np = 0, d = 0, K = 0, V = 0, B = 0;       // V variables with B levels in all; N = 0: nothing begun
+    bool ready = false;                                  // cnmf_harmony_init has run
+    double *Zo = nullptr, *Zcos = nullptr, *Zcorr = nullptr;          // [d][Np]
+    double *R = nullptr, *dist = nullptr, *S = nullptr;              // [K][Np]
+    double *ZoT = nullptr, *ZcT = nullptr, *Rt = nullptr, *Pt = nullptr;   // [N][d], [N][d], [N][K], [N][B + 1] (the ridge step)
+    double *Y = nullptr, *theta = nullptr, *sigma = nullptr, *prb = nullptr;   // [d][K], [B], [K], [B]
+    double *E = nullptr, *O = nullptr, *tab = nullptr, *obj = nullptr;     // [K][B] x 3, [3]
+    double *ypart = nullptr, *opart = nullptr, *part_old = nullptr, *part_new = nullptr;
+    size_t part_old_cap = 0, part_new_cap = 0;           // doubles
+    int *codes = nullptr, *lvar = nullptr, *perm = nullptr;               // [V][Np] level of every cell, [B] variable of a level, [N]
+    void release() {
+        void* all[] = {Zo, Zcos, Zcorr, R, dist, S, ZoT, ZcT, Rt, Pt, Y, theta, sigma, prb, E, O, tab, obj, ypart, opart,
+                       part_old, part_new, codes, lvar, perm};
+        for (void* p : all) hipFree(p);
+        *this = HarStage{};
+    }
+};
+
 static constexpr int RING = 8;
 #ifndef CNMF_GEMM3_DEFAULT
 #define CNMF_GEMM3_DEFAULT 4
@@ -196,6 +217,7 @@ struct cnmf_ctx {
 
     PrepStage prep;                   // cnmf_prepare_* staging (prepare_host.hip.h), apart from the resident matrix
     PreStage pre;                     // cnmf_preprocess_* staging (preprocess_host.hip.h)
+    HarStage har;                     // cnmf_harmony_* state (harmony_host.hip.h)
 };
 
 static const char* ctx_getenv(const cnmf_ctx* ctx, const char* name)

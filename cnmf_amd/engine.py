@@ -439,10 +439,115 @@ class Engine:
                                                             G.ctypes.data_as(dblp)))
         return M, G
 
-    def preprocess_ridge_apply(self, slot, W):
-        """Dense slot X := max(X - sum_k sum_b (R[k] Phi[b])^T W[k, b], 0), W [K][B1][n], factors of the last moments."""
+    def preprocess_ridge_apply(self, slot, W, clip=True):
+        """Dense slot X := max(X - sum_k sum_b (R[k] Phi[b])^T W[k, b], 0), W [K][B1][n], factors of the last moments.
+        ``clip=False``: without the maximum (a matrix with negative entries)."""
         W = np.ascontiguousarray(W, dtype=np.float64)
-        self._check(self._lib.cnmf_preprocess_ridge_apply(self._ctx, int(slot), W.ctypes.data_as(C.POINTER(C.c_double))))
+        dblp = C.POINTER(C.c_double)
+        if clip:
+            self._check(self._lib.cnmf_preprocess_ridge_apply(self._ctx, int(slot), W.ctypes.data_as(dblp)))
+        else:
+            self._check(self._lib.cnmf_preprocess_ridge_apply_mode(self._ctx, int(slot), W.ctypes.data_as(dblp), 0))
+
+    # ------------------------------------------------------------------ harmony (cnmf_harmony_*, harmony_host.hip.h)
+    # Harmony's clustering loop with a state of its own: the preprocess staging stays as it is.
+    @staticmethod
+    def harmony_check_limits(d, K, B):
+        """NotImplementedError above the device limits of the harmony entry points"""
+        if K > _lib.CNMF_HARMONY_KMAX:
+            raise NotImplementedError("K = %d clusters is above the device limit %d" % (K, _lib.CNMF_HARMONY_KMAX))
+        if d > _lib.CNMF_HARMONY_DMAX:
+            raise NotImplementedError("d = %d components is above the device limit %d" % (d, _lib.CNMF_HARMONY_DMAX))
+        if K * (B + 1) > _lib.CNMF_RIDGE_MAX:
+            raise NotImplementedError("K * (B + 1) = %d is above the device limit %d" % (K * (B + 1), _lib.CNMF_RIDGE_MAX))
+
+    def harmony_begin(self, pca, codes, level_var, theta, sigma, pr_b):
+        """pca [N][d]; codes [V][N] int32: every cell's level (an index into the B levels of all variables) per variable;
+        level_var [B]: the variable of each level; theta [B], sigma [K], pr_b [B]."""
+        pca = np.ascontiguousarray(pca, dtype=np.float64)
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        level_var = np.ascontiguousarray(level_var, dtype=np.int32)
+        theta, sigma, pr_b = (np.ascontiguousarray(a, dtype=np.float64) for a in (theta, sigma, pr_b))
+        if pca.ndim != 2 or codes.ndim != 2 or codes.shape[1] != pca.shape[0] or level_var.ndim != 1:
+            raise ValueError("pca %s, codes %s, level_var %s" % (pca.shape, codes.shape, level_var.shape))
+        N, d = pca.shape
+        V, B, K = codes.shape[0], level_var.shape[0], sigma.shape[0]
+        if theta.shape != (B,) or pr_b.shape != (B,) or sigma.ndim != 1 or K < 1 or N < 1 or d < 1:
+            raise ValueError("theta %s, pr_b %s for %d levels; sigma %s" % (theta.shape, pr_b.shape, B, sigma.shape))
+        if not np.isfinite(pca).all():
+            raise ValueError("pca holds non-finite values")
+        if codes.size and (codes.min() < 0 or codes.max() >= B or not (level_var[codes] == np.arange(V)[:, None]).all()):
+            raise ValueError("codes do not name levels of their variable")
+        self.harmony_check_limits(d, K, B)
+        dblp, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        self._check(self._lib.cnmf_harmony_begin(self._ctx, N, d, K, V, B, pca.ctypes.data_as(dblp), codes.ctypes.data_as(i32p),
+                                                 level_var.ctypes.data_as(i32p), theta.ctypes.data_as(dblp),
+                                                 sigma.ctypes.data_as(dblp), pr_b.ctypes.data_as(dblp)))
+        self._har = {"N": N, "d": d, "K": K, "B": B}
+
+    def _har_state(self):
+        har = getattr(self, "_har", None)
+        if har is None:
+            raise RuntimeError("harmony_begin has not been called")
+        return har
+
+    def harmony_init(self, Y):
+        """Y [d][K] unit centroids; returns the three objective terms [3]."""
+        har = self._har_state()
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.shape != (har["d"], har["K"]) or not np.isfinite(Y).all():
+            raise ValueError("centroids %s for d = %d, K = %d (finite values)" % (Y.shape, har["d"], har["K"]))
+        obj = np.empty(3)
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_harmony_init(self._ctx, Y.ctypes.data_as(dblp), obj.ctypes.data_as(dblp)))
+        return obj
+
+    def harmony_kmeans_step(self, perm, n_blocks):
+        """one k-means iteration with update_R over np.array_split(perm, n_blocks); returns the objective terms [3]."""
+        har = self._har_state()
+        perm = np.ascontiguousarray(perm, dtype=np.int32)
+        if perm.shape != (har["N"],):
+            raise ValueError("perm %s for %d cells" % (perm.shape, har["N"]))
+        if not 1 <= int(n_blocks) <= 4096:
+            raise ValueError("n_blocks = %s outside [1, 4096]" % (n_blocks,))
+        obj = np.empty(3)
+        self._check(self._lib.cnmf_harmony_kmeans_step(self._ctx, perm.ctypes.data_as(C.POINTER(C.c_int32)), int(n_blocks),
+                                                       obj.ctypes.data_as(C.POINTER(C.c_double))))
+        return obj
+
+    def harmony_ridge_moments(self):
+        """M [K][B1][d] and gram [K][B1][B1] of the ridge step over Z_orig^T with the current R."""
+        har = self._har_state()
+        K, B1, d = har["K"], har["B"] + 1, har["d"]
+        M, G = np.empty((K, B1, d)), np.empty((K, B1, B1))
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_harmony_ridge_moments(self._ctx, M.ctypes.data_as(dblp), G.ctypes.data_as(dblp)))
+        return M, G
+
+    def harmony_ridge_apply(self, W):
+        har = self._har_state()
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.shape != (har["K"], har["B"] + 1, har["d"]):
+            raise ValueError("W %s, expected %s" % (W.shape, (har["K"], har["B"] + 1, har["d"])))
+        self._check(self._lib.cnmf_harmony_ridge_apply(self._ctx, W.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def harmony_fetch(self, z_cos_only=False):
+        """(Z_corr [d][N], Z_cos [d][N], R [K][N], Y [d][K]); ``z_cos_only``: Z_cos alone."""
+        har = self._har_state()
+        N, d, K = har["N"], har["d"], har["K"]
+        dblp = C.POINTER(C.c_double)
+        Zs = np.empty((d, N))
+        if z_cos_only:
+            self._check(self._lib.cnmf_harmony_fetch(self._ctx, None, Zs.ctypes.data_as(dblp), None, None))
+            return Zs
+        Zc, R, Y = np.empty((d, N)), np.empty((K, N)), np.empty((d, K))
+        self._check(self._lib.cnmf_harmony_fetch(self._ctx, Zc.ctypes.data_as(dblp), Zs.ctypes.data_as(dblp),
+                                                 R.ctypes.data_as(dblp), Y.ctypes.data_as(dblp)))
+        return Zc, Zs, R, Y
+
+    def harmony_release(self):
+        self._check(self._lib.cnmf_harmony_release(self._ctx))
+        self._har = None
 
     def preprocess_row_sums(self):
         """Row sums [N] of the staged counts (the sums normalize_total divides by)."""

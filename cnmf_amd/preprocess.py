@@ -37,6 +37,30 @@ and the library-size-normalised matrix over all genes (``tp10k``); ``normalize_b
 staging that is already there.  Counts are integers, so every sum is exact; ``pct_mito`` and the normalised values are one
 rounding each: all of it equals the reference bit for bit.
 
+``Preprocess.run_harmony`` is harmonypy's ``run_harmony`` with the clustering loop on the device
+(csrc/harmony_host.hip.h), opt-in through ``harmony="device"`` on ``harmony_correct_X``, ``normalize_batchcorrect`` and
+``preprocess_for_cnmf`` (the default, ``"harmonypy"``, calls the library as before; ``harmony_res`` wins over both).  With
+Z = pca^T [d][N], Phi the one-hot levels of the variables in ``pd.get_dummies`` order (B rows), Pr_b their frequencies,
+theta and lamb one value per level and sigma per cluster:
+
+* start: Z_cos = Z / max over a cell's scores, then every cell at unit L2 norm; Y = the centres of KMeans(K, k-means++,
+  n_init=10, max_iter=25, random_state) on Z_cos^T at unit norm -- **this initialisation runs in scikit-learn on the
+  host**; dist = 2 (1 - Y^T Z_cos); R = softmax(-dist / sigma) per cell; E = outer(R 1, Pr_b), O = R Phi^T;
+* objective = sum R dist + sum sigma R log R + sum sigma R (theta log((O + 1) / (E + 1)) Phi);
+* a round: cluster() -- up to max_iter_kmeans times Y = Z_cos R^T at unit norm, dist, update_R, the objective, and from the
+  fifth iteration on a stop when the sums of two overlapping windows of three objectives differ by less than
+  epsilon_cluster (relative) -- then the ridge correction of Z with the current R (Z_corr; Z_cos = Z_corr at unit norm),
+  and a stop when the objective fell by less than epsilon_harmony (relative);
+* update_R: S = exp(-dist / sigma - max); the cells in ``np.random.shuffle`` order, split into ceil(1 / block_size) blocks
+  (``np.array_split``); per block: E, O without the block, R = S * (((E + 1) / (O + 1))^theta Phi) at unit L1 norm per
+  cell, the block put back.
+
+The device differs from a numpy run in the order of its sums and in the last place of exp / log / pow.  **The yardstick is
+the float64 numpy restatement of the above in tests/_harmony_ref.py** (rounds equal; R, Z_corr, Y and the objectives
+within 16 x the restatement's distance from its own long double run).  **Agreement with harmonypy itself is unmeasured on
+this project's machines**: the library is not installed on them; tests/test_host_harmony.py compares the restatement
+with it wherever it can be imported.
+
 Out of scope: the seurat_v3 HVG selection (``n_top_genes`` / ``n_top_rna_genes``: it needs skmisc's loess), plots
 (``makeplots`` is accepted and nothing is drawn) and ``.h5ad`` writing.
 """
@@ -233,6 +257,78 @@ def _import_harmonypy():
     return harmonypy
 
 
+HARMONY_MODES = ("harmonypy", "device")
+SKLEARN_IMPORT_ERROR = ("run_harmony needs scikit-learn for its k-means initialisation (sklearn.cluster.KMeans on the host); "
+                        "install it or pass init_centroids")
+
+
+def _check_harmony_mode(harmony):
+    if harmony not in HARMONY_MODES:
+        raise ValueError("harmony must be one of %s, not %r" % (HARMONY_MODES, harmony))
+
+
+class HarmonyResult:
+    """What ``Preprocess.run_harmony`` returns, in harmonypy's old layout: ``Z_corr`` [d][N], ``Z_cos`` [d][N], ``R``
+    [K][N], ``Y`` [d][K], ``Phi_moe`` [B + 1][N], ``K``, ``lamb`` ((B + 1) x (B + 1) diagonal, first entry 0),
+    ``objective_harmony``, ``objective_kmeans`` and ``kmeans_rounds`` (per cluster() call, the index of its last k-means
+    iteration, as harmonypy records it)."""
+
+
+def harmony_nclust(N):
+    """harmonypy's default number of clusters: N / 30 rounded half to even, at most 100"""
+    return int(min(np.round(N / 30.0), 100))
+
+
+def harmony_per_level(value, n_levels, what):
+    """theta / lamb as one value per level: a scalar is repeated over all levels, one value per variable over its levels"""
+    if np.ndim(value) == 0:
+        return np.repeat([float(value)] * len(n_levels), n_levels).astype(np.float64)
+    value = np.asarray(value, dtype=np.float64).reshape(-1)
+    if len(value) == len(n_levels):
+        return np.repeat(value, n_levels)
+    if len(value) == int(np.sum(n_levels)):
+        return value.copy()
+    raise ValueError("%s has %d values for %d variables with %d levels" % (what, len(value), len(n_levels), np.sum(n_levels)))
+
+
+def harmony_design(obs, harmony_vars):
+    """The batch design of ``obs[harmony_vars]``: ``(Phi, codes, level_var, n_levels)`` with Phi [B][N] the one-hot matrix
+    in ``pd.get_dummies(obs[vars])`` column order, codes [V][N] int32 the row of Phi each cell holds for every variable,
+    level_var [B] the variable of every level and n_levels the levels per variable.  A variable that get_dummies does not
+    expand (a numeric column) is refused: cast it to str or category."""
+    vars_use = _harmony_vars_list(harmony_vars)
+    Phi = pd.get_dummies(obs[vars_use]).to_numpy().T.astype(np.float64)
+    n_levels = [pd.get_dummies(obs[[v]]).shape[1] for v in vars_use]
+    if Phi.shape[0] != int(np.sum(n_levels)):
+        raise ValueError("harmony_vars %s do not expand to one column per level" % (vars_use,))
+    codes = np.empty((len(vars_use), Phi.shape[1]), dtype=np.int32)
+    level_var = np.repeat(np.arange(len(vars_use), dtype=np.int32), n_levels)
+    start = 0
+    for v, L in enumerate(n_levels):
+        block = Phi[start:start + L]
+        if not (np.isin(block, (0.0, 1.0)).all() and (block.sum(axis=0) == 1).all()):
+            raise ValueError("harmony variable %r is not categorical: every cell needs exactly one level (cast numbers "
+                             "to str)" % (vars_use[v],))
+        codes[v] = start + np.argmax(block, axis=0)
+        start += L
+    return Phi, codes, level_var, n_levels
+
+
+def _host_kmeans_centroids(Z_cos, K, random_state):
+    """Harmony's initialisation, the one step of run_harmony left to scikit-learn on the host: the centres [d][K] of
+    KMeans(k-means++, n_init=10, max_iter=25) on the cells' unit scores, exactly the call harmonypy makes.  scikit-learn
+    is an optional dependency of this route alone (as harmonypy is of the other one), so it is looked up by name when
+    the route runs, never when the package is imported."""
+    import importlib
+    try:
+        cluster = importlib.import_module("sklearn.cluster")
+    except Exception:
+        raise ImportError(SKLEARN_IMPORT_ERROR)
+    model = cluster.KMeans(n_clusters=K, init='k-means++', n_init=10, max_iter=25, random_state=random_state)
+    model.fit(Z_cos.T)
+    return model.cluster_centers_.T
+
+
 class Preprocess:
     def __init__(self, random_seed=None, device=0, engine=None):
         """preprocess.py:42-56: ``np.random.seed(random_seed)``.  ``device`` / ``engine``: where the device steps run
@@ -257,17 +353,118 @@ class Preprocess:
         self._engine, self._own_engine = None, False
 
     # ------------------------------------------------------------------ harmony_correct_X (preprocess.py:362-422)
-    def harmony_correct_X(self, X, obs, pca, harmony_vars, theta=1, max_iter_harmony=20, harmony_res=None):
+    def harmony_correct_X(self, X, obs, pca, harmony_vars, theta=1, max_iter_harmony=20, harmony_res=None,
+                          harmony="harmonypy"):
         """Runs Harmony on ``pca`` (or takes ``harmony_res``) and applies its mixture-of-experts ridge correction to the
-        cells x genes ``X`` (sparse or dense).  Returns ``(X_corr, X_pca_harmony)``: X_corr dense float64, clipped at 0."""
+        cells x genes ``X`` (sparse or dense).  Returns ``(X_corr, X_pca_harmony)``: X_corr dense float64, clipped at 0.
+        ``harmony``: "harmonypy" (the library's run_harmony) or "device" (``self.run_harmony``, harmonypy never imported)."""
         import scipy.sparse as sp
+        _check_harmony_mode(harmony)
         if harmony_res is None:
-            harmonypy = _import_harmonypy()
-            _check_harmony_vars(obs, harmony_vars)
-            harmony_res = harmonypy.run_harmony(pca, obs, harmony_vars, max_iter_harmony=max_iter_harmony, theta=theta)
+            harmony_res = self._harmony(pca, obs, harmony_vars, theta, max_iter_harmony, harmony)
         X = X.toarray() if sp.issparse(X) else np.asarray(X)
         X_corr, X_pca_harmony = self._ridge(X, None, pca, harmony_res)
         return X_corr, X_pca_harmony
+
+    def _harmony(self, pca, obs, harmony_vars, theta, max_iter_harmony, harmony):
+        """the Harmony result of the chosen route (a missing harmonypy is reported before a missing variable, as ever)"""
+        run = self.run_harmony if harmony == "device" else _import_harmonypy().run_harmony
+        _check_harmony_vars(obs, harmony_vars)
+        return run(pca, obs, harmony_vars, max_iter_harmony=max_iter_harmony, theta=theta)
+
+    # ------------------------------------------------------------------ run_harmony (harmonypy's run_harmony, on the device)
+    def run_harmony(self, pca, obs, harmony_vars, theta=1, max_iter_harmony=20, *, nclust=None, sigma=0.1, lamb=1,
+                    block_size=0.05, max_iter_kmeans=20, epsilon_cluster=1e-5, epsilon_harmony=1e-4, random_state=0,
+                    init_centroids=None):
+        """Harmony's soft clustering and correction of the PCA scores ``pca`` [N][d] for the batch variables
+        ``obs[harmony_vars]``, with harmonypy's argument meanings and defaults (see the module docstring for the
+        algorithm).  The clustering loop, the objective and the ridge correction run on the device in float64
+        (csrc/harmony_host.hip.h); the k-means initialisation is scikit-learn's KMeans on the host unless
+        ``init_centroids`` [d][K] is given; per k-means iteration the host draws one permutation from numpy's global
+        RandomState (seeded with ``random_state`` at the start, as harmonypy does) and reads the objective back.
+        Returns a HarmonyResult, which ``harmony_res=`` of harmony_correct_X / normalize_batchcorrect accepts.
+
+        The device loop gives the same bits on every run.  scikit-learn's KMeans does not beyond 256 cells (its threads add
+        their partial sums in completion order: the centroids move in the last bit from run to run), so two calls agree bit
+        for bit when they are given the same ``init_centroids``, and to rounding otherwise.
+
+        Limits: K <= 128, d <= 64, K (B + 1) <= 4096 (NotImplementedError above).  ``sigma`` is a scalar."""
+        from .engine import Engine
+        pca = np.asarray(pca, dtype=np.float64)
+        if pca.ndim != 2:
+            raise ValueError("pca must be cells x components, not %s" % (pca.shape,))
+        _check_harmony_vars(obs, harmony_vars)
+        N, d = pca.shape
+        if len(obs) != N:
+            raise ValueError("obs has %d rows for %d cells" % (len(obs), N))
+        if not np.isfinite(pca).all():
+            raise ValueError("pca holds non-finite values")
+        if np.ndim(sigma) != 0 or not float(sigma) > 0:
+            raise ValueError("sigma must be a positive scalar")
+        if not 0 < block_size <= 1:
+            raise ValueError("block_size must be in (0, 1]")
+        if max_iter_harmony < 0 or max_iter_kmeans < 1:
+            raise ValueError("max_iter_harmony >= 0 and max_iter_kmeans >= 1 are required")
+        K = int(nclust) if nclust is not None else harmony_nclust(N)
+        if K < 1 or (K > N and init_centroids is None):
+            raise ValueError("nclust = %d for %d cells (more clusters than cells need init_centroids)" % (K, N))
+        Phi, codes, level_var, n_levels = harmony_design(obs, harmony_vars)
+        B = Phi.shape[0]
+        Engine.harmony_check_limits(d, K, B)
+        theta_b = harmony_per_level(theta, n_levels, "theta")
+        lamb_mat = np.diag(np.insert(harmony_per_level(lamb, n_levels, "lamb"), 0, 0))
+        n_blocks = int(np.ceil(1 / block_size))
+        if n_blocks > 4096:
+            raise ValueError("block_size = %g gives more than 4096 blocks" % block_size)
+        if init_centroids is not None:
+            init_centroids = np.asarray(init_centroids, dtype=np.float64)
+            if init_centroids.shape != (d, K):
+                raise ValueError("init_centroids %s, expected %s" % (init_centroids.shape, (d, K)))
+        Pr_b = Phi.sum(axis=1) / N
+        np.random.seed(random_state)
+        eng = self.engine
+        res = HarmonyResult()
+        res.K, res.lamb = K, lamb_mat
+        res.Phi_moe = np.vstack((np.repeat(1.0, N), Phi))
+        res.objective_harmony, res.objective_kmeans, res.kmeans_rounds = [], [], []
+        total = lambda terms: terms[0] + terms[1] + terms[2]          # (kmeans error + entropy + cross entropy, in this order)
+        try:
+            eng.harmony_begin(pca, codes, level_var, theta_b, np.repeat(float(sigma), K), Pr_b)
+            if init_centroids is None:
+                Y = _host_kmeans_centroids(eng.harmony_fetch(z_cos_only=True), K, random_state)
+            else:
+                Y = init_centroids
+            Y = Y / np.sqrt((Y * Y).sum(axis=0))
+            res.objective_kmeans.append(total(eng.harmony_init(Y)))
+            res.objective_harmony.append(res.objective_kmeans[-1])
+            for _ in range(max_iter_harmony):
+                # cluster()
+                i = -1
+                for i in range(max_iter_kmeans):
+                    order = np.arange(N)
+                    np.random.shuffle(order)
+                    res.objective_kmeans.append(total(eng.harmony_kmeans_step(order, n_blocks)))
+                    if i > 3:
+                        o = res.objective_kmeans
+                        old, new = o[-2] + o[-3] + o[-4], o[-1] + o[-2] + o[-3]
+                        if abs(old - new) / abs(old) < epsilon_cluster:
+                            break
+                res.kmeans_rounds.append(i)
+                res.objective_harmony.append(res.objective_kmeans[-1])
+                # moe_correct_ridge on Z_orig with the current R
+                M, gram = eng.harmony_ridge_moments()
+                W = np.empty_like(M)
+                for k in range(K):
+                    W[k] = np.linalg.inv(gram[k] + lamb_mat) @ M[k]
+                    W[k][0, :] = 0
+                eng.harmony_ridge_apply(W)
+                old, new = res.objective_harmony[-2], res.objective_harmony[-1]
+                if (old - new) / abs(old) < epsilon_harmony:
+                    break
+            res.Z_corr, res.Z_cos, res.R, res.Y = eng.harmony_fetch()
+        finally:
+            eng.harmony_release()
+        return res
 
     def _ridge(self, X, slot, pca, harmony_res):
         """moe_correct_ridge on the device over X (uploaded to slot 1) or over the dense device slot ``slot``."""
@@ -305,17 +502,19 @@ class Preprocess:
     # ------------------------------------------------------------------ normalize_batchcorrect (preprocess.py:246-360)
     def normalize_batchcorrect(self, data, obs=None, highly_variable=None, normalize_librarysize=False, harmony_vars=None,
                                n_top_genes=None, librarysize_targetsum=1e4, max_scaled_thresh=None, quantile_thresh=.9999,
-                               theta=1, makeplots=True, max_iter_harmony=20, harmony_res=None):
+                               theta=1, makeplots=True, max_iter_harmony=20, harmony_res=None, harmony="harmonypy"):
         """Normalises the high-variance genes of raw counts and optionally corrects them with Harmony.  Returns
         ``(result, hvgs)``: ``result.X`` goes straight into ``cNMF.prepare(counts=(result.X, result.obs_names, hvgs),
-        ...)``."""
+        ...)``.  ``harmony``: who runs Harmony when ``harmony_res`` is not given: "harmonypy" (the library) or "device"
+        (``self.run_harmony``)."""
         if n_top_genes is not None:
             raise NotImplementedError(N_TOP_GENES_ERROR)
         if highly_variable is None:
             raise Exception(HVG_REQUIRED_ERROR)
         _check_quantile(quantile_thresh)
+        _check_harmony_mode(harmony)
         if harmony_vars is not None:
-            if harmony_res is None:
+            if harmony_res is None and harmony == "harmonypy":
                 _import_harmonypy()
             _check_harmony_vars(obs, harmony_vars)
         mat, cells, genes, dense = _data_parts(data)
@@ -331,13 +530,14 @@ class Preprocess:
             eng.preprocess_upload(X)
             Xout, obsm = self._batchcorrect_staged(eng, X.shape[0], sel, dense, obs, normalize_librarysize, harmony_vars,
                                                    librarysize_targetsum, max_scaled_thresh, quantile_thresh, theta,
-                                                   max_iter_harmony, harmony_res)
+                                                   max_iter_harmony, harmony_res, harmony)
         finally:
             eng.preprocess_release()
         return PreprocessResult(Xout, cells, pd.Index(hvgs), obs, obsm), hvgs
 
     def _batchcorrect_staged(self, eng, N, sel, dense, obs, normalize_librarysize, harmony_vars, librarysize_targetsum,
-                             max_scaled_thresh, quantile_thresh, theta, max_iter_harmony, harmony_res):
+                             max_scaled_thresh, quantile_thresh, theta, max_iter_harmony, harmony_res,
+                             harmony="harmonypy"):
         """normalize_batchcorrect (preprocess.py:314-358) over the counts ``eng`` has staged (N cells), for the staged
         genes ``sel``: returns ``(X, obsm)``.  The caller uploads and releases."""
         n = int(sel.size)
@@ -355,8 +555,7 @@ class Preprocess:
             slot = 0 if normalize_librarysize else 1
             eng.preprocess_densify(slot)
             if harmony_res is None:
-                harmony_res = _import_harmonypy().run_harmony(obsm["X_pca"], obs, harmony_vars,
-                                                              max_iter_harmony=max_iter_harmony, theta=theta)
+                harmony_res = self._harmony(obsm["X_pca"], obs, harmony_vars, theta, max_iter_harmony, harmony)
             Xout, obsm["X_pca_harmony"] = self._ridge(None, slot, obsm["X_pca"], harmony_res)
         else:
             target = float(librarysize_targetsum) if normalize_librarysize else 0.0
@@ -429,7 +628,8 @@ class Preprocess:
     def preprocess_for_cnmf(self, data, obs=None, highly_variable=None, feature_type=None,
                             adt_feature_name='Antibody Capture', harmony_vars=None, n_top_rna_genes=None,
                             librarysize_targetsum=1e4, max_scaled_thresh=None, quantile_thresh=.9999, makeplots=True,
-                            theta=1, save_output_base=None, max_iter_harmony=20, exclude_genes=None, harmony_res=None):
+                            theta=1, save_output_base=None, max_iter_harmony=20, exclude_genes=None, harmony_res=None,
+                            harmony="harmonypy"):
         """The reference's minimal preprocessing: the HVG-filtered, variance-normalised, optionally Harmony-corrected RNA
         matrix (the ``counts`` input of cNMF) and the library-size-normalised matrix over all genes, ADT features
         appended and normalised on their own (the ``tpm`` input).
@@ -462,8 +662,9 @@ class Preprocess:
         if highly_variable is None:
             raise Exception(HVG_REQUIRED_ERROR)
         _check_quantile(quantile_thresh)
+        _check_harmony_mode(harmony)
         if harmony_vars is not None:
-            if harmony_res is None:
+            if harmony_res is None and harmony == "harmonypy":
                 _import_harmonypy()
             _check_harmony_vars(obs, harmony_vars)
         mat, cells, genes, dense = _data_parts(rna)
@@ -522,7 +723,7 @@ class Preprocess:
                     print("exclude_genes provided but none found in adata_RNA.var_names.")
             Xout, obsm = self._batchcorrect_staged(eng, X.shape[0], sel, dense, obs, False, harmony_vars, target,
                                                    max_scaled_thresh, quantile_thresh, theta, max_iter_harmony,
-                                                   harmony_res)
+                                                   harmony_res, harmony)
             tp_genes, tp_types = genes, types_rna
             if adt is not None:
                 eng.preprocess_upload(Xa)                           # normalised on its own (:254)

@@ -35,6 +35,8 @@ extern "C" {
 #define CNMF_EUNSUPPORTED -5   /* e.g. rank > CNMF_KMAX (NotImplementedError)    */
 #define CNMF_ECOMM        -6   /* RCCL failure                                   */
 
+#define CNMF_HARMONY_KMAX 128  /* most clusters of cnmf_harmony_begin (CNMF_EUNSUPPORTED above)                             */
+#define CNMF_HARMONY_DMAX 64   /* most components of cnmf_harmony_begin                                                     */
 #define CNMF_RIDGE_MAX 4096    /* largest K * (B + 1) of cnmf_preprocess_ridge_moments (CNMF_EUNSUPPORTED above)      */
 #define CNMF_KMAX 128          /* largest rank of the coordinate-descent / NNLS / consensus entry points
                                   (<= 64: register-resident sweep; 65..128: sweep_big_kernel)              */
@@ -201,6 +203,7 @@ int cnmf_prepare_release(cnmf_ctx* ctx);
  *                                M [K*B1][n] = A X and gram [K*B1][B1] = A Phi^T with A[k*B1 + b][i] = R[k][i] Phi[b][i].
  *                                Keeps Rt / Phit for the apply.
  *   cnmf_preprocess_ridge_apply  dense slot X := max(X - A^T W, 0) in place, W [K*B1][n] (the last moments' K, B1).
+ *   cnmf_preprocess_ridge_apply_mode  the same with clip != 0; clip == 0: X := X - A^T W, for a matrix with negative entries.
  *   cnmf_preprocess_row_sums     row_sums [n_cells] of the staged counts (the sums normalize_total divides by).
  *   cnmf_preprocess_normalize_dense  slot := ALL genes of the staged counts as a dense [n_cells][n_genes] matrix, rows
  *                                scaled as cnmf_preprocess_select scales them (target_sum > 0), each column divided by its
@@ -246,6 +249,7 @@ int cnmf_preprocess_project(cnmf_ctx* ctx, int32_t slot, int32_t n_comp, const d
 int cnmf_preprocess_ridge_moments(cnmf_ctx* ctx, int32_t slot, int32_t K, int32_t B1, const double* Rt, const double* Phit,
                                   double* M /* [K*B1][n] */, double* gram /* [K*B1][B1] */);
 int cnmf_preprocess_ridge_apply(cnmf_ctx* ctx, int32_t slot, const double* W /* [K*B1][n] */);
+int cnmf_preprocess_ridge_apply_mode(cnmf_ctx* ctx, int32_t slot, const double* W /* [K*B1][n] */, int32_t clip);
 int cnmf_preprocess_row_sums(cnmf_ctx* ctx, double* row_sums /* [n_cells] */);
 int cnmf_preprocess_normalize_dense(cnmf_ctx* ctx, int32_t slot, double target_sum, double max_value,
                                     double* std_out /* [n_genes] */);
@@ -261,6 +265,36 @@ int cnmf_preprocess_subset(cnmf_ctx* ctx, const uint8_t* keep_cells /* [n_cells]
                            const uint8_t* keep_genes /* [n_genes] or NULL */, int64_t* n_cells_out, int64_t* n_genes_out,
                            int64_t* nnz_out);
 int cnmf_preprocess_fetch_counts(cnmf_ctx* ctx, double target_sum, int64_t* indptr, int32_t* indices, double* values);
+
+/* ---- Harmony's clustering loop (harmony_host.hip.h) -----------------------------------------------------------------
+ * The loop of harmonypy's run_harmony over N cells, d components, K clusters and n_vars batch variables with n_levels
+ * levels in all (B): float64, state of its own in the context, fixed summation orders, no float atomics -- two runs give
+ * the same bits.  The caller keeps the control flow (Preprocess.run_harmony) and supplies the k-means initialisation and
+ * every permutation.  Limits: d <= CNMF_HARMONY_DMAX, K <= CNMF_HARMONY_KMAX, K * (B + 1) <= CNMF_RIDGE_MAX.
+ *   cnmf_harmony_begin         pca [N][d] (row-major scores), codes [n_vars][N] (the level, in [0, B), of every cell for every
+ *                              variable), level_var [B] (the variable of a level), theta [B], sigma [K] (> 0), pr_b [B].
+ *                              Z_cos = the scores of a cell divided by their largest, then by their L2 norm.
+ *   cnmf_harmony_init          Y [d][K] (unit centroids): dist = 2 (1 - Y^T Z_cos), R = softmax(-dist / sigma) per cell,
+ *                              E = outer(R 1, pr_b), O = R Phi^T; objective[3] = sum R dist, sum sigma R log R (0 where not
+ *                              finite), sum sigma R (theta log((O + 1) / (E + 1)) Phi).
+ *   cnmf_harmony_kmeans_step   one k-means iteration: Y = Z_cos R^T with unit columns, dist, S = exp(-dist / sigma - max),
+ *                              then update_R over the n_blocks blocks np.array_split(perm, n_blocks) in order (E, O without
+ *                              the block; R = S ((E + 1) / (O + 1))^theta Phi, every cell divided by its L1 norm; the block
+ *                              put back), and the objective.  perm [N]: a permutation of the cells.
+ *   cnmf_harmony_ridge_moments M [K*B1][d] and gram [K*B1][B1] of cnmf_preprocess_ridge_moments over Z_orig^T with the
+ *                              current R and Phi_moe = [1; Phi] (B1 = B + 1).
+ *   cnmf_harmony_ridge_apply   Z_corr = Z_orig - W^T A (not clipped), W [K*B1][d]; Z_cos = Z_corr, every cell at unit L2 norm.
+ *   cnmf_harmony_fetch         Z_corr [d][N], Z_cos [d][N], R [K][N], Y [d][K]; any may be NULL.
+ *   cnmf_harmony_release       frees the state. */
+int cnmf_harmony_begin(cnmf_ctx* ctx, int64_t n_cells, int32_t d, int32_t K, int32_t n_vars, int32_t n_levels,
+                       const double* pca, const int32_t* codes, const int32_t* level_var, const double* theta,
+                       const double* sigma, const double* pr_b);
+int cnmf_harmony_init(cnmf_ctx* ctx, const double* Y /* [d][K] */, double* objective /* [3] */);
+int cnmf_harmony_kmeans_step(cnmf_ctx* ctx, const int32_t* perm /* [N] */, int32_t n_blocks, double* objective /* [3] */);
+int cnmf_harmony_ridge_moments(cnmf_ctx* ctx, double* M /* [K*B1][d] */, double* gram /* [K*B1][B1] */);
+int cnmf_harmony_ridge_apply(cnmf_ctx* ctx, const double* W /* [K*B1][d] */);
+int cnmf_harmony_fetch(cnmf_ctx* ctx, double* Z_corr, double* Z_cos, double* R, double* Y);
+int cnmf_harmony_release(cnmf_ctx* ctx);
 
 /* ---- the restart hot loop ---------------------------------------------------------
  * Replaces the loop body of cNMF.factorize (cnmf.py:735-741): for every restart r,

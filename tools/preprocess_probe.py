@@ -15,8 +15,14 @@ non-zero, CSR input), end to end as a user calls them (uploads and fetches inclu
 scipy / numpy on the same machine (detection counts, sums, the two subsets, normalize_total, the HVG subset, the
 ddof=1 scaling and the quantile ceiling over the dense N x HVG matrix).
 
+``--harmony`` times Preprocess.run_harmony (the clustering loop on the device) on --cells x --components synthetic PCA
+scores with one batch variable of --batches levels and --K clusters: the k-means initialisation (scikit-learn on the
+host) is timed on its own and its centroids are handed to both runs; then the device loop (best of --repeats), and the
+same run through the numpy restatement tests/_harmony_ref.py on this machine's cores.
+
 Usage:  python tools/preprocess_probe.py [--cells 50000] [--genes 2000] [--K 100] [--batches 4] [--out FILE.json]
         python tools/preprocess_probe.py --filter [--filter-cells 50000] [--filter-genes 20000] [--out FILE.json]
+        python tools/preprocess_probe.py --harmony [--cells 50000] [--components 50] [--K 100] [--batches 4] [--out FILE.json]
 """
 import argparse
 import json
@@ -190,9 +196,50 @@ def filter_leg(a):
     return out
 
 
+def harmony_leg(a):
+    from tests import _harmony_ref as ref
+    N, d, K = a.cells, a.components, a.K
+    pca, obs = ref.make_case(N, d, [a.batches], seed=0)
+    hvars = list(obs.columns)
+    out = {"cells": N, "components": d, "K": K, "batches": a.batches, "host_threads": os.environ.get("OMP_NUM_THREADS"),
+           "device_s": []}
+    Z = pca.T
+    Z_cos = Z / Z.max(axis=0)
+    Z_cos = Z_cos / np.sqrt((Z_cos * Z_cos).sum(axis=0))
+    t0 = time.perf_counter()
+    Y0 = pp._host_kmeans_centroids(Z_cos, K, 0)
+    out["host_kmeans_init_s"] = round(time.perf_counter() - t0, 3)
+    with Engine(0) as eng:
+        P = pp.Preprocess(engine=eng)
+        small = ref.make_case(500, 8, [2], seed=1)
+        P.run_harmony(small[0], small[1], ["var0"], max_iter_harmony=1)              # warm-up (code objects)
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            got = P.run_harmony(pca, obs, hvars, nclust=K, init_centroids=Y0)
+            out["device_s"].append(round(time.perf_counter() - t0, 3))
+    best = min(out["device_s"])
+    iters = sum(r + 1 for r in got.kmeans_rounds)
+    out.update({"harmony_rounds": len(got.kmeans_rounds), "kmeans_rounds": [int(r) for r in got.kmeans_rounds],
+                "kmeans_iterations": iters, "device_s_best": best,
+                "device_s_per_harmony_round": round(best / max(len(got.kmeans_rounds), 1), 4),
+                "device_ms_per_kmeans_iteration": round(1e3 * best / max(iters, 1), 3),
+                "host_kmeans_init_share_of_total": round(out["host_kmeans_init_s"] / (out["host_kmeans_init_s"] + best), 3)})
+    t0 = time.perf_counter()
+    h = ref.run_harmony(pca, obs, hvars, nclust=K, init_centroids=Y0)
+    out["numpy_restatement_s"] = round(time.perf_counter() - t0, 3)
+    out["same_rounds_as_restatement"] = bool(h.kmeans_rounds == got.kmeans_rounds)
+    if out["same_rounds_as_restatement"]:
+        out["max_abs_diff_R"] = float(np.max(np.abs(h.R - got.R)))
+        out["max_abs_diff_Z_corr"] = float(np.max(np.abs(h.Z_corr - got.Z_corr)))
+    out["restatement_over_device_loop"] = round(out["numpy_restatement_s"] / best, 2)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--filter", action="store_true")
+    ap.add_argument("--harmony", action="store_true")
+    ap.add_argument("--components", type=int, default=50)
     ap.add_argument("--filter-cells", type=int, default=50000)
     ap.add_argument("--filter-genes", type=int, default=20000)
     ap.add_argument("--cells", type=int, default=50000)
@@ -203,8 +250,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.filter:
-        out = filter_leg(a)
+    if a.filter or a.harmony:
+        out = filter_leg(a) if a.filter else harmony_leg(a)
         print(json.dumps(out, indent=1))
         if a.out:
             with open(a.out, "w") as F:
