@@ -82,18 +82,30 @@ static hipError_t launch_sweep(hipStream_t st, int nslots, float* V, int ldv, in
 {
     // `parts` = partials per slot = workgroups per slot; a workgroup walks `chunks` 256-row tiles
     dim3 grid(parts, nslots);
+    // the W half-step kernels address a slot with 32-bit byte offsets from its first column (sweep_body, B32): the
+    // largest is 64 columns * ldv * 4.  A leading dimension too long for 31 bits takes their flat-address form.
+    const bool a64 = 64ll * ldv * 4 > 0x7fffffffll;
     if (po.dst) {
         // the W half-step of the f16 paths, planes written by the sweep itself (ranks <= 64 only: the caller checks)
-        if (psum || (rmax_part && rmax_scale) || (tiers & 8)) return hipErrorInvalidValue;
+        if (psum || (rmax_part && rmax_scale) || (tiers & 8) || po.TR != G3_MW) return hipErrorInvalidValue;
         const size_t pl = sweep_lds_bytes(kmax, true);
         const int kgp = sweep_kg(kmax);
         if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<0, false, false, true>, (int)sweep_lds_bytes(KSMALL, true))) return e_;
         if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<1, false, false, true>, (int)sweep_lds_bytes(KSMALL, true))) return e_;
         if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<2, false, false, true>, (int)sweep_lds_bytes(KSMALL, true))) return e_;
-#define CNMF_SWEEP_PLN(T_) sweep_kernel<T_, false, false, true><<<grid, 256, pl, st>>>(V, ldv, L, P, sp, gram, slots, l1, gram_part, viol_part, chunks, want_gram, kgp, kmax, rmax_part, nullptr, po)
-        if (tiers & 1) CNMF_SWEEP_PLN(0);
-        if (tiers & 2) CNMF_SWEEP_PLN(1);
-        if (tiers & 4) CNMF_SWEEP_PLN(2);
+#define CNMF_SWEEP_PLN(T_, A_) sweep_kernel<T_, false, false, true, A_><<<grid, 256, pl, st>>>(V, ldv, L, P, sp, gram, slots, l1, gram_part, viol_part, chunks, want_gram, kgp, kmax, rmax_part, nullptr, po)
+        if (a64) {
+            if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<0, false, false, true, true>, (int)sweep_lds_bytes(KSMALL, true))) return e_;
+            if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<1, false, false, true, true>, (int)sweep_lds_bytes(KSMALL, true))) return e_;
+            if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<2, false, false, true, true>, (int)sweep_lds_bytes(KSMALL, true))) return e_;
+            if (tiers & 1) CNMF_SWEEP_PLN(0, true);
+            if (tiers & 2) CNMF_SWEEP_PLN(1, true);
+            if (tiers & 4) CNMF_SWEEP_PLN(2, true);
+            return hipGetLastError();
+        }
+        if (tiers & 1) CNMF_SWEEP_PLN(0, false);
+        if (tiers & 2) CNMF_SWEEP_PLN(1, false);
+        if (tiers & 4) CNMF_SWEEP_PLN(2, false);
 #undef CNMF_SWEEP_PLN
         return hipGetLastError();
     }
@@ -124,6 +136,15 @@ static hipError_t launch_sweep(hipStream_t st, int nslots, float* V, int ldv, in
         if (tiers & 1) CNMF_SWEEP(0, true);
         if (tiers & 2) CNMF_SWEEP(1, true);
         if (tiers & 4) CNMF_SWEEP(2, true);
+    } else if (a64) {
+#define CNMF_SWEEP_A64(T_) sweep_kernel<T_, false, false, false, true><<<grid, 256, lds, st>>>(V, ldv, L, P, sp, gram, slots, l1, gram_part, viol_part, chunks, want_gram, kg, kmax, rmax_part, rmax_scale)
+        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<0, false, false, false, true>, (int)sweep_lds_bytes(KSMALL))) return e_;
+        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<1, false, false, false, true>, (int)sweep_lds_bytes(KSMALL))) return e_;
+        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<2, false, false, false, true>, (int)sweep_lds_bytes(KSMALL))) return e_;
+        if (tiers & 1) CNMF_SWEEP_A64(0);
+        if (tiers & 2) CNMF_SWEEP_A64(1);
+        if (tiers & 4) CNMF_SWEEP_A64(2);
+#undef CNMF_SWEEP_A64
     } else {
         if (tiers & 1) CNMF_SWEEP(0, false);
         if (tiers & 2) CNMF_SWEEP(1, false);

@@ -72,7 +72,7 @@ struct SplitInfo {                  // further partial planes of a stream-K prod
 struct PlaneOut {
     unsigned short* dst;            // planes of the packed factor (nullptr: none)
     const int* shift;               // [KC] exponent per component row
-    int Kb, TR;                     // 16-cell blocks per row (cells_pad / 16), row-tile height (256)
+    int Kb, TR;                     // 16-cell blocks per row (cells_pad / 16), row-tile height (always G3_MW: launch_sweep checks)
 };
 
 // Body of the sweep for one (row chunk, slot); KP = k rounded up (compile-time register array
@@ -89,10 +89,16 @@ struct PlaneOut {
 // PSUM: the products arrive as `sp.mgroups` split-K partial planes (stride sp.tile_rows * 2^20 + sp.tile_cols floats,
 // see psum_info) that are summed here in split order and scaled by the per-row constant sp.split (reinterpreted as
 // const double*) -- the work of reduce_splits_kernel folded into the H half-step (no extra launch, no extra pass).
-#ifndef CNMF_SWEEP_PF
-#define CNMF_SWEEP_PF 0
-#endif
-template <int KP, bool RMX, bool PSUM = false, bool PLN = false>
+// EX: the rank IS KP (the W half-step of ranks <= 16): no clamped duplicate loads, no `c < k` selects, no padded
+// multiply-adds, divisions by a constant.  The padded terms it drops are fmaf(0, 0, grad): they can at most turn a -0.0
+// gradient into +0.0, which neither fabsf(pg) nor fmaxf(w - grad / hess, 0) can see -- same bits out.
+// B32: every factor / product / cut-plane access of the slot goes through a buffer descriptor rebased to the slot's first
+// column (base + off * ldv, wave-uniform), with ONE 32-bit offset pair shared by all arrays: the row part (row * 4) in the
+// vector offset, the column part (c * ldv * 4) in the scalar offset.  The flat form kept a 64-bit base per column and
+// array in SGPR pairs, ran out of SGPRs, and paid lane reads plus 64-bit vector adds per access.  Rebased, the largest
+// offset is k * ldv * 4 bytes whatever the slot's position in the (possibly > 4 GB) array; launch_sweep takes the flat
+// body when 64 * ldv * 4 does not fit 31 bits.  (PSUM's partial planes stay on the flat form.)
+template <int KP, bool RMX, bool PSUM = false, bool PLN = false, bool EX = false, bool B32 = false>
 __device__ __forceinline__ void sweep_body(
     float* __restrict__ V, int ldv, int L, const float* __restrict__ P, const SplitInfo& sp,
     const float* __restrict__ gram, const SlotDesc& sd, int slot, float l1_reg,
@@ -102,7 +108,9 @@ __device__ __forceinline__ void sweep_body(
 {
     constexpr int GMODE = (KP <= 16) ? 0 : ((KP <= 32) ? 1 : 2);
     constexpr int GR = (GMODE == 0) ? 16 : ((GMODE == 1) ? 32 : 64);       // gram tile edge
-    const int gs = kg + 4, wstride = kg + 1;
+    // (EX: the tile [KP][KP] sits in the same region at a compile-time stride -- row addresses become immediates instead
+    // of one SGPR per component row)
+    const int gs = EX ? 20 : kg + 4, wstride = kg + 1;
     float* Gsb = lds;                                                     // [kg][kg+4]
     double* vred = reinterpret_cast<double*>(lds + kg * gs);
     float* rmx = lds + kg * gs + 8;                                       // [4][64] per-wave row maxima
@@ -113,8 +121,14 @@ __device__ __forceinline__ void sweep_body(
 #define GS(t_, r_) Gsb[(t_) * gs + (r_)]
     constexpr int SR = (GMODE == 0) ? 32 : 64;                            // rows of a wave staged at a time
 #define WS(wv_, r_, c_) Wsb[((wv_) * SR + (r_)) * wstride + (c_)]
-    const int k = sd.k, off = sd.off;
+    static_assert(!(B32 && PSUM) && !(EX && KP > 16), "sweep_body: EX is tier 0, B32 has no PSUM form");
+    const int k = EX ? KP : sd.k, off = sd.off;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // B32: descriptors over the slot's k columns only (out-of-range offsets would be dropped, not faulted)
+    const unsigned slot_bytes = B32 ? (unsigned)k * (unsigned)ldv * 4u : 0u;
+    const int col_bytes = ldv * 4;
+#define CNMF_RSRC(ptr_) __builtin_amdgcn_make_buffer_rsrc((void*)((ptr_) + (size_t)off * ldv), 0, (int)slot_bytes, 0x00020000)
+#define CNMF_BLD(rs_, voff_, c_) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_, voff_, min(c_, k - 1) * col_bytes, 0))
     for (int e = tid; e < KP * KP; e += 256) {
         const int r = e / KP, c = e % KP;
         GS(r, c) = (r < k && c < k) ? gram[(size_t)slot * GRAM_SZ + r * GRAM_LD + c] : 0.f;
@@ -135,20 +149,6 @@ __device__ __forceinline__ void sweep_body(
 #pragma unroll
     for (int c = 0; c < (RMX ? KP : 1); ++c) mx[c] = 0.f;
 
-    // Software prefetch (round 6 experiment, -DCNMF_SWEEP_PF=1; W half-step only; NOT adopted): the factor and product values
-    // of chunk ch + 1 are requested before chunk ch is computed.  Same arithmetic, same bits; 2 KP more registers = 128 + 20
-    // spilled and 4 instead of 5 waves per SIMD: 217.6 against 228.9 restarts/s (profiles/r6_sweep_prefetch_ab.txt).
-    constexpr bool PF = (CNMF_SWEEP_PF != 0) && !PSUM;
-    float wn[PF ? KP : 1], pn[PF ? KP : 1];
-    if constexpr (PF) {
-        const int rowc0 = min((int)(blockIdx.x * chunks_per_block) * 256 + tid, L - 1);
-#pragma unroll
-        for (int c = 0; c < KP; ++c) {
-            const size_t idx = (size_t)(off + min(c, k - 1)) * ldv + rowc0;
-            wn[c] = V[idx];
-            pn[c] = P[idx];
-        }
-    }
     for (int ch = 0; ch < chunks_per_block; ++ch) {
         const int row = (blockIdx.x * chunks_per_block + ch) * 256 + tid;
         const bool live = row < L;
@@ -172,25 +172,22 @@ __device__ __forceinline__ void sweep_body(
             // clamped (always valid) addresses; the values of dead lanes / columns >= k are
             // discarded by selects.  (Per-column branches serialise the memory latency.)
             const int rowc = min(row, L - 1);
-            if constexpr (PF) {
+            const int voff = rowc * 4;             // B32: the one vector offset of every load and store of this lane
+            if constexpr (B32) {
+                const auto rV = CNMF_RSRC(V);
+                const auto rP = CNMF_RSRC(P);
 #pragma unroll
-                for (int c = 0; c < KP; ++c) { w[c] = wn[c]; p[c] = pn[c]; }
-                if (ch + 1 < chunks_per_block) {                 // (uniform over the workgroup)
-                    const int rown = min(row + 256, L - 1);
-#pragma unroll
-                    for (int c = 0; c < KP; ++c) {
-                        const size_t idx = (size_t)(off + min(c, k - 1)) * ldv + rown;
-                        wn[c] = V[idx];
-                        pn[c] = P[idx];
-                    }
+                for (int c = 0; c < KP; ++c) {
+                    w[c] = CNMF_BLD(rV, voff, c);
+                    p[c] = CNMF_BLD(rP, voff, c);
                 }
             } else {
 #pragma unroll
-            for (int c = 0; c < KP; ++c) {
-                const size_t idx = (size_t)(off + min(c, k - 1)) * ldv + rowc;
-                w[c] = V[idx];
-                p[c] = P[idx];
-            }
+                for (int c = 0; c < KP; ++c) {
+                    const size_t idx = (size_t)(off + min(c, k - 1)) * ldv + rowc;
+                    w[c] = V[idx];
+                    p[c] = P[idx];
+                }
             }
             if constexpr (PSUM) {
                 const int nsplit = sp.mgroups;
@@ -226,10 +223,16 @@ __device__ __forceinline__ void sweep_body(
             }
             if ((cut0 | cut1) & 1) {              // wave-uniform: one branch per chunk
                 float qq[KP];
+                if constexpr (B32) {
+                    const auto r1 = CNMF_RSRC(sp.plane1);
 #pragma unroll
-                for (int c = 0; c < KP; ++c) {
-                    const size_t idx = (size_t)(off + min(c, k - 1)) * ldv + rowc;
-                    qq[c] = sp.plane1[idx];
+                    for (int c = 0; c < KP; ++c) qq[c] = CNMF_BLD(r1, voff, c);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < KP; ++c) {
+                        const size_t idx = (size_t)(off + min(c, k - 1)) * ldv + rowc;
+                        qq[c] = sp.plane1[idx];
+                    }
                 }
 #pragma unroll
                 for (int c = 0; c < KP; ++c) {
@@ -239,10 +242,16 @@ __device__ __forceinline__ void sweep_body(
             }
             if ((cut0 | cut1) & 2) {
                 float qq[KP];
+                if constexpr (B32) {
+                    const auto r2 = CNMF_RSRC(sp.plane2);
 #pragma unroll
-                for (int c = 0; c < KP; ++c) {
-                    const size_t idx = (size_t)(off + min(c, k - 1)) * ldv + rowc;
-                    qq[c] = sp.plane2[idx];
+                    for (int c = 0; c < KP; ++c) qq[c] = CNMF_BLD(r2, voff, c);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < KP; ++c) {
+                        const size_t idx = (size_t)(off + min(c, k - 1)) * ldv + rowc;
+                        qq[c] = sp.plane2[idx];
+                    }
                 }
 #pragma unroll
                 for (int c = 0; c < KP; ++c) {
@@ -270,23 +279,35 @@ __device__ __forceinline__ void sweep_body(
                     if (hess != 0.f) w[t] = fmaxf(w[t] - grad / hess, 0.f);
                 }
             }
+            if constexpr (B32) {
+                const auto rV = CNMF_RSRC(V);
 #pragma unroll
-            for (int c = 0; c < KP; ++c)
-                if (c < k) V[(size_t)(off + c) * ldv + row] = w[c];
+                for (int c = 0; c < KP; ++c)       // (live lanes only: row == rowc)
+                    if (c < k) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, w[c]), rV, row * 4, c * col_bytes, 0);
+            } else {
+#pragma unroll
+                for (int c = 0; c < KP; ++c)
+                    if (c < k) V[(size_t)(off + c) * ldv + row] = w[c];
+            }
             if constexpr (RMX) {
 #pragma unroll
                 for (int c = 0; c < KP; ++c) mx[c] = fmaxf(mx[c], w[c] * dsc);
             }
         }
+        // EX: the per-lane constants of the Gram staging and of the plane gather (LDS addresses, block / half indices) are
+        // derived from an opaque copy of the lane index, i.e. recomputed per chunk (a few VALU ops): hoisted out of the chunk
+        // loop they were a dozen registers held across the whole CD section, which ranks 15 and 16 do not have at 5 waves
+        int ln = lane;
+        if constexpr (EX) asm volatile("" : "+v"(ln));
         if (want_gram) {
             // Gram of the updated rows on the (otherwise idle) matrix pipe: acc += Wrows^T . Wrows
             if constexpr (GMODE == 0) {
-                const int li = lane & 15, q = lane >> 4;
+                const int li = ln & 15, q = ln >> 4;
 #pragma unroll
                 for (int hf = 0; hf < 2; ++hf) {   // rows 0..31, then 32..63 of the wave (same order of the additions)
-                    if ((lane >> 5) == hf) {
+                    if ((ln >> 5) == hf) {
 #pragma unroll
-                        for (int c = 0; c < GR; ++c) WS(wave, lane & 31, c) = (c < KP) ? w[c < KP ? c : 0] : 0.f;
+                        for (int c = 0; c < GR; ++c) WS(wave, ln & 31, c) = (c < KP) ? w[c < KP ? c : 0] : 0.f;
                     }
                     __builtin_amdgcn_wave_barrier();   // wave-private tile: LDS ops of one wave are in order
 #pragma unroll
@@ -331,12 +352,12 @@ __device__ __forceinline__ void sweep_body(
                     const float y = ldexpf(w[c], shl[c]);
                     unsigned short hb, mb;
                     split2h(y, hb, mb);
-                    tw[c * 64 + lane] = (unsigned)hb | ((unsigned)mb << 16);
+                    tw[c * 64 + ln] = (unsigned)hb | ((unsigned)mb << 16);
                 }
             }
             __builtin_amdgcn_wave_barrier();
             const int kb0 = ((blockIdx.x * chunks_per_block + ch) * 256 + wave * 64) >> 4;       // first 16-cell block of the wave
-            for (int item = lane; item < 8 * k; item += 64) {
+            for (int item = ln; item < 8 * k; item += 64) {
                 const int c = item >> 3, b = (item >> 1) & 3, hf = item & 1;
                 if (kb0 + b >= po.Kb) continue;                                  // row blocks past the padded length
                 const u32x4 d0 = *reinterpret_cast<const u32x4*>(tw + c * 64 + b * 16 + hf * 8);
@@ -346,8 +367,8 @@ __device__ __forceinline__ void sweep_body(
                 oh.z = (d1.x & 0xffffu) | (d1.y << 16); oh.w = (d1.z & 0xffffu) | (d1.w << 16);
                 om.x = (d0.x >> 16) | (d0.y & 0xffff0000u); om.y = (d0.z >> 16) | (d0.w & 0xffff0000u);
                 om.z = (d1.x >> 16) | (d1.y & 0xffff0000u); om.w = (d1.z >> 16) | (d1.w & 0xffff0000u);
-                const int r = off + c, tr = r / po.TR, rin = r % po.TR, swz = (rin >> 2) & 3;
-                unsigned short* g = po.dst + (((size_t)tr * po.Kb + (kb0 + b)) * po.TR + rin) * 32;
+                const int r = off + c, tr = r / G3_MW, rin = r % G3_MW, swz = (rin >> 2) & 3;
+                unsigned short* g = po.dst + (((size_t)tr * po.Kb + (kb0 + b)) * G3_MW + rin) * 32;
                 *reinterpret_cast<u32x4*>(g + ((0 + hf) ^ swz) * 8) = oh;
                 *reinterpret_cast<u32x4*>(g + ((2 + hf) ^ swz) * 8) = om;
             }
@@ -408,6 +429,8 @@ __device__ __forceinline__ void sweep_body(
                        gred[(2 * GR + tid) * (GR + 1) + tid] + gred[(3 * GR + tid) * (GR + 1) + tid]) * 1.0001f;
         rmax_part[(size_t)(off + tid) * gridDim.x + blockIdx.x] = v;
     }
+#undef CNMF_BLD
+#undef CNMF_RSRC
 #undef WS
 #undef GS
 }
@@ -418,8 +441,10 @@ __device__ __forceinline__ void sweep_body(
 // give the common small-rank case the register allocation of the largest (232 VGPR + 64 AGPR = one
 // wave per SIMD).  The host launches only the tiers present in the batch.
 // (TIER 0 without the exact report is the W half-step of the common ranks: held to 5 waves per SIMD)
-template <int TIER, bool RMX = false, bool PSUM = false, bool PLN = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((TIER == 0 && !RMX && !PLN) ? 5 : (TIER == 0 && !RMX ? 4 : 1), 8))) void sweep_kernel(
+// The W half-step (!RMX) takes one exact-rank body per rank 1..16 in tier 0 and the 32-bit slot-relative addressing in
+// every tier (sweep_body: EX, B32); A64 is its flat-address form for leading dimensions too long for that (launch_sweep).
+template <int TIER, bool RMX = false, bool PSUM = false, bool PLN = false, bool A64 = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((TIER == 0 && !RMX) ? 5 : 1, 8))) void sweep_kernel(
     float* __restrict__ V, int ldv, int L,
     const float* __restrict__ P,             // [KC][ldv] products (split-K already reduced)
     SplitInfo sp,
@@ -437,17 +462,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((TIER == 0 
     const SlotDesc sd = slots[slot];
     if (!sd.active) return;
     extern __shared__ __attribute__((aligned(16))) float sweep_lds[];
+    static_assert(!A64 || (!RMX && !PSUM), "A64 is the flat-address form of the W half-step kernels");
+    constexpr bool B32 = !RMX && !PSUM && !A64, EX = B32 && TIER == 0;
 #define CNMF_SW(KP_)                                                                              \
-        sweep_body<KP_, RMX, PSUM, PLN>(V, ldv, L, P, sp, gram, sd, slot, l1_reg, gram_part, viol_part, \
+        sweep_body<KP_, RMX, PSUM, PLN, EX, B32>(V, ldv, L, P, sp, gram, sd, slot, l1_reg, gram_part, viol_part, \
                         chunks_per_block, want_gram, sweep_lds, kg, gld, rmax_part, rmax_scale, po);
     const int k = sd.k;
-    if (TIER == 0) {
+    if constexpr (TIER == 0) {
         if (k > 16) return;
-        switch ((k + 3) / 4) {
-            case 1: CNMF_SW(4) break;   case 2: CNMF_SW(8) break;   case 3: CNMF_SW(12) break;
-            case 4: CNMF_SW(16) break;  default: break;
+        if constexpr (EX) {
+            switch (k) {
+                case 1: CNMF_SW(1) break;    case 2: CNMF_SW(2) break;    case 3: CNMF_SW(3) break;    case 4: CNMF_SW(4) break;
+                case 5: CNMF_SW(5) break;    case 6: CNMF_SW(6) break;    case 7: CNMF_SW(7) break;    case 8: CNMF_SW(8) break;
+                case 9: CNMF_SW(9) break;    case 10: CNMF_SW(10) break;  case 11: CNMF_SW(11) break;  case 12: CNMF_SW(12) break;
+                case 13: CNMF_SW(13) break;  case 14: CNMF_SW(14) break;  case 15: CNMF_SW(15) break;  case 16: CNMF_SW(16) break;
+                default: break;
+            }
+        } else {
+            switch ((k + 3) / 4) {
+                case 1: CNMF_SW(4) break;   case 2: CNMF_SW(8) break;   case 3: CNMF_SW(12) break;
+                case 4: CNMF_SW(16) break;  default: break;
+            }
         }
-    } else if (TIER == 1) {
+    } else if constexpr (TIER == 1) {
         if (k <= 16 || k > 32) return;
         switch ((k + 3) / 4) {
             case 5: CNMF_SW(20) break;  case 6: CNMF_SW(24) break;
