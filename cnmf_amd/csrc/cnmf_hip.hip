@@ -226,12 +226,12 @@ __global__ void csr_densify_kernel(const long long* __restrict__ indptr, const i
 static int ensure_dense(cnmf_ctx* ctx)
 {
     if (ctx->X) return CNMF_OK;
-    if (ctx->N <= 0 || !ctx->csr_ptr) { SET_ERR(ctx, "cnmf_set_matrix has not been called"); return CNMF_ESTATE; }
+    if (ctx->N <= 0 || !ctx->csr.ptr) { SET_ERR(ctx, "cnmf_set_matrix has not been called"); return CNMF_ESTATE; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = alloc_dense(ctx);
     if (rc) return rc;
-    if (ctx->csr_nnz > 0) {
-        csr_densify_kernel<<<(unsigned)ctx->N, 64, 0, ctx->stream>>>(ctx->csr_ptr, ctx->csr_idx, ctx->csr_val, ctx->X, ctx->G_pad,
+    if (ctx->csr.nnz > 0) {
+        csr_densify_kernel<<<(unsigned)ctx->N, 64, 0, ctx->stream>>>(ctx->csr.ptr, ctx->csr.idx, ctx->csr.val, ctx->X, ctx->G_pad,
                                                                     (int)ctx->N, (int)ctx->G, nullptr);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -257,28 +257,23 @@ extern "C" int cnmf_set_matrix_csr(cnmf_ctx* ctx, const int32_t* indptr, const i
     int* d_ptr32 = pool.get<int>((size_t)(N + 1));
     int* d_bad = pool.get<int>(1, true, ctx->stream);
     POOL_TRY(ctx, pool);
-    long long* d_ptr = nullptr;
-    int* d_idx = nullptr;
-    float* d_val = nullptr;
-    hipError_t e = hipMalloc((void**)&d_ptr, (size_t)(N + 1) * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_idx, (size_t)std::max<int64_t>(nnz, 1) * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_val, (size_t)std::max<int64_t>(nnz, 1) * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ptr32, indptr, (size_t)(N + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(d_idx, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(d_val, data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    int bad = 0;
-    if (e == hipSuccess) {
-        cnmf::csr_widen_ptr_kernel<<<(unsigned)((N + 1 + 255) / 256), 256, 0, ctx->stream>>>(d_ptr32, N + 1, d_ptr);
-        if (nnz > 0)
-            csr_densify_kernel<<<(unsigned)N, 64, 0, ctx->stream>>>(d_ptr, d_idx, d_val, nullptr, ctx->G_pad, (int)N, (int)G, d_bad);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    hipStream_t st = ctx->stream;
+    DevCsrLocal<float> L;
+    HIP_TRY(ctx, L.alloc_ptr(N, G));
+    HIP_TRY(ctx, L.alloc_entries(nnz));
+    HIP_TRY(ctx, hipMemcpyAsync(d_ptr32, indptr, (size_t)(N + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    if (nnz > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(L.idx, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(L.val, data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, st));
     }
-    if (e != hipSuccess || (bad & 2)) { hipFree(d_ptr); hipFree(d_idx); hipFree(d_val); }
-    HIP_TRY(ctx, e);
+    int bad = 0;
+    cnmf::csr_widen_ptr_kernel<<<(unsigned)((N + 1 + 255) / 256), 256, 0, st>>>(d_ptr32, N + 1, L.ptr);
+    if (nnz > 0) csr_densify_kernel<<<(unsigned)N, 64, 0, st>>>(L.ptr, L.idx, L.val, nullptr, ctx->G_pad, (int)N, (int)G, d_bad);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
     if (bad & 2) { SET_ERR(ctx, "column index out of range in the CSR arrays"); return CNMF_EINVAL; }
-    ctx->csr_ptr = d_ptr; ctx->csr_idx = d_idx; ctx->csr_val = d_val; ctx->csr_nnz = nnz;
+    ctx->csr.take(L);
     if (bad & 1) {                      // not canonical: the dense image now (sums duplicates), the arrays are dropped
         rc = ensure_dense(ctx);
         free_csr(ctx);
@@ -312,7 +307,7 @@ extern "C" int cnmf_get_shape(const cnmf_ctx* ctx, int64_t* N, int64_t* G)
     if (!ctx) return CNMF_EINVAL;
     if (N) *N = ctx->N;
     if (G) *G = ctx->G;
-    return (ctx->X || ctx->csr_ptr) ? CNMF_OK : CNMF_ESTATE;
+    return (ctx->X || ctx->csr.ptr) ? CNMF_OK : CNMF_ESTATE;
 }
 
 // which images of the matrix are resident (bit 0: dense float32 image, 1: compressed rows of X, 2: compressed rows of X^T,
@@ -320,7 +315,7 @@ extern "C" int cnmf_get_shape(const cnmf_ctx* ctx, int64_t* N, int64_t* G)
 extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
 {
     if (!ctx || !flags) return CNMF_EINVAL;
-    *flags = (ctx->X ? 1 : 0) | (ctx->csr_ptr ? 2 : 0) | (ctx->csc_ptr ? 4 : 0) | (ctx->XtF ? 8 : 0) |
+    *flags = (ctx->X ? 1 : 0) | (ctx->csr.ptr ? 2 : 0) | (ctx->csc.ptr ? 4 : 0) | (ctx->XtF ? 8 : 0) |
              ((ctx->spA[0].ent && ctx->spB[0].ent) ? 16 : 0) | ((ctx->spA[1].ent && ctx->spB[1].ent) ? 32 : 0) | (ctx->C1 ? 64 : 0);
     return CNMF_OK;
 }

@@ -438,7 +438,7 @@ extern "C" int cnmf_prediction_error(cnmf_ctx* ctx, int k, const double* W, cons
     using namespace cnmf;
     if (!ctx || !W || !H || !err_out || k < 1) { SET_ERR(ctx, "bad argument"); return CNMF_EINVAL; }
     if (k > KMAX) { SET_ERR(ctx, "k=%d > %d", k, KMAX); return CNMF_EUNSUPPORTED; }
-    if (!ctx->X && ctx->csr_ptr) {
+    if (!ctx->X && ctx->csr.ptr) {
         // a matrix that lives as compressed rows only (round 5; the reference densifies it here, cnmf.py:927-928):
         // ||X - W H||^2 = sum_stored [(x - wh)^2 - (wh)^2] + tr(W^T W . H H^T), float64
         CONS_TRY(hipSetDevice(ctx->device));
@@ -458,7 +458,7 @@ extern "C" int cnmf_prediction_error(cnmf_ctx* ctx, int k, const double* W, cons
         if (pool_.err) { SET_ERR(ctx, "device allocation failed"); return CNMF_ENOMEM; }
         CONS_TRY(hipMemcpyAsync(dW_, W, (size_t)N_ * k * sizeof(double), hipMemcpyHostToDevice, st_));
         CONS_TRY(hipMemcpyAsync(dHt_, ht.data(), (size_t)G_ * k * sizeof(double), hipMemcpyHostToDevice, st_));
-        csr_residual_rows_kernel<<<(N_ + 3) / 4, 256, 0, st_>>>(ctx->csr_ptr, ctx->csr_idx, ctx->csr_val, N_, dW_, dHt_, k, dpart_);
+        csr_residual_rows_kernel<<<(N_ + 3) / 4, 256, 0, st_>>>(ctx->csr.ptr, ctx->csr.idx, ctx->csr.val, N_, dW_, dHt_, k, dpart_);
         sum_kernel<<<1, 256, 0, st_>>>(dpart_, N_, dsum_);
         CONS_TRY(hipGetLastError());
         double s_ = 0.0;

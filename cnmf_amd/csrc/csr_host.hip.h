@@ -216,13 +216,7 @@ __global__ __launch_bounds__(256) void csr_residual_rows_kernel(const long long*
 
 }  // namespace cnmf
 
-static void free_csr(cnmf_ctx* c)
-{
-    hipFree(c->csr_ptr); hipFree(c->csr_idx); hipFree(c->csr_val);
-    hipFree(c->csc_ptr); hipFree(c->csc_idx); hipFree(c->csc_val);
-    c->csr_ptr = c->csc_ptr = nullptr; c->csr_idx = c->csc_idx = nullptr; c->csr_val = c->csc_val = nullptr;
-    c->csr_nnz = -1;
-}
+static void free_csr(cnmf_ctx* c) { c->csr.release(); c->csc.release(); }
 
 // exclusive scan of n device counts (64-bit) into ptr[0..n] through the host (n <= 2^30 rows / 2^24 columns: a few MB)
 static int csr_scan_to_ptr(cnmf_ctx* ctx, long long* d_cnt_in_ptr_out, size_t n, long long* total)
@@ -243,76 +237,68 @@ static int csr_scan_to_ptr(cnmf_ctx* ctx, long long* d_cnt_in_ptr_out, size_t n,
 static int ensure_csr(cnmf_ctx* ctx)
 {
     using namespace cnmf;
-    if (ctx->csr_ptr) return CNMF_OK;
+    if (ctx->csr.ptr) return CNMF_OK;
     if (!ctx->X) { SET_ERR(ctx, "cnmf_set_matrix has not been called"); return CNMF_ESTATE; }       // (neither image: no matrix)
     const int N = (int)ctx->N, G = (int)ctx->G;
     hipStream_t st = ctx->stream;
-    long long* ptr = nullptr;
-    int* idx = nullptr;
-    float* val = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&ptr, ((size_t)N + 1) * sizeof(long long)));
-    csr_count_dense_kernel<<<(N + 3) / 4, 256, 0, st>>>(ctx->X, ctx->G_pad, N, G, ptr);
+    DevCsrLocal<float> L;
+    HIP_TRY(ctx, L.alloc_ptr(N, G));
+    csr_count_dense_kernel<<<(N + 3) / 4, 256, 0, st>>>(ctx->X, ctx->G_pad, N, G, L.ptr);
+    HIP_TRY(ctx, hipGetLastError());
     long long nnz = 0;
-    int rc = hipGetLastError() == hipSuccess ? csr_scan_to_ptr(ctx, ptr, (size_t)N, &nnz) : CNMF_EHIP;
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMalloc((void**)&idx, (size_t)std::max<long long>(nnz, 1) * sizeof(int));
-    if (!rc && e == hipSuccess) e = hipMalloc((void**)&val, (size_t)std::max<long long>(nnz, 1) * sizeof(float));
-    if (!rc && e == hipSuccess) {
-        csr_fill_dense_kernel<<<(N + 3) / 4, 256, 0, st>>>(ctx->X, ctx->G_pad, N, G, ptr, idx, val);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (rc || e != hipSuccess) {
-        hipFree(ptr); hipFree(idx); hipFree(val);
-        if (rc) return rc;
-        HIP_TRY(ctx, e);
-    }
-    ctx->csr_ptr = ptr; ctx->csr_idx = idx; ctx->csr_val = val; ctx->csr_nnz = nnz;
+    if (int rc = csr_scan_to_ptr(ctx, L.ptr, (size_t)N, &nnz)) return rc;
+    HIP_TRY(ctx, L.alloc_entries(nnz));
+    csr_fill_dense_kernel<<<(N + 3) / 4, 256, 0, st>>>(ctx->X, ctx->G_pad, N, G, L.ptr, L.idx, L.val);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    ctx->csr.take(L);
     return CNMF_OK;
 }
 
-// compressed rows of X^T, from those of X (device counting sort, fixed order)
-static int ensure_csc(cnmf_ctx* ctx)
+// Counting-sort transpose (the kernels above) of the CSR `in` into `out` (in.cols x n_rows), on the device and in a fixed
+// order.  sel != nullptr: row r of the input is row sel[r] of `in`, r < n_rows (the transpose of a gathered, re-ordered
+// subset of rows); div != nullptr: the values of row r are divided by div[r]; in_val != nullptr: values in place of
+// in.val; `expect` (>= 0): the entries that must arrive (`what` names the transpose in the error when they do not).  The rows go in chunks: as many as keep the chunks x in.cols
+// counters at <= 64 M ints, between min_chunks and 4096 (and no more than there are rows).
+// `out` is taken only when every step has succeeded; until then it keeps what it held.
+template <typename V>
+static int csr_transpose(cnmf_ctx* ctx, const DevCsr<V>& in, const int* sel, const double* div, int64_t n_rows,
+                         int min_chunks, long long expect, const char* what, DevCsr<V>* out, const V* in_val = nullptr)
 {
     using namespace cnmf;
-    if (ctx->csc_ptr) return CNMF_OK;
-    int rc = ensure_csr(ctx);
-    if (rc) return rc;
-    const int N = (int)ctx->N, G = (int)ctx->G;
-    const long long nnz = ctx->csr_nnz;
     hipStream_t st = ctx->stream;
-    // row chunks: as many as keep the counters at <= 64 M ints, between 64 and 4096
-    int T = (int)std::min<long long>(4096, std::max<long long>(64, (64ll << 20) / std::max(1, G)));
-    T = std::min(T, N);
-    const int rpc = (N + T - 1) / T;
-    T = (N + rpc - 1) / rpc;
+    const int R = (int)n_rows, C = (int)in.cols;
+    int64_t chunks = std::min<int64_t>(4096, std::max<int64_t>(min_chunks, (64ll << 20) / std::max(1, C)));
+    chunks = std::max<int64_t>(1, std::min<int64_t>(chunks, R));
+    const int rpc = (int)((R + chunks - 1) / chunks), T = (R + rpc - 1) / rpc;
+    const V* val = in_val ? in_val : in.val;
     DevPool pool;
-    int* cnt = pool.get<int>((size_t)T * G, true, st);
+    int* cnt = pool.get<int>((size_t)T * C, true, st);
     POOL_TRY(ctx, pool);
-    long long* tptr = nullptr;
-    int* tidx = nullptr;
-    float* tval = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&tptr, ((size_t)G + 1) * sizeof(long long)));
-    csr_tr_hist_kernel<<<T, 256, 0, st>>>(ctx->csr_ptr, ctx->csr_idx, nullptr, N, G, rpc, cnt);
-    csr_tr_total_kernel<<<(G + 255) / 256, 256, 0, st>>>(cnt, T, G, tptr);
-    csr_tr_offsets_kernel<<<(G + 255) / 256, 256, 0, st>>>(cnt, T, G);
+    DevCsrLocal<V> L;
+    HIP_TRY(ctx, L.alloc_ptr(C, R));
+    csr_tr_hist_kernel<<<T, 256, 0, st>>>(in.ptr, in.idx, sel, R, C, rpc, cnt);
+    csr_tr_total_kernel<<<(C + 255) / 256, 256, 0, st>>>(cnt, T, C, L.ptr);
+    csr_tr_offsets_kernel<<<(C + 255) / 256, 256, 0, st>>>(cnt, T, C);
+    HIP_TRY(ctx, hipGetLastError());
     long long total = 0;
-    rc = hipGetLastError() == hipSuccess ? csr_scan_to_ptr(ctx, tptr, (size_t)G, &total) : CNMF_EHIP;
-    hipError_t e = hipSuccess;
-    if (!rc && total != nnz) { SET_ERR(ctx, "transpose of the compressed rows: %lld of %lld entries counted", total, nnz); rc = CNMF_EHIP; }
-    if (!rc) e = hipMalloc((void**)&tidx, (size_t)std::max<long long>(nnz, 1) * sizeof(int));
-    if (!rc && e == hipSuccess) e = hipMalloc((void**)&tval, (size_t)std::max<long long>(nnz, 1) * sizeof(float));
-    if (!rc && e == hipSuccess) {
-        csr_tr_fill_kernel<float><<<T, 64, 0, st>>>(ctx->csr_ptr, ctx->csr_idx, ctx->csr_val, nullptr, nullptr, N, G, rpc, cnt,
-                                                    tptr, tidx, tval);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (int rc = csr_scan_to_ptr(ctx, L.ptr, (size_t)C, &total)) return rc;
+    if (expect >= 0 && total != expect) {
+        SET_ERR(ctx, "%s: %lld of %lld entries counted", what, total, expect);
+        return CNMF_EHIP;
     }
-    if (rc || e != hipSuccess) {
-        hipFree(tptr); hipFree(tidx); hipFree(tval);
-        if (rc) return rc;
-        HIP_TRY(ctx, e);
-    }
-    ctx->csc_ptr = tptr; ctx->csc_idx = tidx; ctx->csc_val = tval;
+    HIP_TRY(ctx, L.alloc_entries(total));
+    csr_tr_fill_kernel<V><<<T, 64, 0, st>>>(in.ptr, in.idx, val, sel, div, R, C, rpc, cnt, L.ptr, L.idx, L.val);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    out->take(L);
     return CNMF_OK;
+}
+
+// compressed rows of X^T, from those of X; at least 64 row chunks
+static int ensure_csc(cnmf_ctx* ctx)
+{
+    if (ctx->csc.ptr) return CNMF_OK;
+    if (int rc = ensure_csr(ctx)) return rc;
+    return csr_transpose<float>(ctx, ctx->csr, nullptr, nullptr, ctx->N, 64, ctx->csr.nnz, "transpose of the compressed rows", &ctx->csc);
 }

@@ -213,7 +213,7 @@ static void flt_scan(hipStream_t st, const T* in, long long n, long long* bsum, 
 static int flt_staged(cnmf_ctx* ctx)
 {
     if (!ctx) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
-    if (ctx->pre.nnz < 0) { SET_ERR(ctx, "cnmf_preprocess_upload_csr has not been called"); return CNMF_ESTATE; }
+    if (!ctx->pre.staged()) { SET_ERR(ctx, "cnmf_preprocess_upload_csr has not been called"); return CNMF_ESTATE; }
     return CNMF_OK;
 }
 
@@ -225,9 +225,9 @@ extern "C" int cnmf_preprocess_upload_csr_as_stored(cnmf_ctx* ctx, const int64_t
     PreStage& P = ctx->pre;
     hipStreamSynchronize(ctx->stream);
     P.release();
-    if (int rc = prep_stage_csr(ctx, indptr, indices, data, 1, n_cells, n_genes, &P.ptr, &P.idx, &P.val, true)) return rc;
-    P.N = n_cells; P.G = n_genes; P.nnz = indptr[n_cells];
-    return prep_transpose(ctx, P.ptr, P.idx, P.val, nullptr, nullptr, (int)P.N, (int)P.G, P.nnz, &P.cptr, &P.crow, &P.cval);
+    if (int rc = stage_counts(ctx, indptr, indices, data, 1, n_cells, n_genes, true, true, P)) return rc;
+    P.N = n_cells;
+    return CNMF_OK;
 }
 
 extern "C" int cnmf_preprocess_gene_detect(cnmf_ctx* ctx, const uint8_t* cell_mask, int64_t* n_cells, double* totals)
@@ -236,7 +236,7 @@ extern "C" int cnmf_preprocess_gene_detect(cnmf_ctx* ctx, const uint8_t* cell_ma
     if (int rc = flt_staged(ctx)) return rc;
     if (!n_cells || !totals) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     PreStage& P = ctx->pre;
-    const int N = (int)P.N, G = (int)P.G;
+    const int N = (int)P.N, G = (int)P.counts.cols;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevPool pool;
@@ -245,7 +245,7 @@ extern "C" int cnmf_preprocess_gene_detect(cnmf_ctx* ctx, const uint8_t* cell_ma
     double* dt = pool.get<double>((size_t)G);
     POOL_TRY(ctx, pool);
     if (dm) HIP_TRY(ctx, hipMemcpyAsync(dm, cell_mask, (size_t)N, hipMemcpyHostToDevice, st));
-    flt_gene_detect_kernel<<<(G + 3) / 4, 256, 0, st>>>(P.cptr, P.crow, P.cval, G, N, dm, dn, dt);
+    flt_gene_detect_kernel<<<(G + 3) / 4, 256, 0, st>>>(P.columns.ptr, P.columns.idx, P.columns.val, G, N, dm, dn, dt);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(n_cells, dn, (size_t)G * sizeof(long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(totals, dt, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -259,7 +259,7 @@ extern "C" int cnmf_preprocess_cell_sums(cnmf_ctx* ctx, const uint8_t* gene_mask
     if (int rc = flt_staged(ctx)) return rc;
     if (!sums) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     PreStage& P = ctx->pre;
-    const int N = (int)P.N, G = (int)P.G;
+    const int N = (int)P.N, G = (int)P.counts.cols;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevPool pool;
@@ -267,7 +267,7 @@ extern "C" int cnmf_preprocess_cell_sums(cnmf_ctx* ctx, const uint8_t* gene_mask
     double* ds = pool.get<double>((size_t)N);
     POOL_TRY(ctx, pool);
     if (dm) HIP_TRY(ctx, hipMemcpyAsync(dm, gene_mask, (size_t)G, hipMemcpyHostToDevice, st));
-    flt_cell_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.ptr, P.idx, P.val, N, G, dm, ds);
+    flt_cell_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.idx, P.counts.val, N, G, dm, ds);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(sums, ds, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -281,7 +281,7 @@ extern "C" int cnmf_preprocess_subset(cnmf_ctx* ctx, const uint8_t* keep_cells, 
     if (int rc = flt_staged(ctx)) return rc;
     if (!n_cells_out || !n_genes_out || !nnz_out) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     PreStage& P = ctx->pre;
-    const int N = (int)P.N, G = (int)P.G;
+    const int N = (int)P.N, G = (int)P.counts.cols;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevPool pool;
@@ -308,42 +308,30 @@ extern "C" int cnmf_preprocess_subset(cnmf_ctx* ctx, const uint8_t* keep_cells, 
     if (Nn <= 0) { SET_ERR(ctx, "keep_cells keeps no cell"); return CNMF_EINVAL; }
     if (Gn <= 0) { SET_ERR(ctx, "keep_genes keeps no gene"); return CNMF_EINVAL; }
     // the new arrays first: the old staging stays as it is until every one of them stands
-    long long *nptr = nullptr, *cptr = nullptr;
-    int *nidx = nullptr, *crow = nullptr;
-    double *nval = nullptr, *cval = nullptr;
+    const DevCsr<double>& old = P.counts;
+    DevCsrLocal<double> counts, columns;
     long long nnz = 0;
-    hipError_t e = hipMalloc((void**)&nptr, ((size_t)Nn + 1) * sizeof(long long));
-    if (e == hipSuccess) {
-        flt_row_count_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.ptr, P.idx, N, G, dkc, rowmap, dkg, Nn, nptr);
-        flt_scan<long long>(st, nptr, Nn, bsum, nptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&nnz, nptr + Nn, sizeof(long long), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && (nnz < 0 || nnz > P.nnz)) {
-        hipFree(nptr);
-        SET_ERR(ctx, "subset: %lld entries counted of %lld staged", nnz, (long long)P.nnz);
+    HIP_TRY(ctx, counts.alloc_ptr(Nn, Gn));
+    flt_row_count_kernel<<<(N + 3) / 4, 256, 0, st>>>(old.ptr, old.idx, N, G, dkc, rowmap, dkg, Nn, counts.ptr);
+    flt_scan<long long>(st, counts.ptr, Nn, bsum, counts.ptr);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(&nnz, counts.ptr + Nn, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (nnz < 0 || nnz > old.nnz) {
+        SET_ERR(ctx, "subset: %lld entries counted of %lld staged", nnz, (long long)old.nnz);
         return CNMF_EHIP;
     }
-    const size_t n1 = (size_t)std::max<long long>(nnz, 1);
-    if (e == hipSuccess) e = hipMalloc((void**)&nidx, n1 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&nval, n1 * sizeof(double));
-    if (e == hipSuccess) {
-        flt_compact_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.ptr, P.idx, P.val, N, G, dkc, rowmap, dkg, colmap, Nn, nptr, nidx, nval);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    int rc = CNMF_OK;
-    if (e == hipSuccess) rc = prep_transpose(ctx, nptr, nidx, nval, nullptr, nullptr, (int)Nn, (int)Gn, nnz, &cptr, &crow, &cval);
-    if (e != hipSuccess || rc) {
-        hipFree(nptr); hipFree(nidx); hipFree(nval);
-        if (rc) return rc;
-        HIP_TRY(ctx, e);
-    }
+    HIP_TRY(ctx, counts.alloc_entries(nnz));
+    flt_compact_kernel<<<(N + 3) / 4, 256, 0, st>>>(old.ptr, old.idx, old.val, N, G, dkc, rowmap, dkg, colmap, Nn, counts.ptr,
+                                                    counts.idx, counts.val);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (int rc = prep_transpose(ctx, counts, nullptr, nullptr, Nn, nnz, &columns)) return rc;
     // the slots and the ridge factors spoke of the old cells and genes
     P.release();
-    P.ptr = nptr; P.idx = nidx; P.val = nval; P.cptr = cptr; P.crow = crow; P.cval = cval;
-    P.N = Nn; P.G = Gn; P.nnz = nnz;
+    P.counts.take(counts);
+    P.columns.take(columns);
+    P.N = Nn;
     *n_cells_out = Nn; *n_genes_out = Gn; *nnz_out = nnz;
     return CNMF_OK;
 }
@@ -358,21 +346,18 @@ extern "C" int cnmf_preprocess_fetch_counts(cnmf_ctx* ctx, double target_sum, in
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevPool pool;
-    const bool scaled = target_sum > 0.0 && values && P.nnz > 0;
+    const bool scaled = target_sum > 0.0 && values && P.counts.nnz > 0;
     double* rs = scaled ? pool.get<double>((size_t)N) : nullptr;
     double* scale = scaled ? pool.get<double>((size_t)N) : nullptr;
-    double* sval = scaled ? pool.get<double>((size_t)P.nnz) : nullptr;
+    double* sval = scaled ? pool.get<double>((size_t)P.counts.nnz) : nullptr;
     POOL_TRY(ctx, pool);
     if (scaled) {
-        prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.ptr, P.val, N, rs);
+        prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, rs);
         prep_row_scale_kernel<<<(N + 255) / 256, 256, 0, st>>>(rs, N, target_sum, scale);
-        prep_tpm_values_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.ptr, P.val, N, scale, sval);
+        prep_tpm_values_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, scale, sval);
         HIP_TRY(ctx, hipGetLastError());
     }
-    if (indptr) HIP_TRY(ctx, hipMemcpyAsync(indptr, P.ptr, ((size_t)N + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
-    if (indices && P.nnz > 0) HIP_TRY(ctx, hipMemcpyAsync(indices, P.idx, (size_t)P.nnz * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (values && P.nnz > 0)
-        HIP_TRY(ctx, hipMemcpyAsync(values, scaled ? sval : P.val, (size_t)P.nnz * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (int rc = csr_fetch<double>(ctx, P.counts, indptr, indices, values, sval)) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return CNMF_OK;
 }

@@ -189,7 +189,7 @@ static int mu_sparse_prepare(cnmf_ctx* ctx, int KP, bool* use)
     // (N + 1 counters) -- its compressed rows (12 B per entry) are built below, once the density and memory rules have chosen
     // this path, and not at all when they send the call back to the dense kernels (round-5 advice)
     int rc = CNMF_OK;
-    if (ctx->csr_ptr) ctx->x_nnz = ctx->csr_nnz;
+    if (ctx->csr.ptr) ctx->x_nnz = ctx->csr.nnz;
     else if (ctx->x_nnz < 0) {
         long long* cnt = nullptr;
         HIP_TRY(ctx, hipMalloc((void**)&cnt, ((size_t)N + 1) * sizeof(long long)));
@@ -217,10 +217,10 @@ static int mu_sparse_prepare(cnmf_ctx* ctx, int KP, bool* use)
     rc = ensure_csr(ctx);                                       // (kept from the CSR upload, or two passes over the dense image)
     if (rc == CNMF_ENOMEM && mode != 1) return CNMF_OK;
     if (rc) return rc;
-    if (!ctx->spA[idx].ent) rc = sp_build_image(ctx, ctx->csr_ptr, ctx->csr_idx, ctx->csr_val, N, G, BS, ctx->spA[idx]);
+    if (!ctx->spA[idx].ent) rc = sp_build_image(ctx, ctx->csr.ptr, ctx->csr.idx, ctx->csr.val, N, G, BS, ctx->spA[idx]);
     if (!rc && !ctx->spB[idx].ent) {
         rc = ensure_csc(ctx);
-        if (!rc) rc = sp_build_image(ctx, ctx->csc_ptr, ctx->csc_idx, ctx->csc_val, G, N, BS, ctx->spB[idx]);
+        if (!rc) rc = sp_build_image(ctx, ctx->csc.ptr, ctx->csc.idx, ctx->csc.val, G, N, BS, ctx->spB[idx]);
     }
     if (rc == CNMF_ENOMEM && mode != 1) {                       // an allocation failed after all: the dense kernels still work
         ctx->spA[idx].release(); ctx->spB[idx].release();
@@ -505,7 +505,7 @@ extern "C" int cnmf_nmf_mu_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int in
 {
     using namespace cnmf;
     if (!ctx) { SET_ERR(ctx, "ctx is NULL"); return CNMF_EINVAL; }
-    if (!ctx->X && !ctx->csr_ptr) { SET_ERR(ctx, "cnmf_set_matrix has not been called"); return CNMF_ESTATE; }
+    if (!ctx->X && !ctx->csr.ptr) { SET_ERR(ctx, "cnmf_set_matrix has not been called"); return CNMF_ESTATE; }
     int rc = validate_params(ctx, prm);
     if (rc) return rc;
     if (beta != 0 && beta != 1) { SET_ERR(ctx, "beta_loss must be 1 (kullback-leibler) or 0 (itakura-saito)"); return CNMF_EUNSUPPORTED; }

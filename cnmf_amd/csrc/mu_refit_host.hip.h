@@ -182,7 +182,7 @@ extern "C" int cnmf_mu_refit_f64(cnmf_ctx* ctx, int side, int beta, int k, const
     using namespace cnmf;
     if (!ctx || !H || !prm || !W_out) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     if (beta != 0 && beta != 1) { SET_ERR(ctx, "beta must be 1 (Kullback-Leibler) or 0 (Itakura-Saito)"); return CNMF_EINVAL; }
-    if (!ctx->X && !ctx->csr_ptr) { SET_ERR(ctx, "cnmf_set_matrix has not been called"); return CNMF_ESTATE; }
+    if (!ctx->X && !ctx->csr.ptr) { SET_ERR(ctx, "cnmf_set_matrix has not been called"); return CNMF_ESTATE; }
     if (k < 1 || k > CNMF_MU_KMAX) { SET_ERR(ctx, "rank %d outside 1..%d (multiplicative updates)", k, CNMF_MU_KMAX); return CNMF_EUNSUPPORTED; }
     if (side != 0 && side != 1) { SET_ERR(ctx, "side must be 0 (rows = cells) or 1 (rows = genes)"); return CNMF_EINVAL; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -190,9 +190,9 @@ extern "C" int cnmf_mu_refit_f64(cnmf_ctx* ctx, int side, int beta, int k, const
     if (rc) return rc;
     hipStream_t st = ctx->stream;
     const int nrows = side == 0 ? (int)ctx->N : (int)ctx->G, ncols = side == 0 ? (int)ctx->G : (int)ctx->N;
-    const long long* ptr = side == 0 ? ctx->csr_ptr : ctx->csc_ptr;
-    const int* idx = side == 0 ? ctx->csr_idx : ctx->csc_idx;
-    const float* val = side == 0 ? ctx->csr_val : ctx->csc_val;
+    const long long* ptr = side == 0 ? ctx->csr.ptr : ctx->csc.ptr;
+    const int* idx = side == 0 ? ctx->csr.idx : ctx->csc.idx;
+    const float* val = side == 0 ? ctx->csr.val : ctx->csc.val;
     const int KP = k <= 8 ? 8 : (k <= 16 ? 16 : (k <= 32 ? 32 : 64));
     if (beta == 0) {
         // scikit-learn's own refusal (_nmf.py:1679-1684): every entry must be positive, i.e. every entry is stored

@@ -117,66 +117,19 @@ __global__ __launch_bounds__(256) void prep_store_kernel(const long long* __rest
 
 }  // namespace cnmf
 
-// rows per chunk of a transpose of an R x C CSR: as many chunks as keep the T x C counters at <= 64 M ints, at most 4096
-static int prep_chunks(int64_t R, int64_t C, int* rows_per_chunk)
+// the transpose of the staging paths: float64 values, at least one row chunk (csr_host.hip.h)
+static int prep_transpose(cnmf_ctx* ctx, const DevCsr<double>& in, const int* sel, const double* div, int64_t n_rows,
+                          long long expect, DevCsr<double>* out, const double* in_val = nullptr)
 {
-    int64_t T = std::min<int64_t>(4096, std::max<int64_t>(1, (64ll << 20) / std::max<int64_t>(1, C)));
-    T = std::max<int64_t>(1, std::min<int64_t>(T, R));
-    const int rpc = (int)((R + T - 1) / T);
-    *rows_per_chunk = rpc;
-    return (int)((R + rpc - 1) / rpc);
-}
-
-// Counting-sort transpose (csr_host.hip.h's kernels) of the R x C CSR (ptr, idx, val), restricted to the rows sel[0..R)
-// when sel != nullptr, values divided by div[r] when div != nullptr, into freshly allocated (tptr [C + 1], tidx, tval);
-// `expect` (>= 0): the entries that must arrive.
-static int prep_transpose(cnmf_ctx* ctx, const long long* ptr, const int* idx, const double* val, const int* sel,
-                          const double* div, int R, int C, long long expect, long long** tptr_out, int** tidx_out,
-                          double** tval_out)
-{
-    using namespace cnmf;
-    hipStream_t st = ctx->stream;
-    int rpc = 1;
-    const int T = prep_chunks(R, C, &rpc);
-    DevPool pool;
-    int* cnt = pool.get<int>((size_t)T * C, true, st);
-    POOL_TRY(ctx, pool);
-    long long* tptr = nullptr;
-    int* tidx = nullptr;
-    double* tval = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&tptr, ((size_t)C + 1) * sizeof(long long)));
-    csr_tr_hist_kernel<<<T, 256, 0, st>>>(ptr, idx, sel, R, C, rpc, cnt);
-    csr_tr_total_kernel<<<(C + 255) / 256, 256, 0, st>>>(cnt, T, C, tptr);
-    csr_tr_offsets_kernel<<<(C + 255) / 256, 256, 0, st>>>(cnt, T, C);
-    long long total = 0;
-    int rc = hipGetLastError() == hipSuccess ? csr_scan_to_ptr(ctx, tptr, (size_t)C, &total) : CNMF_EHIP;
-    hipError_t e = hipSuccess;
-    if (!rc && expect >= 0 && total != expect) {
-        SET_ERR(ctx, "prepare transpose: %lld of %lld entries counted", total, expect);
-        rc = CNMF_EHIP;
-    }
-    if (!rc) e = hipMalloc((void**)&tidx, (size_t)std::max<long long>(total, 1) * sizeof(int));
-    if (!rc && e == hipSuccess) e = hipMalloc((void**)&tval, (size_t)std::max<long long>(total, 1) * sizeof(double));
-    if (!rc && e == hipSuccess) {
-        csr_tr_fill_kernel<double><<<T, 64, 0, st>>>(ptr, idx, val, sel, div, R, C, rpc, cnt, tptr, tidx, tval);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (rc || e != hipSuccess) {
-        hipFree(tptr); hipFree(tidx); hipFree(tval);
-        if (rc) return rc;
-        HIP_TRY(ctx, e);
-    }
-    *tptr_out = tptr; *tidx_out = tidx; *tval_out = tval;
-    return CNMF_OK;
+    return csr_transpose<double>(ctx, in, sel, div, n_rows, 1, expect, "prepare transpose", out, in_val);
 }
 
 // the columns of the staged counts (their transpose), built once per upload
 static int prep_ensure_columns(cnmf_ctx* ctx)
 {
     PrepStage& P = ctx->prep;
-    if (P.cptr) return CNMF_OK;
-    return prep_transpose(ctx, P.ptr, P.idx, P.val, nullptr, nullptr, (int)P.N, (int)P.G, P.nnz, &P.cptr, &P.crow, &P.cval);
+    if (P.columns.ptr) return CNMF_OK;
+    return prep_transpose(ctx, P.counts, nullptr, nullptr, P.counts.rows, P.counts.nnz, &P.columns);
 }
 
 // the host-side checks of a CSR upload (shape, row pointers, null arrays)
@@ -196,58 +149,65 @@ static int prep_csr_args(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* in
     return CNMF_OK;
 }
 
-// stages raw counts (checked by prep_csr_args) as CSR with float64 values into freshly allocated (*ptr_out, *idx_out,
-// *val_out); frees them again on any failure.  Shared by cnmf_prepare_upload_csr and cnmf_preprocess_upload_csr.
-// as_stored: the rows may list their (distinct) columns in any order and zeros may be stored
-// (cnmf_preprocess_upload_csr_as_stored).
-static int prep_stage_csr(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data, int data_is_f64,
-                          int64_t n_cells, int64_t n_genes, long long** ptr_out, int** idx_out, double** val_out,
-                          bool as_stored = false)
+// Stages raw counts (checked by prep_csr_args) into S: CSR with float64 values, checked on the device, and with_columns
+// their transpose too.  Both are built in locals and committed together at the end: after a failure S is as the caller
+// left it (released: nothing staged).  as_stored: the rows may list their (distinct) columns in any order and zeros may be
+// stored (cnmf_preprocess_upload_csr_as_stored).
+static int stage_counts(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data, int data_is_f64,
+                        int64_t n_cells, int64_t n_genes, bool as_stored, bool with_columns, CountStage& S)
 {
     using namespace cnmf;
     const int64_t nnz = indptr[n_cells];
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const size_t n1 = (size_t)std::max<int64_t>(nnz, 1);
     DevPool pool;
     int* d_bad = pool.get<int>(1, true, st);
-    float* tmp32 = data_is_f64 ? nullptr : pool.get<float>(n1);
+    float* tmp32 = data_is_f64 ? nullptr : pool.get<float>((size_t)std::max<int64_t>(nnz, 1));
     POOL_TRY(ctx, pool);
-    long long* ptr = nullptr;
-    int* idx = nullptr;
-    double* val = nullptr;
-    hipError_t e = hipMalloc((void**)&ptr, (size_t)(n_cells + 1) * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&idx, n1 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&val, n1 * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(ptr, indptr, (size_t)(n_cells + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(idx, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && nnz > 0) {
+    DevCsrLocal<double> counts, columns;
+    HIP_TRY(ctx, counts.alloc_ptr(n_cells, n_genes));
+    HIP_TRY(ctx, counts.alloc_entries(nnz));
+    HIP_TRY(ctx, hipMemcpyAsync(counts.ptr, indptr, (size_t)(n_cells + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    if (nnz > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(counts.idx, indices, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, st));
         if (data_is_f64) {
-            e = hipMemcpyAsync(val, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st);
+            HIP_TRY(ctx, hipMemcpyAsync(counts.val, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st));
         } else {
-            e = hipMemcpyAsync(tmp32, data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) {
-                const long long blocks = std::min<long long>((nnz + 255) / 256, 8192);
-                prep_widen_kernel<<<(unsigned)blocks, 256, 0, st>>>(tmp32, nnz, val);
-                e = hipGetLastError();
-            }
+            HIP_TRY(ctx, hipMemcpyAsync(tmp32, data, (size_t)nnz * sizeof(float), hipMemcpyHostToDevice, st));
+            const long long blocks = std::min<long long>((nnz + 255) / 256, 8192);
+            prep_widen_kernel<<<(unsigned)blocks, 256, 0, st>>>(tmp32, nnz, counts.val);
+            HIP_TRY(ctx, hipGetLastError());
         }
     }
     int bad = 0;
-    if (e == hipSuccess) {
-        prep_check_kernel<<<(unsigned)((n_cells + 3) / 4), 256, 0, st>>>(ptr, idx, val, (int)n_cells, (int)n_genes, d_bad);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
+    prep_check_kernel<<<(unsigned)((n_cells + 3) / 4), 256, 0, st>>>(counts.ptr, counts.idx, counts.val, (int)n_cells,
+                                                                    (int)n_genes, d_bad);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
     if (as_stored) bad &= 2 | 8;
-    if (e != hipSuccess || bad) { hipFree(ptr); hipFree(idx); hipFree(val); }
-    HIP_TRY(ctx, e);
     if (bad & 2) { SET_ERR(ctx, "column index out of range in the CSR arrays"); return CNMF_EINVAL; }
     if (bad & 1) { SET_ERR(ctx, "every row must list strictly increasing columns (canonical CSR)"); return CNMF_EINVAL; }
     if (bad & 4) { SET_ERR(ctx, "stored values must be finite and > 0 (counts without stored zeros)"); return CNMF_EINVAL; }
     if (bad & 8) { SET_ERR(ctx, "stored values must be finite and >= 0"); return CNMF_EINVAL; }
-    *ptr_out = ptr; *idx_out = idx; *val_out = val;
+    if (with_columns)
+        if (int rc = prep_transpose(ctx, counts, nullptr, nullptr, n_cells, nnz, &columns)) return rc;
+    S.counts.take(counts);
+    S.columns.take(columns);
+    return CNMF_OK;
+}
+
+// the three copies of a device CSR to the host, queued on the stream (the caller synchronises); a null host array is
+// skipped; values_override != nullptr: device values in place of csr.val
+template <typename V>
+static int csr_fetch(cnmf_ctx* ctx, const DevCsr<V>& csr, int64_t* indptr, int32_t* indices, V* values,
+                     const V* values_override = nullptr)
+{
+    hipStream_t st = ctx->stream;
+    const size_t n = (size_t)std::max<int64_t>(csr.nnz, 0);
+    if (indptr) HIP_TRY(ctx, hipMemcpyAsync(indptr, csr.ptr, ((size_t)csr.rows + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (indices && n > 0) HIP_TRY(ctx, hipMemcpyAsync(indices, csr.idx, n * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (values && n > 0)
+        HIP_TRY(ctx, hipMemcpyAsync(values, values_override ? values_override : csr.val, n * sizeof(V), hipMemcpyDeviceToHost, st));
     return CNMF_OK;
 }
 
@@ -256,12 +216,9 @@ extern "C" int cnmf_prepare_upload_csr(cnmf_ctx* ctx, const int64_t* indptr, con
 {
     if (int rc = prep_csr_args(ctx, indptr, indices, data, n_cells, n_genes)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    PrepStage& P = ctx->prep;
     hipStreamSynchronize(ctx->stream);
-    P.release();
-    if (int rc = prep_stage_csr(ctx, indptr, indices, data, data_is_f64, n_cells, n_genes, &P.ptr, &P.idx, &P.val)) return rc;
-    P.N = n_cells; P.G = n_genes; P.nnz = indptr[n_cells];
-    return CNMF_OK;
+    ctx->prep.release();
+    return stage_counts(ctx, indptr, indices, data, data_is_f64, n_cells, n_genes, false, false, ctx->prep);
 }
 
 extern "C" int cnmf_prepare_tpm_stats(cnmf_ctx* ctx, double target_sum, double* row_sums, double* mean, double* var,
@@ -270,31 +227,80 @@ extern "C" int cnmf_prepare_tpm_stats(cnmf_ctx* ctx, double target_sum, double* 
     using namespace cnmf;
     if (!ctx || !row_sums || !mean || !var) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     PrepStage& P = ctx->prep;
-    if (P.nnz < 0) { SET_ERR(ctx, "cnmf_prepare_upload_csr has not been called"); return CNMF_ESTATE; }
+    if (!P.staged()) { SET_ERR(ctx, "cnmf_prepare_upload_csr has not been called"); return CNMF_ESTATE; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const int N = (int)P.N, G = (int)P.G;
+    const int N = (int)P.counts.rows, G = (int)P.counts.cols;
     if (int rc = prep_ensure_columns(ctx)) return rc;
     DevPool pool;
     double* rs = pool.get<double>(N);
     double* scale = target_sum > 0.0 ? pool.get<double>(N) : nullptr;
     double* m = pool.get<double>(G);
     double* q = pool.get<double>(G);
-    double* tv = tpm_data ? pool.get<double>((size_t)std::max<long long>(P.nnz, 1)) : nullptr;
+    double* tv = tpm_data ? pool.get<double>((size_t)std::max<long long>(P.counts.nnz, 1)) : nullptr;
     POOL_TRY(ctx, pool);
-    prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.ptr, P.val, N, rs);
+    prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, rs);
     if (scale) prep_row_scale_kernel<<<(N + 255) / 256, 256, 0, st>>>(rs, N, target_sum, scale);
-    prep_col_moments_kernel<<<(G + 3) / 4, 256, 0, st>>>(P.cptr, P.crow, P.cval, nullptr, G, N, scale, m, q);
-    if (tv) prep_tpm_values_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.ptr, P.val, N, scale, tv);
+    prep_col_moments_kernel<<<(G + 3) / 4, 256, 0, st>>>(P.columns.ptr, P.columns.idx, P.columns.val, nullptr, G, N, scale, m, q);
+    if (tv) prep_tpm_values_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, scale, tv);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(row_sums, rs, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(mean, m, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(var, q, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (tv && P.nnz > 0)
-        HIP_TRY(ctx, hipMemcpyAsync(tpm_data, tv, (size_t)P.nnz * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (tv && P.counts.nnz > 0)
+        HIP_TRY(ctx, hipMemcpyAsync(tpm_data, tv, (size_t)P.counts.nnz * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     for (int g = 0; g < G; ++g) var[g] /= (double)N;
     return CNMF_OK;
+}
+
+// the checks of a gene list against the staged counts S, shared by cnmf_prepare_select and cnmf_preprocess_select
+static int select_check_genes(cnmf_ctx* ctx, const CountStage& S, int32_t n_sel, const int32_t* genes)
+{
+    const int N = (int)S.counts.rows, G = (int)S.counts.cols;
+    if (n_sel <= 0 || n_sel > G) { SET_ERR(ctx, "n_sel = %d outside [1, %d]", n_sel, G); return CNMF_EINVAL; }
+    if (N < 2) { SET_ERR(ctx, "need at least two cells for a variance"); return CNMF_EINVAL; }
+    for (int j = 0; j < n_sel; ++j)
+        if (genes[j] < 0 || genes[j] >= G) { SET_ERR(ctx, "gene index %d outside [0, %d)", genes[j], G); return CNMF_EINVAL; }
+    return CNMF_OK;
+}
+
+// The columns genes[0..n_sel) (checked) of the staged counts, scaled to unit variance and transposed back into the rows of
+// `out` (cells x n_sel, columns ascending within every row whatever the order of the list): over the column values cval
+// (S.columns.val, or a row-scaled copy of it) std_out[j] = the ddof = 1 standard deviation of column genes[j], y = x / std
+// -- a column of zero variance (std_out[j] == 0) is left as it is, like sc.pp.scale(zero_center=False); a caller that
+// cannot accept one passes zero_std_at: the first such column j ends the call before the transpose with *zero_std_at = j
+// and CNMF_EINVAL (the caller words the error).
+static int select_scaled_columns(cnmf_ctx* ctx, const CountStage& S, const double* cval, int32_t n_sel, const int32_t* genes,
+                                 double* std_out, DevCsr<double>* out, int* zero_std_at = nullptr)
+{
+    using namespace cnmf;
+    hipStream_t st = ctx->stream;
+    const int N = (int)S.counts.rows, G = (int)S.counts.cols;
+    DevPool pool;
+    int* d_genes = pool.get<int>(n_sel);
+    double* m = pool.get<double>(n_sel);
+    double* q = pool.get<double>(n_sel);
+    double* d_div = pool.get<double>(n_sel);
+    POOL_TRY(ctx, pool);
+    HIP_TRY(ctx, hipMemcpyAsync(d_genes, genes, (size_t)n_sel * sizeof(int), hipMemcpyHostToDevice, st));
+    prep_col_moments_kernel<<<(n_sel + 3) / 4, 256, 0, st>>>(S.columns.ptr, S.columns.idx, cval, d_genes, n_sel, N, nullptr, m, q);
+    HIP_TRY(ctx, hipGetLastError());
+    // one wait for both read-backs: the column pointers (the stored entries of the chosen columns) and the moments
+    std::vector<long long> hc((size_t)G + 1);
+    std::vector<double> hq(n_sel), div(n_sel);
+    HIP_TRY(ctx, hipMemcpyAsync(hc.data(), S.columns.ptr, ((size_t)G + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(hq.data(), q, (size_t)n_sel * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    long long nnz_sel = 0;
+    for (int j = 0; j < n_sel; ++j) {
+        nnz_sel += hc[genes[j] + 1] - hc[genes[j]];
+        std_out[j] = std::sqrt(hq[j] / (double)(N - 1));
+        if (std_out[j] == 0.0 && zero_std_at) { *zero_std_at = j; return CNMF_EINVAL; }
+        div[j] = std_out[j] == 0.0 ? 1.0 : std_out[j];
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(d_div, div.data(), (size_t)n_sel * sizeof(double), hipMemcpyHostToDevice, st));
+    return prep_transpose(ctx, S.columns, d_genes, d_div, n_sel, nnz_sel, out, cval);
 }
 
 extern "C" int cnmf_prepare_select(cnmf_ctx* ctx, int32_t n_sel, const int32_t* genes, int32_t densify, double* std_out,
@@ -303,84 +309,57 @@ extern "C" int cnmf_prepare_select(cnmf_ctx* ctx, int32_t n_sel, const int32_t* 
     using namespace cnmf;
     if (!ctx || !genes || !std_out || !row_sums_out || !nnz_out) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     PrepStage& P = ctx->prep;
-    if (P.nnz < 0) { SET_ERR(ctx, "cnmf_prepare_upload_csr has not been called"); return CNMF_ESTATE; }
-    const int N = (int)P.N, G = (int)P.G;
-    if (n_sel <= 0 || n_sel > G) { SET_ERR(ctx, "n_sel = %d outside [1, %d]", n_sel, G); return CNMF_EINVAL; }
-    if (N < 2) { SET_ERR(ctx, "need at least two cells for a variance"); return CNMF_EINVAL; }
-    for (int j = 0; j < n_sel; ++j)
-        if (genes[j] < 0 || genes[j] >= G) { SET_ERR(ctx, "gene index %d outside [0, %d)", genes[j], G); return CNMF_EINVAL; }
+    if (!P.staged()) { SET_ERR(ctx, "cnmf_prepare_upload_csr has not been called"); return CNMF_ESTATE; }
+    if (int rc = select_check_genes(ctx, P, n_sel, genes)) return rc;
+    const int N = (int)P.counts.rows;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     if (int rc = prep_ensure_columns(ctx)) return rc;
     P.release_out();
-    // the stored entries of the chosen columns
-    std::vector<long long> hc((size_t)G + 1);
-    HIP_TRY(ctx, hipMemcpyAsync(hc.data(), P.cptr, ((size_t)G + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    long long nnz_sel = 0;
-    for (int j = 0; j < n_sel; ++j) nnz_sel += hc[genes[j] + 1] - hc[genes[j]];
-    DevPool pool;
-    int* d_genes = pool.get<int>(n_sel);
-    double* m = pool.get<double>(n_sel);
-    double* q = pool.get<double>(n_sel);
-    double* d_div = pool.get<double>(n_sel);
-    POOL_TRY(ctx, pool);
-    HIP_TRY(ctx, hipMemcpyAsync(d_genes, genes, (size_t)n_sel * sizeof(int), hipMemcpyHostToDevice, st));
-    prep_col_moments_kernel<<<(n_sel + 3) / 4, 256, 0, st>>>(P.cptr, P.crow, P.cval, d_genes, n_sel, N, nullptr, m, q);
-    HIP_TRY(ctx, hipGetLastError());
-    std::vector<double> hq(n_sel), div(n_sel);
-    HIP_TRY(ctx, hipMemcpyAsync(hq.data(), q, (size_t)n_sel * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    for (int j = 0; j < n_sel; ++j) {
-        std_out[j] = std::sqrt(hq[j] / (double)(N - 1));
-        if (std_out[j] == 0.0 && densify) {
-            SET_ERR(ctx, "column %d (gene %d) has zero variance: X /= X.std(ddof=1) would leave NaN / inf", j, genes[j]);
-            return CNMF_EINVAL;
-        }
-        div[j] = std_out[j] == 0.0 ? 1.0 : std_out[j];        // sc.pp.scale(zero_center=False) leaves such a column as is
+    // Everything below is formed first; P.out and ctx->csr are published by the last statements of this function, when
+    // all of it stands.  A failure before them leaves "no selection to fetch" (P.out.nnz = -1).
+    DevCsrLocal<double> out;
+    int j0 = -1;
+    if (int rc = select_scaled_columns(ctx, P, P.columns.val, n_sel, genes, std_out, &out, densify ? &j0 : nullptr)) {
+        if (j0 >= 0) SET_ERR(ctx, "column %d (gene %d) has zero variance: X /= X.std(ddof=1) would leave NaN / inf", j0, genes[j0]);
+        return rc;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(d_div, div.data(), (size_t)n_sel * sizeof(double), hipMemcpyHostToDevice, st));
-    // rows of the result = the chosen columns of the counts in list order, transposed back: y = x / div, CSR, columns
-    // ascending within every row
-    long long* optr = nullptr;
-    int* oidx = nullptr;
-    double* oval = nullptr;
-    if (int rc = prep_transpose(ctx, P.cptr, P.crow, P.cval, d_genes, d_div, n_sel, N, nnz_sel, &optr, &oidx, &oval)) return rc;
-    P.optr = optr; P.oidx = oidx; P.oval = oval; P.out_nnz = nnz_sel; P.out_n = n_sel; P.out_dense = densify ? 1 : 0;
+    const long long nnz_sel = out.nnz;
+    DevPool pool;
     double* rs = pool.get<double>(N);
     POOL_TRY(ctx, pool);
-    prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.optr, P.oval, N, rs);
+    const unsigned rows_grid = (unsigned)((N + 3) / 4);
+    prep_row_sums_kernel<<<rows_grid, 256, 0, st>>>(out.ptr, out.val, N, rs);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(row_sums_out, rs, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    P.release_counts();                      // (the staging counts are done with)
+    // The staged counts and their transpose go BEFORE the images of the new resident matrix are allocated (alloc_matrix
+    // lets go of the old resident matrix first): the peak is the larger of the two, not their sum.
+    P.release_counts();
     // the new resident matrix: the images cnmf_set_matrix / cnmf_set_matrix_csr form from float32(y)
     if (int rc = alloc_matrix(ctx, N, n_sel, densify != 0)) return rc;
-    const unsigned rows_grid = (unsigned)((N + 3) / 4);
+    DevCsrLocal<float> img;
+    double* odense = nullptr;                // (a local until the commit; freed below if a step after it fails)
+    hipError_t e = hipSuccess;
     if (densify) {
-        HIP_TRY(ctx, hipMalloc((void**)&P.odense, (size_t)N * n_sel * sizeof(double)));
-        HIP_TRY(ctx, hipMemsetAsync(P.odense, 0, (size_t)N * n_sel * sizeof(double), st));
-        prep_store_kernel<<<rows_grid, 256, 0, st>>>(P.optr, P.oidx, P.oval, N, n_sel, ctx->G_pad, ctx->X, nullptr, P.odense);
-        HIP_TRY(ctx, hipGetLastError());
+        const size_t bytes = (size_t)N * n_sel * sizeof(double);
+        HIP_TRY(ctx, hipMalloc((void**)&odense, bytes));
+        e = hipMemsetAsync(odense, 0, bytes, st);
+        prep_store_kernel<<<rows_grid, 256, 0, st>>>(out.ptr, out.idx, out.val, N, n_sel, ctx->G_pad, ctx->X, nullptr, odense);
     } else {
-        const size_t n1 = (size_t)std::max<long long>(nnz_sel, 1);
-        long long* cp = nullptr;
-        int* ci = nullptr;
-        float* cv = nullptr;
-        hipError_t e = hipMalloc((void**)&cp, ((size_t)N + 1) * sizeof(long long));
-        if (e == hipSuccess) e = hipMalloc((void**)&ci, n1 * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&cv, n1 * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpyAsync(cp, P.optr, ((size_t)N + 1) * sizeof(long long), hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess && nnz_sel > 0) e = hipMemcpyAsync(ci, P.oidx, (size_t)nnz_sel * sizeof(int), hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) {
-            prep_store_kernel<<<rows_grid, 256, 0, st>>>(P.optr, P.oidx, P.oval, N, n_sel, 0, nullptr, cv, nullptr);
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) { hipFree(cp); hipFree(ci); hipFree(cv); }
-        HIP_TRY(ctx, e);
-        ctx->csr_ptr = cp; ctx->csr_idx = ci; ctx->csr_val = cv; ctx->csr_nnz = nnz_sel;
+        HIP_TRY(ctx, img.alloc_ptr(N, n_sel));
+        HIP_TRY(ctx, img.alloc_entries(nnz_sel));
+        HIP_TRY(ctx, hipMemcpyAsync(img.ptr, out.ptr, ((size_t)N + 1) * sizeof(long long), hipMemcpyDeviceToDevice, st));
+        if (nnz_sel > 0) HIP_TRY(ctx, hipMemcpyAsync(img.idx, out.idx, (size_t)nnz_sel * sizeof(int), hipMemcpyDeviceToDevice, st));
+        prep_store_kernel<<<rows_grid, 256, 0, st>>>(out.ptr, out.idx, out.val, N, n_sel, 0, nullptr, img.val, nullptr);
     }
-    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) hipFree(odense);
+    HIP_TRY(ctx, e);
+    P.odense = odense; P.out_dense = densify ? 1 : 0;
+    P.out.take(out);
+    if (!densify) ctx->csr.take(img);
     *nnz_out = nnz_sel;
     return CNMF_OK;
 }
@@ -389,19 +368,15 @@ extern "C" int cnmf_prepare_fetch(cnmf_ctx* ctx, int64_t* indptr, int32_t* indic
 {
     if (!ctx || !values) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     PrepStage& P = ctx->prep;
-    if (P.out_nnz < 0) { SET_ERR(ctx, "cnmf_prepare_select has not been called"); return CNMF_ESTATE; }
+    if (P.out.nnz < 0) { SET_ERR(ctx, "cnmf_prepare_select has not been called"); return CNMF_ESTATE; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const size_t N = (size_t)ctx->N;
     if (P.out_dense) {
-        HIP_TRY(ctx, hipMemcpyAsync(values, P.odense, N * (size_t)P.out_n * sizeof(double), hipMemcpyDeviceToHost, st));
+        const size_t bytes = (size_t)P.out.rows * (size_t)P.out.cols * sizeof(double);
+        HIP_TRY(ctx, hipMemcpyAsync(values, P.odense, bytes, hipMemcpyDeviceToHost, st));
     } else {
-        if (!indptr || (!indices && P.out_nnz > 0)) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
-        HIP_TRY(ctx, hipMemcpyAsync(indptr, P.optr, (N + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
-        if (P.out_nnz > 0) {
-            HIP_TRY(ctx, hipMemcpyAsync(indices, P.oidx, (size_t)P.out_nnz * sizeof(int), hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipMemcpyAsync(values, P.oval, (size_t)P.out_nnz * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
+        if (!indptr || (!indices && P.out.nnz > 0)) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
+        if (int rc = csr_fetch<double>(ctx, P.out, indptr, indices, values)) return rc;
     }
     HIP_TRY(ctx, hipStreamSynchronize(st));
     P.release_out();

@@ -254,7 +254,7 @@ static int pre_slot_arg(cnmf_ctx* ctx, int slot, bool need_data)
 {
     if (!ctx) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     if (slot < 0 || slot > 1) { SET_ERR(ctx, "slot %d outside [0, 1]", slot); return CNMF_EINVAL; }
-    if (need_data && ctx->pre.slot[slot].nnz == -1) { SET_ERR(ctx, "preprocess slot %d is empty", slot); return CNMF_ESTATE; }
+    if (need_data && ctx->pre.slot[slot].empty()) { SET_ERR(ctx, "preprocess slot %d is empty", slot); return CNMF_ESTATE; }
     return CNMF_OK;
 }
 
@@ -271,8 +271,8 @@ static double* pre_values(cnmf_ctx* ctx, int slot, long long* n, long long* zero
     PreSlot& S = ctx->pre.slot[slot];
     const long long all = ctx->pre.N * S.n;
     if (S.dense) { *n = all; *zeros = 0; return S.dense; }
-    *n = S.nnz; *zeros = all - S.nnz;
-    return S.val;
+    *n = S.csr.nnz; *zeros = all - S.csr.nnz;
+    return S.csr.val;
 }
 
 extern "C" int cnmf_preprocess_upload_csr(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data,
@@ -283,9 +283,9 @@ extern "C" int cnmf_preprocess_upload_csr(cnmf_ctx* ctx, const int64_t* indptr, 
     PreStage& P = ctx->pre;
     hipStreamSynchronize(ctx->stream);
     P.release();
-    if (int rc = prep_stage_csr(ctx, indptr, indices, data, data_is_f64, n_cells, n_genes, &P.ptr, &P.idx, &P.val)) return rc;
-    P.N = n_cells; P.G = n_genes; P.nnz = indptr[n_cells];
-    return prep_transpose(ctx, P.ptr, P.idx, P.val, nullptr, nullptr, (int)P.N, (int)P.G, P.nnz, &P.cptr, &P.crow, &P.cval);
+    if (int rc = stage_counts(ctx, indptr, indices, data, data_is_f64, n_cells, n_genes, false, true, P)) return rc;
+    P.N = n_cells;
+    return CNMF_OK;
 }
 
 extern "C" int cnmf_preprocess_set_dense(cnmf_ctx* ctx, int32_t slot, const double* X, int64_t n_rows, int64_t n_cols)
@@ -297,7 +297,7 @@ extern "C" int cnmf_preprocess_set_dense(cnmf_ctx* ctx, int32_t slot, const doub
         SET_ERR(ctx, "bad matrix shape %lld x %lld", (long long)n_rows, (long long)n_cols);
         return CNMF_EINVAL;
     }
-    const bool other = P.nnz >= 0 || P.slot[1 - slot].nnz != -1;
+    const bool other = P.staged() || !P.slot[1 - slot].empty();
     if (other && P.N != n_rows) {
         SET_ERR(ctx, "%lld rows where the staged data has %lld cells", (long long)n_rows, (long long)P.N);
         return CNMF_EINVAL;
@@ -313,7 +313,7 @@ extern "C" int cnmf_preprocess_set_dense(cnmf_ctx* ctx, int32_t slot, const doub
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) S.release();
     HIP_TRY(ctx, e);
-    P.N = n_rows; S.n = n_cols; S.nnz = -2;
+    P.N = n_rows; S.n = n_cols;
     return CNMF_OK;
 }
 
@@ -324,57 +324,32 @@ extern "C" int cnmf_preprocess_select(cnmf_ctx* ctx, int32_t slot, int32_t n_sel
     if (int rc = pre_slot_arg(ctx, slot, false)) return rc;
     if (!genes || !std_out || !nnz_out) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     PreStage& P = ctx->pre;
-    if (P.nnz < 0) { SET_ERR(ctx, "cnmf_preprocess_upload_csr has not been called"); return CNMF_ESTATE; }
-    const int N = (int)P.N, G = (int)P.G;
-    if (n_sel <= 0 || n_sel > G) { SET_ERR(ctx, "n_sel = %d outside [1, %d]", n_sel, G); return CNMF_EINVAL; }
-    if (N < 2) { SET_ERR(ctx, "need at least two cells for a variance"); return CNMF_EINVAL; }
-    for (int j = 0; j < n_sel; ++j)
-        if (genes[j] < 0 || genes[j] >= G) { SET_ERR(ctx, "gene index %d outside [0, %d)", genes[j], G); return CNMF_EINVAL; }
+    if (!P.staged()) { SET_ERR(ctx, "cnmf_preprocess_upload_csr has not been called"); return CNMF_ESTATE; }
+    if (int rc = select_check_genes(ctx, P, n_sel, genes)) return rc;
     if (std::isnan(max_value)) { SET_ERR(ctx, "max_value is NaN"); return CNMF_EINVAL; }
+    const int N = (int)P.N;
+    const long long nnz = P.counts.nnz;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     PreSlot& S = P.slot[slot];
     hipStreamSynchronize(st);
     S.release();
-    std::vector<long long> hc((size_t)G + 1);
-    HIP_TRY(ctx, hipMemcpyAsync(hc.data(), P.cptr, ((size_t)G + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    long long nnz_sel = 0;
-    for (int j = 0; j < n_sel; ++j) nnz_sel += hc[genes[j] + 1] - hc[genes[j]];
     DevPool pool;
-    int* d_genes = pool.get<int>(n_sel);
-    double* m = pool.get<double>(n_sel);
-    double* q = pool.get<double>(n_sel);
-    double* d_div = pool.get<double>(n_sel);
     double* scale = target_sum > 0.0 ? pool.get<double>(N) : nullptr;
     double* rs = target_sum > 0.0 ? pool.get<double>(N) : nullptr;
-    double* sval = target_sum > 0.0 ? pool.get<double>((size_t)std::max<long long>(P.nnz, 1)) : nullptr;
+    double* sval = target_sum > 0.0 ? pool.get<double>((size_t)std::max<long long>(nnz, 1)) : nullptr;
     POOL_TRY(ctx, pool);
-    HIP_TRY(ctx, hipMemcpyAsync(d_genes, genes, (size_t)n_sel * sizeof(int), hipMemcpyHostToDevice, st));
     if (scale) {
         // normalize_total over ALL genes of the staged counts, then the row-scaled values of the transpose
-        prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.ptr, P.val, N, rs);
+        prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, rs);
         prep_row_scale_kernel<<<(N + 255) / 256, 256, 0, st>>>(rs, N, target_sum, scale);
-        pre_scale_cols_kernel<<<pre_grid(P.nnz), 256, 0, st>>>(P.crow, P.cval, P.nnz, scale, sval);
+        pre_scale_cols_kernel<<<pre_grid(nnz), 256, 0, st>>>(P.columns.idx, P.columns.val, nnz, scale, sval);
     }
-    const double* cv = scale ? sval : P.cval;
-    prep_col_moments_kernel<<<(n_sel + 3) / 4, 256, 0, st>>>(P.cptr, P.crow, cv, d_genes, n_sel, N, nullptr, m, q);
-    HIP_TRY(ctx, hipGetLastError());
-    std::vector<double> hq(n_sel), div(n_sel);
-    HIP_TRY(ctx, hipMemcpyAsync(hq.data(), q, (size_t)n_sel * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    for (int j = 0; j < n_sel; ++j) {
-        std_out[j] = std::sqrt(hq[j] / (double)(N - 1));
-        div[j] = std_out[j] == 0.0 ? 1.0 : std_out[j];       // sc.pp.scale leaves a zero-variance column as it is
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(d_div, div.data(), (size_t)n_sel * sizeof(double), hipMemcpyHostToDevice, st));
-    long long* optr = nullptr;
-    int* oidx = nullptr;
-    double* oval = nullptr;
-    if (int rc = prep_transpose(ctx, P.cptr, P.crow, cv, d_genes, d_div, n_sel, N, nnz_sel, &optr, &oidx, &oval)) return rc;
-    S.ptr = optr; S.idx = oidx; S.val = oval; S.n = n_sel; S.nnz = nnz_sel;
+    if (int rc = select_scaled_columns(ctx, P, scale ? sval : P.columns.val, n_sel, genes, std_out, &S.csr)) return rc;
+    S.n = n_sel;
+    const long long nnz_sel = S.csr.nnz;
     if (!(max_value == INFINITY) && nnz_sel > 0) {
-        pre_ceiling_kernel<<<pre_grid(nnz_sel), 256, 0, st>>>(S.val, nnz_sel, max_value);
+        pre_ceiling_kernel<<<pre_grid(nnz_sel), 256, 0, st>>>(S.csr.val, nnz_sel, max_value);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -454,15 +429,14 @@ extern "C" int cnmf_preprocess_densify(cnmf_ctx* ctx, int32_t slot)
     HIP_TRY(ctx, hipMalloc((void**)&d, bytes));
     hipError_t e = hipMemsetAsync(d, 0, bytes, st);
     if (e == hipSuccess) {
-        prep_store_kernel<<<(unsigned)((N + 3) / 4), 256, 0, st>>>(S.ptr, S.idx, S.val, N, C, 0, nullptr, nullptr, d);
+        prep_store_kernel<<<(unsigned)((N + 3) / 4), 256, 0, st>>>(S.csr.ptr, S.csr.idx, S.csr.val, N, C, 0, nullptr, nullptr, d);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) hipFree(d);
     HIP_TRY(ctx, e);
-    hipFree(S.ptr); hipFree(S.idx); hipFree(S.val);
-    S.ptr = nullptr; S.idx = nullptr; S.val = nullptr;
-    S.dense = d; S.nnz = -2;
+    S.csr.release();
+    S.dense = d;
     return CNMF_OK;
 }
 
@@ -477,12 +451,8 @@ extern "C" int cnmf_preprocess_fetch(cnmf_ctx* ctx, int32_t slot, int64_t* indpt
     if (S.dense) {
         HIP_TRY(ctx, hipMemcpyAsync(values, S.dense, N * (size_t)S.n * sizeof(double), hipMemcpyDeviceToHost, st));
     } else {
-        if (!indptr || (!indices && S.nnz > 0)) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
-        HIP_TRY(ctx, hipMemcpyAsync(indptr, S.ptr, (N + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
-        if (S.nnz > 0) {
-            HIP_TRY(ctx, hipMemcpyAsync(indices, S.idx, (size_t)S.nnz * sizeof(int), hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipMemcpyAsync(values, S.val, (size_t)S.nnz * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
+        if (!indptr || (!indices && S.csr.nnz > 0)) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
+        if (int rc = csr_fetch<double>(ctx, S.csr, indptr, indices, values)) return rc;
     }
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return CNMF_OK;

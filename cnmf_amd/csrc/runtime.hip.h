@@ -44,47 +44,82 @@ struct SpImage {
     void release() { hipFree(perm); hipFree(off); hipFree(len); hipFree(ent); *this = SpImage{}; }
 };
 
-// staging of the cnmf_prepare_* entry points (prepare_host.hip.h): the raw cells x all-genes counts as CSR (float64
-// values), their transpose (built on first use), and the float64 result of cnmf_prepare_select until it is fetched
-struct PrepStage {
-    int64_t N = 0, G = 0, nnz = -1;                 // nnz = -1: nothing uploaded
-    long long* ptr = nullptr; int* idx = nullptr; double* val = nullptr;
-    long long* cptr = nullptr; int* crow = nullptr; double* cval = nullptr;
-    int64_t out_n = 0, out_nnz = -1; int out_dense = 0;   // out_nnz = -1: no selection to fetch
-    long long* optr = nullptr; int* oidx = nullptr; double* oval = nullptr;
+// A rows x cols compressed-row matrix on the device that owns its arrays: 64-bit row pointers, values of type V (float:
+// the resident matrix, double: the staging paths).  nnz = -1: empty.  Not copyable, and no destructor: like Arena and
+// SpImage it is released explicitly, by an owner that has synchronised the stream that may still use the arrays.
+template <typename V>
+struct DevCsr {
+    int64_t rows = 0, cols = 0, nnz = -1;
+    long long* ptr = nullptr; int* idx = nullptr; V* val = nullptr;
+    DevCsr() = default;
+    DevCsr(const DevCsr&) = delete;
+    DevCsr& operator=(const DevCsr&) = delete;
+    void release() {
+        hipFree(ptr); hipFree(idx); hipFree(val);
+        ptr = nullptr; idx = nullptr; val = nullptr; rows = cols = 0; nnz = -1;
+    }
+    hipError_t alloc_ptr(int64_t r, int64_t c) {
+        rows = r; cols = c;
+        return hipMalloc((void**)&ptr, ((size_t)r + 1) * sizeof(long long));
+    }
+    hipError_t alloc_entries(long long n) {           // (an array without entries still gets one element)
+        const size_t n1 = (size_t)std::max<long long>(n, 1);
+        hipError_t e = hipMalloc((void**)&idx, n1 * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void**)&val, n1 * sizeof(V));
+        if (e == hipSuccess) nnz = n;
+        return e;
+    }
+    // the commit step: this matrix becomes s (what it held is released), s is left empty
+    void take(DevCsr& s) {
+        release();
+        rows = s.rows; cols = s.cols; nnz = s.nnz; ptr = s.ptr; idx = s.idx; val = s.val;
+        s.ptr = nullptr; s.idx = nullptr; s.val = nullptr;
+        s.release();
+    }
+};
+
+// A DevCsr under construction, local to one call: released on EVERY return path (the HIP_TRY early returns included;
+// hipFree waits for work that still uses the arrays, as for DevPool) unless an owner took it.  The one place where the
+// three arrays are cleaned up after a failure.
+template <typename V>
+struct DevCsrLocal : DevCsr<V> {
+    ~DevCsrLocal() { this->release(); }
+};
+
+// the raw cells x genes counts a stage keeps (CSR, float64 values) and their transpose (genes x cells)
+struct CountStage {
+    DevCsr<double> counts, columns;
+    bool staged() const { return counts.nnz >= 0; }
+    void release_counts() { counts.release(); columns.release(); }
+};
+
+// staging of the cnmf_prepare_* entry points (prepare_host.hip.h): the counts (their transpose is built on first use)
+// and the float64 result of cnmf_prepare_select until it is fetched: `out` (cells x selected genes; out.nnz = -1: no
+// selection to fetch) and, for a densified selection, its dense image `odense` beside it
+struct PrepStage : CountStage {
+    DevCsr<double> out;
     double* odense = nullptr;
-    void release_counts() {
-        hipFree(ptr); hipFree(idx); hipFree(val); hipFree(cptr); hipFree(crow); hipFree(cval);
-        ptr = cptr = nullptr; idx = crow = nullptr; val = cval = nullptr; nnz = -1;
-    }
-    void release_out() {
-        hipFree(optr); hipFree(oidx); hipFree(oval); hipFree(odense);
-        optr = nullptr; oidx = nullptr; oval = odense = nullptr; out_nnz = -1;
-    }
+    int out_dense = 0;
+    void release_out() { out.release(); hipFree(odense); odense = nullptr; }
     void release() { release_counts(); release_out(); }
 };
 
 // staging of the cnmf_preprocess_* entry points (preprocess_host.hip.h), apart from both the resident matrix and the
-// prepare staging: the raw counts (CSR, float64 values) and their transpose, two result slots (cells x selected genes,
-// CSR or dense float64) and the ridge factors R^T / Phi^T of the last moments pass
+// prepare staging: the counts and their transpose, two result slots (cells x selected genes, CSR or dense float64) and
+// the ridge factors R^T / Phi^T of the last moments pass
 struct PreSlot {
-    int64_t n = 0, nnz = -1;                         // columns; nnz = -1: empty, -2: dense
-    long long* ptr = nullptr; int* idx = nullptr; double* val = nullptr;
-    double* dense = nullptr;                         // [N][n] row-major
-    void release() { hipFree(ptr); hipFree(idx); hipFree(val); hipFree(dense); *this = PreSlot{}; }
+    int64_t n = 0;                                   // columns
+    DevCsr<double> csr;
+    double* dense = nullptr;                         // [N][n] row-major; a dense slot has no csr
+    bool empty() const { return !dense && csr.nnz < 0; }
+    void release() { csr.release(); hipFree(dense); dense = nullptr; n = 0; }
 };
 
-struct PreStage {
-    int64_t N = 0, G = 0, nnz = -1;                  // the staged counts; nnz = -1: none
-    long long* ptr = nullptr; int* idx = nullptr; double* val = nullptr;
-    long long* cptr = nullptr; int* crow = nullptr; double* cval = nullptr;
+struct PreStage : CountStage {
+    int64_t N = 0;                                   // cells of the staged counts and of the slots
     PreSlot slot[2];
     double *Rt = nullptr, *Pt = nullptr;             // [N][K], [N][B1]
     int K = 0, B1 = 0;
-    void release_counts() {
-        hipFree(ptr); hipFree(idx); hipFree(val); hipFree(cptr); hipFree(crow); hipFree(cval);
-        ptr = cptr = nullptr; idx = crow = nullptr; val = cval = nullptr; nnz = -1; G = 0;
-    }
     void release_ridge() { hipFree(Rt); hipFree(Pt); Rt = Pt = nullptr; K = B1 = 0; }
     void release() { release_counts(); release_ridge(); slot[0].release(); slot[1].release(); N = 0; }
 };
@@ -175,10 +210,7 @@ struct cnmf_ctx {
     long long x_nnz = -1;
     // compressed rows of X (cells x genes) and of X^T (genes x cells), csr_host.hip.h: kept from cnmf_set_matrix_csr or
     // built from the dense matrix on first use; 64-bit row pointers, float32 values like the dense image
-    long long *csr_ptr = nullptr, *csc_ptr = nullptr;
-    int *csr_idx = nullptr, *csc_idx = nullptr;
-    float *csr_val = nullptr, *csc_val = nullptr;
-    long long csr_nnz = -1;
+    DevCsr<float> csr, csc;
 
     // batch buffers (sized for kc_alloc columns)
     int kc_alloc = 0, nsplit_alloc = 0, nsplitA_alloc = 0, parts_alloc = 0;

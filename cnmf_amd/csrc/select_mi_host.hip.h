@@ -595,14 +595,14 @@ extern "C" int cnmf_preprocess_row_sums(cnmf_ctx* ctx, double* row_sums)
     using namespace cnmf;
     if (!ctx || !row_sums) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     PreStage& P = ctx->pre;
-    if (P.nnz < 0) { SET_ERR(ctx, "cnmf_preprocess_upload_csr has not been called"); return CNMF_ESTATE; }
+    if (!P.staged()) { SET_ERR(ctx, "cnmf_preprocess_upload_csr has not been called"); return CNMF_ESTATE; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const int N = (int)P.N;
     DevPool pool;
     double* rs = pool.get<double>(N);
     POOL_TRY(ctx, pool);
-    prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.ptr, P.val, N, rs);
+    prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, rs);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(row_sums, rs, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -616,8 +616,8 @@ extern "C" int cnmf_preprocess_normalize_dense(cnmf_ctx* ctx, int32_t slot, doub
     if (int rc = pre_slot_arg(ctx, slot, false)) return rc;
     if (!std_out) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     PreStage& P = ctx->pre;
-    if (P.nnz < 0) { SET_ERR(ctx, "cnmf_preprocess_upload_csr has not been called"); return CNMF_ESTATE; }
-    const int N = (int)P.N, G = (int)P.G;
+    if (!P.staged()) { SET_ERR(ctx, "cnmf_preprocess_upload_csr has not been called"); return CNMF_ESTATE; }
+    const int N = (int)P.N, G = (int)P.counts.cols;
     if (N < 2) { SET_ERR(ctx, "need at least two cells for a variance"); return CNMF_EINVAL; }
     if (std::isnan(max_value)) { SET_ERR(ctx, "max_value is NaN"); return CNMF_EINVAL; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -632,13 +632,13 @@ extern "C" int cnmf_preprocess_normalize_dense(cnmf_ctx* ctx, int32_t slot, doub
     POOL_TRY(ctx, pool);
     const long long n = (long long)N * G;
     HIP_TRY(ctx, hipMalloc((void**)&S.dense, (size_t)n * sizeof(double)));
-    S.n = G; S.nnz = -2;
+    S.n = G;
     HIP_TRY(ctx, hipMemsetAsync(S.dense, 0, (size_t)n * sizeof(double), st));
     if (scale) {
-        prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.ptr, P.val, N, rs);
+        prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, rs);
         prep_row_scale_kernel<<<(N + 255) / 256, 256, 0, st>>>(rs, N, target_sum, scale);
     }
-    mi_store_scaled_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.ptr, P.idx, P.val, N, G, scale, S.dense);
+    mi_store_scaled_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.idx, P.counts.val, N, G, scale, S.dense);
     mi_col_std_kernel<<<(G + 255) / 256, 256, 0, st>>>(S.dense, N, G, sd);
     mi_scale_clip_kernel<<<pre_grid(n), 256, 0, st>>>(S.dense, n, G, sd, max_value);
     HIP_TRY(ctx, hipGetLastError());

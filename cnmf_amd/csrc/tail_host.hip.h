@@ -214,7 +214,7 @@ extern "C" int cnmf_xt_matmul_f64(cnmf_ctx* ctx, int k, const double* W, int zsc
                                   const double* inv_std, double* out)
 {
     if (!ctx || !W || !out || k < 1 || (zscore && (!mean || !inv_std))) { SET_ERR(ctx, "bad argument"); return CNMF_EINVAL; }
-    const bool on_rows = !ctx->X && ctx->csr_ptr;          // compressed rows only (round 5): walk the stored entries of X^T
+    const bool on_rows = !ctx->X && ctx->csr.ptr;          // compressed rows only (round 5): walk the stored entries of X^T
     if (!on_rows) { if (int rcd_ = ensure_dense(ctx)) return rcd_; }
     if (k > KMAX) { SET_ERR(ctx, "k=%d > %d", k, KMAX); return CNMF_EUNSUPPORTED; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -237,7 +237,7 @@ extern "C" int cnmf_xt_matmul_f64(cnmf_ctx* ctx, int k, const double* W, int zsc
         rc = ensure_csc(ctx);
         if (rc) return rc;
         cnmf::colsum_f64_kernel<<<k, 256, 0, st>>>(dW, N, k, dws);
-        cnmf::csc_xtw_f64_kernel<<<(G + 3) / 4, 256, 0, st>>>(ctx->csc_ptr, ctx->csc_idx, ctx->csc_val, G, dW, k, zscore, dmean, dinv, dws, dout);
+        cnmf::csc_xtw_f64_kernel<<<(G + 3) / 4, 256, 0, st>>>(ctx->csc.ptr, ctx->csc.idx, ctx->csc.val, G, dW, k, zscore, dmean, dinv, dws, dout);
         HIP_TRY(ctx, hipGetLastError());
     } else
         rc = xtw_f64_device(ctx, pool, dW, k, zscore, dmean, dinv, dout);

@@ -172,6 +172,36 @@ def test_as_stored_upload_still_checks_its_values(engine):
         engine.preprocess_upload_as_stored(X)
 
 
+# ---------------------------------------------------------------- the chunk edge of the staging transpose
+def test_select_across_the_chunk_edge_of_the_staging_transpose(engine):
+    """4133 cells x 37 genes: the counting-sort transpose of the upload walks at most 4096 row chunks, so here a chunk
+    holds two rows and the last one a single row; cell 2000 and the last cell are empty, gene 11 too.  All genes in
+    reversed order, no target_sum, no ceiling, against scipy: the structure exactly, the values bit for bit -- the fill
+    kernel forms the one correctly rounded float64 quotient x / div, div = the returned std (1 where it is 0)."""
+    rs = np.random.RandomState(4133)
+    D = rs.poisson(3.0, size=(4133, 37)) * (rs.random_sample((4133, 37)) < 0.15)
+    D[2000] = 0
+    D[-1] = 0
+    D[:, 11] = 0
+    X = sp.csr_matrix(D.astype(np.float64))
+    N, G = X.shape
+    assert N > 4096 and (N + 4095) // 4096 == 2 and N % 2 == 1
+    lens = np.diff(X.indptr)
+    assert lens[2000] == 0 and lens[-1] == 0 and lens[1999] > 0 and not (X.indices == 11).any()
+    genes = np.arange(G)[::-1]
+    engine.preprocess_upload(X)
+    std = engine.preprocess_select(0, genes, 0.0, None)
+    Y = engine.preprocess_fetch(0)
+    want = sp.csr_matrix(X[:, genes])
+    want.sum_duplicates()
+    want.sort_indices()
+    assert Y.shape == want.shape and Y.nnz == want.nnz == X.nnz
+    assert np.array_equal(Y.indptr, want.indptr) and np.array_equal(Y.indices, want.indices)
+    assert std.dtype == np.float64 and std[genes == 11][0] == 0.0 and np.count_nonzero(std == 0.0) == 1
+    div = np.where(std == 0.0, 1.0, std)
+    assert np.array_equal(Y.data.view(np.uint64), (want.data / div[want.indices]).view(np.uint64))
+
+
 # ---------------------------------------------------------------- real values: the sums against math.fsum
 def test_real_valued_sums_are_within_their_bounds(engine):
     """4 097 cells of at most 700 stored entries, gamma values.  A float64 sum of n non-negative terms in any order is

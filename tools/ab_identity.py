@@ -1,7 +1,9 @@
 """Fixed seeded jobs through whichever build of the library CNMF_LIB_PATH names, for bit-identity A/B runs of two builds:
-    CNMF_LIB_PATH=/path/to/libcnmf_hip.so [CNMF_GEMM3=2 ...] python tools/ab_identity.py wide|general|f32|mode|init|streamk|streamk_general
+    CNMF_LIB_PATH=/path/to/libcnmf_hip.so [CNMF_GEMM3=2 ...] python tools/ab_identity.py wide|general|f32|mode|init|streamk|streamk_general|staging
 Prints one JSON line: SHA-256 digests of everything the job's batch calls returned (H, n_iter, viol) and of the
-last_stats fields that describe the schedule.  One process per library and per knob value; the lines must be equal."""
+last_stats fields that describe the schedule.  One process per library and per knob value; the lines must be equal.
+``staging`` runs no coordinate-descent batch: it digests every array the prepare / preprocess / filter entry points and
+a Kullback-Leibler batch on the non-zeros return for one small count matrix (staging_matrix)."""
 import hashlib
 import json
 import os
@@ -58,8 +60,83 @@ def calls(job):
     raise SystemExit("unknown job %r" % job)
 
 
+def staging_matrix():
+    """4133 cells x 37 genes of integer counts, about 15 % stored: more than 4096 rows, so the staging transpose puts two
+    rows into a chunk and its last chunk is short; cell 2000 and the last cell are empty, and so is gene 11"""
+    import scipy.sparse as sp
+    rs = np.random.RandomState(4133)
+    D = rs.poisson(3.0, size=(4133, 37)) * (rs.random_sample((4133, 37)) < 0.15)
+    D[2000] = 0
+    D[-1] = 0
+    D[:, 11] = 0
+    return sp.csr_matrix(D.astype(np.float64))
+
+
+def staging():
+    """{name: SHA-256} of every array the staging entry points return for staging_matrix()"""
+    import ctypes as C
+    import scipy.sparse as sp
+    out = {}
+
+    def put(name, *arrays):
+        h = hashlib.sha256()
+        for a in arrays:
+            if sp.issparse(a):
+                a = np.concatenate([np.asarray(a.shape, dtype=np.int64), a.indptr.astype(np.int64), a.indices.astype(np.int64),
+                                    a.data.view(np.int64)])
+            h.update(np.ascontiguousarray(a).tobytes())
+        assert name not in out
+        out[name] = h.hexdigest()
+
+    X = staging_matrix()
+    N, G = X.shape
+    genes = np.arange(G - 1, -1, -3)                          # descending, gene 11 (no entries: zero variance) among them
+    live = genes[genes != 11]
+    eng = Engine(0)
+    for dt in (np.float32, np.float64):
+        t = np.dtype(dt).name
+        Xd = X.astype(dt)
+        for densify, sel in ((False, genes), (True, live)):
+            eng.prepare_upload(Xd)
+            put("prepare_tpm_stats_%s_%d" % (t, densify), *eng.prepare_tpm_stats(1e6, want_tpm=True))
+            put("prepare_select_%s_%d" % (t, densify), *eng.prepare_select(sel, densify))
+            put("prepare_resident_%s_%d" % (t, densify), eng.get_matrix())
+        if dt == np.float32:                                   # (Engine.preprocess_upload widens on the host: the float32 upload by hand)
+            ip, ix, v = X.indptr.astype(np.int64), X.indices.astype(np.int32), Xd.data
+            eng._check(eng._lib.cnmf_preprocess_upload_csr(eng._ctx, ip.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                           ix.ctypes.data_as(C.POINTER(C.c_int32)), v.ctypes.data_as(C.c_void_p),
+                                                           0, N, G))
+            eng._pre = {"N": N, "G": G, 0: None, 1: None}
+        else:
+            eng.preprocess_upload(Xd)
+        put("select_std_%s" % t, eng.preprocess_select(0, genes, 1e4, 2.5), eng.preprocess_select(1, genes, 0.0, 2.5))
+        put("select_fetch_%s" % t, eng.preprocess_fetch(0), eng.preprocess_fetch(1))
+        eng.preprocess_densify(1)
+        put("select_dense_%s" % t, eng.preprocess_fetch(1))
+        cells, kept = np.arange(N) % 3 != 1, np.arange(G) % 5 != 2
+        put("gene_detect_%s" % t, *eng.preprocess_gene_detect(), *eng.preprocess_gene_detect(cells))
+        put("cell_sums_%s" % t, eng.preprocess_cell_sums(), eng.preprocess_cell_sums(kept))
+        put("subset_%s" % t, np.asarray(eng.preprocess_subset(cells, kept), dtype=np.int64))
+        put("fetch_counts_%s" % t, eng.preprocess_fetch_counts(), eng.preprocess_fetch_counts(1e4))
+        put("select_after_subset_%s" % t, eng.preprocess_select(0, np.arange(int(kept.sum()))[::-1], 1e4, None),
+            eng.preprocess_fetch(0))
+        eng.preprocess_release()
+    # the resident matrix as CSR, Kullback-Leibler on the non-zeros: the compressed rows of X^T come from ensure_csc
+    eng.set_matrix(X.astype(np.float32))
+    H, W, n_iter, err = eng.nmf_mu_batch([5, 5], seeds=[11, 12], max_iter=10, return_W=True, warn=False)
+    images = eng.matrix_images()
+    assert images["csr_of_transpose"] and images["non_zero_images_16"], images
+    put("kl_batch", *H, *W, n_iter, err)
+    eng.close()
+    return out
+
+
 def main():
     job = sys.argv[1]
+    env = {k: v for k, v in sorted(os.environ.items()) if k.startswith("CNMF_") and k != "CNMF_LIB_PATH"}
+    if job == "staging":
+        print(json.dumps({"job": job, "env": env, "seen": [], "sha256": staging()}))
+        return
     X, jobs = calls(job)
     eng = Engine(0)
     eng.set_matrix(X)
@@ -74,7 +151,6 @@ def main():
         for name in STATS:
             h[name].update(str(int(eng.last_stats[name])).encode() + b";")
         seen.append({name: int(eng.last_stats[name]) for name in ("kc", "gemm_mode", "outer_iterations", "tail_iterations")})
-    env = {k: v for k, v in sorted(os.environ.items()) if k.startswith("CNMF_") and k != "CNMF_LIB_PATH"}
     print(json.dumps({"job": job, "env": env, "seen": seen,
                       "sha256": {name: d.hexdigest() for name, d in h.items()}}))
 
