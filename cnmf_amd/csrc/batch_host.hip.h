@@ -265,7 +265,7 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
         (int64_t)ctx->N_pad * ctx->G_pad >= (1ll << 24)) {
         rc = ensure_counts(ctx);
         if (rc) return rc;
-        if (ctx->count_state == 1) KC = 256;
+        if (ctx->counts.state == 1) KC = 256;
     }
     const int KC0 = KC;
     rc = ensure_batch(ctx, KC, max_k, min_k);
@@ -277,22 +277,19 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
     if (use3 && kn.gemm3 >= 3) {
         rc = ensure_counts(ctx);
         if (rc) return rc;
-        usec = ctx->count_state == 1;
+        usec = ctx->counts.state == 1;
     }
     // any OTHER matrix in the default mode: X itself as two f16 planes with a per-row exponent, 4 MFMAs per product
     // (gemm_mode 5; CNMF_GEMM3=1|2 keep the 3 x 3 bf16 planes of rounds 1-2, 6 MFMAs)
     bool use2g = use3 && !usec && kn.gemm3 >= 4 && ctx->G_pad % G3C_JW == 0 && ctx->N_pad % G3C_JW == 0;
     if (use2g) { rc = ensure_x2planes(ctx); if (rc) return rc; }
-    bool use2h = (usec && ctx->count_fmt == 4) || use2g;      // ... on the f16 pipe: two f16 factor planes
+    bool use2h = (usec && ctx->counts.fmt == 4) || use2g;      // ... on the f16 pipe: two f16 factor planes
     const int gemm_mode_used = !use3 ? 0 : (use2g ? 5 : (usec ? (use2h ? 4 : 3) : std::min(kn.gemm3, 2)));
     const int KbA = ctx->G_pad / 16, KbB = ctx->N_pad / 16;
-    // the X-side operands of the f16 kernels: the integer count plane(s), or the two planes of a general matrix
-    const unsigned char *xA = use2g ? ctx->X2h : ctx->C1, *xAhi = use2g ? ctx->X2m : ctx->C1h;
-    const unsigned char *xB = use2g ? ctx->Xt2h : ctx->Ct1, *xBhi = use2g ? ctx->Xt2m : ctx->Ct1h;
-    const unsigned int *xAfl = use2g ? ctx->onesA : ctx->hiA, *xBfl = use2g ? ctx->onesB : ctx->hiB;
-    const float *csA = use2g ? ctx->x2sA : nullptr, *csB = use2g ? ctx->x2sB : nullptr;      // 2^-s per output column
-    const double* dsc = use2g ? nullptr : ctx->d_scale;                                      // per-gene scale of the count path
-    const int nsubA = use2h ? gemm2h_nsub(xAhi != nullptr, KbA) : 1, nsubB = use2h ? gemm2h_nsub(xBhi != nullptr, KbB) : 1;
+    // the X-side operands of the count and f16 kernels: the integer count plane(s), or the two planes of a general matrix
+    const XOperand xA = use2g ? ctx->x2.passA() : ctx->counts.passA(), xB = use2g ? ctx->x2.passB() : ctx->counts.passB();
+    const double* dsc = use2g ? nullptr : ctx->counts.d_scale;                               // per-gene scale of the count path
+    const int nsubA = use2h ? gemm2h_nsub(xA.hi != nullptr, KbA) : 1, nsubB = use2h ? gemm2h_nsub(xB.hi != nullptr, KbB) : 1;
     // W planes written by the W sweep itself (kernels_sweep.hip.h, PLN) instead of a separate pass over W; ranks above
     // 64 (sweep_big_kernel) keep the separate split for the whole call.
     const bool fuseW = use2h && max_k <= KSMALL && ctx->shiftW != nullptr;
@@ -667,27 +664,27 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
                 HIP_TRY(ctx, launch_split2h(st, ctx->H, ctx->G_pad, KC, ctx->G_pad, ctx->H3, G3_MW, dsc, ctx->rmaxH,
                                             partsH, ctx->iscaleH));
             } else if (n_new > 0 || !h3_valid)
-                HIP_TRY(ctx, launch_split3(st, ctx->H, ctx->G_pad, KC, ctx->G_pad, ctx->H3, G3_MW, usec ? ctx->d_scale : nullptr));
+                HIP_TRY(ctx, launch_split3(st, ctx->H, ctx->G_pad, KC, ctx->G_pad, ctx->H3, G3_MW, usec ? ctx->counts.d_scale : nullptr));
             if (time_gemm) hipEventRecord(gev[gev.size() - 4], st);
             if (sk3.on) {
                 if (use2h) {
-                    HIP_TRY(ctx, launch_gemm2h_streamk(st, sk3, ctx->H3, xA, xAhi, xAfl, ctx->iscaleH, KbA,
-                                                       ctx->XHt, ctx->XHt1, ctx->XHt2, ctx->N_pad, csA, livemask));
+                    HIP_TRY(ctx, launch_gemm2h_streamk(st, sk3, ctx->H3, xA.plane, xA.hi, xA.flags, ctx->iscaleH, KbA,
+                                                       ctx->XHt, ctx->XHt1, ctx->XHt2, ctx->N_pad, xA.colscale, livemask));
                 }
                 else if (usec)
-                    HIP_TRY(ctx, launch_gemm3c_streamk(st, sk3, ctx->H3, ctx->C1, ctx->C1h, ctx->hiA, ctx->XHt, ctx->XHt1,
+                    HIP_TRY(ctx, launch_gemm3c_streamk(st, sk3, ctx->H3, xA.plane, xA.hi, xA.flags, ctx->XHt, ctx->XHt1,
                                                        ctx->XHt2, ctx->N_pad));
                 else
-                    HIP_TRY(ctx, launch_gemm3_streamk(st, sk3, ctx->H3, ctx->X3, ctx->XHt, ctx->XHt1, ctx->XHt2, ctx->N_pad));
+                    HIP_TRY(ctx, launch_gemm3_streamk(st, sk3, ctx->H3, ctx->planes.X3, ctx->XHt, ctx->XHt1, ctx->XHt2, ctx->N_pad));
                 spA = SplitInfo{ctx->XHt1, ctx->d_split, jwA, G3_MW, sk3.MG, ctx->XHt2};
             } else if (use2h) {
-                HIP_TRY(ctx, launch_gemm2h(st, ctx->H3, xA, xAhi, xAfl, ctx->iscaleH, KbA, ctx->XHt, ctx->N_pad,
-                                           (long long)KC * ctx->N_pad, KC, ctx->N_pad, nsplitA, csA, livemask));
+                HIP_TRY(ctx, launch_gemm2h(st, ctx->H3, xA.plane, xA.hi, xA.flags, ctx->iscaleH, KbA, ctx->XHt, ctx->N_pad,
+                                           (long long)KC * ctx->N_pad, KC, ctx->N_pad, nsplitA, xA.colscale, livemask));
             } else if (usec) {
-                HIP_TRY(ctx, launch_gemm3c(st, ctx->H3, ctx->C1, ctx->C1h, ctx->hiA, ctx->G_pad / 16, ctx->XHt, ctx->N_pad,
+                HIP_TRY(ctx, launch_gemm3c(st, ctx->H3, xA.plane, xA.hi, xA.flags, ctx->G_pad / 16, ctx->XHt, ctx->N_pad,
                                            (long long)KC * ctx->N_pad, KC, ctx->N_pad, nsplitA));
             } else {
-                HIP_TRY(ctx, launch_gemm3(st, ctx->H3, ctx->X3, ctx->G_pad / 16, ctx->XHt, ctx->N_pad,
+                HIP_TRY(ctx, launch_gemm3(st, ctx->H3, ctx->planes.X3, ctx->G_pad / 16, ctx->XHt, ctx->N_pad,
                                           (long long)KC * ctx->N_pad, KC, ctx->N_pad, nsplitA));
             }
         } else if (sk.on) {
@@ -730,13 +727,13 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
         // pass B : XtW[S][KC][G] = Wt_all . X  (split over cells)  (sklearn _nmf.py:505-507)
         const int nsB = use2h ? gemm2h_splits(KbB, nsplit3, nsubB) : (use3 ? nsplit3 : nsplit);
         if (use2h)
-            HIP_TRY(ctx, launch_gemm2h(st, ctx->Wt3, xB, xBhi, xBfl, ctx->iscaleW, KbB, ctx->XtW, ctx->G_pad,
-                                       (long long)KC * ctx->G_pad, KC, ctx->G_pad, nsplit3, csB, livemask));
+            HIP_TRY(ctx, launch_gemm2h(st, ctx->Wt3, xB.plane, xB.hi, xB.flags, ctx->iscaleW, KbB, ctx->XtW, ctx->G_pad,
+                                       (long long)KC * ctx->G_pad, KC, ctx->G_pad, nsplit3, xB.colscale, livemask));
         else if (usec)
-            HIP_TRY(ctx, launch_gemm3c(st, ctx->Wt3, ctx->Ct1, ctx->Ct1h, ctx->hiB, ctx->N_pad / 16, ctx->XtW, ctx->G_pad,
+            HIP_TRY(ctx, launch_gemm3c(st, ctx->Wt3, xB.plane, xB.hi, xB.flags, ctx->N_pad / 16, ctx->XtW, ctx->G_pad,
                                        (long long)KC * ctx->G_pad, KC, ctx->G_pad, nsplit3));
         else if (use3)
-            HIP_TRY(ctx, launch_gemm3(st, ctx->Wt3, ctx->Xt3, ctx->N_pad / 16, ctx->XtW, ctx->G_pad,
+            HIP_TRY(ctx, launch_gemm3(st, ctx->Wt3, ctx->planes.Xt3, ctx->N_pad / 16, ctx->XtW, ctx->G_pad,
                                       (long long)KC * ctx->G_pad, KC, ctx->G_pad, nsplit3));
         else
             HIP_TRY(ctx, launch_gemm<true>(st, 0, ctx->Wt, ctx->N_pad, ctx->X, ctx->G_pad, ctx->XtW,
@@ -771,7 +768,7 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
             const FinalizeArgs fa{ctx->gram_part, ctx->viol_part, partsH, ctx->gramH, l2W, ctx->d_slots, 1, prm->tol,
                                   prm->max_iter, 1, max_k, snap_dev, (int)(it + 1)};
             HIP_TRY(ctx, launch_split3_finalize(st, ctx->H, ctx->G_pad, KC, ctx->G_pad, ctx->H3, G3_MW,
-                                                usec ? ctx->d_scale : nullptr, fa, nslots, fin_y));
+                                                usec ? ctx->counts.d_scale : nullptr, fa, nslots, fin_y));
             h3_valid = true;
         } else {
             finalize_kernel<<<dim3(nslots, fin_y), 256, 0, st>>>(ctx->gram_part, ctx->viol_part, partsH, ctx->gramH, l2W,

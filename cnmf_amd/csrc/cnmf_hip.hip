@@ -99,17 +99,17 @@ extern "C" int cnmf_reload_env(cnmf_ctx* ctx)
     return CNMF_OK;
 }
 
-static void free_x2(cnmf_ctx* c)
+// Every image derived from the resident matrix describes the OLD values: dropped, all of them and only here, whenever
+// X is replaced (alloc_matrix), rewritten in place (cnmf_scale_columns) or goes away (cnmf_destroy).
+// (the resident spectra store outlives a change of the matrix: it carries its own gene count)
+static void drop_derived_images(cnmf_ctx* c)
 {
-    hipFree(c->X2h); hipFree(c->X2m); hipFree(c->Xt2h); hipFree(c->Xt2m); hipFree(c->x2sA); hipFree(c->x2sB);
-    hipFree(c->onesA); hipFree(c->onesB);
-    c->X2h = c->X2m = c->Xt2h = c->Xt2m = nullptr; c->x2sA = c->x2sB = nullptr; c->onesA = c->onesB = nullptr;
-}
-
-static void free_mu_sparse(cnmf_ctx* c)
-{
+    hipStreamSynchronize(c->stream);
+    c->planes.release(); c->counts.release(); c->x2.release();
+    hipFree(c->XtF); c->XtF = nullptr;
     for (int i = 0; i < 2; ++i) { c->spA[i].release(); c->spB[i].release(); }
     c->x_nnz = -1;
+    free_csr(c);
 }
 
 static void free_batch(cnmf_ctx* c)
@@ -137,10 +137,8 @@ extern "C" void cnmf_destroy(cnmf_ctx* ctx)
     hipStreamSynchronize(ctx->stream);
     free_batch(ctx);
     cnmf_comm_finalize(ctx);
-    hipFree(ctx->X); hipFree(ctx->X3); hipFree(ctx->Xt3); hipFree(ctx->XtF);
-    free_x2(ctx); free_mu_sparse(ctx); free_csr(ctx);
-    hipFree(ctx->C1); hipFree(ctx->Ct1); hipFree(ctx->d_scale);
-    hipFree(ctx->C1h); hipFree(ctx->Ct1h); hipFree(ctx->hiA); hipFree(ctx->hiB);
+    drop_derived_images(ctx);
+    hipFree(ctx->X);
     hipFree(ctx->stageW); hipFree(ctx->stageH); hipFree(ctx->spectra);
     ctx->cons_ws.release();
     ctx->prep.release();
@@ -170,15 +168,8 @@ static int alloc_matrix(cnmf_ctx* ctx, int64_t N, int64_t G, bool dense = true)
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     free_batch(ctx);
+    drop_derived_images(ctx);
     hipFree(ctx->X); ctx->X = nullptr;
-    hipFree(ctx->XtF); ctx->XtF = nullptr;
-    free_mu_sparse(ctx); free_csr(ctx);
-    hipFree(ctx->X3); hipFree(ctx->Xt3); ctx->X3 = ctx->Xt3 = nullptr;
-    free_x2(ctx);
-    hipFree(ctx->C1); hipFree(ctx->Ct1); hipFree(ctx->d_scale);
-    hipFree(ctx->C1h); hipFree(ctx->Ct1h); hipFree(ctx->hiA); hipFree(ctx->hiB);
-    ctx->C1 = ctx->Ct1 = ctx->C1h = ctx->Ct1h = nullptr; ctx->hiA = ctx->hiB = nullptr;
-    ctx->d_scale = nullptr; ctx->count_state = 0; ctx->count_fmt = 0;
     ctx->iter_prior.clear(); ctx->iter_hint.clear();     // iteration counts of another matrix say nothing about this one
     // (the resident spectra store survives a change of matrix: consensus() alternates between the normalised counts and
     //  the TPM matrix while the spectra of the factorize call keep serving k selection and further consensus calls;
@@ -291,12 +282,9 @@ extern "C" int cnmf_set_count_detection(cnmf_ctx* ctx, int enabled)
     if (!ctx) return CNMF_EINVAL;
     if (ctx->count_detect != (enabled != 0)) {
         ctx->count_detect = enabled != 0;
-        if (ctx->count_state == -1 || !ctx->count_detect) {      // forget a previous decision
+        if (ctx->counts.state == -1 || !ctx->count_detect) {     // forget a previous decision
             hipStreamSynchronize(ctx->stream);
-            hipFree(ctx->C1); hipFree(ctx->Ct1); hipFree(ctx->d_scale);
-            hipFree(ctx->C1h); hipFree(ctx->Ct1h); hipFree(ctx->hiA); hipFree(ctx->hiB);
-            ctx->C1 = ctx->Ct1 = ctx->C1h = ctx->Ct1h = nullptr; ctx->hiA = ctx->hiB = nullptr;
-            ctx->d_scale = nullptr; ctx->count_state = 0; ctx->count_fmt = 0;
+            ctx->counts.release();
         }
     }
     return CNMF_OK;
@@ -316,7 +304,7 @@ extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
 {
     if (!ctx || !flags) return CNMF_EINVAL;
     *flags = (ctx->X ? 1 : 0) | (ctx->csr.ptr ? 2 : 0) | (ctx->csc.ptr ? 4 : 0) | (ctx->XtF ? 8 : 0) |
-             ((ctx->spA[0].ent && ctx->spB[0].ent) ? 16 : 0) | ((ctx->spA[1].ent && ctx->spB[1].ent) ? 32 : 0) | (ctx->C1 ? 64 : 0);
+             ((ctx->spA[0].ent && ctx->spB[0].ent) ? 16 : 0) | ((ctx->spA[1].ent && ctx->spB[1].ent) ? 32 : 0) | (ctx->counts.C1 ? 64 : 0);
     return CNMF_OK;
 }
 

@@ -332,25 +332,28 @@ static hipError_t launch_gemm3_streamk(hipStream_t st, const StreamK3& sk, const
 static int ensure_planes(cnmf_ctx* ctx)
 {
     const int TR = gemm3_jw();
-    if (ctx->X3 && ctx->Xt3 && ctx->planes_tr == TR) return CNMF_OK;
-    hipFree(ctx->X3); hipFree(ctx->Xt3); ctx->X3 = ctx->Xt3 = nullptr;
-    ctx->planes_tr = TR;
+    if (ctx->planes.X3 && ctx->planes.tr == TR) return CNMF_OK;
+    ctx->planes.release();                                 // (planes of another tile height go before their successors are allocated)
     const size_t bA = (size_t)ctx->N_pad * (ctx->G_pad / 16) * G3_ROWB;
     const size_t bB = (size_t)ctx->G_pad * (ctx->N_pad / 16) * G3_ROWB;
-    HIP_TRY(ctx, hipMalloc(&ctx->X3, bA));
-    HIP_TRY(ctx, hipMalloc(&ctx->Xt3, bB));
-    HIP_TRY(ctx, launch_split3(ctx->stream, ctx->X, ctx->G_pad, ctx->N_pad, ctx->G_pad, ctx->X3, TR));
+    OwnedLocal<Bf16PlanesF> L;
+    L.tr = TR;
+    HIP_TRY(ctx, hipMalloc(&L.X3, bA));
+    HIP_TRY(ctx, hipMalloc(&L.Xt3, bB));
+    HIP_TRY(ctx, launch_split3(ctx->stream, ctx->X, ctx->G_pad, ctx->N_pad, ctx->G_pad, L.X3, TR));
     dim3 grid(ctx->N_pad / 16, (ctx->G_pad + 255) / 256);
     split3_transpose_kernel<<<grid, 256, 0, ctx->stream>>>(ctx->X, ctx->G_pad, ctx->N_pad, ctx->G_pad, ctx->N_pad,
-                                                            TR, (unsigned short*)ctx->Xt3);
+                                                            TR, (unsigned short*)L.Xt3);
     HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->planes.take(L);
     return CNMF_OK;
 }
 
 // planes of a general (not count-structured) matrix for the f16 pipe (gemm_mode 5, kernels_gemm2h.hip.h)
 static int ensure_x2planes(cnmf_ctx* ctx)
 {
-    if (ctx->X2h) return CNMF_OK;
+    if (ctx->x2.X2h) return CNMF_OK;
     hipStream_t st = ctx->stream;
     const int N = (int)ctx->N, G = (int)ctx->G, Np = ctx->N_pad, Gp = ctx->G_pad;
     const size_t pb = (size_t)Np * Gp * 2;
@@ -359,35 +362,27 @@ static int ensure_x2planes(cnmf_ctx* ctx)
     int* shA = pool.get<int>(Np);
     int* shB = pool.get<int>(Gp);
     POOL_TRY(ctx, pool);
-    unsigned char *a = nullptr, *am = nullptr, *b = nullptr, *bm = nullptr;
-    float *sa = nullptr, *sb = nullptr;
-    unsigned *oa = nullptr, *ob = nullptr;
-    hipError_t e = hipMalloc(&a, pb);
-    if (e == hipSuccess) e = hipMalloc(&am, pb);
-    if (e == hipSuccess) e = hipMalloc(&b, pb);
-    if (e == hipSuccess) e = hipMalloc(&bm, pb);
-    if (e == hipSuccess) e = hipMalloc(&sa, (size_t)Np * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&sb, (size_t)Gp * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&oa, fa);
-    if (e == hipSuccess) e = hipMalloc(&ob, fb);
-    if (e == hipSuccess) e = hipMemsetAsync(oa, 0xff, fa, st);
-    if (e == hipSuccess) e = hipMemsetAsync(ob, 0xff, fb, st);
-    if (e == hipSuccess) {
-        x2h_rowshift_kernel<<<(Np + 3) / 4, 256, 0, st>>>(ctx->X, Gp, N, G, 0, Np, shA, sa);
-        x2h_rowshift_kernel<<<(Gp + 255) / 256, 256, 0, st>>>(ctx->X, Gp, N, G, 1, Gp, shB, sb);
-        const long long total = (long long)Np * (Gp / 16);
-        x2h_planes_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(ctx->X, Gp, N, G, Np, Gp, G3C_JW, shA,
-                                                                            (unsigned short*)a, (unsigned short*)am);
-        x2h_planes_transpose_kernel<<<dim3(Np / 16, (Gp + 255) / 256), 256, 0, st>>>(ctx->X, Gp, N, G, Gp, Np, G3C_JW, shB,
-                                                                                    (unsigned short*)b, (unsigned short*)bm);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);      // the shift scratch is freed on return
-    if (e != hipSuccess) {
-        hipFree(a); hipFree(am); hipFree(b); hipFree(bm); hipFree(sa); hipFree(sb); hipFree(oa); hipFree(ob);
-        HIP_TRY(ctx, e);
-    }
-    ctx->X2h = a; ctx->X2m = am; ctx->Xt2h = b; ctx->Xt2m = bm; ctx->x2sA = sa; ctx->x2sB = sb; ctx->onesA = oa; ctx->onesB = ob;
+    OwnedLocal<GeneralPlanesF> L;
+    HIP_TRY(ctx, hipMalloc(&L.X2h, pb));
+    HIP_TRY(ctx, hipMalloc(&L.X2m, pb));
+    HIP_TRY(ctx, hipMalloc(&L.Xt2h, pb));
+    HIP_TRY(ctx, hipMalloc(&L.Xt2m, pb));
+    HIP_TRY(ctx, hipMalloc(&L.sA, (size_t)Np * sizeof(float)));
+    HIP_TRY(ctx, hipMalloc(&L.sB, (size_t)Gp * sizeof(float)));
+    HIP_TRY(ctx, hipMalloc(&L.onesA, fa));
+    HIP_TRY(ctx, hipMalloc(&L.onesB, fb));
+    HIP_TRY(ctx, hipMemsetAsync(L.onesA, 0xff, fa, st));
+    HIP_TRY(ctx, hipMemsetAsync(L.onesB, 0xff, fb, st));
+    x2h_rowshift_kernel<<<(Np + 3) / 4, 256, 0, st>>>(ctx->X, Gp, N, G, 0, Np, shA, L.sA);
+    x2h_rowshift_kernel<<<(Gp + 255) / 256, 256, 0, st>>>(ctx->X, Gp, N, G, 1, Gp, shB, L.sB);
+    const long long total = (long long)Np * (Gp / 16);
+    x2h_planes_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(ctx->X, Gp, N, G, Np, Gp, G3C_JW, shA,
+                                                                        (unsigned short*)L.X2h, (unsigned short*)L.X2m);
+    x2h_planes_transpose_kernel<<<dim3(Np / 16, (Gp + 255) / 256), 256, 0, st>>>(ctx->X, Gp, N, G, Gp, Np, G3C_JW, shB,
+                                                                                (unsigned short*)L.Xt2h, (unsigned short*)L.Xt2m);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));                // the shift scratch is freed on return
+    ctx->x2.take(L);
     return CNMF_OK;
 }
 
@@ -568,23 +563,21 @@ static hipError_t launch_rowmax_part(hipStream_t st, const float* V, int ld, int
 }
 
 // Examine the resident matrix once: is every column (integers <= 256) x one constant?  If so build the
-// integer planes of X and X^T and the per-gene scale (kernels_counts.hip.h).
+// integer planes of X and X^T and the per-gene scale (kernels_counts.hip.h).  counts.state leaves "not examined" at two
+// points only: `absent`, where the examination has decided so, and the commit after the last synchronisation -- a
+// failed call leaves it "not examined", and the next call on this matrix examines it again.
 static int ensure_counts(cnmf_ctx* ctx)
 {
     const int fmt = ctx->knobs.gemm3 == 4 ? 4 : 3;      // plane format the current mode multiplies
-    if (ctx->count_state == 1 && ctx->count_fmt != fmt) {
+    if (ctx->counts.state == 1 && ctx->counts.fmt != fmt) {
         // the mode was switched between two calls on the same matrix (tests, A/B runs): rebuild the planes
         hipStreamSynchronize(ctx->stream);
-        hipFree(ctx->C1); hipFree(ctx->Ct1); hipFree(ctx->d_scale);
-        hipFree(ctx->C1h); hipFree(ctx->Ct1h); hipFree(ctx->hiA); hipFree(ctx->hiB);
-        ctx->C1 = ctx->Ct1 = ctx->C1h = ctx->Ct1h = nullptr; ctx->hiA = ctx->hiB = nullptr;
-        ctx->d_scale = nullptr; ctx->count_state = 0;
+        ctx->counts.release();
     }
-    if (ctx->count_state != 0) return CNMF_OK;
-    ctx->count_state = -1;
-    ctx->count_fmt = fmt;
+    if (ctx->counts.state != 0) return CNMF_OK;
+    auto absent = [ctx] { ctx->counts.state = -1; return CNMF_OK; };
     const int N = (int)ctx->N, G = (int)ctx->G;
-    if (ctx->N_pad % G3C_JW || ctx->G_pad % G3C_JW || ctx->knobs.no_counts || !ctx->count_detect) return CNMF_OK;
+    if (ctx->N_pad % G3C_JW || ctx->G_pad % G3C_JW || ctx->knobs.no_counts || !ctx->count_detect) return absent();
     hipStream_t st = ctx->stream;
     const int chunks = (N + CNT_ROWS - 1) / CNT_ROWS;
     DevPool pool;
@@ -608,13 +601,15 @@ static int ensure_counts(cnmf_ctx* ctx)
     for (int g = 0; g < G; ++g) {
         int m = 0;
         for (int c = 1; c <= CNT_MAXMULT && !m; ++c) if (!(h_fail[g] & (1u << (c - 1)))) m = c;
-        if (!m) return CNMF_OK;                            // this gene is not (small integers) x constant
+        if (!m) return absent();                           // this gene is not (small integers) x constant
         h_unit[g] = h_v[g] > 0.f ? h_v[g] / (float)m : 0.f;
     }
     HIP_TRY(ctx, hipMemcpyAsync(unit, h_unit.data(), (size_t)G * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMalloc(&ctx->d_scale, (size_t)ctx->G_pad * sizeof(double)));
+    OwnedLocal<CountPlanesF> L;
+    L.fmt = fmt;
+    HIP_TRY(ctx, hipMalloc(&L.d_scale, (size_t)ctx->G_pad * sizeof(double)));
     count_sums_kernel<<<grid, 256, 0, st>>>(ctx->X, ctx->G_pad, N, G, unit, psx, psn);
-    count_scale_kernel<<<(ctx->G_pad + 255) / 256, 256, 0, st>>>(psx, psn, chunks, G, ctx->G_pad, ctx->d_scale);
+    count_scale_kernel<<<(ctx->G_pad + 255) / 256, 256, 0, st>>>(psx, psn, chunks, G, ctx->G_pad, L.d_scale);
     // does any count exceed 256?  then a second plane (256 hi) with per-block flags rides along
     unsigned* any_big = pool.get<unsigned>(1, true, st);
     POOL_TRY(ctx, pool);
@@ -623,40 +618,41 @@ static int ensure_counts(cnmf_ctx* ctx)
     HIP_TRY(ctx, hipMemcpyAsync(&h_big, any_big, sizeof h_big, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     const size_t bytes = (size_t)ctx->N_pad * ctx->G_pad * 2;
-    HIP_TRY(ctx, hipMalloc(&ctx->C1, bytes));
-    HIP_TRY(ctx, hipMalloc(&ctx->Ct1, bytes));
+    HIP_TRY(ctx, hipMalloc(&L.C1, bytes));
+    HIP_TRY(ctx, hipMalloc(&L.Ct1, bytes));
     if (h_big) {
         const size_t nfA = (size_t)(ctx->N_pad / G3C_JW) * ((ctx->G_pad / 16 + 31) / 32) * sizeof(unsigned int);
         const size_t nfB = (size_t)(ctx->G_pad / G3C_JW) * ((ctx->N_pad / 16 + 31) / 32) * sizeof(unsigned int);
-        HIP_TRY(ctx, hipMalloc(&ctx->C1h, bytes));
-        HIP_TRY(ctx, hipMalloc(&ctx->Ct1h, bytes));
-        HIP_TRY(ctx, hipMalloc(&ctx->hiA, nfA));
-        HIP_TRY(ctx, hipMalloc(&ctx->hiB, nfB));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->hiA, 0, nfA, st));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->hiB, 0, nfB, st));
+        HIP_TRY(ctx, hipMalloc(&L.C1h, bytes));
+        HIP_TRY(ctx, hipMalloc(&L.Ct1h, bytes));
+        HIP_TRY(ctx, hipMalloc(&L.hiA, nfA));
+        HIP_TRY(ctx, hipMalloc(&L.hiB, nfB));
+        HIP_TRY(ctx, hipMemsetAsync(L.hiA, 0, nfA, st));
+        HIP_TRY(ctx, hipMemsetAsync(L.hiB, 0, nfB, st));
     }
     {
         const long long total = (long long)ctx->N_pad * (ctx->G_pad / 16);
         dim3 gt(ctx->N_pad / 16, (ctx->G_pad + 255) / 256);
         if (fmt == 4) {
             count_planes_f16_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(
-                ctx->X, ctx->G_pad, N, G, ctx->N_pad, ctx->G_pad, G3C_JW, unit, (unsigned short*)ctx->C1,
-                (unsigned short*)ctx->C1h, ctx->hiA);
+                ctx->X, ctx->G_pad, N, G, ctx->N_pad, ctx->G_pad, G3C_JW, unit, (unsigned short*)L.C1,
+                (unsigned short*)L.C1h, L.hiA);
             count_planes_f16_transpose_kernel<<<gt, 256, 0, st>>>(
-                ctx->X, ctx->G_pad, N, G, ctx->G_pad, ctx->N_pad, G3C_JW, unit, (unsigned short*)ctx->Ct1,
-                (unsigned short*)ctx->Ct1h, ctx->hiB);
+                ctx->X, ctx->G_pad, N, G, ctx->G_pad, ctx->N_pad, G3C_JW, unit, (unsigned short*)L.Ct1,
+                (unsigned short*)L.Ct1h, L.hiB);
         } else {
             count_planes_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(
-                ctx->X, ctx->G_pad, N, G, ctx->N_pad, ctx->G_pad, G3C_JW, unit, (unsigned short*)ctx->C1,
-                (unsigned short*)ctx->C1h, ctx->hiA);
+                ctx->X, ctx->G_pad, N, G, ctx->N_pad, ctx->G_pad, G3C_JW, unit, (unsigned short*)L.C1,
+                (unsigned short*)L.C1h, L.hiA);
             count_planes_transpose_kernel<<<gt, 256, 0, st>>>(
-                ctx->X, ctx->G_pad, N, G, ctx->G_pad, ctx->N_pad, G3C_JW, unit, (unsigned short*)ctx->Ct1,
-                (unsigned short*)ctx->Ct1h, ctx->hiB);
+                ctx->X, ctx->G_pad, N, G, ctx->G_pad, ctx->N_pad, G3C_JW, unit, (unsigned short*)L.Ct1,
+                (unsigned short*)L.Ct1h, L.hiB);
         }
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));                // the pool's scratch is freed on return
-    ctx->count_state = 1;
+    L.state = 1;
+    ctx->counts.take(L);
     return CNMF_OK;
 }
 

@@ -64,21 +64,6 @@ __global__ __launch_bounds__(256) void row_sum_kernel(const float* __restrict__ 
 
 }  // namespace cnmf
 
-// the planes of X (split-operand GEMM) and the count structure (integer planes, per-gene scale) describe
-// the old values: drop them whenever X changes (mirrors alloc_matrix)
-static void invalidate_planes(cnmf_ctx* ctx)
-{
-    hipStreamSynchronize(ctx->stream);
-    hipFree(ctx->X3); hipFree(ctx->Xt3); hipFree(ctx->XtF);
-    ctx->X3 = ctx->Xt3 = nullptr; ctx->XtF = nullptr;
-    free_mu_sparse(ctx); free_csr(ctx);
-    hipFree(ctx->C1); hipFree(ctx->Ct1); hipFree(ctx->d_scale);
-    hipFree(ctx->C1h); hipFree(ctx->Ct1h); hipFree(ctx->hiA); hipFree(ctx->hiB);
-    ctx->C1 = ctx->Ct1 = ctx->C1h = ctx->Ct1h = nullptr; ctx->hiA = ctx->hiB = nullptr;
-    ctx->d_scale = nullptr; ctx->count_state = 0; ctx->count_fmt = 0;
-    // (the resident spectra store outlives a change of the matrix, like in alloc_matrix: it carries its own gene count)
-}
-
 extern "C" int cnmf_col_moments(cnmf_ctx* ctx, double* mean_out, double* ssd_out)
 {
     using namespace cnmf;
@@ -142,7 +127,7 @@ extern "C" int cnmf_scale_columns(cnmf_ctx* ctx, const double* divisor)
     scale_cols_kernel<<<grid, 256, 0, st>>>(ctx->X, ctx->G_pad, N, G, d);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    invalidate_planes(ctx);
+    drop_derived_images(ctx);                          // every one of them describes the unscaled values
     return CNMF_OK;
 }
 

@@ -44,20 +44,34 @@ struct SpImage {
     void release() { hipFree(perm); hipFree(off); hipFree(len); hipFree(ent); *this = SpImage{}; }
 };
 
-// A rows x cols compressed-row matrix on the device that owns its arrays: 64-bit row pointers, values of type V (float:
-// the resident matrix, double: the staging paths).  nnz = -1: empty.  Not copyable, and no destructor: like Arena and
-// SpImage it is released explicitly, by an owner that has synchronised the stream that may still use the arrays.
+// An owning group of device arrays.  F is a plain struct of device pointers (and what describes them) with a free_all().
+// Not copyable, and no destructor: like Arena and SpImage a group is released explicitly, by an owner that has
+// synchronised the stream that may still use the arrays.
+template <typename F>
+struct Owned : F {
+    Owned() = default;
+    Owned(const Owned&) = delete;
+    Owned& operator=(const Owned&) = delete;
+    void release() { this->free_all(); static_cast<F&>(*this) = F{}; }
+    // the commit step: this group becomes s (what it held is released), s is left empty
+    void take(Owned& s) { release(); static_cast<F&>(*this) = s; static_cast<F&>(s) = F{}; }
+};
+// A group under construction, local to one call: released on EVERY return path (the HIP_TRY early returns included;
+// hipFree waits for work that still uses the arrays, as for DevPool) unless an owner took it -- the one place where its
+// arrays are cleaned up after a failure.  Whoever builds an image fills a local and commits it with take() after the
+// final stream synchronisation succeeded: a failed build leaves the owner as it was, never with half an image.
+template <typename F>
+struct OwnedLocal : Owned<F> {
+    ~OwnedLocal() { this->release(); }
+};
+
+// A rows x cols compressed-row matrix on the device: 64-bit row pointers, values of type V (float: the resident matrix,
+// double: the staging paths).  nnz = -1: empty.
 template <typename V>
-struct DevCsr {
+struct CsrF {
     int64_t rows = 0, cols = 0, nnz = -1;
     long long* ptr = nullptr; int* idx = nullptr; V* val = nullptr;
-    DevCsr() = default;
-    DevCsr(const DevCsr&) = delete;
-    DevCsr& operator=(const DevCsr&) = delete;
-    void release() {
-        hipFree(ptr); hipFree(idx); hipFree(val);
-        ptr = nullptr; idx = nullptr; val = nullptr; rows = cols = 0; nnz = -1;
-    }
+    void free_all() { hipFree(ptr); hipFree(idx); hipFree(val); }
     hipError_t alloc_ptr(int64_t r, int64_t c) {
         rows = r; cols = c;
         return hipMalloc((void**)&ptr, ((size_t)r + 1) * sizeof(long long));
@@ -69,21 +83,44 @@ struct DevCsr {
         if (e == hipSuccess) nnz = n;
         return e;
     }
-    // the commit step: this matrix becomes s (what it held is released), s is left empty
-    void take(DevCsr& s) {
-        release();
-        rows = s.rows; cols = s.cols; nnz = s.nnz; ptr = s.ptr; idx = s.idx; val = s.val;
-        s.ptr = nullptr; s.idx = nullptr; s.val = nullptr;
-        s.release();
-    }
+};
+template <typename V> using DevCsr = Owned<CsrF<V>>;
+template <typename V> using DevCsrLocal = OwnedLocal<CsrF<V>>;
+
+// ---- the images of the resident matrix X that the GEMM passes of the coordinate-descent batch read (gemm_host.hip.h)
+// What a GEMM pass reads of X: the plane, an optional second plane with its block flags (one bit per tile row and block),
+// an optional 2^-s per output column.  Both providers below hand it out for pass A (X) and pass B (X^T).
+struct XOperand { const unsigned char *plane, *hi; const unsigned int* flags; const float* colscale; };
+
+// bf16 planes of X and X^T (split-operand GEMM, CNMF_GEMM3=1|2), built on first use
+struct Bf16PlanesF {
+    unsigned char *X3 = nullptr, *Xt3 = nullptr;
+    int tr = 0;                                      // row-tile height they were built with
+    void free_all() { hipFree(X3); hipFree(Xt3); }
 };
 
-// A DevCsr under construction, local to one call: released on EVERY return path (the HIP_TRY early returns included;
-// hipFree waits for work that still uses the arrays, as for DevPool) unless an owner took it.  The one place where the
-// three arrays are cleaned up after a failure.
-template <typename V>
-struct DevCsrLocal : DevCsr<V> {
-    ~DevCsrLocal() { this->release(); }
+// count structure X = n * d (kernels_counts.hip.h)
+struct CountPlanesF {
+    int state = 0;                                   // 0 = not examined, 1 = present (the planes below exist), -1 = absent
+    int fmt = 0;                                     // 3 = bf16 planes (base 256), 4 = f16 planes (base 2048, swizzled slots)
+    unsigned char *C1 = nullptr, *Ct1 = nullptr;     // integer planes of n and n^T (one plane, 256-row tiles)
+    unsigned char *C1h = nullptr, *Ct1h = nullptr;   // second planes (the high digit) when some count exceeds the base, else NULL
+    unsigned int *hiA = nullptr, *hiB = nullptr;     // their flags
+    double* d_scale = nullptr;                       // per-gene scale d [G_pad]
+    void free_all() { hipFree(C1); hipFree(Ct1); hipFree(C1h); hipFree(Ct1h); hipFree(hiA); hipFree(hiB); hipFree(d_scale); }
+    XOperand passA() const { return {C1, C1h, hiA, nullptr}; }
+    XOperand passB() const { return {Ct1, Ct1h, hiB, nullptr}; }
+};
+
+// any OTHER matrix on the f16 pipe (gemm_mode 5): two f16 planes of x * 2^s_row for X (rows = cells) and X^T (rows =
+// genes), the per-row 2^-s, and all-ones block flags for the two-plane ("HI") instantiation of the count kernels
+struct GeneralPlanesF {
+    unsigned char *X2h = nullptr, *X2m = nullptr, *Xt2h = nullptr, *Xt2m = nullptr;
+    float *sA = nullptr, *sB = nullptr;
+    unsigned int *onesA = nullptr, *onesB = nullptr;
+    void free_all() { hipFree(X2h); hipFree(X2m); hipFree(Xt2h); hipFree(Xt2m); hipFree(sA); hipFree(sB); hipFree(onesA); hipFree(onesB); }
+    XOperand passA() const { return {X2h, X2m, onesA, sA}; }
+    XOperand passB() const { return {Xt2h, Xt2m, onesB, sB}; }
 };
 
 // the raw cells x genes counts a stage keeps (CSR, float64 values) and their transpose (genes x cells)
@@ -187,21 +224,12 @@ struct cnmf_ctx {
     int64_t N = 0, G = 0;
     int N_pad = 0, G_pad = 0;
     float* X = nullptr;
-    unsigned char *X3 = nullptr, *Xt3 = nullptr;   // bf16 planes of X and X^T (split-operand GEMM), built on first use
-    int planes_tr = 0;                             // row-tile height they were built with
-    // count structure X = n * d (kernels_counts.hip.h): 0 = not examined, 1 = present, -1 = absent
     bool count_detect = true;                      // cnmf_set_count_detection(): look for the count structure at all?
-    int count_state = 0;
-    unsigned char *C1 = nullptr, *Ct1 = nullptr;   // integer planes of n and n^T (one bf16 plane, 256-row tiles)
-    unsigned char *C1h = nullptr, *Ct1h = nullptr; // second planes (256 hi) when some count exceeds 256, else NULL
-    unsigned int *hiA = nullptr, *hiB = nullptr;   // their flags: one bit per (tile row, block)
-    double* d_scale = nullptr;                     // per-gene scale d [G_pad]
-    int count_fmt = 0;                             // 3 = bf16 planes (base 256), 4 = f16 planes (base 2048, swizzled slots)
-    // any OTHER matrix on the f16 pipe (gemm_mode 5): two f16 planes of x * 2^s_row for X (rows = cells) and X^T (rows =
-    // genes), the per-row 2^-s, and all-ones block flags for the two-plane ("HI") instantiation of the count kernels
-    unsigned char *X2h = nullptr, *X2m = nullptr, *Xt2h = nullptr, *Xt2m = nullptr;
-    float *x2sA = nullptr, *x2sB = nullptr;
-    unsigned int *onesA = nullptr, *onesB = nullptr;
+    // Everything from here to csr / csc is an image DERIVED from X, built on first use.  drop_derived_images
+    // (cnmf_hip.hip) is the one function that drops them all: whoever replaces or rewrites X calls it.
+    Owned<Bf16PlanesF> planes;                     // ensure_planes
+    Owned<CountPlanesF> counts;                    // ensure_counts; counts.state says whether X has the structure at all
+    Owned<GeneralPlanesF> x2;                      // ensure_x2planes
     float* XtF = nullptr;                          // X^T [round_up(G_pad, 64)][N_pad] float32, built on first use by the
                                                    // Kullback-Leibler solver (kernels_mu_mfma.hip.h)
     // Kullback-Leibler on the non-zeros (kernels_mu_sparse.hip.h): images for padded ranks 16 and 32, cells x genes (A) and

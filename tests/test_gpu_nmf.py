@@ -215,6 +215,35 @@ def test_count_structure_is_detected_only_where_it_exists(engine):
         engine.set_count_detection(True)
 
 
+def test_column_scaling_drops_the_general_f16_planes(engine):
+    """scale_genes_unit_variance() rewrites the resident matrix in place, so every image derived from it must go: a batch
+    on the general f16 path (gemm_mode 5) after the scaling equals, bit for bit, the same batch after a fresh upload of
+    the scaled matrix.  Before all derived images had one owner and one drop function, cnmf_scale_columns kept the two
+    f16 planes of the UNSCALED matrix and the second batch multiplied those in both GEMM passes: H_b == H_c failed.
+    The factors are the caller's (not seeds): init='random' scales by the engine's x_mean, which is a float64 from row
+    sums after the scaling and the float32 matrix mean after an upload -- a difference that is not this test's subject."""
+    rs = np.random.RandomState(1024520)
+    X = rs.gamma(0.4, 1.0, size=(1024, 520)) + 0.01              # no gene is (small integers) x constant: the general path
+    ks = [9] * 29                                                 # 261 columns: the smallest batch on the matrix pipe
+    W0 = [rs.random_sample((X.shape[0], k)).astype(np.float32) for k in ks]
+    H0 = [rs.random_sample((k, X.shape[1])).astype(np.float32) for k in ks]
+
+    def batch():
+        H, _, _, _ = engine.nmf_batch(ks, W0=W0, H0=H0, max_iter=20, warn=False)
+        assert engine.last_stats["kc"] == 256 and engine.last_stats["gemm_mode"] == 5, engine.last_stats
+        return H
+
+    engine.set_matrix(X)
+    H_a = batch()
+    engine.scale_genes_unit_variance()
+    H_b = batch()
+    Xs = engine.get_matrix()
+    engine.set_matrix(Xs)
+    H_c = batch()
+    assert all(np.array_equal(b, c) for b, c in zip(H_b, H_c))
+    assert not any(np.array_equal(a, b) for a, b in zip(H_a, H_b))
+
+
 def test_general_matrix_on_the_f16_pipe_matches_oracle(engine):
     """gemm_mode 5 (the default for any matrix that is NOT count-structured: Harmony-corrected, TPM-normalised ...): X
     and X^T as two f16 planes of x * 2^s_row each, the factor likewise, all four plane products (4 MFMAs), the per-row
