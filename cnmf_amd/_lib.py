@@ -28,7 +28,7 @@ SYMBOLS = [
     "cnmf_preprocess_project", "cnmf_preprocess_ridge_moments", "cnmf_preprocess_ridge_apply", "cnmf_preprocess_release",
     "cnmf_preprocess_ridge_apply_mode",
     "cnmf_harmony_begin", "cnmf_harmony_init", "cnmf_harmony_kmeans_step", "cnmf_harmony_ridge_moments",
-    "cnmf_harmony_ridge_apply", "cnmf_harmony_fetch", "cnmf_harmony_release",
+    "cnmf_harmony_ridge_apply", "cnmf_harmony_fetch", "cnmf_harmony_release", "cnmf_harmony_kmeans_init",
     "cnmf_preprocess_row_sums", "cnmf_preprocess_normalize_dense", "cnmf_preprocess_select_mi",
     "cnmf_preprocess_upload_csr_as_stored", "cnmf_preprocess_gene_detect", "cnmf_preprocess_cell_sums",
     "cnmf_preprocess_subset", "cnmf_preprocess_fetch_counts",
@@ -224,6 +224,8 @@ def load():
     lib.cnmf_harmony_fetch.argtypes = [vp, dblp, dblp, dblp, dblp]
     lib.cnmf_harmony_release.restype = i32
     lib.cnmf_harmony_release.argtypes = [vp]
+    lib.cnmf_harmony_kmeans_init.restype = i32
+    lib.cnmf_harmony_kmeans_init.argtypes = [vp, i32, i32, C.c_double, dblp, dblp, dblp, i32p, dblp, i32p, i32p]
     lib.cnmf_preprocess_row_sums.restype = i32
     lib.cnmf_preprocess_row_sums.argtypes = [vp, dblp]
     lib.cnmf_preprocess_normalize_dense.restype = i32

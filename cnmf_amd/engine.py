@@ -545,6 +545,45 @@ class Engine:
                                                  R.ctypes.data_as(dblp), Y.ctypes.data_as(dblp)))
         return Zc, Zs, R, Y
 
+    @staticmethod
+    def kmeans_uniforms(K, n_init, random_state):
+        """The doubles scikit-learn's KMeans(k-means++) draws from RandomState(random_state), [n_init][1 + (K - 1) L]:
+        per init one for the first centre, then L = 2 + int(ln K) local trials per further centre.  The count does not
+        depend on the data, so the whole stream is drawn up front."""
+        L = 2 + int(np.log(K))
+        per_init = 1 + (K - 1) * L
+        return np.random.RandomState(random_state).random_sample(n_init * per_init).reshape(n_init, per_init)
+
+    def harmony_kmeans_init(self, random_state, n_init=10, max_iter=25, tol=1e-4, init_centers=None):
+        """scikit-learn's KMeans(K, init='k-means++', n_init, max_iter, tol, random_state) on the unit scores of
+        harmony_begin, on the device (harmony_init_host.hip.h); the same bits on every run.  ``init_centers``
+        [n_init][K][d]: Lloyd starts from these centres instead of k-means++ (``random_state`` is not used).
+        Returns ``(Y [d][K], labels [N], inertia [n_init], n_iter [n_init], best)``: the centres (not normalised) and
+        labels of the best init, every init's inertia and iteration count, the index of the best.  Harmony's own state
+        (R, E, O) is left as it is.  With fewer distinct cells than clusters the surplus centres are unspecified."""
+        har = self._har_state()
+        N, d, K = har["N"], har["d"], har["K"]
+        n_init, max_iter = int(n_init), int(max_iter)
+        if not 1 <= n_init <= 16 or max_iter < 1:
+            raise ValueError("n_init = %d outside [1, 16] or max_iter = %d below 1" % (n_init, max_iter))
+        if K > N:
+            raise ValueError("K = %d clusters for %d cells" % (K, N))
+        dblp, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        u = c0 = None
+        if init_centers is not None:
+            c0 = np.ascontiguousarray(init_centers, dtype=np.float64)
+            if c0.shape != (n_init, K, d) or not np.isfinite(c0).all():
+                raise ValueError("init_centers %s, expected %s (finite values)" % (c0.shape, (n_init, K, d)))
+        else:
+            u = self.kmeans_uniforms(K, n_init, random_state)
+        Y, labels = np.empty((d, K)), np.empty(N, dtype=np.int32)
+        inertia, n_iter, best = np.empty(n_init), np.empty(n_init, dtype=np.int32), C.c_int32(-1)
+        self._check(self._lib.cnmf_harmony_kmeans_init(
+            self._ctx, n_init, max_iter, float(tol), None if u is None else u.ctypes.data_as(dblp),
+            None if c0 is None else c0.ctypes.data_as(dblp), Y.ctypes.data_as(dblp), labels.ctypes.data_as(i32p),
+            inertia.ctypes.data_as(dblp), n_iter.ctypes.data_as(i32p), C.byref(best)))
+        return Y, labels, inertia, n_iter, int(best.value)
+
     def harmony_release(self):
         self._check(self._lib.cnmf_harmony_release(self._ctx))
         self._har = None

@@ -38,14 +38,19 @@ staging that is already there.  Counts are integers, so every sum is exact; ``pc
 rounding each: all of it equals the reference bit for bit.
 
 ``Preprocess.run_harmony`` is harmonypy's ``run_harmony`` with the clustering loop on the device
-(csrc/harmony_host.hip.h), opt-in through ``harmony="device"`` on ``harmony_correct_X``, ``normalize_batchcorrect`` and
-``preprocess_for_cnmf`` (the default, ``"harmonypy"``, calls the library as before; ``harmony_res`` wins over both).  With
+(csrc/harmony_host.hip.h), opt-in through ``harmony="device"`` or ``harmony="device_full"`` on ``harmony_correct_X``,
+``normalize_batchcorrect`` and ``preprocess_for_cnmf`` (the default, ``"harmonypy"``, calls the library as before;
+``harmony_res`` wins over all).  ``"device"`` leaves the k-means initialisation to scikit-learn on the host,
+``"device_full"`` (``run_harmony(kmeans_init="device")``) runs it on the device too (csrc/harmony_init_host.hip.h) and
+imports neither harmonypy nor scikit-learn.  With
 Z = pca^T [d][N], Phi the one-hot levels of the variables in ``pd.get_dummies`` order (B rows), Pr_b their frequencies,
 theta and lamb one value per level and sigma per cluster:
 
 * start: Z_cos = Z / max over a cell's scores, then every cell at unit L2 norm; Y = the centres of KMeans(K, k-means++,
-  n_init=10, max_iter=25, random_state) on Z_cos^T at unit norm -- **this initialisation runs in scikit-learn on the
-  host**; dist = 2 (1 - Y^T Z_cos); R = softmax(-dist / sigma) per cell; E = outer(R 1, Pr_b), O = R Phi^T;
+  n_init=10, max_iter=25, random_state) on Z_cos^T at unit norm -- **by default this initialisation runs in scikit-learn
+  on the host**; with ``kmeans_init="device"`` the same steps (centring, k-means++ from the same RandomState draws, Lloyd
+  with relocation of empty clusters, best of 10) run on the device, with fixed-order sums; dist = 2 (1 - Y^T Z_cos);
+  R = softmax(-dist / sigma) per cell; E = outer(R 1, Pr_b), O = R Phi^T;
 * objective = sum R dist + sum sigma R log R + sum sigma R (theta log((O + 1) / (E + 1)) Phi);
 * a round: cluster() -- up to max_iter_kmeans times Y = Z_cos R^T at unit norm, dist, update_R, the objective, and from the
   fifth iteration on a stop when the sums of two overlapping windows of three objectives differ by less than
@@ -59,7 +64,10 @@ The device differs from a numpy run in the order of its sums and in the last pla
 the float64 numpy restatement of the above in tests/_harmony_ref.py** (rounds equal; R, Z_corr, Y and the objectives
 within 16 x the restatement's distance from its own long double run).  **Agreement with harmonypy itself is unmeasured on
 this project's machines**: the library is not installed on them; tests/test_host_harmony.py compares the restatement
-with it wherever it can be imported.
+with it wherever it can be imported.  The device initialisation is held to oracle/consensus.py's numpy restatement of
+scikit-learn's KMeans (tests/test_gpu_harmony_init.py: the best init, its labels and every iteration count equal, the
+centres within the rounding of a mean).  With fewer distinct cells than clusters the centres of the surplus clusters are
+unspecified: the restatement and scikit-learn disagree there themselves, and no parity is claimed.
 
 Out of scope: the seurat_v3 HVG selection (``n_top_genes`` / ``n_top_rna_genes``: it needs skmisc's loess), plots
 (``makeplots`` is accepted and nothing is drawn) and ``.h5ad`` writing.
@@ -257,14 +265,21 @@ def _import_harmonypy():
     return harmonypy
 
 
-HARMONY_MODES = ("harmonypy", "device")
-SKLEARN_IMPORT_ERROR = ("run_harmony needs scikit-learn for its k-means initialisation (sklearn.cluster.KMeans on the host); "
-                        "install it or pass init_centroids")
+HARMONY_MODES = ("harmonypy", "device", "device_full")
+KMEANS_INIT_MODES = ("sklearn", "device")
+SKLEARN_IMPORT_ERROR = ("run_harmony(kmeans_init='sklearn') needs scikit-learn for its k-means initialisation "
+                        "(sklearn.cluster.KMeans on the host); install it, pass init_centroids, or run the initialisation "
+                        "on the device: kmeans_init='device' (harmony='device_full')")
 
 
 def _check_harmony_mode(harmony):
     if harmony not in HARMONY_MODES:
         raise ValueError("harmony must be one of %s, not %r" % (HARMONY_MODES, harmony))
+
+
+def _check_kmeans_init(kmeans_init):
+    if kmeans_init not in KMEANS_INIT_MODES:
+        raise ValueError("kmeans_init must be one of %s, not %r" % (KMEANS_INIT_MODES, kmeans_init))
 
 
 class HarmonyResult:
@@ -315,7 +330,7 @@ def harmony_design(obs, harmony_vars):
 
 
 def _host_kmeans_centroids(Z_cos, K, random_state):
-    """Harmony's initialisation, the one step of run_harmony left to scikit-learn on the host: the centres [d][K] of
+    """Harmony's initialisation in scikit-learn on the host (``kmeans_init="sklearn"``): the centres [d][K] of
     KMeans(k-means++, n_init=10, max_iter=25) on the cells' unit scores, exactly the call harmonypy makes.  scikit-learn
     is an optional dependency of this route alone (as harmonypy is of the other one), so it is looked up by name when
     the route runs, never when the package is imported."""
@@ -357,7 +372,8 @@ class Preprocess:
                           harmony="harmonypy"):
         """Runs Harmony on ``pca`` (or takes ``harmony_res``) and applies its mixture-of-experts ridge correction to the
         cells x genes ``X`` (sparse or dense).  Returns ``(X_corr, X_pca_harmony)``: X_corr dense float64, clipped at 0.
-        ``harmony``: "harmonypy" (the library's run_harmony) or "device" (``self.run_harmony``, harmonypy never imported)."""
+        ``harmony``: "harmonypy" (the library's run_harmony), "device" (``self.run_harmony``, harmonypy never imported) or
+        "device_full" (``self.run_harmony(kmeans_init="device")``: scikit-learn never imported either)."""
         import scipy.sparse as sp
         _check_harmony_mode(harmony)
         if harmony_res is None:
@@ -368,25 +384,32 @@ class Preprocess:
 
     def _harmony(self, pca, obs, harmony_vars, theta, max_iter_harmony, harmony):
         """the Harmony result of the chosen route (a missing harmonypy is reported before a missing variable, as ever)"""
-        run = self.run_harmony if harmony == "device" else _import_harmonypy().run_harmony
+        run = _import_harmonypy().run_harmony if harmony == "harmonypy" else self.run_harmony
         _check_harmony_vars(obs, harmony_vars)
-        return run(pca, obs, harmony_vars, max_iter_harmony=max_iter_harmony, theta=theta)
+        kw = dict(kmeans_init="device") if harmony == "device_full" else {}
+        return run(pca, obs, harmony_vars, max_iter_harmony=max_iter_harmony, theta=theta, **kw)
 
     # ------------------------------------------------------------------ run_harmony (harmonypy's run_harmony, on the device)
     def run_harmony(self, pca, obs, harmony_vars, theta=1, max_iter_harmony=20, *, nclust=None, sigma=0.1, lamb=1,
                     block_size=0.05, max_iter_kmeans=20, epsilon_cluster=1e-5, epsilon_harmony=1e-4, random_state=0,
-                    init_centroids=None):
+                    init_centroids=None, kmeans_init="sklearn"):
         """Harmony's soft clustering and correction of the PCA scores ``pca`` [N][d] for the batch variables
         ``obs[harmony_vars]``, with harmonypy's argument meanings and defaults (see the module docstring for the
         algorithm).  The clustering loop, the objective and the ridge correction run on the device in float64
-        (csrc/harmony_host.hip.h); the k-means initialisation is scikit-learn's KMeans on the host unless
-        ``init_centroids`` [d][K] is given; per k-means iteration the host draws one permutation from numpy's global
-        RandomState (seeded with ``random_state`` at the start, as harmonypy does) and reads the objective back.
-        Returns a HarmonyResult, which ``harmony_res=`` of harmony_correct_X / normalize_batchcorrect accepts.
+        (csrc/harmony_host.hip.h).  The k-means initialisation, KMeans(K, k-means++, n_init=10, max_iter=25,
+        random_state) on the unit scores, is skipped when ``init_centroids`` [d][K] is given; otherwise ``kmeans_init``
+        says who runs it: "sklearn" (the default: scikit-learn on the host) or "device" (``Engine.harmony_kmeans_init``,
+        csrc/harmony_init_host.hip.h: scikit-learn is never imported).  Per k-means iteration the host draws one
+        permutation from numpy's global RandomState (seeded with ``random_state`` at the start, as harmonypy does) and
+        reads the objective back.  Returns a HarmonyResult, which ``harmony_res=`` of harmony_correct_X /
+        normalize_batchcorrect accepts.
 
-        The device loop gives the same bits on every run.  scikit-learn's KMeans does not beyond 256 cells (its threads add
-        their partial sums in completion order: the centroids move in the last bit from run to run), so two calls agree bit
-        for bit when they are given the same ``init_centroids``, and to rounding otherwise.
+        The device loop and the device initialisation give the same bits on every run.  scikit-learn's KMeans does not
+        beyond 256 cells (its threads add their partial sums in completion order: the centroids move in the last bit from
+        run to run), so with ``kmeans_init="sklearn"`` two calls agree bit for bit when they are given the same
+        ``init_centroids``, and to rounding otherwise.  The device initialisation follows scikit-learn step by step from
+        the same random draws; it differs in the order of its sums.  With fewer distinct cells than clusters the centres
+        of the surplus clusters are unspecified (scikit-learn and its numpy restatement disagree there themselves).
 
         Limits: K <= 128, d <= 64, K (B + 1) <= 4096 (NotImplementedError above).  ``sigma`` is a scalar."""
         from .engine import Engine
@@ -394,6 +417,7 @@ class Preprocess:
         if pca.ndim != 2:
             raise ValueError("pca must be cells x components, not %s" % (pca.shape,))
         _check_harmony_vars(obs, harmony_vars)
+        _check_kmeans_init(kmeans_init)
         N, d = pca.shape
         if len(obs) != N:
             raise ValueError("obs has %d rows for %d cells" % (len(obs), N))
@@ -430,7 +454,9 @@ class Preprocess:
         total = lambda terms: terms[0] + terms[1] + terms[2]          # (kmeans error + entropy + cross entropy, in this order)
         try:
             eng.harmony_begin(pca, codes, level_var, theta_b, np.repeat(float(sigma), K), Pr_b)
-            if init_centroids is None:
+            if init_centroids is None and kmeans_init == "device":
+                Y = eng.harmony_kmeans_init(random_state, n_init=10, max_iter=25)[0]
+            elif init_centroids is None:
                 Y = _host_kmeans_centroids(eng.harmony_fetch(z_cos_only=True), K, random_state)
             else:
                 Y = init_centroids
@@ -505,8 +531,8 @@ class Preprocess:
                                theta=1, makeplots=True, max_iter_harmony=20, harmony_res=None, harmony="harmonypy"):
         """Normalises the high-variance genes of raw counts and optionally corrects them with Harmony.  Returns
         ``(result, hvgs)``: ``result.X`` goes straight into ``cNMF.prepare(counts=(result.X, result.obs_names, hvgs),
-        ...)``.  ``harmony``: who runs Harmony when ``harmony_res`` is not given: "harmonypy" (the library) or "device"
-        (``self.run_harmony``)."""
+        ...)``.  ``harmony``: who runs Harmony when ``harmony_res`` is not given: "harmonypy" (the library), "device"
+        (``self.run_harmony``) or "device_full" (``self.run_harmony(kmeans_init="device")``)."""
         if n_top_genes is not None:
             raise NotImplementedError(N_TOP_GENES_ERROR)
         if highly_variable is None:

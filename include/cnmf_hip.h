@@ -296,6 +296,24 @@ int cnmf_harmony_ridge_apply(cnmf_ctx* ctx, const double* W /* [K*B1][d] */);
 int cnmf_harmony_fetch(cnmf_ctx* ctx, double* Z_corr, double* Z_cos, double* R, double* Y);
 int cnmf_harmony_release(cnmf_ctx* ctx);
 
+/* ---- Harmony's k-means initialisation (harmony_init_host.hip.h) ---------------------------------------------------
+ * scikit-learn's KMeans(n_clusters = K, init = 'k-means++', n_init, max_iter, tol) on the unit scores Z_cos of
+ * cnmf_harmony_begin (N cells, d components, K clusters), in float64 on the device, with scikit-learn's steps: centred
+ * scores, tol_ = mean variance * tol, k-means++ with L = 2 + int(ln K) local trials per draw, Lloyd with empty clusters
+ * moved to the farthest cells, one final E step unless no label changed, the best of n_init by inertia (an init with the
+ * same clustering as the best so far does not replace it).  Every sum over cells has a fixed order: the same input gives
+ * the same bits.  Needs cnmf_harmony_begin, not cnmf_harmony_init; R, E and O stay as they are.
+ *   uniforms   [n_init][1 + (K - 1) L]: per init the doubles numpy's RandomState(random_state) hands KMeans -- one for the
+ *              first centre, then L per further centre.  Ignored when centers0 is given.
+ *   centers0   NULL, or [n_init][K][d] (in the coordinates of Z_cos): k-means++ is skipped and Lloyd starts there.
+ *   Y          [d][K]: cluster_centers_ of the best init (not normalised); labels [N] of the best init, may be NULL;
+ *              inertia [n_init], n_iter [n_init], best: the index of the best init.
+ * With fewer distinct cells than clusters the centres of the surplus clusters are unspecified.
+ * CNMF_EINVAL: n_init outside [1, 16], max_iter < 1, K > N.  CNMF_ESTATE: no cnmf_harmony_begin. */
+int cnmf_harmony_kmeans_init(cnmf_ctx* ctx, int32_t n_init, int32_t max_iter, double tol,
+                             const double* uniforms, const double* centers0, double* Y, int32_t* labels,
+                             double* inertia, int32_t* n_iter, int32_t* best);
+
 /* ---- the restart hot loop ---------------------------------------------------------
  * Replaces the loop body of cNMF.factorize (cnmf.py:735-741): for every restart r,
  *   (usages, spectra, n_iter) = non_negative_factorization(X, n_components=k[r],

@@ -16,9 +16,11 @@ scipy / numpy on the same machine (detection counts, sums, the two subsets, norm
 ddof=1 scaling and the quantile ceiling over the dense N x HVG matrix).
 
 ``--harmony`` times Preprocess.run_harmony (the clustering loop on the device) on --cells x --components synthetic PCA
-scores with one batch variable of --batches levels and --K clusters: the k-means initialisation (scikit-learn on the
-host) is timed on its own and its centroids are handed to both runs; then the device loop (best of --repeats), and the
-same run through the numpy restatement tests/_harmony_ref.py on this machine's cores.
+scores with one batch variable of --batches levels and --K clusters: the k-means initialisation is timed on its own both
+ways in the same run -- scikit-learn on the host, and Engine.harmony_kmeans_init on the device (best of --repeats, after
+harmony_begin) -- and the device loop after each (best of --repeats, the centroids handed over as init_centroids);
+then the whole device route (run_harmony(kmeans_init="device")), and the loop from scikit-learn's centroids through the
+numpy restatement tests/_harmony_ref.py on this machine's cores.
 
 Usage:  python tools/preprocess_probe.py [--cells 50000] [--genes 2000] [--K 100] [--batches 4] [--out FILE.json]
         python tools/preprocess_probe.py --filter [--filter-cells 50000] [--filter-genes 20000] [--out FILE.json]
@@ -217,6 +219,34 @@ def harmony_leg(a):
             t0 = time.perf_counter()
             got = P.run_harmony(pca, obs, hvars, nclust=K, init_centroids=Y0)
             out["device_s"].append(round(time.perf_counter() - t0, 3))
+        # the initialisation on the device: alone (after harmony_begin), then the loop from its centroids, then the whole route
+        Phi, codes, level_var, n_levels = pp.harmony_design(obs, hvars)
+        out["device_kmeans_init_s"], out["device_s_after_device_init"], out["device_full_route_s"] = [], [], []
+        for _ in range(a.repeats):
+            eng.harmony_begin(pca, codes, level_var, np.ones(Phi.shape[0]), np.repeat(0.1, K), Phi.sum(axis=1) / N)
+            try:
+                t0 = time.perf_counter()
+                Yd, _, inertia, n_iter, best_init = eng.harmony_kmeans_init(0)
+                out["device_kmeans_init_s"].append(round(time.perf_counter() - t0, 4))
+            finally:
+                eng.harmony_release()
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            got_d = P.run_harmony(pca, obs, hvars, nclust=K, init_centroids=Yd)
+            out["device_s_after_device_init"].append(round(time.perf_counter() - t0, 3))
+            t0 = time.perf_counter()
+            full = P.run_harmony(pca, obs, hvars, nclust=K, kmeans_init="device")
+            out["device_full_route_s"].append(round(time.perf_counter() - t0, 3))
+        out["device_full_route_equals_init_centroids_run"] = bool(np.array_equal(full.Z_corr, got_d.Z_corr))
+    init_d = min(out["device_kmeans_init_s"])
+    out.update({"device_kmeans_init_s_best": init_d, "device_kmeans_n_iter": [int(x) for x in n_iter],
+                "device_kmeans_best_init": int(best_init), "device_kmeans_inertia": float(inertia[best_init]),
+                "host_over_device_kmeans_init": round(out["host_kmeans_init_s"] / init_d, 1),
+                "kmeans_rounds_after_device_init": [int(r) for r in got_d.kmeans_rounds],
+                "device_s_after_device_init_best": min(out["device_s_after_device_init"]),
+                "device_full_route_s_best": min(out["device_full_route_s"]),
+                "device_kmeans_init_share_of_full_route": round(init_d / min(out["device_full_route_s"]), 3),
+                "max_abs_diff_Y_host_vs_device_init": float(np.max(np.abs(Y0 - Yd)))})
     best = min(out["device_s"])
     iters = sum(r + 1 for r in got.kmeans_rounds)
     out.update({"harmony_rounds": len(got.kmeans_rounds), "kmeans_rounds": [int(r) for r in got.kmeans_rounds],
