@@ -1,6 +1,8 @@
 // The restart engine: batch buffers, the slot scheduler (run_batch) and the NNLS refit
-// (included by cnmf_hip.hip after gemm_host.hip.h).
+// (included by cnmf_hip.hip after gemm_host.hip.h).  The scheduler's decisions and books are batch_sched.h (no HIP).
 #pragma once
+
+#include "batch_sched.h"
 
 // ------------------------------------------------------------------ batch buffers
 static int sweep_chunks(const cnmf_ctx* ctx, int L) { const int64_t m = 256ll * ctx->knobs.sweep_parts; return std::max(1, (int)(((int64_t)L + m - 1) / m)); }
@@ -55,53 +57,54 @@ static int ensure_batch(cnmf_ctx* ctx, int KC, int max_k = KMAX, int min_k = 1)
                              : pick_nsplit_A(ctx, KC);
     const int parts = std::max(sweep_parts(ctx, (int)ctx->N), sweep_parts(ctx, (int)ctx->G));
     const size_t gp_need = (size_t)(KC / std::max(1, min_k) + 1) * parts * max_k * max_k;
-    if (ctx->kc_alloc == KC && ctx->nsplit_alloc == nsplit && ctx->nsplitA_alloc == nsplitA &&
-        ctx->parts_alloc == parts && ctx->gram_part_floats >= gp_need && (!use3 || ctx->H3)) return CNMF_OK;
-    free_batch(ctx);
+    if (ctx->bat.kc == KC && ctx->bat.nsplit == nsplit && ctx->bat.nsplitA == nsplitA &&
+        ctx->bat.parts == parts && ctx->bat.gram_part_floats >= gp_need && (!use3 || ctx->bat.H3)) return CNMF_OK;
+    ctx->bat.release();
+    OwnedLocal<BatchBuffersF> b;          // committed below: a failed allocation leaves the context without batch buffers
     const size_t hb = (size_t)KC * ctx->G_pad * sizeof(float);
     const size_t wb = (size_t)KC * ctx->N_pad * sizeof(float);
-    HIP_TRY(ctx, hipMalloc(&ctx->H, hb));
-    HIP_TRY(ctx, hipMalloc(&ctx->Wt, wb));
-    HIP_TRY(ctx, hipMalloc(&ctx->XHt, wb * nsplitA));
-    HIP_TRY(ctx, hipMalloc(&ctx->XHt1, wb));
+    HIP_TRY(ctx, hipMalloc(&b.H, hb));
+    HIP_TRY(ctx, hipMalloc(&b.Wt, wb));
+    HIP_TRY(ctx, hipMalloc(&b.XHt, wb * nsplitA));
+    HIP_TRY(ctx, hipMalloc(&b.XHt1, wb));
     if (use3) {
-        HIP_TRY(ctx, hipMalloc(&ctx->XHt2, wb));
-        HIP_TRY(ctx, hipMalloc(&ctx->H3, (size_t)KC * (ctx->G_pad / 16) * G3_ROWB));
-        HIP_TRY(ctx, hipMalloc(&ctx->Wt3, (size_t)KC * (ctx->N_pad / 16) * G3_ROWB));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->Wt3, 0, (size_t)KC * (ctx->N_pad / 16) * G3_ROWB, ctx->stream));
+        HIP_TRY(ctx, hipMalloc(&b.XHt2, wb));
+        HIP_TRY(ctx, hipMalloc(&b.H3, (size_t)KC * (ctx->G_pad / 16) * G3_ROWB));
+        HIP_TRY(ctx, hipMalloc(&b.Wt3, (size_t)KC * (ctx->N_pad / 16) * G3_ROWB));
+        HIP_TRY(ctx, hipMemsetAsync(b.Wt3, 0, (size_t)KC * (ctx->N_pad / 16) * G3_ROWB, ctx->stream));
         // f16 two-plane split: row-maximum partials written by the sweeps ([KC][parts]) and 2^-s per row
-        HIP_TRY(ctx, hipMalloc(&ctx->rmaxH, (size_t)KC * parts * sizeof(float)));
-        HIP_TRY(ctx, hipMalloc(&ctx->rmaxW, (size_t)KC * parts * sizeof(float)));
-        HIP_TRY(ctx, hipMalloc(&ctx->iscaleH, (size_t)KC * sizeof(float)));
-        HIP_TRY(ctx, hipMalloc(&ctx->iscaleW, (size_t)KC * sizeof(float)));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->rmaxH, 0, (size_t)KC * parts * sizeof(float), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->rmaxW, 0, (size_t)KC * parts * sizeof(float), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->iscaleH, 0, (size_t)KC * sizeof(float), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->iscaleW, 0, (size_t)KC * sizeof(float), ctx->stream));
-        HIP_TRY(ctx, hipMalloc(&ctx->shiftW, (size_t)3 * KC * sizeof(int)));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->shiftW, 0, (size_t)3 * KC * sizeof(int), ctx->stream));
+        HIP_TRY(ctx, hipMalloc(&b.rmaxH, (size_t)KC * parts * sizeof(float)));
+        HIP_TRY(ctx, hipMalloc(&b.rmaxW, (size_t)KC * parts * sizeof(float)));
+        HIP_TRY(ctx, hipMalloc(&b.iscaleH, (size_t)KC * sizeof(float)));
+        HIP_TRY(ctx, hipMalloc(&b.iscaleW, (size_t)KC * sizeof(float)));
+        HIP_TRY(ctx, hipMemsetAsync(b.rmaxH, 0, (size_t)KC * parts * sizeof(float), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(b.rmaxW, 0, (size_t)KC * parts * sizeof(float), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(b.iscaleH, 0, (size_t)KC * sizeof(float), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(b.iscaleW, 0, (size_t)KC * sizeof(float), ctx->stream));
+        HIP_TRY(ctx, hipMalloc(&b.shiftW, (size_t)3 * KC * sizeof(int)));
+        HIP_TRY(ctx, hipMemsetAsync(b.shiftW, 0, (size_t)3 * KC * sizeof(int), ctx->stream));
     }
-    HIP_TRY(ctx, hipMalloc(&ctx->d_split, (size_t)(KC / 32 + 1) * (ctx->N_pad / 128 + 1)));
-    HIP_TRY(ctx, hipMalloc(&ctx->XtW, hb * nsplit));
-    HIP_TRY(ctx, hipMalloc(&ctx->gramH, (size_t)KC * GRAM_SZ * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc(&ctx->gramW, (size_t)KC * GRAM_SZ * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc(&ctx->gram_part, gp_need * sizeof(float)));
-    ctx->gram_part_floats = gp_need;
-    HIP_TRY(ctx, hipMalloc(&ctx->viol_part, (size_t)KC * parts * sizeof(double)));
-    HIP_TRY(ctx, hipMalloc(&ctx->d_slots, (size_t)KC * sizeof(SlotDesc)));
-    HIP_TRY(ctx, hipMalloc(&ctx->d_slot_list, (size_t)KC * RING * sizeof(int)));
-    HIP_TRY(ctx, hipHostMalloc(&ctx->h_slots, (size_t)KC * sizeof(SlotDesc)));
+    HIP_TRY(ctx, hipMalloc(&b.d_split, (size_t)(KC / 32 + 1) * (ctx->N_pad / 128 + 1)));
+    HIP_TRY(ctx, hipMalloc(&b.XtW, hb * nsplit));
+    HIP_TRY(ctx, hipMalloc(&b.gramH, (size_t)KC * GRAM_SZ * sizeof(float)));
+    HIP_TRY(ctx, hipMalloc(&b.gramW, (size_t)KC * GRAM_SZ * sizeof(float)));
+    HIP_TRY(ctx, hipMalloc(&b.gram_part, gp_need * sizeof(float)));
+    HIP_TRY(ctx, hipMalloc(&b.viol_part, (size_t)KC * parts * sizeof(double)));
+    HIP_TRY(ctx, hipMalloc(&b.d_slots, (size_t)KC * sizeof(SlotDesc)));
+    HIP_TRY(ctx, hipMalloc(&b.d_slot_list, (size_t)KC * RING * sizeof(int)));
+    HIP_TRY(ctx, hipHostMalloc(&b.h_slots, (size_t)KC * sizeof(SlotDesc)));
     // device-written, host-polled: coherent mapped pinned memory (zero-copy snapshots of the slot table)
-    HIP_TRY(ctx, hipHostMalloc(&ctx->h_snap, (size_t)KC * RING * sizeof(SlotDesc),
+    HIP_TRY(ctx, hipHostMalloc(&b.h_snap, (size_t)KC * RING * sizeof(SlotDesc),
                                hipHostMallocMapped | hipHostMallocCoherent));
-    memset(ctx->h_snap, 0, (size_t)KC * RING * sizeof(SlotDesc));
-    HIP_TRY(ctx, hipHostMalloc(&ctx->h_slot_list, (size_t)KC * RING * sizeof(int)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->H, 0, hb, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->Wt, 0, wb, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->XHt, 0, wb * nsplitA, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->XtW, 0, hb * nsplit, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_slots, 0, (size_t)KC * sizeof(SlotDesc), ctx->stream));
-    ctx->kc_alloc = KC; ctx->nsplit_alloc = nsplit; ctx->nsplitA_alloc = nsplitA; ctx->parts_alloc = parts;
+    memset(b.h_snap, 0, (size_t)KC * RING * sizeof(SlotDesc));
+    HIP_TRY(ctx, hipHostMalloc(&b.h_slot_list, (size_t)KC * RING * sizeof(int)));
+    HIP_TRY(ctx, hipMemsetAsync(b.H, 0, hb, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(b.Wt, 0, wb, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(b.XHt, 0, wb * nsplitA, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(b.XtW, 0, hb * nsplit, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(b.d_slots, 0, (size_t)KC * sizeof(SlotDesc), ctx->stream));
+    b.kc = KC; b.nsplit = nsplit; b.nsplitA = nsplitA; b.parts = parts; b.gram_part_floats = gp_need;
+    ctx->bat.take(b);
     return CNMF_OK;
 }
 
@@ -119,34 +122,6 @@ static int ensure_stage(cnmf_ctx* ctx, size_t wfloats, size_t hfloats)
     }
     return CNMF_OK;
 }
-
-// simple first-fit interval allocator over the packed component columns
-struct ColAlloc {
-    std::vector<std::pair<int, int>> free_;   // (begin, length), sorted by begin
-    explicit ColAlloc(int n) { free_.push_back({0, n}); }
-    int alloc(int k) {
-        for (size_t i = 0; i < free_.size(); ++i)
-            if (free_[i].second >= k) {
-                int b = free_[i].first;
-                free_[i].first += k; free_[i].second -= k;
-                if (free_[i].second == 0) free_.erase(free_.begin() + i);
-                return b;
-            }
-        return -1;
-    }
-    void release(int b, int k) {
-        auto it = std::lower_bound(free_.begin(), free_.end(), std::make_pair(b, 0));
-        it = free_.insert(it, {b, k});
-        if (it + 1 != free_.end() && it->first + it->second == (it + 1)->first) {
-            it->second += (it + 1)->second; free_.erase(it + 1);
-        }
-        if (it != free_.begin() && (it - 1)->first + (it - 1)->second == it->first) {
-            (it - 1)->second += it->second; free_.erase(it);
-        }
-    }
-};
-
-struct HostSlot { int state = 0; int restart = -1; int off = 0; int k = 0; int64_t installed_at = 0; };
 
 // Poll the stamps of one zero-copy snapshot (finalize_kernel -> publish_slot) until all `n` slots carry
 // `stamp`.  The snapshot is `lag` iterations old when it is needed, so this normally returns at once.
@@ -220,7 +195,612 @@ static int validate_params(cnmf_ctx* ctx, const cnmf_cd_params* p)
     return CNMF_OK;
 }
 
+// ------------------------------------------------------------------ the operand scheme of the GEMM passes
+static_assert(SCHED_KMAX == KMAX && SCHED_RING == RING, "batch_sched.h repeats KMAX and RING");
+
+// Which kernels the two GEMM passes of an iteration run on, and what they read of X.  Filled once per call by
+// pick_scheme; the tail turns it into the f32 scheme when it narrows below 256 packed columns.
+struct PassScheme {
+    bool use3 = false;      // split-operand bf16 MFMA path (whole 256-column tiles only)
+    bool usec = false;      // ... with X as one integer plane (count-structured data)
+    bool use2g = false;     // any OTHER matrix in the default mode: X itself as two f16 planes with a per-row exponent, 4 MFMAs
+                            // per product (gemm_mode 5; CNMF_GEMM3=1|2 keep the 3 x 3 bf16 planes of rounds 1-2, 6 MFMAs)
+    bool use2h = false;     // ... on the f16 pipe: two f16 factor planes
+    int mode = 0;           // cnmf_batch_stats.gemm_mode
+    // the X-side operands of the count and f16 kernels: the integer count plane(s), or the two planes of a general matrix
+    XOperand xA{}, xB{};
+    const double* dsc = nullptr;            // per-gene scale of the count path
+    int jwA = G3_JW;                        // width of a pass-A / pass-B tile
+    int nsubA = 1, nsubB = 1, KbA = 0, KbB = 0;
+    void leave_matrix_pipe() { use3 = usec = use2h = use2g = false; }     // fewer than 256 packed columns: the f32 pipe
+};
+
+static int pick_scheme(cnmf_ctx* ctx, int KC, PassScheme* out)
+{
+    const CdKnobs& kn = ctx->knobs;
+    PassScheme p;
+    int rc;
+    p.use3 = gemm3_enabled(ctx, KC);
+    if (p.use3 && kn.gemm3 >= 3) {
+        if ((rc = ensure_counts(ctx))) return rc;
+        p.usec = ctx->counts.state == 1;
+    }
+    p.use2g = p.use3 && !p.usec && kn.gemm3 >= 4 && ctx->G_pad % G3C_JW == 0 && ctx->N_pad % G3C_JW == 0;
+    if (p.use2g && (rc = ensure_x2planes(ctx))) return rc;
+    p.use2h = (p.usec && ctx->counts.fmt == 4) || p.use2g;
+    p.mode = !p.use3 ? 0 : (p.use2g ? 5 : (p.usec ? (p.use2h ? 4 : 3) : std::min(kn.gemm3, 2)));
+    p.KbA = ctx->G_pad / 16; p.KbB = ctx->N_pad / 16;
+    p.xA = p.use2g ? ctx->x2.passA() : ctx->counts.passA();
+    p.xB = p.use2g ? ctx->x2.passB() : ctx->counts.passB();
+    p.dsc = p.use2g ? nullptr : ctx->counts.d_scale;
+    p.nsubA = p.use2h ? gemm2h_nsub(p.xA.hi != nullptr, p.KbA) : 1;
+    p.nsubB = p.use2h ? gemm2h_nsub(p.xB.hi != nullptr, p.KbB) : 1;
+    if (p.use3 && !p.usec && !p.use2g && (rc = ensure_planes(ctx))) return rc;
+    p.jwA = (p.usec || p.use2g) ? G3C_JW : G3_JW;
+    *out = p;
+    return CNMF_OK;
+}
+
 // ------------------------------------------------------------------ the restart hot loop
+// Everything one call of run_batch works with: the job, the call's device buffers, the operand scheme and pass plan, and
+// the scheduler (batch_sched.h), which decides and keeps the books while the functions below copy and launch.
+struct BatchRun {
+    cnmf_ctx* ctx; const cnmf_cd_params* prm; hipStream_t st;
+    int n; const int32_t* kk; int init_mode; const double* avg; const float *W0, *H0;
+    int32_t* n_iter_out; double* viol_out; bool resident;
+    int N, G, max_k; int64_t total_k;
+    std::vector<size_t> hoff, woff;                  // first float of restart r in the H / W results and inits
+    DevPool pool;
+    EventPool events;
+    struct PinnedInts { int* p = nullptr; ~PinnedInts() { if (p) hipHostFree(p); } } repack_host;
+    float *d_Hres = nullptr, *d_Wres = nullptr;      // device result buffers
+    float *d_H0 = nullptr, *d_Wt0 = nullptr;         // init_mode 1: the random factors of every restart, component-major
+    int* d_repack = nullptr;                         // re-packing: column map, moved slot ids, their new offsets
+    int n_repack = 0;
+    PassScheme ps;
+    // W planes written by the W sweep itself (kernels_sweep.hip.h, PLN) instead of a separate pass over W; ranks above
+    // 64 (sweep_big_kernel) keep the separate split for the whole call.
+    bool fuseW = false;
+    int shgen = 0;                                   // generation of the exponents the NEXT W sweep uses
+    int* shW[2] = {nullptr, nullptr};
+    bool h3_valid = false;                           // H3 holds the planes of the current H (split-operand modes)
+    int fin_y = 1, lag = 2;                          // finalize blocks per slot; iterations the inspected snapshot lies behind
+    int chunksW, partsW, chunksH, partsH;
+    float l1W, l2W, l1H, l2H;
+    // The plan of the two GEMM passes at the current width, on the pipe `ps.use3` names (plan_passes)
+    int nsplit = 1, nsplit3 = 1, nsplitA = 1;
+    StreamK sk;
+    StreamK3 sk3;
+    // HIP events around the two GEMM passes of every `time_stride`-th iteration (an event record costs
+    // ~6 us of queue time: bracketing every launch would take 4 % off the throughput it measures)
+    int time_stride = 0;
+    std::vector<hipEvent_t> gev;                     // (a0,a1,b0,b1) per iteration when timing is requested
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_tail = nullptr;     // ev_tail: recorded when the queue runs dry
+    int nsplit3_first = 1;                           // (reported: the tail narrows the batch and re-plans)
+    BatchSched sched;
+    BatchRun(int n_, const int32_t* kk_, int KC, const double* hint, bool dbg) : n(n_), kk(kk_), sched(n_, kk_, KC, hint, dbg) {}
+};
+
+// The plan of the two GEMM passes at the current width KC, on the pipe `use3` names: K splits of pass B (nsplit3 on
+// the split-operand kernels, nsplit on the f32 pipe), and pass A either as a stream-K plan (sk3 / sk, its cut flags
+// uploaded to d_split) or, on few tiles, as nsplitA K splits + reduce.  cap / capA: the partial planes the product
+// buffers hold at this width.  Made before the loop, and again whenever compact() narrows the batch.
+static int plan_passes(BatchRun& b, int cap, int capA)
+{
+    cnmf_ctx* ctx = b.ctx;
+    const int KC = b.sched.KC;
+    const std::vector<unsigned char>* flags = nullptr;
+    if (b.ps.use3) {
+        b.nsplit3 = std::max(1, std::min(pick_nsplit3(ctx, KC, b.ps.jwA), cap));
+        b.sk3 = plan_streamk3(KC, ctx->N_pad, ctx->G_pad, gemm3_wg_slots(ctx->knobs), b.ps.jwA, b.ps.nsubA);
+        if (b.sk3.on) flags = &b.sk3.flags;
+        else b.nsplitA = std::max(1, std::min(pick_nsplit_A3(ctx, KC, b.ps.jwA), capA));
+    } else {
+        b.nsplit = std::max(1, std::min(pick_nsplit(ctx, KC), cap));
+        b.sk = plan_streamk(KC, ctx->N_pad, ctx->G_pad, 2 * 256);       // T-layout pass A: 2 workgroups per CU (73.7 KB LDS each)
+        if (b.sk.on) { flags = &b.sk.split; b.nsplitA = 1; }
+        else b.nsplitA = std::max(1, std::min(pick_nsplit_A(ctx, KC), capA));
+    }
+    // (the flags of the old plan may still be read by an in-flight sweep: same stream -> ordered)
+    if (flags) HIP_TRY(ctx, hipMemcpyAsync(ctx->bat.d_split, flags->data(), flags->size(), hipMemcpyHostToDevice, b.st));
+    return CNMF_OK;
+}
+
+// copy the factors of a finished slot out of the packed columns and clear its rows; the books: sched.retire
+static int retire_slot(BatchRun& b, int s, const SlotDesc& snap)
+{
+    cnmf_ctx* ctx = b.ctx;
+    hipStream_t st = b.st;
+    const HostSlot& h = b.sched.hs[s];
+    const int r = h.restart, k = h.k, N = b.N, G = b.G;
+    dim3 gH((G + 255) / 256, k), gW((N + 255) / 256, k);
+    extract_kernel<<<gH, 256, 0, st>>>(ctx->bat.H, ctx->G_pad, G, h.off, k, b.d_Hres + b.hoff[r], 0);
+    if (b.d_Wres) extract_kernel<<<gW, 256, 0, st>>>(ctx->bat.Wt, ctx->N_pad, N, h.off, k, b.d_Wres + b.woff[r], 1);
+    clear_rows_kernel<<<gH, 256, 0, st>>>(ctx->bat.H, ctx->G_pad, ctx->G_pad, h.off, k);
+    clear_rows_kernel<<<gW, 256, 0, st>>>(ctx->bat.Wt, ctx->N_pad, ctx->N_pad, h.off, k);
+    HIP_TRY(ctx, hipGetLastError());
+    if (b.n_iter_out) b.n_iter_out[r] = snap.iter;
+    if (b.viol_out) b.viol_out[r] = snap.viol_last;
+    b.sched.retire(s, snap.iter);
+    return CNMF_OK;
+}
+
+// Move the live slots as sched.plan_repack says (through the stage buffers) and zero the rows it leaves free up to
+// `width`.  Used by the tail compaction (narrower batch, or balanced at the same width) and by the refill's
+// defragmentation (same width).
+// (one launch sequence per re-packing, whatever the number of slots: at 1024 packed columns the per-slot moves of
+//  round 2 -- four launches each, host-bound at ~5 us per launch -- had grown to 10 % of the wall time)
+static int repack(BatchRun& b, int width, bool balanced = false)
+{
+    cnmf_ctx* ctx = b.ctx;
+    hipStream_t st = b.st;
+    const int KC0 = b.sched.KC0;
+    int* hm = b.repack_host.p + (size_t)(b.n_repack++ % RING) * 3 * KC0;      // [colmap | slot ids | new offsets], pinned
+    int* d_colmap = b.d_repack, *d_ids = b.d_repack + KC0, *d_offs = b.d_repack + 2 * KC0;
+    const RepackPlan pl = b.sched.plan_repack(width, balanced, hm);
+    if (pl.nmove || pl.pos < width) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_colmap, hm, (size_t)width * sizeof(int), hipMemcpyHostToDevice, st));
+        // staging = the product buffers (scratch between two iterations): XHt [>= KC0][N_pad], XtW [>= KC0][G_pad]
+        gather_rows_cm_kernel<<<dim3((ctx->N_pad / 4 + 255) / 256, width), 256, 0, st>>>(ctx->bat.Wt, ctx->N_pad, d_colmap, ctx->bat.XHt);
+        gather_rows_cm_kernel<<<dim3((ctx->G_pad / 4 + 255) / 256, width), 256, 0, st>>>(ctx->bat.H, ctx->G_pad, d_colmap, ctx->bat.XtW);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->bat.Wt, ctx->bat.XHt, (size_t)width * ctx->N_pad * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->bat.H, ctx->bat.XtW, (size_t)width * ctx->G_pad * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (b.fuseW) {
+            int* tmp = ctx->bat.shiftW + 2 * ctx->bat.kc;
+            for (int g2 = 0; g2 < 2; ++g2) {
+                permute_ints_kernel<<<(width + 255) / 256, 256, 0, st>>>(b.shW[g2], d_colmap, tmp, width);
+                HIP_TRY(ctx, hipMemcpyAsync(b.shW[g2], tmp, (size_t)width * sizeof(int), hipMemcpyDeviceToDevice, st));
+            }
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        if (pl.nmove) {
+            HIP_TRY(ctx, hipMemcpyAsync(d_ids, hm + KC0, (size_t)pl.nmove * sizeof(int), hipMemcpyHostToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(d_offs, hm + 2 * KC0, (size_t)pl.nmove * sizeof(int), hipMemcpyHostToDevice, st));
+            set_slot_offs_kernel<<<(pl.nmove + 255) / 256, 256, 0, st>>>(ctx->bat.d_slots, d_ids, d_offs, pl.nmove);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    b.h3_valid = false;               // rows of H moved: its planes are stale
+    // moved rows of slots that no longer iterate are not swept again: refresh their row maxima here
+    if (b.ps.use2h) HIP_TRY(ctx, launch_rowmax_part(st, ctx->bat.Wt, ctx->N_pad, b.N, b.sched.KC, b.chunksW * 256, nullptr, b.partsW, ctx->bat.rmaxW));
+    return CNMF_OK;
+}
+
+// copy the initial factors of one placed restart into its packed columns and write its slot descriptor
+static int install(BatchRun& b, const Placement& p)
+{
+    cnmf_ctx* ctx = b.ctx;
+    hipStream_t st = b.st;
+    const int r = p.restart, k = p.k, off = p.off, N = b.N, G = b.G;
+    dim3 gI((std::max(N, G) + 255) / 256, k);
+    if (b.init_mode == 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->stageH, b.H0 + b.hoff[r], (size_t)k * G * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->stageW, b.W0 + b.woff[r], (size_t)k * N * sizeof(float), hipMemcpyHostToDevice, st));
+        install_kernel<<<gI, 256, 0, st>>>(ctx->stageH, ctx->stageW, ctx->bat.H, ctx->G_pad, G, ctx->bat.Wt, ctx->N_pad, N, off, k);
+    } else {
+        install_cm_kernel<<<gI, 256, 0, st>>>(b.d_H0 + b.hoff[r], b.d_Wt0 + b.woff[r], ctx->bat.H, ctx->G_pad, G, ctx->bat.Wt, ctx->N_pad, N, off);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    if (b.fuseW) {
+        // exponent of the planes the FIRST W sweep of this restart writes: from the size of its W0 (random init:
+        // avg |N(0,1)|, the maximum of 50 000 draws is ~4.5 avg), two bits of headroom; the check behind the sweep
+        // re-converts the rows whose first update left the window
+        float mx = 0.f;
+        if (b.init_mode == 1) mx = 6.0f * (float)b.avg[r];
+        else for (size_t q = 0; q < (size_t)k * N; ++q) mx = std::max(mx, b.W0[b.woff[r] + q]);
+        int e2 = 0;
+        if (mx > 0.f) std::frexp(mx, &e2);
+        const int sh0 = mx > 0.f ? std::max(-110, std::min(120, 13 - e2)) : 0;
+        set_ints_kernel<<<1, 128, 0, st>>>(b.shW[0], b.shW[1], off, k, sh0);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    SlotDesc* d = &ctx->bat.h_slots[p.slot];
+    memset(d, 0, sizeof *d);
+    d->off = off; d->k = k; d->active = 1; d->iter = 0; d->restart = r;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->bat.d_slots + p.slot, d, sizeof(SlotDesc), hipMemcpyHostToDevice, st));
+    return CNMF_OK;
+}
+
+// ---- step 1: refill free columns from the pending list (n_new = slots installed)
+static int refill(BatchRun& b, int& n_new)
+{
+    cnmf_ctx* ctx = b.ctx;
+    BatchSched& sc = b.sched;
+    n_new = 0;
+    int* new_list = ctx->bat.h_slot_list + (size_t)(sc.it % RING) * sc.KC0;
+    int rc;
+    sc.begin_refill();
+    while (true) {
+        Placement p;
+        while (sc.next_placement(&p)) {
+            if ((rc = install(b, p))) return rc;
+            new_list[n_new++] = p.slot;
+        }
+        if (!sc.defrag_due()) break;
+        if ((rc = repack(b, sc.KC))) return rc;
+        sc.defragmented();
+    }
+    if (n_new) {
+        int* dl = ctx->bat.d_slot_list + (size_t)(sc.it % RING) * sc.KC0;
+        HIP_TRY(ctx, hipMemcpyAsync(dl, new_list, n_new * sizeof(int), hipMemcpyHostToDevice, b.st));
+        gram_rows_kernel<<<n_new, 256, 0, b.st>>>(ctx->bat.H, ctx->G_pad, b.G, ctx->bat.d_slots, dl, ctx->bat.gramH, b.l2W);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return CNMF_OK;
+}
+
+// ---- step 2: the launches of one coordinate-descent outer iteration, in order
+// pass A : XHt[KC][N] = H_all . X^T                       (sklearn _nmf.py:387)
+// *spA: where the W sweep finds the stream-K partial planes (plane1 = NULL: one plane, after launch_reduce_splits)
+static int launch_pass_a(BatchRun& b, int n_new, unsigned long long livemask, hipEvent_t ev_begin, SplitInfo* spA)
+{
+    cnmf_ctx* ctx = b.ctx;
+    hipStream_t st = b.st;
+    const PassScheme& ps = b.ps;
+    const int KC = b.sched.KC;
+    const long long plane = (long long)KC * ctx->N_pad;
+    *spA = SplitInfo{nullptr, nullptr, 1, 1, 1};
+    if (!ps.use3) {
+        if (b.sk.on) {
+            HIP_TRY(ctx, launch_streamk_passA(st, b.sk, ctx->bat.H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->bat.XHt,
+                                              ctx->bat.XHt1, ctx->N_pad, ctx->N_pad));
+            *spA = SplitInfo{ctx->bat.XHt1, ctx->bat.d_split, 128, b.sk.mw, b.sk.MG};
+        } else
+            HIP_TRY(ctx, launch_gemm<false>(st, 0, ctx->bat.H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->bat.XHt,
+                                            ctx->N_pad, plane, KC, ctx->G_pad, ctx->N_pad, b.nsplitA));
+        return CNMF_OK;
+    }
+    // H3 was produced together with the previous iteration's H finalize; rows installed since then
+    // (and the very first iteration) need a split of their own.  Count path: H' = H * d.
+    if ((n_new > 0 || !b.h3_valid) && ps.use2h) {
+        HIP_TRY(ctx, launch_rowmax_part(st, ctx->bat.H, ctx->G_pad, b.G, KC, b.chunksH * 256, ps.dsc, b.partsH, ctx->bat.rmaxH));
+        HIP_TRY(ctx, launch_split2h(st, ctx->bat.H, ctx->G_pad, KC, ctx->G_pad, ctx->bat.H3, G3_MW, ps.dsc, ctx->bat.rmaxH,
+                                    b.partsH, ctx->bat.iscaleH));
+    } else if (n_new > 0 || !b.h3_valid)
+        HIP_TRY(ctx, launch_split3(st, ctx->bat.H, ctx->G_pad, KC, ctx->G_pad, ctx->bat.H3, G3_MW, ps.usec ? ctx->counts.d_scale : nullptr));
+    if (ev_begin) hipEventRecord(ev_begin, st);          // (timed iterations: the pass without the split in front of it)
+    if (b.sk3.on) {
+        if (ps.use2h)
+            HIP_TRY(ctx, launch_gemm2h_streamk(st, b.sk3, ctx->bat.H3, ps.xA.plane, ps.xA.hi, ps.xA.flags, ctx->bat.iscaleH, ps.KbA,
+                                               ctx->bat.XHt, ctx->bat.XHt1, ctx->bat.XHt2, ctx->N_pad, ps.xA.colscale, livemask));
+        else if (ps.usec)
+            HIP_TRY(ctx, launch_gemm3c_streamk(st, b.sk3, ctx->bat.H3, ps.xA.plane, ps.xA.hi, ps.xA.flags, ctx->bat.XHt, ctx->bat.XHt1,
+                                               ctx->bat.XHt2, ctx->N_pad));
+        else
+            HIP_TRY(ctx, launch_gemm3_streamk(st, b.sk3, ctx->bat.H3, ctx->planes.X3, ctx->bat.XHt, ctx->bat.XHt1, ctx->bat.XHt2, ctx->N_pad));
+        *spA = SplitInfo{ctx->bat.XHt1, ctx->bat.d_split, ps.jwA, G3_MW, b.sk3.MG, ctx->bat.XHt2};
+    } else if (ps.use2h)
+        HIP_TRY(ctx, launch_gemm2h(st, ctx->bat.H3, ps.xA.plane, ps.xA.hi, ps.xA.flags, ctx->bat.iscaleH, ps.KbA, ctx->bat.XHt, ctx->N_pad,
+                                   plane, KC, ctx->N_pad, b.nsplitA, ps.xA.colscale, livemask));
+    else if (ps.usec)
+        HIP_TRY(ctx, launch_gemm3c(st, ctx->bat.H3, ps.xA.plane, ps.xA.hi, ps.xA.flags, ctx->G_pad / 16, ctx->bat.XHt, ctx->N_pad,
+                                   plane, KC, ctx->N_pad, b.nsplitA));
+    else
+        HIP_TRY(ctx, launch_gemm3(st, ctx->bat.H3, ctx->planes.X3, ctx->G_pad / 16, ctx->bat.XHt, ctx->N_pad,
+                                  plane, KC, ctx->N_pad, b.nsplitA));
+    return CNMF_OK;
+}
+
+// the finalize of a half-step on the f32 pipe, without a plane split
+static void launch_finalize(BatchRun& b, const FinalizeArgs& fa)
+{
+    finalize_kernel<<<dim3(b.sched.nslots, b.fin_y), 256, 0, b.st>>>(fa.gram_part, fa.viol_part, fa.nparts, fa.gram_out, fa.l2_reg,
+                                                                   fa.slots, fa.phase, fa.tol, fa.max_iter, fa.want_gram, fa.gld,
+                                                                   fa.snap_out, fa.stamp);
+}
+
+// finalize of the W sweep: Gram matrix of W and the stopping rule's sums; on the split-operand paths the plane split of
+// the sweep's result rides in the same launch (writing the bf16 planes from inside the sweep was measured slower: 2-byte
+// stores, lower occupancy; f16, fused: the sweep wrote the planes, this launch checks their exponents, publishes 2^-s and
+// the next exponents)
+static int launch_w_finalize(BatchRun& b)
+{
+    cnmf_ctx* ctx = b.ctx;
+    const int KC = b.sched.KC, nslots = b.sched.nslots;
+    const FinalizeArgs fa{ctx->bat.gram_part, ctx->bat.viol_part, b.partsW, ctx->bat.gramW, b.l2H, ctx->bat.d_slots, 0, b.prm->tol,
+                          b.prm->max_iter, 1, b.max_k, nullptr, 0};
+    if (b.ps.use2h) {
+        const bool fuse_now = b.fuseW;
+        HIP_TRY(ctx, launch_split2h_finalize(b.st, ctx->bat.Wt, ctx->N_pad, KC, ctx->N_pad, ctx->bat.Wt3, G3_MW, nullptr, ctx->bat.rmaxW,
+                                             b.partsW, ctx->bat.iscaleW, fa, nslots, b.fin_y,
+                                             fuse_now ? SplitFused{b.shW[b.shgen], b.shW[b.shgen ^ 1]} : SplitFused{nullptr, nullptr}));
+        if (fuse_now) b.shgen ^= 1;
+    } else if (b.ps.use3)
+        HIP_TRY(ctx, launch_split3_finalize(b.st, ctx->bat.Wt, ctx->N_pad, KC, ctx->N_pad, ctx->bat.Wt3, G3_MW, nullptr, fa,
+                                            nslots, b.fin_y));
+    else
+        launch_finalize(b, fa);
+    return CNMF_OK;
+}
+
+// pass B : XtW[S][KC][G] = Wt_all . X  (split over cells)  (sklearn _nmf.py:505-507); *nsB: partial planes it wrote
+static int launch_pass_b(BatchRun& b, unsigned long long livemask, int* nsB)
+{
+    cnmf_ctx* ctx = b.ctx;
+    hipStream_t st = b.st;
+    const PassScheme& ps = b.ps;
+    const int KC = b.sched.KC;
+    const long long plane = (long long)KC * ctx->G_pad;
+    *nsB = ps.use2h ? gemm2h_splits(ps.KbB, b.nsplit3, ps.nsubB) : (ps.use3 ? b.nsplit3 : b.nsplit);
+    if (ps.use2h)
+        HIP_TRY(ctx, launch_gemm2h(st, ctx->bat.Wt3, ps.xB.plane, ps.xB.hi, ps.xB.flags, ctx->bat.iscaleW, ps.KbB, ctx->bat.XtW, ctx->G_pad,
+                                   plane, KC, ctx->G_pad, b.nsplit3, ps.xB.colscale, livemask));
+    else if (ps.usec)
+        HIP_TRY(ctx, launch_gemm3c(st, ctx->bat.Wt3, ps.xB.plane, ps.xB.hi, ps.xB.flags, ctx->N_pad / 16, ctx->bat.XtW, ctx->G_pad,
+                                   plane, KC, ctx->G_pad, b.nsplit3));
+    else if (ps.use3)
+        HIP_TRY(ctx, launch_gemm3(st, ctx->bat.Wt3, ctx->planes.Xt3, ctx->N_pad / 16, ctx->bat.XtW, ctx->G_pad,
+                                  plane, KC, ctx->G_pad, b.nsplit3));
+    else
+        HIP_TRY(ctx, launch_gemm<true>(st, 0, ctx->bat.Wt, ctx->N_pad, ctx->X, ctx->G_pad, ctx->bat.XtW,
+                                       ctx->G_pad, plane, KC, ctx->N_pad, ctx->G_pad, b.nsplit));
+    return CNMF_OK;
+}
+
+// H half-step.  On the f16 path the split-K partials are summed (and scaled by d) inside the sweep itself.
+static int launch_h_sweep(BatchRun& b, int tiers, int nsB)
+{
+    cnmf_ctx* ctx = b.ctx;
+    hipStream_t st = b.st;
+    const PassScheme& ps = b.ps;
+    const int KC = b.sched.KC, nslots = b.sched.nslots;
+    const long long plane = (long long)KC * ctx->G_pad;
+    if (ps.use2h && !ctx->knobs.no_psum && !(tiers & 8)) {      // (ranks above 64 take the separately reduced product)
+        HIP_TRY(ctx, launch_sweep(st, nslots, ctx->bat.H, ctx->G_pad, b.G, ctx->bat.XtW, ctx->bat.gramW,
+                                  ctx->bat.d_slots, b.l1H, ctx->bat.gram_part, ctx->bat.viol_part, b.chunksH, b.partsH, 1, b.max_k, tiers,
+                                  psum_info(nsB, plane, ps.dsc), ctx->bat.rmaxH, ps.dsc, true));
+    } else {
+        HIP_TRY(ctx, launch_reduce_splits(st, ctx->bat.XtW, nsB, plane, plane, ps.usec ? ps.dsc : nullptr, ctx->G_pad));
+        HIP_TRY(ctx, launch_sweep(st, nslots, ctx->bat.H, ctx->G_pad, b.G, ctx->bat.XtW, ctx->bat.gramW,
+                                  ctx->bat.d_slots, b.l1H, ctx->bat.gram_part, ctx->bat.viol_part, b.chunksH, b.partsH, 1, b.max_k, tiers,
+                                  SplitInfo{nullptr, nullptr, 1, 1, 1}, ps.use2h ? ctx->bat.rmaxH : nullptr,
+                                  ps.use2h ? ps.dsc : nullptr));
+    }
+    return CNMF_OK;
+}
+
+// the H finalize also publishes every slot's state into the host-mapped ring entry of this
+// iteration (stamp it + 1): no copy kernel and no event per iteration
+static int launch_h_finalize(BatchRun& b)
+{
+    cnmf_ctx* ctx = b.ctx;
+    const PassScheme& ps = b.ps;
+    const BatchSched& sc = b.sched;
+    SlotDesc* snap = ctx->bat.h_snap + (size_t)(sc.it % RING) * sc.KC0;
+    SlotDesc* snap_dev = nullptr;
+    HIP_TRY(ctx, hipHostGetDevicePointer((void**)&snap_dev, snap, 0));
+    const FinalizeArgs fa{ctx->bat.gram_part, ctx->bat.viol_part, b.partsH, ctx->bat.gramH, b.l2W, ctx->bat.d_slots, 1, b.prm->tol,
+                          b.prm->max_iter, 1, b.max_k, snap_dev, (int)(sc.it + 1)};
+    if (ps.use2h)
+        HIP_TRY(ctx, launch_split2h_finalize(b.st, ctx->bat.H, ctx->G_pad, sc.KC, ctx->G_pad, ctx->bat.H3, G3_MW, ps.dsc,
+                                             ctx->bat.rmaxH, b.partsH, ctx->bat.iscaleH, fa, sc.nslots, b.fin_y));
+    else if (ps.use3)
+        HIP_TRY(ctx, launch_split3_finalize(b.st, ctx->bat.H, ctx->G_pad, sc.KC, ctx->G_pad, ctx->bat.H3, G3_MW,
+                                            ps.usec ? ctx->counts.d_scale : nullptr, fa, sc.nslots, b.fin_y));
+    else
+        launch_finalize(b, fa);
+    if (ps.use3) b.h3_valid = true;
+    HIP_TRY(ctx, hipGetLastError());
+    return CNMF_OK;
+}
+
+// enqueue one coordinate-descent outer iteration for every slot in flight
+static int iterate(BatchRun& b, int n_new)
+{
+    cnmf_ctx* ctx = b.ctx;
+    hipStream_t st = b.st;
+    const PassScheme& ps = b.ps;
+    BatchSched& sc = b.sched;
+    int tiers = 0, rc;
+    for (int s2 = 0; s2 < sc.nslots; ++s2)
+        if (sc.hs[s2].state) tiers |= sc.hs[s2].k <= 16 ? 1 : (sc.hs[s2].k <= 32 ? 2 : (sc.hs[s2].k <= KSMALL ? 4 : 8));
+    // the tail (nothing left to refill with): the f16 kernels skip the 32-column tiles without a live restart.
+    // Partial-tile passes were built and measured in round 3 -- 183.0 vs 182.2 restarts/s on the 113-restart shard, 216.5 vs
+    // 215.7 on the full job: within noise (a tail pass is bound by streaming the count plane as much as by its MFMAs).
+    // Opt-in: CNMF_PART=1 (knobs.part).
+    unsigned long long livemask = ~0ull;
+    if (ps.use2h && sc.n_pending == 0 && ctx->knobs.part) {
+        // the skipping variant of the kernels is ~4 % slower with everything live, and a pass lasts as long as its
+        // fullest component group: use it only when EVERY group has at least two dead tiles
+        int fullest = 0;
+        livemask = sc.live_tiles(&fullest);
+        if (fullest > 6) livemask = ~0ull;
+    }
+    hipEvent_t* ev = nullptr;                       // (a0, a1, b0, b1) of a timed iteration
+    if (b.time_stride > 0 && sc.it % b.time_stride == 0) {
+        for (int i = 0; i < 4; ++i) b.gev.push_back(b.events.get());
+        POOL_TRY(ctx, b.events);
+        ev = &b.gev[b.gev.size() - 4];
+        hipEventRecord(ev[0], st);
+    }
+    SplitInfo spA;
+    if ((rc = launch_pass_a(b, n_new, livemask, ev ? ev[0] : nullptr, &spA))) return rc;
+    if (ev) hipEventRecord(ev[1], st);
+    if (!spA.plane1)
+        HIP_TRY(ctx, launch_reduce_splits(st, ctx->bat.XHt, ps.use2h ? gemm2h_splits(ps.KbA, b.nsplitA, ps.nsubA) : b.nsplitA,
+                                          (long long)sc.KC * ctx->N_pad, (long long)sc.KC * ctx->N_pad));
+    // W half-step                                             (sklearn _nmf.py:500)
+    const bool fuse_now = b.fuseW && ps.use2h;
+    HIP_TRY(ctx, launch_sweep(st, sc.nslots, ctx->bat.Wt, ctx->N_pad, b.N, ctx->bat.XHt, ctx->bat.gramH,
+                              ctx->bat.d_slots, b.l1W, ctx->bat.gram_part, ctx->bat.viol_part, b.chunksW, b.partsW, 1, b.max_k, tiers, spA,
+                              ps.use2h ? ctx->bat.rmaxW : nullptr, nullptr, false,
+                              fuse_now ? PlaneOut{(unsigned short*)ctx->bat.Wt3, b.shW[b.shgen], ps.KbB, G3_MW} : PlaneOut{nullptr, nullptr, 0, 0}));
+    if ((rc = launch_w_finalize(b))) return rc;
+    if (ev) hipEventRecord(ev[2], st);
+    int nsB = 1;
+    if ((rc = launch_pass_b(b, livemask, &nsB))) return rc;
+    if (ev) hipEventRecord(ev[3], st);
+    if ((rc = launch_h_sweep(b, tiers, nsB))) return rc;
+    if ((rc = launch_h_finalize(b))) return rc;
+    sc.end_iteration();
+    return CNMF_OK;
+}
+
+// ---- step 3: look at the snapshot `lag` iterations behind the GPU and retire what has converged
+static int inspect(BatchRun& b)
+{
+    BatchSched& sc = b.sched;
+    const int64_t si = sc.it - 1 - b.lag;   // snapshot index to inspect now
+    if (si < 0) return CNMF_OK;
+    const SlotDesc* sp = b.ctx->bat.h_snap + (size_t)(si % RING) * sc.KC0;
+    const int ns = sc.snap_nslots[si % RING];
+    int rc = wait_snapshot(b.ctx, sp, ns, (int)(si + 1));
+    if (rc) return rc;
+    for (int s = 0; s < ns; ++s)
+        if (sc.retirable(s, si, sp[s].active, sp[s].restart) && (rc = retire_slot(b, s, sp[s]))) return rc;
+    sc.resort_pending();
+    return CNMF_OK;
+}
+
+// ---- step 4: tail compaction -- nothing left to refill with and at most half of the packed
+// columns still iterate: repack the live slots into a narrower batch so the two GEMM passes
+// shrink with the work (their cost is proportional to KC).
+static int compact(BatchRun& b)
+{
+    BatchSched& sc = b.sched;
+    PassScheme& ps = b.ps;
+    if (!sc.in_tail()) return CNMF_OK;
+    const bool part = b.ctx->knobs.part;
+    const TailPlan t = sc.tail_plan(ps.use3, ps.usec, ps.use2h, part);
+    int rc;
+    if (t.rebalance) {
+        if ((rc = repack(b, sc.KC, true))) return rc;
+        sc.rebalanced();
+    }
+    if (t.width < sc.KC) {
+        const int KC0 = sc.KC0;
+        if ((rc = repack(b, t.width, t.stay3 && ps.use2h && part))) return rc;
+        sc.narrowed(t.width);
+        if (!t.stay3) ps.leave_matrix_pipe();
+        // (the buffers were sized for KC0 columns: a narrower batch may keep more partial planes in them)
+        if ((rc = plan_passes(b, (b.ctx->bat.nsplit * KC0) / sc.KC, (b.ctx->bat.nsplitA * KC0) / sc.KC))) return rc;
+    }
+    return CNMF_OK;
+}
+
+// where the call's results go: the resident spectra store (grown as needed) or a buffer of the call; the re-packing
+// scratch on both sides
+static int alloc_call_buffers(BatchRun& b, bool want_W)
+{
+    cnmf_ctx* ctx = b.ctx;
+    const int G = b.G, n = b.n, KC0 = b.sched.KC0;
+    if (b.resident) {
+        if (ctx->spectra_rows && ctx->spectra_G != G) {
+            SET_ERR(ctx, "the resident store holds spectra over %lld genes, this matrix has %d: cnmf_spectra_reset first",
+                    (long long)ctx->spectra_G, G);
+            return CNMF_ESTATE;
+        }
+        ctx->spectra_G = G;
+        const size_t need = (ctx->spectra_rows + (size_t)b.total_k) * G;
+        if (need > ctx->spectra_cap) {
+            float* nb = nullptr;
+            const size_t cap = std::max(need, ctx->spectra_cap * 2);
+            HIP_TRY(ctx, hipMalloc(&nb, cap * sizeof(float)));
+            hipError_t ce = hipSuccess;
+            if (ctx->spectra_rows)
+                ce = hipMemcpyAsync(nb, ctx->spectra, ctx->spectra_rows * G * sizeof(float), hipMemcpyDeviceToDevice, b.st);
+            if (ce == hipSuccess) ce = hipStreamSynchronize(b.st);
+            if (ce != hipSuccess) { hipFree(nb); HIP_TRY(ctx, ce); }
+            hipFree(ctx->spectra);
+            ctx->spectra = nb; ctx->spectra_cap = cap;
+        }
+        b.d_Hres = ctx->spectra + ctx->spectra_rows * G;
+    } else {
+        b.d_Hres = b.pool.get<float>(b.hoff[n]);
+    }
+    if (want_W) b.d_Wres = b.pool.get<float>(b.woff[n]);
+    b.d_repack = b.pool.get<int>((size_t)3 * KC0);
+    POOL_TRY(ctx, b.pool);
+    HIP_TRY(ctx, hipHostMalloc(&b.repack_host.p, (size_t)RING * 3 * KC0 * sizeof(int)));
+    return CNMF_OK;
+}
+
+// init_mode 1: sklearn's init='random' for EVERY restart of the call, generated up front on the
+// device (one workgroup per restart) into a component-major store; install = row copy.
+static int generate_inits(BatchRun& b, const uint32_t* seeds)
+{
+    cnmf_ctx* ctx = b.ctx;
+    const int n = b.n, N = b.N, G = b.G;
+    b.d_H0 = b.pool.get<float>(b.hoff[n]);
+    b.d_Wt0 = b.pool.get<float>(b.woff[n]);
+    RngJob* d_jobs = b.pool.get<RngJob>((size_t)n);
+    POOL_TRY(ctx, b.pool);
+    std::vector<RngJob> jobs(n);
+    int rowoff = 0;
+    for (int r = 0; r < n; ++r) {
+        jobs[r] = RngJob{seeds[r], b.kk[r], rowoff, b.avg[r], (long long)b.kk[r] * ((long long)G + N)};
+        rowoff += b.kk[r];
+    }
+    HIP_TRY(ctx, hipMemcpy(d_jobs, jobs.data(), (size_t)n * sizeof(RngJob), hipMemcpyHostToDevice));
+    rng_kernel<1><<<n, 256, 0, b.st>>>(d_jobs, nullptr, b.d_H0, G, G, b.d_Wt0, N, N);
+    HIP_TRY(ctx, hipGetLastError());
+    return CNMF_OK;
+}
+
+// Packed columns of the call: pick_kc on the job's total rank, wide where the matrix-pipe kernels can run it
+static int pick_batch_width(cnmf_ctx* ctx, const cnmf_cd_params* prm, int64_t total_k, int max_k, int* KC_out)
+{
+    const CdKnobs& kn = ctx->knobs;
+    // (wide batches need the whole-tile matrix-pipe kernels and a matrix large enough to be worth them)
+    const bool wide_can = kn.gemm3 != 0 && gemm3_enabled(ctx, 512);
+    // round 6: a SMALL matrix (BASELINE config 2: 2 700 x 2 000) is launch-latency-bound -- an iteration costs its six
+    // launches whatever the width -- so a job of >= 512 columns also runs wide there (C2: 1 000 columns in one batch instead
+    // of four 256-column rounds, 17 -> 8 ms per job); CNMF_WIDE_SMALL=0: the round-5 rule (A/B)
+    const bool wide_small = total_k >= 512 && kn.wide_small;
+    const bool wide_auto = wide_can && ((int64_t)ctx->N_pad * ctx->G_pad >= (1ll << 24) || wide_small);
+    int KC = pick_kc(ctx, total_k, max_k, prm->kc_max, (prm->kc_max > 256 || kn.kc_set) ? wide_can : wide_auto);
+    // 65..128 columns of a count-structured matrix: the 256-column integer-plane kernels (half empty) are still
+    // faster than 128 columns on the f32 pipe
+    if (KC == 128 && prm->kc_max <= 0 && !kn.kc_set && kn.gemm3 >= 3 && gemm3_enabled(ctx, 256) &&
+        (int64_t)ctx->N_pad * ctx->G_pad >= (1ll << 24)) {
+        int rc = ensure_counts(ctx);
+        if (rc) return rc;
+        if (ctx->counts.state == 1) KC = 256;
+    }
+    *KC_out = KC;
+    return CNMF_OK;
+}
+
+// the end of a call: results to the host, what the call learned about its ranks, the statistics
+static int finish_batch(BatchRun& b, float* H_out, float* W_out, cnmf_batch_stats* stats)
+{
+    cnmf_ctx* ctx = b.ctx;
+    const BatchSched& sc = b.sched;
+    if (sc.dbg) sc.print_debug();
+    HIP_TRY(ctx, hipEventRecord(b.ev_end, b.st));
+    if (!b.resident)
+        HIP_TRY(ctx, hipMemcpyAsync(H_out, b.d_Hres, b.hoff[b.n] * sizeof(float), hipMemcpyDeviceToHost, b.st));
+    if (W_out)
+        HIP_TRY(ctx, hipMemcpyAsync(W_out, b.d_Wres, b.woff[b.n] * sizeof(float), hipMemcpyDeviceToHost, b.st));
+    HIP_TRY(ctx, hipStreamSynchronize(b.st));
+    if (b.resident) ctx->spectra_rows += (size_t)b.total_k;
+    // the mean iteration count per rank this call saw (cnmf_get_iteration_means)
+    if (ctx->iter_prior.size() != (size_t)KMAX + 1) ctx->iter_prior.assign((size_t)KMAX + 1, 0.0);
+    for (int k = 1; k <= KMAX; ++k)
+        if (sc.k_done[k]) ctx->iter_prior[k] = (double)sc.k_iters[k] / (double)sc.k_done[k];
+    if (!stats) return CNMF_OK;
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, b.ev_begin, b.ev_end);
+    stats->gpu_ms = ms;
+    stats->outer_iterations = sc.it;
+    stats->restart_iterations = sc.restart_iters;
+    stats->column_iterations = sc.column_iters;
+    stats->restart_column_iterations = sc.restart_col_iters;
+    stats->kc = sc.KC0; stats->nsplit = b.ps.mode ? b.nsplit3_first : ctx->bat.nsplit;
+    stats->gemm_mode = b.ps.mode;
+    stats->tail_iterations = sc.tail_its; stats->tail_live_columns = sc.tail_live;
+    if (b.ev_tail) { float tms = 0.f; hipEventElapsedTime(&tms, b.ev_tail, b.ev_end); stats->tail_ms = tms; }
+    for (size_t i = 0; i + 3 < b.gev.size(); i += 4) {
+        float a = 0.f, c = 0.f;
+        hipEventElapsedTime(&a, b.gev[i], b.gev[i + 1]);
+        hipEventElapsedTime(&c, b.gev[i + 2], b.gev[i + 3]);
+        stats->passA_ms += a; stats->passB_ms += c;
+        stats->passA_launches++; stats->passB_launches++;
+    }
+    return CNMF_OK;
+}
+
 static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, const uint32_t* seeds,
                      const double* avg, const float* W0, const float* H0, const cnmf_cd_params* prm,
                      float* H_out, float* W_out, bool resident, int32_t* n_iter_out,
@@ -251,685 +831,53 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
         hoff[r + 1] = hoff[r] + (size_t)kk[r] * G;
         woff[r + 1] = woff[r] + (size_t)kk[r] * N;
     }
-    // (wide batches need the whole-tile matrix-pipe kernels and a matrix large enough to be worth them)
-    const bool wide_can = kn.gemm3 != 0 && gemm3_enabled(ctx, 512);
-    // round 6: a SMALL matrix (BASELINE config 2: 2 700 x 2 000) is launch-latency-bound -- an iteration costs its six
-    // launches whatever the width -- so a job of >= 512 columns also runs wide there (C2: 1 000 columns in one batch instead
-    // of four 256-column rounds, 17 -> 8 ms per job); CNMF_WIDE_SMALL=0: the round-5 rule (A/B)
-    const bool wide_small = total_k >= 512 && kn.wide_small;
-    const bool wide_auto = wide_can && ((int64_t)ctx->N_pad * ctx->G_pad >= (1ll << 24) || wide_small);
-    int KC = pick_kc(ctx, total_k, max_k, prm->kc_max, (prm->kc_max > 256 || kn.kc_set) ? wide_can : wide_auto);
-    // 65..128 columns of a count-structured matrix: the 256-column integer-plane kernels (half empty) are still
-    // faster than 128 columns on the f32 pipe
-    if (KC == 128 && prm->kc_max <= 0 && !kn.kc_set && kn.gemm3 >= 3 && gemm3_enabled(ctx, 256) &&
-        (int64_t)ctx->N_pad * ctx->G_pad >= (1ll << 24)) {
-        rc = ensure_counts(ctx);
-        if (rc) return rc;
-        if (ctx->counts.state == 1) KC = 256;
-    }
-    const int KC0 = KC;
-    rc = ensure_batch(ctx, KC, max_k, min_k);
-    if (rc) return rc;
-    rc = ensure_stage(ctx, (size_t)N * KMAX, (size_t)G * KMAX);
-    if (rc) return rc;
-    bool use3 = gemm3_enabled(ctx, KC);            // split-operand bf16 MFMA path (whole 256-column tiles only)
-    bool usec = false;                             // ... with X as one integer plane (count-structured data)
-    if (use3 && kn.gemm3 >= 3) {
-        rc = ensure_counts(ctx);
-        if (rc) return rc;
-        usec = ctx->counts.state == 1;
-    }
-    // any OTHER matrix in the default mode: X itself as two f16 planes with a per-row exponent, 4 MFMAs per product
-    // (gemm_mode 5; CNMF_GEMM3=1|2 keep the 3 x 3 bf16 planes of rounds 1-2, 6 MFMAs)
-    bool use2g = use3 && !usec && kn.gemm3 >= 4 && ctx->G_pad % G3C_JW == 0 && ctx->N_pad % G3C_JW == 0;
-    if (use2g) { rc = ensure_x2planes(ctx); if (rc) return rc; }
-    bool use2h = (usec && ctx->counts.fmt == 4) || use2g;      // ... on the f16 pipe: two f16 factor planes
-    const int gemm_mode_used = !use3 ? 0 : (use2g ? 5 : (usec ? (use2h ? 4 : 3) : std::min(kn.gemm3, 2)));
-    const int KbA = ctx->G_pad / 16, KbB = ctx->N_pad / 16;
-    // the X-side operands of the count and f16 kernels: the integer count plane(s), or the two planes of a general matrix
-    const XOperand xA = use2g ? ctx->x2.passA() : ctx->counts.passA(), xB = use2g ? ctx->x2.passB() : ctx->counts.passB();
-    const double* dsc = use2g ? nullptr : ctx->counts.d_scale;                               // per-gene scale of the count path
-    const int nsubA = use2h ? gemm2h_nsub(xA.hi != nullptr, KbA) : 1, nsubB = use2h ? gemm2h_nsub(xB.hi != nullptr, KbB) : 1;
-    // W planes written by the W sweep itself (kernels_sweep.hip.h, PLN) instead of a separate pass over W; ranks above
-    // 64 (sweep_big_kernel) keep the separate split for the whole call.
-    const bool fuseW = use2h && max_k <= KSMALL && ctx->shiftW != nullptr;
-    int shgen = 0;                                        // generation of the exponents the NEXT W sweep uses
-    int* const shW[2] = {ctx->shiftW, ctx->shiftW ? ctx->shiftW + ctx->kc_alloc : nullptr};
-    if (fuseW) HIP_TRY(ctx, hipMemsetAsync(ctx->shiftW, 0, (size_t)3 * ctx->kc_alloc * sizeof(int), ctx->stream));
-    if (use3 && !usec && !use2g) { rc = ensure_planes(ctx); if (rc) return rc; }
-    const int jwA = (usec || use2g) ? G3C_JW : G3_JW;         // width of a pass-A / pass-B tile
-    const int fin_y = (max_k * max_k + 255) / 256;       // finalize blocks per slot
-    const int lag = std::max(1, std::min(RING - 2, prm->lag > 0 ? prm->lag : (kn.lag > 0 ? kn.lag : 2)));
-    hipStream_t st = ctx->stream;
+    int KC = 0;
+    if ((rc = pick_batch_width(ctx, prm, total_k, max_k, &KC))) return rc;
+    if ((rc = ensure_batch(ctx, KC, max_k, min_k))) return rc;
+    if ((rc = ensure_stage(ctx, (size_t)N * KMAX, (size_t)G * KMAX))) return rc;
 
-    // device result buffers
-    DevPool pool;
-    EventPool events;
-    float* d_Hres = nullptr; float* d_Wres = nullptr;
-    if (resident) {
-        if (ctx->spectra_rows && ctx->spectra_G != G) {
-            SET_ERR(ctx, "the resident store holds spectra over %lld genes, this matrix has %d: cnmf_spectra_reset first",
-                    (long long)ctx->spectra_G, G);
-            return CNMF_ESTATE;
-        }
-        ctx->spectra_G = G;
-        const size_t need = (ctx->spectra_rows + (size_t)total_k) * G;
-        if (need > ctx->spectra_cap) {
-            float* nb = nullptr;
-            const size_t cap = std::max(need, ctx->spectra_cap * 2);
-            HIP_TRY(ctx, hipMalloc(&nb, cap * sizeof(float)));
-            hipError_t ce = hipSuccess;
-            if (ctx->spectra_rows)
-                ce = hipMemcpyAsync(nb, ctx->spectra, ctx->spectra_rows * G * sizeof(float), hipMemcpyDeviceToDevice, st);
-            if (ce == hipSuccess) ce = hipStreamSynchronize(st);
-            if (ce != hipSuccess) { hipFree(nb); HIP_TRY(ctx, ce); }
-            hipFree(ctx->spectra);
-            ctx->spectra = nb; ctx->spectra_cap = cap;
-        }
-        d_Hres = ctx->spectra + ctx->spectra_rows * G;
-    } else {
-        d_Hres = pool.get<float>(hoff[n]);
-    }
-    if (W_out) d_Wres = pool.get<float>(woff[n]);
-    int* d_repack = pool.get<int>((size_t)3 * KC0);            // re-packing: column map, moved slot ids, their new offsets
-    POOL_TRY(ctx, pool);
-    struct PinnedInts { int* p = nullptr; ~PinnedInts() { if (p) hipHostFree(p); } } repack_host;
-    HIP_TRY(ctx, hipHostMalloc(&repack_host.p, (size_t)RING * 3 * KC0 * sizeof(int)));
-    int* h_repack = repack_host.p;
+    BatchRun b(n, kk, KC, ctx->iter_hint.size() == (size_t)KMAX + 1 ? ctx->iter_hint.data() : nullptr, kn.debug);
+    b.ctx = ctx; b.prm = prm; b.st = ctx->stream;
+    b.init_mode = init_mode; b.avg = avg; b.W0 = W0; b.H0 = H0;
+    b.n_iter_out = n_iter_out; b.viol_out = viol_out; b.resident = resident;
+    b.N = N; b.G = G; b.max_k = max_k; b.total_k = total_k;
+    b.hoff.swap(hoff); b.woff.swap(woff);
+    if ((rc = pick_scheme(ctx, KC, &b.ps))) return rc;
+    b.fuseW = b.ps.use2h && max_k <= KSMALL && ctx->bat.shiftW != nullptr;
+    b.shW[0] = ctx->bat.shiftW; b.shW[1] = ctx->bat.shiftW ? ctx->bat.shiftW + ctx->bat.kc : nullptr;
+    if (b.fuseW) HIP_TRY(ctx, hipMemsetAsync(ctx->bat.shiftW, 0, (size_t)3 * ctx->bat.kc * sizeof(int), b.st));
+    b.fin_y = (max_k * max_k + 255) / 256;
+    b.lag = std::max(1, std::min(RING - 2, prm->lag > 0 ? prm->lag : (kn.lag > 0 ? kn.lag : 2)));
+    b.chunksW = sweep_chunks(ctx, N); b.partsW = sweep_parts(ctx, N);
+    b.chunksH = sweep_chunks(ctx, G); b.partsH = sweep_parts(ctx, G);
+    b.l1W = (float)prm->l1_reg_W; b.l2W = (float)prm->l2_reg_W;
+    b.l1H = (float)prm->l1_reg_H; b.l2H = (float)prm->l2_reg_H;
+    b.time_stride = (stats && prm->profile > 0) ? prm->profile : 0;
+    if ((rc = alloc_call_buffers(b, W_out != nullptr))) return rc;
+    if (init_mode == 1 && (rc = generate_inits(b, seeds))) return rc;
 
-    // init_mode 1: sklearn's init='random' for EVERY restart of the call, generated up front on the
-    // device (one workgroup per restart) into a component-major store; install = row copy.
-    float *d_H0 = nullptr, *d_Wt0 = nullptr;
-    RngJob* d_jobs = nullptr;
-    if (init_mode == 1) {
-        d_H0 = pool.get<float>(hoff[n]);
-        d_Wt0 = pool.get<float>(woff[n]);
-        d_jobs = pool.get<RngJob>((size_t)n);
-        POOL_TRY(ctx, pool);
-        std::vector<RngJob> jobs(n);
-        int rowoff = 0;
-        for (int r = 0; r < n; ++r) {
-            jobs[r] = RngJob{seeds[r], kk[r], rowoff, avg[r], (long long)kk[r] * ((long long)G + N)};
-            rowoff += kk[r];
-        }
-        HIP_TRY(ctx, hipMemcpy(d_jobs, jobs.data(), (size_t)n * sizeof(RngJob), hipMemcpyHostToDevice));
-        rng_kernel<1><<<n, 256, 0, st>>>(d_jobs, nullptr, d_H0, G, G, d_Wt0, N, N);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-
-    // Queue order.  Restarts are independent, so the order they run in is free; what it decides is the TAIL of the
-    // call: once the queue is dry the columns of finished restarts stay empty, and the call ends when the LONGEST
-    // restart still in flight converges (iterations per restart span 35 ... 1000 and depend mostly on the rank: ranks
-    // far from the data's own need the most).  Hence longest-expected-first:
-    //   * start: the ranks interleaved (round-robin over the distinct ranks, largest first inside a round), so every
-    //     rank is sampled within the first fill of the packed columns;
-    //   * as restarts retire, the mean iteration count per rank is learned and the pending queue is re-sorted by it,
-    //     descending (LPT) -- the short restarts are kept for the end, where they fill the columns the long ones free.
-    std::vector<int> order(n);
-    // round 4: the caller's iteration hints (cnmf_set_iteration_hints: mean iterations per rank, e.g. what an earlier call
-    // on this matrix learned -- cnmf_get_iteration_means) order the queue from the start: a second factorize with more
-    // restarts, a resumed ledger do not have to re-learn that k = 13 runs 1000 iterations and k = 9 runs 37.  Explicit only:
-    // the order decides the packed columns a restart occupies and with them the last bits of its float32 result
-    // (tests/test_gpu_determinism.py); without hints a call's result depends on its own arguments alone.
-    const bool have_prior = ctx->iter_hint.size() == (size_t)KMAX + 1;
-    auto prior_of = [&](int k) { return have_prior ? ctx->iter_hint[k] : 0.0; };
-    {
-        std::vector<std::vector<int>> by_k(KMAX + 1);
-        for (int r = 0; r < n; ++r) by_k[kk[r]].push_back(r);
-        size_t pos = 0;
-        for (size_t j = 0; pos < (size_t)n; ++j)
-            for (int k = KMAX; k >= 1; --k)
-                if (j < by_k[k].size()) order[pos++] = by_k[k][j];
-        if (have_prior)            // ranks never seen count as longest (sampled first), the others by their learned mean
-            std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-                const double ea = prior_of(kk[a]) > 0 ? prior_of(kk[a]) : 1e30, eb = prior_of(kk[b]) > 0 ? prior_of(kk[b]) : 1e30;
-                return ea > eb;
-            });
-    }
-    std::vector<int64_t> k_iters(KMAX + 1, 0), k_done(KMAX + 1, 0);     // learned per rank: sum of n_iter, restarts retired
-    int last_resort_done = 0;
-    size_t next = 0;                 // first queue position that may still be pending
-    int n_pending = n;
-
-    ColAlloc cols(KC);
-    std::vector<HostSlot> hs(KC0);
-    int nslots = 0;          // highest used slot index + 1
-    int n_active = 0;
-    int64_t it = 0;          // batch iterations enqueued so far
-    int snap_nslots[RING] = {0};
-    auto live_columns = [&]() { int c = 0; for (int s = 0; s < nslots; ++s) if (hs[s].state) c += hs[s].k; return c; };
-    // bit t: the 32 packed columns 32 t .. 32 t + 31 hold a live restart; *fullest: most live tiles in one 256-column group
-    auto live_tiles = [&](int* fullest) {
-        unsigned long long m = 0ull;
-        for (int s = 0; s < nslots; ++s)
-            if (hs[s].state)
-                for (int t = hs[s].off / 32; t <= (hs[s].off + hs[s].k - 1) / 32 && t < 64; ++t) m |= 1ull << t;
-        *fullest = 0;
-        for (int g = 0; g < KC / 256; ++g) *fullest = std::max(*fullest, __builtin_popcountll((m >> (8 * g)) & 0xffull));
-        return m;
-    };
-    // partial-tile passes in the tail (the f16 kernels skip the MFMAs of 32-column tiles without a live restart, the live
-    // restarts dealt evenly to the component groups): built and measured in round 3 -- 183.0 vs 182.2 restarts/s on the
-    // 113-restart shard, 216.5 vs 215.7 on the full job: within noise (the skipping variant is ~4 % slower with all tiles
-    // live, and a tail pass is bound by streaming the count plane as much as by its MFMAs).  Opt-in: CNMF_PART=1 (kn.part).
-    int64_t last_tail_repack = -1000;
-    int64_t last_defrag = -8, n_defrag = 0;
-    bool h3_valid = false;           // H3 holds the planes of the current H (split-operand modes)
     // stamps restart at 1 in every call: forget the ones a previous call left in the ring (nothing is in flight here)
-    memset(ctx->h_snap, 0, (size_t)ctx->kc_alloc * RING * sizeof(SlotDesc));
-    hipEvent_t ev_begin = events.get(), ev_end = events.get();
-    POOL_TRY(ctx, events);
-    HIP_TRY(ctx, hipEventRecord(ev_begin, st));
-    // HIP events around the two GEMM passes of every `time_stride`-th iteration (an event record costs
-    // ~6 us of queue time: bracketing every launch would take 4 % off the throughput it measures)
-    const int time_stride = (stats && prm->profile > 0) ? prm->profile : 0;
-    std::vector<hipEvent_t> gev;   // (a0,a1,b0,b1) per iteration when timing is requested
-
-    const int chunksW = sweep_chunks(ctx, N), partsW = sweep_parts(ctx, N);
-    const int chunksH = sweep_chunks(ctx, G), partsH = sweep_parts(ctx, G);
-    const float l1W = (float)prm->l1_reg_W, l2W = (float)prm->l2_reg_W;
-    const float l1H = (float)prm->l1_reg_H, l2H = (float)prm->l2_reg_H;
-    int64_t restart_iters = 0, column_iters = 0, restart_col_iters = 0;
-    const bool dbg = kn.debug;
-    int64_t dbg_it[65] = {0}, dbg_live[65] = {0};          // by KC / 32 (up to 2048 packed columns)
-    // The plan of the two GEMM passes at the current width KC, on the pipe `use3` names: K splits of pass B (nsplit3 on
-    // the split-operand kernels, nsplit on the f32 pipe), and pass A either as a stream-K plan (sk3 / sk, its cut flags
-    // uploaded to d_split) or, on few tiles, as nsplitA K splits + reduce.  cap / capA: the partial planes the product
-    // buffers hold at this width.  Made before the loop, and again whenever compact() narrows the batch.
-    int nsplit = 1, nsplit3 = 1, nsplitA = 1;
-    StreamK sk;
-    StreamK3 sk3;
-    auto plan_passes = [&](int cap, int capA) -> int {
-        const std::vector<unsigned char>* flags = nullptr;
-        if (use3) {
-            nsplit3 = std::max(1, std::min(pick_nsplit3(ctx, KC, jwA), cap));
-            sk3 = plan_streamk3(KC, ctx->N_pad, ctx->G_pad, gemm3_wg_slots(ctx->knobs), jwA, nsubA);
-            if (sk3.on) flags = &sk3.flags;
-            else nsplitA = std::max(1, std::min(pick_nsplit_A3(ctx, KC, jwA), capA));
-        } else {
-            nsplit = std::max(1, std::min(pick_nsplit(ctx, KC), cap));
-            sk = plan_streamk(KC, ctx->N_pad, ctx->G_pad, 2 * 256);       // T-layout pass A: 2 workgroups per CU (73.7 KB LDS each)
-            if (sk.on) { flags = &sk.split; nsplitA = 1; }
-            else nsplitA = std::max(1, std::min(pick_nsplit_A(ctx, KC), capA));
-        }
-        // (the flags of the old plan may still be read by an in-flight sweep: same stream -> ordered)
-        if (flags) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_split, flags->data(), flags->size(), hipMemcpyHostToDevice, st));
-        return CNMF_OK;
-    };
-    if ((rc = plan_passes(ctx->nsplit_alloc, ctx->nsplitA_alloc))) return rc;
-    const int nsplit3_first = nsplit3;             // (reported: the tail narrows the batch and re-plans)
-    int n_done = 0;
-    hipEvent_t ev_tail = nullptr;    // recorded when the queue runs dry
-    int64_t tail_its = 0, tail_live = 0;
-
-    auto retire = [&](int s, const SlotDesc& snap) -> int {
-        HostSlot& h = hs[s];
-        const int r = h.restart, k = h.k;
-        dim3 gH((G + 255) / 256, k), gW((N + 255) / 256, k);
-        extract_kernel<<<gH, 256, 0, st>>>(ctx->H, ctx->G_pad, G, h.off, k, d_Hres + hoff[r], 0);
-        if (d_Wres) extract_kernel<<<gW, 256, 0, st>>>(ctx->Wt, ctx->N_pad, N, h.off, k, d_Wres + woff[r], 1);
-        clear_rows_kernel<<<gH, 256, 0, st>>>(ctx->H, ctx->G_pad, ctx->G_pad, h.off, k);
-        clear_rows_kernel<<<gW, 256, 0, st>>>(ctx->Wt, ctx->N_pad, ctx->N_pad, h.off, k);
-        HIP_TRY(ctx, hipGetLastError());
-        if (n_iter_out) n_iter_out[r] = snap.iter;
-        if (viol_out) viol_out[r] = snap.viol_last;
-        restart_iters += snap.iter;
-        restart_col_iters += (int64_t)snap.iter * k;
-        k_iters[k] += snap.iter; k_done[k] += 1;
-        if (n_pending > 0) cols.release(h.off, k);       // (after the queue ran dry nothing is allocated any more)
-        h.state = 0; h.restart = -1;
-        --n_active; ++n_done;
-        return CNMF_OK;
-    };
-
-    // Move the live slots to the left end of the packed columns (ascending offset order, through the stage
-    // buffers) and zero everything from the first free column up to `width`.  Used by the tail compaction
-    // (narrower batch) and by the refill's defragmentation (same width).
-    // (one launch sequence per re-packing, whatever the number of slots: at 1024 packed columns the per-slot moves of
-    //  round 2 -- four launches each, host-bound at ~5 us per launch -- had grown to 10 % of the wall time)
-    int n_repack = 0;
-    // balanced (the tail of a wide batch only: nothing will be installed any more): the live restarts are dealt to the
-    // 256-column component groups so that every group holds about the same number of live 32-column tiles -- the GEMM
-    // workgroups of ALL groups then skip the same share of their MFMAs (a pass lasts as long as its slowest workgroup)
-    auto repack_left = [&](int width, bool balanced = false) -> int {
-        std::vector<int> idx;
-        for (int s = 0; s < nslots; ++s) if (hs[s].state) idx.push_back(s);
-        std::sort(idx.begin(), idx.end(), [&](int a, int b) { return hs[a].off < hs[b].off; });
-        int* hm = h_repack + (size_t)(n_repack++ % RING) * 3 * KC0;      // [colmap | slot ids | new offsets], pinned
-        int* d_colmap = d_repack, *d_ids = d_repack + KC0, *d_offs = d_repack + 2 * KC0;
-        int pos = 0, nmove = 0;
-        const int ngroups = width / 256;
-        if (balanced && ngroups > 1) {
-            for (int c = 0; c < width; ++c) hm[c] = -1;
-            std::vector<int> fill(ngroups, 0), byk(idx);
-            std::stable_sort(byk.begin(), byk.end(), [&](int a, int b) { return hs[a].k > hs[b].k; });
-            bool ok = true;
-            std::vector<int> newoff(nslots, -1);
-            for (int s : byk) {
-                int g = -1;
-                for (int q = 0; q < ngroups; ++q) if (fill[q] + hs[s].k <= 256 && (g < 0 || fill[q] < fill[g])) g = q;
-                if (g < 0) { ok = false; break; }
-                newoff[s] = g * 256 + fill[g]; fill[g] += hs[s].k;
-            }
-            if (ok) {
-                for (int s : idx) {
-                    HostSlot& h = hs[s];
-                    for (int c = 0; c < h.k; ++c) hm[newoff[s] + c] = h.off + c;
-                    if (h.off != newoff[s]) { hm[KC0 + nmove] = s; hm[2 * KC0 + nmove] = newoff[s]; ++nmove; h.off = newoff[s]; }
-                }
-                pos = 0;                                                  // (there are zero rows inside [0, width) now)
-            } else balanced = false;
-        } else balanced = false;
-        if (!balanced) {
-        for (int s : idx) {
-            HostSlot& h = hs[s];
-            for (int c = 0; c < h.k; ++c) hm[pos + c] = h.off + c;
-            if (h.off != pos) { hm[KC0 + nmove] = s; hm[2 * KC0 + nmove] = pos; ++nmove; h.off = pos; }
-            pos += h.k;
-        }
-        for (int c = pos; c < width; ++c) hm[c] = -1;                    // zero rows behind the live ones
-        }
-        if (nmove || pos < width) {
-            HIP_TRY(ctx, hipMemcpyAsync(d_colmap, hm, (size_t)width * sizeof(int), hipMemcpyHostToDevice, st));
-            // staging = the product buffers (scratch between two iterations): XHt [>= KC0][N_pad], XtW [>= KC0][G_pad]
-            gather_rows_cm_kernel<<<dim3((ctx->N_pad / 4 + 255) / 256, width), 256, 0, st>>>(ctx->Wt, ctx->N_pad, d_colmap, ctx->XHt);
-            gather_rows_cm_kernel<<<dim3((ctx->G_pad / 4 + 255) / 256, width), 256, 0, st>>>(ctx->H, ctx->G_pad, d_colmap, ctx->XtW);
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->Wt, ctx->XHt, (size_t)width * ctx->N_pad * sizeof(float), hipMemcpyDeviceToDevice, st));
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->H, ctx->XtW, (size_t)width * ctx->G_pad * sizeof(float), hipMemcpyDeviceToDevice, st));
-            if (fuseW) {
-                int* tmp = ctx->shiftW + 2 * ctx->kc_alloc;
-                for (int g2 = 0; g2 < 2; ++g2) {
-                    permute_ints_kernel<<<(width + 255) / 256, 256, 0, st>>>(shW[g2], d_colmap, tmp, width);
-                    HIP_TRY(ctx, hipMemcpyAsync(shW[g2], tmp, (size_t)width * sizeof(int), hipMemcpyDeviceToDevice, st));
-                }
-                HIP_TRY(ctx, hipGetLastError());
-            }
-            if (nmove) {
-                HIP_TRY(ctx, hipMemcpyAsync(d_ids, hm + KC0, (size_t)nmove * sizeof(int), hipMemcpyHostToDevice, st));
-                HIP_TRY(ctx, hipMemcpyAsync(d_offs, hm + 2 * KC0, (size_t)nmove * sizeof(int), hipMemcpyHostToDevice, st));
-                set_slot_offs_kernel<<<(nmove + 255) / 256, 256, 0, st>>>(ctx->d_slots, d_ids, d_offs, nmove);
-                HIP_TRY(ctx, hipGetLastError());
-            }
-        }
-        h3_valid = false;                 // rows of H moved: its planes are stale
-        // moved rows of slots that no longer iterate are not swept again: refresh their row maxima here
-        if (use2h) HIP_TRY(ctx, launch_rowmax_part(st, ctx->Wt, ctx->N_pad, N, KC, chunksW * 256, nullptr, partsW, ctx->rmaxW));
-        return CNMF_OK;
-    };
-
-    // ---- step 1: refill free columns from the pending list (n_new = slots installed)
-    auto refill = [&](int& n_new) -> int {
-        n_new = 0;
-        int* new_list = ctx->h_slot_list + (size_t)(it % RING) * KC0;
-        // pending restarts are sorted by descending rank; a hole too small for the head of the
-        // queue is filled with the largest pending rank that fits (restarts are independent, so
-        // the order they run in is free) -> the packed columns stay full in the main phase
-        // (letting a hole wait for the head of the queue instead was measured and not adopted: DESIGN.md section 8)
-        for (int attempt = 0; attempt < 2; ++attempt) {
-        int failed_k = 1 << 30;                       // smallest rank that did not fit in this pass
-        for (size_t pi = next; pi < order.size() && n_pending > 0; ++pi) {
-            const int r = order[pi];
-            if (r < 0) { if (pi == next) ++next; continue; }      // already taken
-            const int k = kk[r];
-            if (k >= failed_k) continue;
-            const int off = cols.alloc(k);
-            if (off < 0) { failed_k = k; continue; }
-            order[pi] = -1; --n_pending;
-            if (pi == next) ++next;
-            int s = 0;
-            while (s < KC0 && hs[s].state != 0) ++s;
-            hs[s].state = 1; hs[s].restart = r; hs[s].off = off; hs[s].k = k; hs[s].installed_at = it;
-            nslots = std::max(nslots, s + 1);
-            dim3 gI((std::max(N, G) + 255) / 256, k);
-            if (init_mode == 0) {
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->stageH, H0 + hoff[r], (size_t)k * G * sizeof(float), hipMemcpyHostToDevice, st));
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->stageW, W0 + woff[r], (size_t)k * N * sizeof(float), hipMemcpyHostToDevice, st));
-                install_kernel<<<gI, 256, 0, st>>>(ctx->stageH, ctx->stageW, ctx->H, ctx->G_pad, G, ctx->Wt, ctx->N_pad, N, off, k);
-            } else {
-                install_cm_kernel<<<gI, 256, 0, st>>>(d_H0 + hoff[r], d_Wt0 + woff[r], ctx->H, ctx->G_pad, G, ctx->Wt, ctx->N_pad, N, off);
-            }
-            HIP_TRY(ctx, hipGetLastError());
-            if (fuseW) {
-                // exponent of the planes the FIRST W sweep of this restart writes: from the size of its W0 (random init:
-                // avg |N(0,1)|, the maximum of 50 000 draws is ~4.5 avg), two bits of headroom; the check behind the sweep
-                // re-converts the rows whose first update left the window
-                float mx = 0.f;
-                if (init_mode == 1) mx = 6.0f * (float)avg[r];
-                else for (size_t q = 0; q < (size_t)k * N; ++q) mx = std::max(mx, W0[woff[r] + q]);
-                int e2 = 0;
-                if (mx > 0.f) std::frexp(mx, &e2);
-                const int sh0 = mx > 0.f ? std::max(-110, std::min(120, 13 - e2)) : 0;
-                set_ints_kernel<<<1, 128, 0, st>>>(shW[0], shW[1], off, k, sh0);
-                HIP_TRY(ctx, hipGetLastError());
-            }
-            SlotDesc* d = &ctx->h_slots[s];
-            memset(d, 0, sizeof *d);
-            d->off = off; d->k = k; d->active = 1; d->iter = 0; d->restart = r;
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_slots + s, d, sizeof(SlotDesc), hipMemcpyHostToDevice, st));
-            new_list[n_new++] = s;
-            ++n_active;
-        }
-        // Defragmentation: a pending restart did not fit although enough columns are free in total (holes
-        // left by retired slots of other ranks).  Repacking costs about one iteration and buys a restart
-        // that runs for hundreds -- at most once every 8 iterations.
-        if (attempt == 0 && n_pending > 0 && failed_k < (1 << 30) && it - last_defrag >= 8) {
-            if (KC - live_columns() >= failed_k) {
-                int rcd = repack_left(KC);
-                if (rcd) return rcd;
-                cols = ColAlloc(KC);
-                for (int s2 = 0; s2 < nslots; ++s2) if (hs[s2].state) cols.alloc(hs[s2].k);
-                last_defrag = it; ++n_defrag;
-                continue;                               // place again into the contiguous free tail
-            }
-        }
-        break;
-        }
-        if (n_new) {
-            int* dl = ctx->d_slot_list + (size_t)(it % RING) * KC0;
-            HIP_TRY(ctx, hipMemcpyAsync(dl, new_list, n_new * sizeof(int), hipMemcpyHostToDevice, st));
-            gram_rows_kernel<<<n_new, 256, 0, st>>>(ctx->H, ctx->G_pad, G, ctx->d_slots, dl, ctx->gramH, l2W);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-        return CNMF_OK;
-    };
-
-    // ---- step 2: enqueue one coordinate-descent outer iteration for every slot in flight
-    auto iterate = [&](int n_new) -> int {
-        int tiers = 0;
-        for (int s2 = 0; s2 < nslots; ++s2)
-            if (hs[s2].state) tiers |= hs[s2].k <= 16 ? 1 : (hs[s2].k <= 32 ? 2 : (hs[s2].k <= KSMALL ? 4 : 8));
-        // the tail (nothing left to refill with): the f16 kernels skip the 32-column tiles without a live restart
-        unsigned long long livemask = ~0ull;
-        if (use2h && n_pending == 0 && kn.part) {
-            // the skipping variant of the kernels is ~4 % slower with everything live, and a pass lasts as long as its
-            // fullest component group: use it only when EVERY group has at least two dead tiles
-            int fullest = 0;
-            livemask = live_tiles(&fullest);
-            if (fullest > 6) livemask = ~0ull;
-        }
-        const bool time_gemm = time_stride > 0 && it % time_stride == 0;
-        if (time_gemm) {
-            for (int i = 0; i < 4; ++i) gev.push_back(events.get());
-            POOL_TRY(ctx, events);
-            hipEventRecord(gev[gev.size() - 4], st);
-        }
-        // pass A : XHt[KC][N] = H_all . X^T                       (sklearn _nmf.py:387)
-        SplitInfo spA{nullptr, nullptr, 1, 1, 1};
-        if (use3) {
-            // H3 was produced together with the previous iteration's H finalize; rows installed since then
-            // (and the very first iteration) need a split of their own.  Count path: H' = H * d.
-            if ((n_new > 0 || !h3_valid) && use2h) {
-                HIP_TRY(ctx, launch_rowmax_part(st, ctx->H, ctx->G_pad, G, KC, chunksH * 256, dsc, partsH, ctx->rmaxH));
-                HIP_TRY(ctx, launch_split2h(st, ctx->H, ctx->G_pad, KC, ctx->G_pad, ctx->H3, G3_MW, dsc, ctx->rmaxH,
-                                            partsH, ctx->iscaleH));
-            } else if (n_new > 0 || !h3_valid)
-                HIP_TRY(ctx, launch_split3(st, ctx->H, ctx->G_pad, KC, ctx->G_pad, ctx->H3, G3_MW, usec ? ctx->counts.d_scale : nullptr));
-            if (time_gemm) hipEventRecord(gev[gev.size() - 4], st);
-            if (sk3.on) {
-                if (use2h) {
-                    HIP_TRY(ctx, launch_gemm2h_streamk(st, sk3, ctx->H3, xA.plane, xA.hi, xA.flags, ctx->iscaleH, KbA,
-                                                       ctx->XHt, ctx->XHt1, ctx->XHt2, ctx->N_pad, xA.colscale, livemask));
-                }
-                else if (usec)
-                    HIP_TRY(ctx, launch_gemm3c_streamk(st, sk3, ctx->H3, xA.plane, xA.hi, xA.flags, ctx->XHt, ctx->XHt1,
-                                                       ctx->XHt2, ctx->N_pad));
-                else
-                    HIP_TRY(ctx, launch_gemm3_streamk(st, sk3, ctx->H3, ctx->planes.X3, ctx->XHt, ctx->XHt1, ctx->XHt2, ctx->N_pad));
-                spA = SplitInfo{ctx->XHt1, ctx->d_split, jwA, G3_MW, sk3.MG, ctx->XHt2};
-            } else if (use2h) {
-                HIP_TRY(ctx, launch_gemm2h(st, ctx->H3, xA.plane, xA.hi, xA.flags, ctx->iscaleH, KbA, ctx->XHt, ctx->N_pad,
-                                           (long long)KC * ctx->N_pad, KC, ctx->N_pad, nsplitA, xA.colscale, livemask));
-            } else if (usec) {
-                HIP_TRY(ctx, launch_gemm3c(st, ctx->H3, xA.plane, xA.hi, xA.flags, ctx->G_pad / 16, ctx->XHt, ctx->N_pad,
-                                           (long long)KC * ctx->N_pad, KC, ctx->N_pad, nsplitA));
-            } else {
-                HIP_TRY(ctx, launch_gemm3(st, ctx->H3, ctx->planes.X3, ctx->G_pad / 16, ctx->XHt, ctx->N_pad,
-                                          (long long)KC * ctx->N_pad, KC, ctx->N_pad, nsplitA));
-            }
-        } else if (sk.on) {
-            HIP_TRY(ctx, launch_streamk_passA(st, sk, ctx->H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->XHt,
-                                              ctx->XHt1, ctx->N_pad, ctx->N_pad));
-            spA = SplitInfo{ctx->XHt1, ctx->d_split, 128, sk.mw, sk.MG};
-        } else
-            HIP_TRY(ctx, launch_gemm<false>(st, 0, ctx->H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->XHt,
-                                            ctx->N_pad, (long long)KC * ctx->N_pad, KC, ctx->G_pad, ctx->N_pad, nsplitA));
-        if (time_gemm) hipEventRecord(gev[gev.size() - 3], st);
-        if (!spA.plane1)
-            HIP_TRY(ctx, launch_reduce_splits(st, ctx->XHt, use2h ? gemm2h_splits(KbA, nsplitA, nsubA) : nsplitA,
-                                              (long long)KC * ctx->N_pad, (long long)KC * ctx->N_pad));
-        // W half-step                                             (sklearn _nmf.py:500)
-        const bool fuse_now = fuseW && use2h;
-        HIP_TRY(ctx, launch_sweep(st, nslots, ctx->Wt, ctx->N_pad, N, ctx->XHt, ctx->gramH,
-                                  ctx->d_slots, l1W, ctx->gram_part, ctx->viol_part, chunksW, partsW, 1, max_k, tiers, spA,
-                                  use2h ? ctx->rmaxW : nullptr, nullptr, false,
-                                  fuse_now ? PlaneOut{(unsigned short*)ctx->Wt3, shW[shgen], KbB, G3_MW} : PlaneOut{nullptr, nullptr, 0, 0}));
-        if (use2h) {
-            const FinalizeArgs fa{ctx->gram_part, ctx->viol_part, partsW, ctx->gramW, l2H, ctx->d_slots, 0, prm->tol,
-                                  prm->max_iter, 1, max_k, nullptr, 0};
-            // (fused: the sweep wrote the planes; this launch checks their exponents, publishes 2^-s and the next exponents)
-            HIP_TRY(ctx, launch_split2h_finalize(st, ctx->Wt, ctx->N_pad, KC, ctx->N_pad, ctx->Wt3, G3_MW, nullptr, ctx->rmaxW,
-                                                 partsW, ctx->iscaleW, fa, nslots, fin_y,
-                                                 fuse_now ? SplitFused{shW[shgen], shW[shgen ^ 1]} : SplitFused{nullptr, nullptr}));
-            if (fuse_now) shgen ^= 1;
-        } else if (use3) {
-            // finalize of the W sweep + the plane split of its result in one launch (writing the planes from
-            // inside the sweep was measured slower: 2-byte stores, lower occupancy)
-            const FinalizeArgs fa{ctx->gram_part, ctx->viol_part, partsW, ctx->gramW, l2H, ctx->d_slots, 0, prm->tol,
-                                  prm->max_iter, 1, max_k, nullptr, 0};
-            HIP_TRY(ctx, launch_split3_finalize(st, ctx->Wt, ctx->N_pad, KC, ctx->N_pad, ctx->Wt3, G3_MW, nullptr, fa,
-                                                nslots, fin_y));
-        } else {
-            finalize_kernel<<<dim3(nslots, fin_y), 256, 0, st>>>(ctx->gram_part, ctx->viol_part, partsW, ctx->gramW, l2H,
-                                                    ctx->d_slots, 0, prm->tol, prm->max_iter, 1, max_k);
-        }
-        if (time_gemm) hipEventRecord(gev[gev.size() - 2], st);
-        // pass B : XtW[S][KC][G] = Wt_all . X  (split over cells)  (sklearn _nmf.py:505-507)
-        const int nsB = use2h ? gemm2h_splits(KbB, nsplit3, nsubB) : (use3 ? nsplit3 : nsplit);
-        if (use2h)
-            HIP_TRY(ctx, launch_gemm2h(st, ctx->Wt3, xB.plane, xB.hi, xB.flags, ctx->iscaleW, KbB, ctx->XtW, ctx->G_pad,
-                                       (long long)KC * ctx->G_pad, KC, ctx->G_pad, nsplit3, xB.colscale, livemask));
-        else if (usec)
-            HIP_TRY(ctx, launch_gemm3c(st, ctx->Wt3, xB.plane, xB.hi, xB.flags, ctx->N_pad / 16, ctx->XtW, ctx->G_pad,
-                                       (long long)KC * ctx->G_pad, KC, ctx->G_pad, nsplit3));
-        else if (use3)
-            HIP_TRY(ctx, launch_gemm3(st, ctx->Wt3, ctx->planes.Xt3, ctx->N_pad / 16, ctx->XtW, ctx->G_pad,
-                                      (long long)KC * ctx->G_pad, KC, ctx->G_pad, nsplit3));
-        else
-            HIP_TRY(ctx, launch_gemm<true>(st, 0, ctx->Wt, ctx->N_pad, ctx->X, ctx->G_pad, ctx->XtW,
-                                           ctx->G_pad, (long long)KC * ctx->G_pad, KC, ctx->N_pad,
-                                           ctx->G_pad, nsplit));
-        if (time_gemm) hipEventRecord(gev[gev.size() - 1], st);
-        // H half-step.  On the f16 path the split-K partials are summed (and scaled by d) inside the sweep itself.
-        if (use2h && !kn.no_psum && !(tiers & 8)) {      // (ranks above 64 take the separately reduced product)
-            HIP_TRY(ctx, launch_sweep(st, nslots, ctx->H, ctx->G_pad, G, ctx->XtW, ctx->gramW,
-                                      ctx->d_slots, l1H, ctx->gram_part, ctx->viol_part, chunksH, partsH, 1, max_k, tiers,
-                                      psum_info(nsB, (long long)KC * ctx->G_pad, dsc), ctx->rmaxH, dsc, true));
-        } else {
-            HIP_TRY(ctx, launch_reduce_splits(st, ctx->XtW, nsB, (long long)KC * ctx->G_pad,
-                                              (long long)KC * ctx->G_pad, usec ? dsc : nullptr, ctx->G_pad));
-            HIP_TRY(ctx, launch_sweep(st, nslots, ctx->H, ctx->G_pad, G, ctx->XtW, ctx->gramW,
-                                      ctx->d_slots, l1H, ctx->gram_part, ctx->viol_part, chunksH, partsH, 1, max_k, tiers,
-                                      SplitInfo{nullptr, nullptr, 1, 1, 1}, use2h ? ctx->rmaxH : nullptr,
-                                      use2h ? dsc : nullptr));
-        }
-        // the H finalize also publishes every slot's state into the host-mapped ring entry of this
-        // iteration (stamp it + 1): no copy kernel and no event per iteration
-        SlotDesc* snap = ctx->h_snap + (size_t)(it % RING) * KC0;
-        SlotDesc* snap_dev = nullptr;
-        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&snap_dev, snap, 0));
-        if (use2h) {
-            const FinalizeArgs fa{ctx->gram_part, ctx->viol_part, partsH, ctx->gramH, l2W, ctx->d_slots, 1, prm->tol,
-                                  prm->max_iter, 1, max_k, snap_dev, (int)(it + 1)};
-            HIP_TRY(ctx, launch_split2h_finalize(st, ctx->H, ctx->G_pad, KC, ctx->G_pad, ctx->H3, G3_MW, dsc,
-                                                 ctx->rmaxH, partsH, ctx->iscaleH, fa, nslots, fin_y));
-            h3_valid = true;
-        } else if (use3) {
-            const FinalizeArgs fa{ctx->gram_part, ctx->viol_part, partsH, ctx->gramH, l2W, ctx->d_slots, 1, prm->tol,
-                                  prm->max_iter, 1, max_k, snap_dev, (int)(it + 1)};
-            HIP_TRY(ctx, launch_split3_finalize(st, ctx->H, ctx->G_pad, KC, ctx->G_pad, ctx->H3, G3_MW,
-                                                usec ? ctx->counts.d_scale : nullptr, fa, nslots, fin_y));
-            h3_valid = true;
-        } else {
-            finalize_kernel<<<dim3(nslots, fin_y), 256, 0, st>>>(ctx->gram_part, ctx->viol_part, partsH, ctx->gramH, l2W,
-                                                    ctx->d_slots, 1, prm->tol, prm->max_iter, 1, max_k,
-                                                    snap_dev, (int)(it + 1));
-        }
-        HIP_TRY(ctx, hipGetLastError());
-        snap_nslots[it % RING] = nslots;
-        column_iters += KC;
-        if (n_pending == 0) { ++tail_its; tail_live += live_columns(); }
-        if (dbg) { dbg_it[KC / 32] += 1; dbg_live[KC / 32] += live_columns(); }
-        ++it;
-        return CNMF_OK;
-    };
-
-    // ---- step 3: look at the snapshot `lag` iterations behind the GPU and retire what has converged
-    auto inspect = [&]() -> int {
-        const int64_t si = it - 1 - lag;   // snapshot index to inspect now
-        if (si < 0) return CNMF_OK;
-        const SlotDesc* sp = ctx->h_snap + (size_t)(si % RING) * KC0;
-        int rc2 = wait_snapshot(ctx, sp, snap_nslots[si % RING], (int)(si + 1));
-        if (rc2) return rc2;
-        for (int s = 0; s < snap_nslots[si % RING]; ++s)
-            if (hs[s].state == 1 && hs[s].installed_at <= si && sp[s].active == 0 && sp[s].restart == hs[s].restart) {
-                rc2 = retire(s, sp[s]);
-                if (rc2) return rc2;
-            }
-        // longest-expected-first: re-sort what is still pending by the mean iteration count learned per rank (ranks
-        // without a finished restart yet count as longest: they are sampled first), every 8 retirements
-        if (n_pending > 1 && n_done - last_resort_done >= 8) {
-            last_resort_done = n_done;
-            std::vector<int> rest;
-            rest.reserve(n_pending);
-            for (size_t pi = next; pi < order.size(); ++pi) if (order[pi] >= 0) rest.push_back(order[pi]);
-            // expected iterations of a rank: mean over the restarts that have STARTED -- the finished ones with their count,
-            // the ones in flight with their age (a lower bound).  Counting only the finished ones is biased low while it
-            // matters most: of a rank whose restarts take 300 or 1000 iterations the 300s retire first.  An earlier call's
-            // mean (prior) enters as four pseudo-observations.
-            std::vector<double> fly_age(KMAX + 1, 0.0); std::vector<int> fly_n(KMAX + 1, 0);
-            for (int s2 = 0; s2 < nslots; ++s2)
-                if (hs[s2].state) { fly_age[hs[s2].k] += (double)(it - hs[s2].installed_at); fly_n[hs[s2].k] += 1; }
-            auto expect = [&](int r) {
-                const int k = kk[r];
-                double num = (double)k_iters[k] + fly_age[k], den = (double)k_done[k] + fly_n[k];
-                if (prior_of(k) > 0) { num += 4.0 * prior_of(k); den += 4.0; }
-                return den > 0 ? num / den : 1e30;
-            };
-            if (dbg && n_done % 64 < 8) {
-                fprintf(stderr, "[cnmf] it %lld done %d pending %d expected per rank:", (long long)it, n_done, n_pending);
-                for (int k = 1; k <= KMAX; ++k)
-                    if (k_done[k] + fly_n[k] > 0)
-                        fprintf(stderr, " k%d=%.0f(%lld done, %d fly)", k, ((double)k_iters[k] + fly_age[k]) / ((double)k_done[k] + fly_n[k]),
-                                (long long)k_done[k], fly_n[k]);
-                fprintf(stderr, "\n");
-            }
-            std::stable_sort(rest.begin(), rest.end(), [&](int a, int b) {
-                const double ea = expect(a), eb = expect(b);
-                return ea != eb ? ea > eb : kk[a] > kk[b];
-            });
-            order.resize(next);
-            order.insert(order.end(), rest.begin(), rest.end());
-        }
-        return CNMF_OK;
-    };
-
-    // ---- step 4: tail compaction -- nothing left to refill with and at most half of the packed
-    // columns still iterate: repack the live slots into a narrower batch so the two GEMM passes
-    // shrink with the work (their cost is proportional to KC).
-    auto compact = [&]() -> int {
-        if (n_pending == 0 && n_active > 0 && KC > 32) {
-            const int live_cols = live_columns();
-            int KCn = 32;
-            while (KCn < live_cols && KCn < 256) KCn *= 2;
-            if (live_cols > 256) KCn = round_up(live_cols, 256);
-            // On the count path a 256-column iteration (~250 us of GEMM at 50k x 2000) costs no more than a
-            // 64-column one on the f32 pipe and far less than a 128-column one: leave it only for 32 columns.
-            // General (non-count) split-operand path, 6 MFMAs per product: a 256-column iteration still beats 128
-            // columns on the f32 pipe (417 / 2 vs 157 TF of roof per live column), not 64.
-            // A WIDE batch (512+) narrows in steps of 256 columns and stays on the same kernels.
-            bool stay3 = false;
-            if (use3 && KCn > (usec ? 32 : 64)) { KCn = round_up(std::max(live_cols, 1), 256); stay3 = true; }
-            if (KCn == KC && use2h && kn.part && it - last_tail_repack >= 16) {
-                // same width, but the live restarts lie scattered: pack them to the left so that whole 32-column
-                // tiles fall dead (the GEMM passes skip those) -- when that frees at least 2 tiles and an eighth of them
-                const int ng = KC / 256;
-                int fullest = 0;
-                live_tiles(&fullest);
-                const int ideal = ((live_cols + 31) / 32 + ng - 1) / ng;       // tiles per group if dealt evenly
-                if (ideal <= 6 && fullest >= ideal + 2) {
-                    int rcp = repack_left(KC, true);
-                    if (rcp) return rcp;
-                    last_tail_repack = it;
-                }
-            }
-            if (KCn < KC) {
-                last_tail_repack = it;
-                int rcp = repack_left(KCn, stay3 && use2h && kn.part);
-                if (rcp) return rcp;
-                KC = KCn;
-                cols = ColAlloc(KC);
-                for (int s = 0; s < nslots; ++s) if (hs[s].state) cols.alloc(hs[s].k);
-                if (!stay3) use3 = usec = use2h = use2g = false;     // fewer than 256 packed columns: the f32 pipe takes over
-                // (the buffers were sized for KC0 columns: a narrower batch may keep more partial planes in them)
-                if ((rcp = plan_passes((ctx->nsplit_alloc * KC0) / KC, (ctx->nsplitA_alloc * KC0) / KC))) return rcp;
-            }
-        }
-        return CNMF_OK;
-    };
+    memset(ctx->bat.h_snap, 0, (size_t)ctx->bat.kc * RING * sizeof(SlotDesc));
+    b.ev_begin = b.events.get(); b.ev_end = b.events.get();
+    POOL_TRY(ctx, b.events);
+    HIP_TRY(ctx, hipEventRecord(b.ev_begin, b.st));
+    if ((rc = plan_passes(b, ctx->bat.nsplit, ctx->bat.nsplitA))) return rc;
+    b.nsplit3_first = b.nsplit3;
 
     while (true) {
         int n_new = 0;
-        if ((rc = refill(n_new))) return rc;
-        if (n_active == 0 && n_pending == 0) break;
-        if (n_pending == 0 && !ev_tail && stats) {
-            ev_tail = events.get();
-            POOL_TRY(ctx, events);
-            HIP_TRY(ctx, hipEventRecord(ev_tail, st));
+        if ((rc = refill(b, n_new))) return rc;
+        if (b.sched.finished()) break;
+        if (b.sched.n_pending == 0 && !b.ev_tail && stats) {
+            b.ev_tail = b.events.get();
+            POOL_TRY(ctx, b.events);
+            HIP_TRY(ctx, hipEventRecord(b.ev_tail, b.st));
         }
-        if ((rc = iterate(n_new))) return rc;
-        if ((rc = inspect())) return rc;
-        if ((rc = compact())) return rc;
+        if ((rc = iterate(b, n_new))) return rc;
+        if ((rc = inspect(b))) return rc;
+        if ((rc = compact(b))) return rc;
     }
-
-    if (dbg) fprintf(stderr, "[cnmf] %lld defragmentations\n", (long long)n_defrag);
-    if (dbg)
-        for (int i = 1; i <= 64; ++i)
-            if (dbg_it[i]) fprintf(stderr, "[cnmf] KC=%d: %lld iterations, mean host-live columns %.1f\n", i * 32,
-                                   (long long)dbg_it[i], (double)dbg_live[i] / dbg_it[i]);
-    HIP_TRY(ctx, hipEventRecord(ev_end, st));
-    if (!resident)
-        HIP_TRY(ctx, hipMemcpyAsync(H_out, d_Hres, hoff[n] * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (W_out)
-        HIP_TRY(ctx, hipMemcpyAsync(W_out, d_Wres, woff[n] * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (resident) ctx->spectra_rows += (size_t)total_k;
-    {   // the mean iteration count per rank this call saw (cnmf_get_iteration_means)
-        if (ctx->iter_prior.size() != (size_t)KMAX + 1) ctx->iter_prior.assign((size_t)KMAX + 1, 0.0);
-        for (int k = 1; k <= KMAX; ++k)
-            if (k_done[k]) ctx->iter_prior[k] = (double)k_iters[k] / (double)k_done[k];
-    }
-    if (stats) {
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, ev_begin, ev_end);
-        stats->gpu_ms = ms;
-        stats->outer_iterations = it;
-        stats->restart_iterations = restart_iters;
-        stats->column_iterations = column_iters;
-        stats->restart_column_iterations = restart_col_iters;
-        stats->kc = KC0; stats->nsplit = gemm_mode_used ? nsplit3_first : ctx->nsplit_alloc;
-        stats->gemm_mode = gemm_mode_used;
-        stats->tail_iterations = tail_its; stats->tail_live_columns = tail_live;
-        if (ev_tail) { float tms = 0.f; hipEventElapsedTime(&tms, ev_tail, ev_end); stats->tail_ms = tms; }
-        for (size_t i = 0; i + 3 < gev.size(); i += 4) {
-            float a = 0.f, b = 0.f;
-            hipEventElapsedTime(&a, gev[i], gev[i + 1]);
-            hipEventElapsedTime(&b, gev[i + 2], gev[i + 3]);
-            stats->passA_ms += a; stats->passB_ms += b;
-            stats->passA_launches++; stats->passB_launches++;
-        }
-    }
-    return CNMF_OK;
+    return finish_batch(b, H_out, W_out, stats);
 }
 
 // mean outer iterations per rank seen by the batch calls on the resident matrix: out[KMAX + 1], 0 = rank not seen
@@ -994,20 +942,20 @@ extern "C" int cnmf_nnls(cnmf_ctx* ctx, int k, const float* Hin, const cnmf_cd_p
     hipStream_t st = ctx->stream;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->stageH, Hin, (size_t)k * G * sizeof(float), hipMemcpyHostToDevice, st));
     dim3 gI((std::max(N, G) + 255) / 256, k);
-    install_kernel<<<gI, 256, 0, st>>>(ctx->stageH, nullptr, ctx->H, ctx->G_pad, G, ctx->Wt, ctx->N_pad, N, 0, k);
+    install_kernel<<<gI, 256, 0, st>>>(ctx->stageH, nullptr, ctx->bat.H, ctx->G_pad, G, ctx->bat.Wt, ctx->N_pad, N, 0, k);
     if (k < KC) {   // unused component rows of the 32-wide tile must be zero
         dim3 gc((ctx->G_pad + 255) / 256, KC - k), gw((ctx->N_pad + 255) / 256, KC - k);
-        clear_rows_kernel<<<gc, 256, 0, st>>>(ctx->H, ctx->G_pad, ctx->G_pad, k, KC - k);
-        clear_rows_kernel<<<gw, 256, 0, st>>>(ctx->Wt, ctx->N_pad, ctx->N_pad, k, KC - k);
+        clear_rows_kernel<<<gc, 256, 0, st>>>(ctx->bat.H, ctx->G_pad, ctx->G_pad, k, KC - k);
+        clear_rows_kernel<<<gw, 256, 0, st>>>(ctx->bat.Wt, ctx->N_pad, ctx->N_pad, k, KC - k);
     }
-    SlotDesc* d = &ctx->h_slots[0];
+    SlotDesc* d = &ctx->bat.h_slots[0];
     memset(d, 0, sizeof *d);
     d->off = 0; d->k = k; d->active = 1; d->restart = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_slots, d, sizeof(SlotDesc), hipMemcpyHostToDevice, st));
-    ctx->h_slot_list[0] = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_slot_list, ctx->h_slot_list, sizeof(int), hipMemcpyHostToDevice, st));
-    gram_rows_kernel<<<1, 256, 0, st>>>(ctx->H, ctx->G_pad, G, ctx->d_slots, ctx->d_slot_list, ctx->gramH, (float)prm->l2_reg_W);
-    HIP_TRY(ctx, launch_gemm<false>(st, 0, ctx->H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->XHt, ctx->N_pad, 0, KC, ctx->G_pad, ctx->N_pad, 1));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->bat.d_slots, d, sizeof(SlotDesc), hipMemcpyHostToDevice, st));
+    ctx->bat.h_slot_list[0] = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->bat.d_slot_list, ctx->bat.h_slot_list, sizeof(int), hipMemcpyHostToDevice, st));
+    gram_rows_kernel<<<1, 256, 0, st>>>(ctx->bat.H, ctx->G_pad, G, ctx->bat.d_slots, ctx->bat.d_slot_list, ctx->bat.gramH, (float)prm->l2_reg_W);
+    HIP_TRY(ctx, launch_gemm<false>(st, 0, ctx->bat.H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->bat.XHt, ctx->N_pad, 0, KC, ctx->G_pad, ctx->N_pad, 1));
     const int chunksW = sweep_chunks(ctx, N), partsW = sweep_parts(ctx, N);
     DevPool pool;
     EventPool events;
@@ -1017,26 +965,26 @@ extern "C" int cnmf_nnls(cnmf_ctx* ctx, int k, const float* Hin, const cnmf_cd_p
     POOL_TRY(ctx, pool);
     const int burst = 8;        // sweeps enqueued between two looks at the slot state
     int done = 0;
-    SlotDesc* snap = ctx->h_snap;
+    SlotDesc* snap = ctx->bat.h_snap;
     for (int it = 0; it < prm->max_iter && !done; it += burst) {
         for (int b = 0; b < burst; ++b) {
-            HIP_TRY(ctx, launch_sweep(st, 1, ctx->Wt, ctx->N_pad, N, ctx->XHt, ctx->gramH,
-                                      ctx->d_slots, (float)prm->l1_reg_W, ctx->gram_part, ctx->viol_part,
+            HIP_TRY(ctx, launch_sweep(st, 1, ctx->bat.Wt, ctx->N_pad, N, ctx->bat.XHt, ctx->bat.gramH,
+                                      ctx->bat.d_slots, (float)prm->l1_reg_W, ctx->bat.gram_part, ctx->bat.viol_part,
                                       chunksW, partsW, 0, k, k <= 16 ? 1 : (k <= 32 ? 2 : (k <= KSMALL ? 4 : 8))));
-            finalize_kernel<<<dim3(1, 1), 256, 0, st>>>(ctx->gram_part, ctx->viol_part, partsW, ctx->gramW, 0.f,
-                                               ctx->d_slots, 2, prm->tol, prm->max_iter, 0, k);
+            finalize_kernel<<<dim3(1, 1), 256, 0, st>>>(ctx->bat.gram_part, ctx->bat.viol_part, partsW, ctx->bat.gramW, 0.f,
+                                               ctx->bat.d_slots, 2, prm->tol, prm->max_iter, 0, k);
         }
-        HIP_TRY(ctx, hipMemcpyAsync(snap, ctx->d_slots, sizeof(SlotDesc), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(snap, ctx->bat.d_slots, sizeof(SlotDesc), hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipEventRecord(ev, st));
         HIP_TRY(ctx, hipEventSynchronize(ev));
         done = (snap->active == 0);
     }
     dim3 gW((N + 255) / 256, k);
-    extract_kernel<<<gW, 256, 0, st>>>(ctx->Wt, ctx->N_pad, N, 0, k, d_W, 1);
+    extract_kernel<<<gW, 256, 0, st>>>(ctx->bat.Wt, ctx->N_pad, N, 0, k, d_W, 1);
     HIP_TRY(ctx, hipMemcpyAsync(W_out, d_W, (size_t)N * k * sizeof(float), hipMemcpyDeviceToHost, st));
     dim3 gH((ctx->G_pad + 255) / 256, k), gWc((ctx->N_pad + 255) / 256, k);
-    clear_rows_kernel<<<gH, 256, 0, st>>>(ctx->H, ctx->G_pad, ctx->G_pad, 0, k);
-    clear_rows_kernel<<<gWc, 256, 0, st>>>(ctx->Wt, ctx->N_pad, ctx->N_pad, 0, k);
+    clear_rows_kernel<<<gH, 256, 0, st>>>(ctx->bat.H, ctx->G_pad, ctx->G_pad, 0, k);
+    clear_rows_kernel<<<gWc, 256, 0, st>>>(ctx->bat.Wt, ctx->N_pad, ctx->N_pad, 0, k);
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (n_iter_out) *n_iter_out = snap->iter;
     if (viol_out) *viol_out = snap->viol_last;

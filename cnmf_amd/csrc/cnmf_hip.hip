@@ -16,7 +16,8 @@
 //   runtime.hip.h        cnmf_ctx, error plumbing, scope-bound device buffers / events
 //   gemm_host.hip.h      GEMM / sweep launchers, stream-K plans, operand planes, count-structure detection
 //   (this file)          lifecycle, upload of the data matrix
-//   batch_host.hip.h     batch buffers, the slot scheduler (run_batch), NNLS refit
+//   batch_host.hip.h     batch buffers, the restart loop (run_batch: operand scheme, installs, launches), NNLS refit;
+//                        includes batch_sched.h, the restart scheduler itself (standard library only, no HIP)
 //   consensus_host / mu_host / comm_host / normalize_host .hip.h   the other entry points
 //   debug_host.hip.h     products with X for NNDSVD, diagnostics used by the tests
 #include <hip/hip_runtime.h>
@@ -112,30 +113,12 @@ static void drop_derived_images(cnmf_ctx* c)
     free_csr(c);
 }
 
-static void free_batch(cnmf_ctx* c)
-{
-    hipFree(c->H); hipFree(c->Wt); hipFree(c->XHt); hipFree(c->XHt1); hipFree(c->XHt2); hipFree(c->XtW); hipFree(c->d_split);
-    hipFree(c->H3); hipFree(c->Wt3);
-    hipFree(c->rmaxH); hipFree(c->rmaxW); hipFree(c->iscaleH); hipFree(c->iscaleW); hipFree(c->shiftW);
-    c->rmaxH = c->rmaxW = c->iscaleH = c->iscaleW = nullptr; c->shiftW = nullptr;
-    c->XHt1 = c->XHt2 = nullptr; c->d_split = nullptr; c->H3 = c->Wt3 = nullptr;
-    hipFree(c->gramH); hipFree(c->gramW); hipFree(c->gram_part); hipFree(c->viol_part);
-    hipFree(c->d_slots); hipFree(c->d_slot_list);
-    if (c->h_slots) hipHostFree(c->h_slots);
-    if (c->h_snap) hipHostFree(c->h_snap);
-    if (c->h_slot_list) hipHostFree(c->h_slot_list);
-    c->H = c->Wt = c->XHt = c->XtW = c->gramH = c->gramW = c->gram_part = nullptr;
-    c->viol_part = nullptr; c->d_slots = nullptr; c->d_slot_list = nullptr;
-    c->h_slots = c->h_snap = nullptr; c->h_slot_list = nullptr;
-    c->kc_alloc = 0; c->gram_part_floats = 0;
-}
-
 extern "C" void cnmf_destroy(cnmf_ctx* ctx)
 {
     if (!ctx) return;
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
-    free_batch(ctx);
+    ctx->bat.release();
     cnmf_comm_finalize(ctx);
     drop_derived_images(ctx);
     hipFree(ctx->X);
@@ -167,7 +150,7 @@ static int alloc_matrix(cnmf_ctx* ctx, int64_t N, int64_t G, bool dense = true)
         return CNMF_EINVAL;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    free_batch(ctx);
+    ctx->bat.release();
     drop_derived_images(ctx);
     hipFree(ctx->X); ctx->X = nullptr;
     ctx->iter_prior.clear(); ctx->iter_hint.clear();     // iteration counts of another matrix say nothing about this one

@@ -182,6 +182,34 @@ struct HarStage {
     }
 };
 
+// The buffers of the coordinate-descent batch and of the NNLS refits, sized for kc packed columns (ensure_batch,
+// batch_host.hip.h); kc = 0: none.  Device memory but for the three pinned host blocks.
+struct BatchBuffersF {
+    int kc = 0, nsplit = 0, nsplitA = 0, parts = 0;
+    size_t gram_part_floats = 0;
+    float *H = nullptr, *Wt = nullptr, *XHt = nullptr, *XHt1 = nullptr, *XHt2 = nullptr, *XtW = nullptr;
+    unsigned char *H3 = nullptr, *Wt3 = nullptr;   // planes of the packed factors, refreshed every iteration
+    unsigned char* d_split = nullptr;   // stream-K cut flags of the current plan
+    // f16 two-plane factor split (kernels_gemm2h.hip.h): per-row maxima reported by the sweeps, 2^-s per row
+    float *rmaxH = nullptr, *rmaxW = nullptr, *iscaleH = nullptr, *iscaleW = nullptr;
+    int* shiftW = nullptr;              // [3][kc]: exponents of the W planes written by the sweep (two generations + scratch)
+    float *gramH = nullptr, *gramW = nullptr, *gram_part = nullptr;
+    double* viol_part = nullptr;
+    SlotDesc* d_slots = nullptr;
+    int* d_slot_list = nullptr;
+    SlotDesc* h_slots = nullptr;      // pinned: per-slot install descriptors
+    SlotDesc* h_snap = nullptr;       // pinned: snapshot ring [RING][kc]
+    int* h_slot_list = nullptr;       // pinned ring of new-slot lists
+    void free_all() {
+        void* dev[] = {H, Wt, XHt, XHt1, XHt2, XtW, H3, Wt3, d_split, rmaxH, rmaxW, iscaleH, iscaleW, shiftW, gramH, gramW,
+                       gram_part, viol_part, d_slots, d_slot_list};
+        for (void* p : dev) hipFree(p);
+        if (h_slots) hipHostFree(h_slots);
+        if (h_snap) hipHostFree(h_snap);
+        if (h_slot_list) hipHostFree(h_slot_list);
+    }
+};
+
 static constexpr int RING = 8;
 #ifndef CNMF_GEMM3_DEFAULT
 #define CNMF_GEMM3_DEFAULT 4
@@ -240,22 +268,7 @@ struct cnmf_ctx {
     // built from the dense matrix on first use; 64-bit row pointers, float32 values like the dense image
     DevCsr<float> csr, csc;
 
-    // batch buffers (sized for kc_alloc columns)
-    int kc_alloc = 0, nsplit_alloc = 0, nsplitA_alloc = 0, parts_alloc = 0;
-    size_t gram_part_floats = 0;
-    float *H = nullptr, *Wt = nullptr, *XHt = nullptr, *XHt1 = nullptr, *XHt2 = nullptr, *XtW = nullptr;
-    unsigned char *H3 = nullptr, *Wt3 = nullptr;   // planes of the packed factors, refreshed every iteration
-    unsigned char* d_split = nullptr;   // stream-K cut flags of the current plan
-    // f16 two-plane factor split (kernels_gemm2h.hip.h): per-row maxima reported by the sweeps, 2^-s per row
-    float *rmaxH = nullptr, *rmaxW = nullptr, *iscaleH = nullptr, *iscaleW = nullptr;
-    int* shiftW = nullptr;              // [3][kc_alloc]: exponents of the W planes written by the sweep (two generations + scratch)
-    float *gramH = nullptr, *gramW = nullptr, *gram_part = nullptr;
-    double* viol_part = nullptr;
-    SlotDesc* d_slots = nullptr;
-    int* d_slot_list = nullptr;
-    SlotDesc* h_slots = nullptr;      // pinned: per-slot install descriptors
-    SlotDesc* h_snap = nullptr;       // pinned: snapshot ring [RING][kc_alloc]
-    int* h_slot_list = nullptr;       // pinned ring of new-slot lists
+    Owned<BatchBuffersF> bat;                      // ensure_batch (batch_host.hip.h); bat.kc = 0: none
     float *stageW = nullptr, *stageH = nullptr;
     size_t stageW_sz = 0, stageH_sz = 0;
 

@@ -259,16 +259,16 @@ static int nnls_sweep_loop(cnmf_ctx* ctx, int nslots, float* V, int ldv, int L, 
     hipEvent_t ev = events.get(hipEventDisableTiming);
     POOL_TRY(ctx, events);
     const int burst = 8;
-    SlotDesc* snap = ctx->h_snap;
+    SlotDesc* snap = ctx->bat.h_snap;
     bool done = false;
     for (int it = 0; it < prm->max_iter && !done; it += burst) {
         for (int b = 0; b < burst; ++b) {
-            HIP_TRY(ctx, launch_sweep(st, nslots, V, ldv, L, P, gram, ctx->d_slots, l1, ctx->gram_part, ctx->viol_part,
+            HIP_TRY(ctx, launch_sweep(st, nslots, V, ldv, L, P, gram, ctx->bat.d_slots, l1, ctx->bat.gram_part, ctx->bat.viol_part,
                                       chunks, parts, 0, kmax, tiers));
-            finalize_kernel<<<dim3(nslots, 1), 256, 0, st>>>(ctx->gram_part, ctx->viol_part, parts, ctx->gramW, 0.f,
-                                                          ctx->d_slots, 2, prm->tol, prm->max_iter, 0, kmax);
+            finalize_kernel<<<dim3(nslots, 1), 256, 0, st>>>(ctx->bat.gram_part, ctx->bat.viol_part, parts, ctx->bat.gramW, 0.f,
+                                                          ctx->bat.d_slots, 2, prm->tol, prm->max_iter, 0, kmax);
         }
-        HIP_TRY(ctx, hipMemcpyAsync(snap, ctx->d_slots, (size_t)nslots * sizeof(SlotDesc), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(snap, ctx->bat.d_slots, (size_t)nslots * sizeof(SlotDesc), hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipEventRecord(ev, st));
         HIP_TRY(ctx, hipEventSynchronize(ev));
         done = true;
@@ -289,14 +289,14 @@ static int install_nnls_slots(cnmf_ctx* ctx, int n, const int32_t* ks)
 {
     int off = 0;
     for (int s = 0; s < n; ++s) {
-        SlotDesc* d = &ctx->h_slots[s];
+        SlotDesc* d = &ctx->bat.h_slots[s];
         memset(d, 0, sizeof *d);
         d->off = off; d->k = ks[s]; d->active = 1; d->restart = s;
-        ctx->h_slot_list[s] = s;
+        ctx->bat.h_slot_list[s] = s;
         off += ks[s];
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_slots, ctx->h_slots, (size_t)n * sizeof(SlotDesc), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_slot_list, ctx->h_slot_list, (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->bat.d_slots, ctx->bat.h_slots, (size_t)n * sizeof(SlotDesc), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->bat.d_slot_list, ctx->bat.h_slot_list, (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     return CNMF_OK;
 }
 
@@ -464,10 +464,10 @@ static int nnls_batch_impl(cnmf_ctx* ctx, int n, const int32_t* ks, const float*
         POOL_TRY(ctx, pool);
         HIP_TRY(ctx, hipMemcpyAsync(dHin, Hin + hoff, (size_t)cols * G * sizeof(float), hipMemcpyHostToDevice, st));
         dim3 gc((ctx->G_pad + 255) / 256, KC), gw((ctx->N_pad + 255) / 256, KC);
-        clear_rows_kernel<<<gc, 256, 0, st>>>(ctx->H, ctx->G_pad, ctx->G_pad, 0, KC);
-        clear_rows_kernel<<<gw, 256, 0, st>>>(ctx->Wt, ctx->N_pad, ctx->N_pad, 0, KC);
+        clear_rows_kernel<<<gc, 256, 0, st>>>(ctx->bat.H, ctx->G_pad, ctx->G_pad, 0, KC);
+        clear_rows_kernel<<<gw, 256, 0, st>>>(ctx->bat.Wt, ctx->N_pad, ctx->N_pad, 0, KC);
         dim3 gI((G + 255) / 256, cols);
-        install_kernel<<<gI, 256, 0, st>>>(dHin, nullptr, ctx->H, ctx->G_pad, G, ctx->Wt, ctx->N_pad, 0, 0, cols);
+        install_kernel<<<gI, 256, 0, st>>>(dHin, nullptr, ctx->bat.H, ctx->G_pad, G, ctx->bat.Wt, ctx->N_pad, 0, 0, cols);
         rc = install_nnls_slots(ctx, m, kg);
         if (rc) return rc;
         if (gram_in) {
@@ -476,25 +476,25 @@ static int nnls_batch_impl(cnmf_ctx* ctx, int n, const int32_t* ks, const float*
             size_t go = goff;
             for (int s = 0; s < m; ++s) {
                 HIP_TRY(ctx, hipMemcpyAsync(dg, gram_in + go, (size_t)kg[s] * kg[s] * sizeof(float), hipMemcpyHostToDevice, st));
-                set_gram_kernel<<<(kg[s] * kg[s] + 255) / 256, 256, 0, st>>>(dg, kg[s], ctx->gramH, s, (float)prm->l2_reg_W);
+                set_gram_kernel<<<(kg[s] * kg[s] + 255) / 256, 256, 0, st>>>(dg, kg[s], ctx->bat.gramH, s, (float)prm->l2_reg_W);
                 HIP_TRY(ctx, hipStreamSynchronize(st));
                 go += (size_t)kg[s] * kg[s];
             }
         } else {
-            gram_rows_kernel<<<m, 256, 0, st>>>(ctx->H, ctx->G_pad, G, ctx->d_slots, ctx->d_slot_list, ctx->gramH, (float)prm->l2_reg_W);
+            gram_rows_kernel<<<m, 256, 0, st>>>(ctx->bat.H, ctx->G_pad, G, ctx->bat.d_slots, ctx->bat.d_slot_list, ctx->bat.gramH, (float)prm->l2_reg_W);
         }
         // ONE pass over X for every refit of the group
-        HIP_TRY(ctx, launch_gemm<false>(st, 0, ctx->H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->XHt, ctx->N_pad, 0, KC, ctx->G_pad, ctx->N_pad, 1));
-        rc = nnls_sweep_loop(ctx, m, ctx->Wt, ctx->N_pad, N, ctx->XHt, ctx->gramH, (float)prm->l1_reg_W, prm, kmax, tiers_of(kg, m));
+        HIP_TRY(ctx, launch_gemm<false>(st, 0, ctx->bat.H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->bat.XHt, ctx->N_pad, 0, KC, ctx->G_pad, ctx->N_pad, 1));
+        rc = nnls_sweep_loop(ctx, m, ctx->bat.Wt, ctx->N_pad, N, ctx->bat.XHt, ctx->bat.gramH, (float)prm->l1_reg_W, prm, kmax, tiers_of(kg, m));
         if (rc) return rc;
         int off = 0;
         for (int s = 0; s < m; ++s) {
             const int k = kg[s];
-            if (n_iter_out) n_iter_out[done_n + s] = ctx->h_snap[s].iter;
-            if (viol_out) viol_out[done_n + s] = ctx->h_snap[s].viol_last;
+            if (n_iter_out) n_iter_out[done_n + s] = ctx->bat.h_snap[s].iter;
+            if (viol_out) viol_out[done_n + s] = ctx->bat.h_snap[s].viol_last;
             if (W_out) {
                 dim3 gW((N + 255) / 256, k);
-                extract_kernel<<<gW, 256, 0, st>>>(ctx->Wt, ctx->N_pad, N, off, k, dW, 1);
+                extract_kernel<<<gW, 256, 0, st>>>(ctx->bat.Wt, ctx->N_pad, N, off, k, dW, 1);
                 HIP_TRY(ctx, hipMemcpyAsync(W_out + woff, dW, (size_t)N * k * sizeof(float), hipMemcpyDeviceToHost, st));
                 HIP_TRY(ctx, hipStreamSynchronize(st));
             }
@@ -509,7 +509,7 @@ static int nnls_batch_impl(cnmf_ctx* ctx, int n, const int32_t* ks, const float*
                 double* dsum = p2.get<double>(1);
                 POOL_TRY(ctx, p2);
                 dim3 gW((N + 255) / 256, k);
-                rows_to_f64_kernel<<<gW, 256, 0, st>>>(ctx->Wt, ctx->N_pad, N, off, k, dW64);
+                rows_to_f64_kernel<<<gW, 256, 0, st>>>(ctx->bat.Wt, ctx->N_pad, N, off, k, dW64);
                 // residual_sq_kernel wants H as [k][G]: the packed input block is exactly that (float32 -> float64)
                 {
                     const long long nh = (long long)k * G;
@@ -528,8 +528,8 @@ static int nnls_batch_impl(cnmf_ctx* ctx, int n, const int32_t* ks, const float*
             }
             off += k; woff += (size_t)N * k;
         }
-        clear_rows_kernel<<<gc, 256, 0, st>>>(ctx->H, ctx->G_pad, ctx->G_pad, 0, KC);
-        clear_rows_kernel<<<gw, 256, 0, st>>>(ctx->Wt, ctx->N_pad, ctx->N_pad, 0, KC);
+        clear_rows_kernel<<<gc, 256, 0, st>>>(ctx->bat.H, ctx->G_pad, ctx->G_pad, 0, KC);
+        clear_rows_kernel<<<gw, 256, 0, st>>>(ctx->bat.Wt, ctx->N_pad, ctx->N_pad, 0, KC);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipStreamSynchronize(st));
         hoff += (size_t)cols * G;

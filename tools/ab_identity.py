@@ -1,5 +1,5 @@
 """Fixed seeded jobs through whichever build of the library CNMF_LIB_PATH names, for bit-identity A/B runs of two builds:
-    CNMF_LIB_PATH=/path/to/libcnmf_hip.so [CNMF_GEMM3=2 ...] python tools/ab_identity.py wide|general|f32|mode|init|streamk|streamk_general|staging
+    CNMF_LIB_PATH=/path/to/libcnmf_hip.so [CNMF_GEMM3=2 ...] python tools/ab_identity.py wide|general|f32|mode|init|streamk|streamk_general|hints|staging
 Prints one JSON line: SHA-256 digests of everything the job's batch calls returned (H, n_iter, viol) and of the
 last_stats fields that describe the schedule.  One process per library and per knob value; the lines must be equal.
 ``staging`` runs no coordinate-descent batch: it digests every array the prepare / preprocess / filter entry points and
@@ -27,13 +27,16 @@ def draw(rs, n, lo=5, hi=14):
 def calls(job):
     """(matrix, [keyword arguments of one nmf_batch call, ...]) of a job"""
     rs = np.random.RandomState(5)
-    if job in ("wide", "mode", "init"):            # count path; 150 restarts: 1024 columns, refill, defragmentation, 768 / 512 / 256, f32 tail
+    if job in ("wide", "mode", "init", "hints"):            # count path; 150 restarts: 1024 columns, refill, defragmentation, 768 / 512 / 256, f32 tail
         X = synth.make_config("C3", dtype=np.float32, n_cells=6000)
         if job == "init":                           # caller-supplied factors of very different size (the exponent guess of the W planes)
             ks = [40, 64, 50, 30, 60, 45, 33]
             W0 = [np.abs(rs.standard_normal((X.shape[0], k))).astype(np.float32) * np.float32(10.0 ** (i - 3)) for i, k in enumerate(ks)]
             H0 = [np.abs(rs.standard_normal((k, X.shape[1]))).astype(np.float32) for k in ks]
             return X, [dict(ks=ks, W0=W0, H0=H0, max_iter=40)]
+        if job == "hints":                          # the same call twice: the second one ordered by what the first one learned
+            ks, seeds = draw(rs, 60)
+            return X, [dict(ks=ks, seeds=seeds, max_iter=60), dict(ks=ks, seeds=seeds, max_iter=60, hints=True)]
         ks, seeds = draw(rs, 150 if job == "wide" else 44)
         return X, [dict(ks=ks, seeds=seeds, max_iter=60)]
     if job == "general":                            # tests/test_gpu_nmf.py: the perturbed matrix, 256 and 1024 columns
@@ -143,6 +146,8 @@ def main():
     h = {name: hashlib.sha256() for name in ("H", "n_iter", "viol") + STATS}
     seen = []
     for kw in jobs:
+        if kw.pop("hints", False):
+            eng.set_iteration_hints(eng.iteration_means())
         H, _, n_iter, viol = eng.nmf_batch(kw.pop("ks"), warn=False, **kw)
         for a in H:
             h["H"].update(np.ascontiguousarray(a).tobytes())

@@ -1,4 +1,5 @@
-"""Offline simulation of the restart scheduler (batch_host.hip.h::run_batch) on MEASURED iteration counts
+"""Offline simulation of the restart scheduler (cnmf_amd/csrc/batch_sched.h, driven by batch_host.hip.h::run_batch; a
+simplified restatement, not a port of that header) on MEASURED iteration counts
 (gpurun_out/iters_c3.json from tools/dump_iters.py): queue orders and batch widths for the north-star job and its
 strong-scaling shards.  Cost model per batch iteration (microseconds, measured at C3 on one MI355X, round 3):
 T(256) = 270, T(512) = 450, T(1024) = 800 when the batch is full; the tail narrows in 256-column steps."""
