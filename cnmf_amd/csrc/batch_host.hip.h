@@ -5,56 +5,17 @@
 #include "batch_sched.h"
 
 // ------------------------------------------------------------------ batch buffers
-static int sweep_chunks(const cnmf_ctx* ctx, int L) { const int64_t m = 256ll * ctx->knobs.sweep_parts; return std::max(1, (int)(((int64_t)L + m - 1) / m)); }
-// partials per slot of a half-step: one per sweep workgroup (sweep_chunks 256-row tiles each)
-static int sweep_parts(const cnmf_ctx* ctx, int L) { const int c = sweep_chunks(ctx, L); return (L + 256 * c - 1) / (256 * c); }
-
-static int pick_nsplit(const cnmf_ctx* ctx, int KC)
-{
-    // pass B grid = ceil(G_pad/128) x (KC/128 or 1) x nsplit ; aim at ~2 workgroups per CU
-    const int jt = (ctx->G_pad + 127) / 128;
-    const int mg = std::max(1, KC / 128);
-    int s = std::max(1, 512 / (jt * mg));
-    const int max_by_k = std::max(1, ctx->N_pad / 256);   // at least 256 cells of K per split
-    return std::min(s, max_by_k);
-}
-
-// splits that actually receive work once the per-split K range is rounded up to whole stages
-static int effective_splits(int Ktot, int nsplit)
-{
-    const int Kper = round_up((Ktot + nsplit - 1) / nsplit, BK);
-    return (Ktot + Kper - 1) / Kper;
-}
-
-// pass A on few cells: fewer than one 128-cell tile per CU -> split the gene (K) range too, so
-// that ~2 workgroups per CU are in flight; the planes are summed by reduce_splits_kernel.
-static int pick_nsplit_A(const cnmf_ctx* ctx, int KC)
-{
-    const int T = (ctx->N_pad / 128) * std::max(1, KC / 128);
-    if (T > 256) return 1;                                  // stream-K territory
-    int s = std::max(1, 512 / T);
-    s = std::min(s, std::max(1, ctx->G_pad / (4 * BK)));    // at least 4 stages per split
-    return effective_splits(ctx->G_pad, std::min(s, 16));
-}
-
-// pass A of the split-operand kernels on few cell tiles (no stream-K below 3/4 of the workgroup slots):
-// K splits so that about one workgroup per slot is in flight, >= 8 blocks each
-static int pick_nsplit_A3(const cnmf_ctx* ctx, int KC, int jw)
-{
-    const int T = std::max(1, ctx->N_pad / jw) * std::max(1, KC / G3_MW);
-    const int Kb = ctx->G_pad / G3_BK;
-    int s = std::max(1, std::min(gemm3_wg_slots(ctx->knobs) / T, Kb / 8));
-    const int kb_per = (Kb + s - 1) / s;
-    return (Kb + kb_per - 1) / kb_per;
-}
+static_assert(PLAN_BK == BK && PLAN_G3_MW == G3_MW && PLAN_G3_JW == G3_JW && PLAN_G3C_JW == G3C_JW && PLAN_G3_BK == G3_BK &&
+              PLAN_KSMALL == KSMALL, "pass_plan.h repeats the tile constants of the kernel headers");
+static PadShape pad_shape(const cnmf_ctx* ctx) { return PadShape{ctx->N_pad, ctx->G_pad}; }
+static int sweep_chunks(const cnmf_ctx* ctx, int L) { return sweep_chunks(ctx->knobs.sweep_parts, L); }
+static int sweep_parts(const cnmf_ctx* ctx, int L) { return sweep_parts(ctx->knobs.sweep_parts, L); }
 
 static int ensure_batch(cnmf_ctx* ctx, int KC, int max_k = KMAX, int min_k = 1)
 {
     const bool use3 = gemm3_enabled(ctx, KC);
-    const int nsplit = use3 ? std::max(pick_nsplit(ctx, KC), std::max(pick_nsplit3(ctx, KC, G3_JW), pick_nsplit3(ctx, KC, G3C_JW)))
-                            : pick_nsplit(ctx, KC);
-    const int nsplitA = use3 ? std::max(pick_nsplit_A(ctx, KC), std::max(pick_nsplit_A3(ctx, KC, G3_JW), pick_nsplit_A3(ctx, KC, G3C_JW)))
-                             : pick_nsplit_A(ctx, KC);
+    const SplitCaps caps = size_splits(pad_shape(ctx), KC, use3, gemm3_wg_slots(ctx->knobs));
+    const int nsplit = caps.nsplit, nsplitA = caps.nsplitA;
     const int parts = std::max(sweep_parts(ctx, (int)ctx->N), sweep_parts(ctx, (int)ctx->G));
     const size_t gp_need = (size_t)(KC / std::max(1, min_k) + 1) * parts * max_k * max_k;
     if (ctx->bat.kc == KC && ctx->bat.nsplit == nsplit && ctx->bat.nsplitA == nsplitA &&
@@ -158,33 +119,6 @@ static int wait_snapshot(cnmf_ctx* ctx, const SlotDesc* sp, int n, int stamp)
     return CNMF_OK;
 }
 
-// Packed component columns of a call.  32 ... 256 by the total rank of the job (powers of two); on the matrix-pipe
-// split-operand paths (`wide_ok`) a larger job runs WIDE, up to 1024 columns = four 256-column component groups per GEMM
-// pass: both passes then read every X tile once per 1024 columns instead of once per 256, the stream-K partial planes of
-// pass A and the latency-bound H half-step are amortised over four times the columns (169 -> 198 -> 215 restarts/s at
-// 256 / 512 / 1024 columns, 50 000 x 2000); the batch narrows in 256-column steps once the queue is dry (compact()).
-// kc_max: 0 = auto, else an upper bound (multiple of 32; above 256 in steps of 256, up to CNMF_KC_LIMIT, default 1024).
-static int pick_kc(const cnmf_ctx* ctx, int64_t total_k, int max_k, int kc_max, bool wide_ok)
-{
-    if (ctx->knobs.kc >= 32) kc_max = ctx->knobs.kc;
-    const bool autosize = kc_max <= 0;
-    if (autosize) kc_max = 256;
-    kc_max = std::max(32, std::min(ctx->knobs.kc_limit, (kc_max / 32) * 32));
-    if (kc_max > 256) kc_max = wide_ok ? (kc_max / 256) * 256 : 256;
-    int kc = 32;
-    while (kc < std::min(kc_max, 256) && kc < total_k) kc *= 2;
-    kc = std::min(kc, kc_max);
-    if (wide_ok && kc == 256 && total_k > 256) {
-        // as wide as the job, up to the limit: a job that fits entirely starts every restart at once and the batch
-        // narrows behind the ones that finish (compact()); measured and simulated on the iteration counts of the
-        // north-star job (tools/sim_schedule.py): 113 restarts run 187 / 172 / 145 restarts/s at 1024 / 512 / 256 columns
-        if (autosize) kc = (int)std::min<int64_t>(ctx->knobs.kc_limit, round_up(total_k, 256));
-        else if (!autosize && kc_max > 256) kc = (int)std::min<int64_t>(kc_max, round_up(total_k, 256));
-    }
-    if (kc < max_k) kc = round_up(max_k, 32);
-    return kc;
-}
-
 static int validate_params(cnmf_ctx* ctx, const cnmf_cd_params* p)
 {
     if (!p) { SET_ERR(ctx, "params is NULL"); return CNMF_EINVAL; }
@@ -233,8 +167,8 @@ static int pick_scheme(cnmf_ctx* ctx, int KC, PassScheme* out)
     p.xA = p.use2g ? ctx->x2.passA() : ctx->counts.passA();
     p.xB = p.use2g ? ctx->x2.passB() : ctx->counts.passB();
     p.dsc = p.use2g ? nullptr : ctx->counts.d_scale;
-    p.nsubA = p.use2h ? gemm2h_nsub(p.xA.hi != nullptr, p.KbA) : 1;
-    p.nsubB = p.use2h ? gemm2h_nsub(p.xB.hi != nullptr, p.KbB) : 1;
+    p.nsubA = p.use2h ? gemm2h_nsub(p.xA.hi != nullptr, p.KbA, kn.g2_nsub) : 1;
+    p.nsubB = p.use2h ? gemm2h_nsub(p.xB.hi != nullptr, p.KbB, kn.g2_nsub) : 1;
     if (p.use3 && !p.usec && !p.use2g && (rc = ensure_planes(ctx))) return rc;
     p.jwA = (p.usec || p.use2g) ? G3C_JW : G3_JW;
     *out = p;
@@ -267,10 +201,7 @@ struct BatchRun {
     int fin_y = 1, lag = 2;                          // finalize blocks per slot; iterations the inspected snapshot lies behind
     int chunksW, partsW, chunksH, partsH;
     float l1W, l2W, l1H, l2H;
-    // The plan of the two GEMM passes at the current width, on the pipe `ps.use3` names (plan_passes)
-    int nsplit = 1, nsplit3 = 1, nsplitA = 1;
-    StreamK sk;
-    StreamK3 sk3;
+    PassPlan plan;                                   // the two GEMM passes at the current width, on the pipe `ps.use3` names (plan_passes)
     // HIP events around the two GEMM passes of every `time_stride`-th iteration (an event record costs
     // ~6 us of queue time: bracketing every launch would take 4 % off the throughput it measures)
     int time_stride = 0;
@@ -281,26 +212,15 @@ struct BatchRun {
     BatchRun(int n_, const int32_t* kk_, int KC, const double* hint, bool dbg) : n(n_), kk(kk_), sched(n_, kk_, KC, hint, dbg) {}
 };
 
-// The plan of the two GEMM passes at the current width KC, on the pipe `use3` names: K splits of pass B (nsplit3 on
-// the split-operand kernels, nsplit on the f32 pipe), and pass A either as a stream-K plan (sk3 / sk, its cut flags
-// uploaded to d_split) or, on few tiles, as nsplitA K splits + reduce.  cap / capA: the partial planes the product
-// buffers hold at this width.  Made before the loop, and again whenever compact() narrows the batch.
+// The plan of the two GEMM passes at the current width KC (plan_pass_splits, pass_plan.h), the cut flags of a stream-K
+// pass A uploaded to d_split.  cap / capA: the partial planes the product buffers hold at this width.  Made before the
+// loop, and again whenever compact() narrows the batch.
 static int plan_passes(BatchRun& b, int cap, int capA)
 {
     cnmf_ctx* ctx = b.ctx;
-    const int KC = b.sched.KC;
-    const std::vector<unsigned char>* flags = nullptr;
-    if (b.ps.use3) {
-        b.nsplit3 = std::max(1, std::min(pick_nsplit3(ctx, KC, b.ps.jwA), cap));
-        b.sk3 = plan_streamk3(KC, ctx->N_pad, ctx->G_pad, gemm3_wg_slots(ctx->knobs), b.ps.jwA, b.ps.nsubA);
-        if (b.sk3.on) flags = &b.sk3.flags;
-        else b.nsplitA = std::max(1, std::min(pick_nsplit_A3(ctx, KC, b.ps.jwA), capA));
-    } else {
-        b.nsplit = std::max(1, std::min(pick_nsplit(ctx, KC), cap));
-        b.sk = plan_streamk(KC, ctx->N_pad, ctx->G_pad, 2 * 256);       // T-layout pass A: 2 workgroups per CU (73.7 KB LDS each)
-        if (b.sk.on) { flags = &b.sk.split; b.nsplitA = 1; }
-        else b.nsplitA = std::max(1, std::min(pick_nsplit_A(ctx, KC), capA));
-    }
+    PassPlan& p = b.plan;
+    plan_pass_splits(p, pad_shape(ctx), b.sched.KC, b.ps.use3, b.ps.jwA, b.ps.nsubA, gemm3_wg_slots(ctx->knobs), ctx->knobs.no_streamk, cap, capA);
+    const std::vector<unsigned char>* flags = b.ps.use3 ? (p.sk3.on ? &p.sk3.flags : nullptr) : (p.sk.on ? &p.sk.split : nullptr);
     // (the flags of the old plan may still be read by an in-flight sweep: same stream -> ordered)
     if (flags) HIP_TRY(ctx, hipMemcpyAsync(ctx->bat.d_split, flags->data(), flags->size(), hipMemcpyHostToDevice, b.st));
     return CNMF_OK;
@@ -432,23 +352,24 @@ static int refill(BatchRun& b, int& n_new)
 
 // ---- step 2: the launches of one coordinate-descent outer iteration, in order
 // pass A : XHt[KC][N] = H_all . X^T                       (sklearn _nmf.py:387)
-// *spA: where the W sweep finds the stream-K partial planes (plane1 = NULL: one plane, after launch_reduce_splits)
-static int launch_pass_a(BatchRun& b, int n_new, unsigned long long livemask, hipEvent_t ev_begin, SplitInfo* spA)
+// *cutA: where the W sweep finds the stream-K partial planes (plane1 = NULL: one plane, after launch_reduce_splits)
+static int launch_pass_a(BatchRun& b, int n_new, unsigned long long livemask, hipEvent_t ev_begin, CutPlanes* cutA)
 {
     cnmf_ctx* ctx = b.ctx;
     hipStream_t st = b.st;
     const PassScheme& ps = b.ps;
-    const int KC = b.sched.KC;
+    const PassPlan& pl = b.plan;
+    const int KC = b.sched.KC, gm = ctx->knobs.gemm3;
     const long long plane = (long long)KC * ctx->N_pad;
-    *spA = SplitInfo{nullptr, nullptr, 1, 1, 1};
+    *cutA = NO_CUT;
     if (!ps.use3) {
-        if (b.sk.on) {
-            HIP_TRY(ctx, launch_streamk_passA(st, b.sk, ctx->bat.H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->bat.XHt,
+        if (pl.sk.on) {
+            HIP_TRY(ctx, launch_streamk_passA(st, pl.sk, ctx->bat.H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->bat.XHt,
                                               ctx->bat.XHt1, ctx->N_pad, ctx->N_pad));
-            *spA = SplitInfo{ctx->bat.XHt1, ctx->bat.d_split, 128, b.sk.mw, b.sk.MG};
+            *cutA = CutPlanes{ctx->bat.XHt1, ctx->bat.d_split, 128, pl.sk.mw, pl.sk.MG, nullptr};
         } else
             HIP_TRY(ctx, launch_gemm<false>(st, 0, ctx->bat.H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->bat.XHt,
-                                            ctx->N_pad, plane, KC, ctx->G_pad, ctx->N_pad, b.nsplitA));
+                                            ctx->N_pad, plane, KC, ctx->G_pad, ctx->N_pad, pl.nsplitA));
         return CNMF_OK;
     }
     // H3 was produced together with the previous iteration's H finalize; rows installed since then
@@ -460,25 +381,26 @@ static int launch_pass_a(BatchRun& b, int n_new, unsigned long long livemask, hi
     } else if (n_new > 0 || !b.h3_valid)
         HIP_TRY(ctx, launch_split3(st, ctx->bat.H, ctx->G_pad, KC, ctx->G_pad, ctx->bat.H3, G3_MW, ps.usec ? ctx->counts.d_scale : nullptr));
     if (ev_begin) hipEventRecord(ev_begin, st);          // (timed iterations: the pass without the split in front of it)
-    if (b.sk3.on) {
-        if (ps.use2h)
-            HIP_TRY(ctx, launch_gemm2h_streamk(st, b.sk3, ctx->bat.H3, ps.xA.plane, ps.xA.hi, ps.xA.flags, ctx->bat.iscaleH, ps.KbA,
-                                               ctx->bat.XHt, ctx->bat.XHt1, ctx->bat.XHt2, ctx->N_pad, ps.xA.colscale, livemask));
-        else if (ps.usec)
-            HIP_TRY(ctx, launch_gemm3c_streamk(st, b.sk3, ctx->bat.H3, ps.xA.plane, ps.xA.hi, ps.xA.flags, ctx->bat.XHt, ctx->bat.XHt1,
+    if (ps.use2h) {
+        G2Launch g;
+        g.A2 = ctx->bat.H3; g.rscale = ctx->bat.iscaleH; g.x = ps.xA; g.Kb = ps.KbA;
+        g.C[0] = ctx->bat.XHt; g.C[1] = ctx->bat.XHt1; g.C[2] = ctx->bat.XHt2; g.ldc = ctx->N_pad;
+        g.livemask = livemask; g.kn = &ctx->knobs;
+        if (pl.sk3.on) { g.sk = &pl.sk3; HIP_TRY(ctx, launch_gemm2h_streamk(st, g)); }
+        else { g.cstride = plane; g.KC = KC; g.Jpad = ctx->N_pad; g.nsplit = pl.nsplitA; HIP_TRY(ctx, launch_gemm2h(st, g)); }
+    } else if (pl.sk3.on) {
+        if (ps.usec)
+            HIP_TRY(ctx, launch_gemm3c_streamk(st, pl.sk3, ctx->bat.H3, ps.xA.plane, ps.xA.hi, ps.xA.flags, ctx->bat.XHt, ctx->bat.XHt1,
                                                ctx->bat.XHt2, ctx->N_pad));
         else
-            HIP_TRY(ctx, launch_gemm3_streamk(st, b.sk3, ctx->bat.H3, ctx->planes.X3, ctx->bat.XHt, ctx->bat.XHt1, ctx->bat.XHt2, ctx->N_pad));
-        *spA = SplitInfo{ctx->bat.XHt1, ctx->bat.d_split, ps.jwA, G3_MW, b.sk3.MG, ctx->bat.XHt2};
-    } else if (ps.use2h)
-        HIP_TRY(ctx, launch_gemm2h(st, ctx->bat.H3, ps.xA.plane, ps.xA.hi, ps.xA.flags, ctx->bat.iscaleH, ps.KbA, ctx->bat.XHt, ctx->N_pad,
-                                   plane, KC, ctx->N_pad, b.nsplitA, ps.xA.colscale, livemask));
-    else if (ps.usec)
+            HIP_TRY(ctx, launch_gemm3_streamk(st, pl.sk3, ctx->bat.H3, ctx->planes.X3, ctx->bat.XHt, ctx->bat.XHt1, ctx->bat.XHt2, ctx->N_pad, gm));
+    } else if (ps.usec)
         HIP_TRY(ctx, launch_gemm3c(st, ctx->bat.H3, ps.xA.plane, ps.xA.hi, ps.xA.flags, ctx->G_pad / 16, ctx->bat.XHt, ctx->N_pad,
-                                   plane, KC, ctx->N_pad, b.nsplitA));
+                                   plane, KC, ctx->N_pad, pl.nsplitA));
     else
         HIP_TRY(ctx, launch_gemm3(st, ctx->bat.H3, ctx->planes.X3, ctx->G_pad / 16, ctx->bat.XHt, ctx->N_pad,
-                                  plane, KC, ctx->N_pad, b.nsplitA));
+                                  plane, KC, ctx->N_pad, pl.nsplitA, gm));
+    if (pl.sk3.on) *cutA = CutPlanes{ctx->bat.XHt1, ctx->bat.d_split, ps.jwA, G3_MW, pl.sk3.MG, ctx->bat.XHt2};
     return CNMF_OK;
 }
 
@@ -520,43 +442,52 @@ static int launch_pass_b(BatchRun& b, unsigned long long livemask, int* nsB)
     cnmf_ctx* ctx = b.ctx;
     hipStream_t st = b.st;
     const PassScheme& ps = b.ps;
+    const PassPlan& pl = b.plan;
     const int KC = b.sched.KC;
     const long long plane = (long long)KC * ctx->G_pad;
-    *nsB = ps.use2h ? gemm2h_splits(ps.KbB, b.nsplit3, ps.nsubB) : (ps.use3 ? b.nsplit3 : b.nsplit);
-    if (ps.use2h)
-        HIP_TRY(ctx, launch_gemm2h(st, ctx->bat.Wt3, ps.xB.plane, ps.xB.hi, ps.xB.flags, ctx->bat.iscaleW, ps.KbB, ctx->bat.XtW, ctx->G_pad,
-                                   plane, KC, ctx->G_pad, b.nsplit3, ps.xB.colscale, livemask));
-    else if (ps.usec)
+    *nsB = ps.use2h ? gemm2h_splits(ps.KbB, pl.nsplit3, ps.nsubB) : (ps.use3 ? pl.nsplit3 : pl.nsplit);
+    if (ps.use2h) {
+        G2Launch g;
+        g.A2 = ctx->bat.Wt3; g.rscale = ctx->bat.iscaleW; g.x = ps.xB; g.Kb = ps.KbB;
+        g.C[0] = ctx->bat.XtW; g.ldc = ctx->G_pad; g.livemask = livemask; g.kn = &ctx->knobs;
+        g.cstride = plane; g.KC = KC; g.Jpad = ctx->G_pad; g.nsplit = pl.nsplit3;
+        HIP_TRY(ctx, launch_gemm2h(st, g));
+    } else if (ps.usec)
         HIP_TRY(ctx, launch_gemm3c(st, ctx->bat.Wt3, ps.xB.plane, ps.xB.hi, ps.xB.flags, ctx->N_pad / 16, ctx->bat.XtW, ctx->G_pad,
-                                   plane, KC, ctx->G_pad, b.nsplit3));
+                                   plane, KC, ctx->G_pad, pl.nsplit3));
     else if (ps.use3)
         HIP_TRY(ctx, launch_gemm3(st, ctx->bat.Wt3, ctx->planes.Xt3, ctx->N_pad / 16, ctx->bat.XtW, ctx->G_pad,
-                                  plane, KC, ctx->G_pad, b.nsplit3));
+                                  plane, KC, ctx->G_pad, pl.nsplit3, ctx->knobs.gemm3));
     else
         HIP_TRY(ctx, launch_gemm<true>(st, 0, ctx->bat.Wt, ctx->N_pad, ctx->X, ctx->G_pad, ctx->bat.XtW,
-                                       ctx->G_pad, plane, KC, ctx->N_pad, ctx->G_pad, b.nsplit));
+                                       ctx->G_pad, plane, KC, ctx->N_pad, ctx->G_pad, pl.nsplit));
     return CNMF_OK;
+}
+
+// what every sweep on the batch buffers shares: the slot table and the partials its finalize reduces
+static SweepLaunch batch_sweep(const cnmf_ctx* ctx, int nslots, int kmax, int tiers)
+{
+    SweepLaunch s;
+    s.nslots = nslots; s.kmax = kmax; s.tiers = tiers;
+    s.slots = ctx->bat.d_slots; s.gram_part = ctx->bat.gram_part; s.viol_part = ctx->bat.viol_part;
+    return s;
 }
 
 // H half-step.  On the f16 path the split-K partials are summed (and scaled by d) inside the sweep itself.
 static int launch_h_sweep(BatchRun& b, int tiers, int nsB)
 {
     cnmf_ctx* ctx = b.ctx;
-    hipStream_t st = b.st;
     const PassScheme& ps = b.ps;
-    const int KC = b.sched.KC, nslots = b.sched.nslots;
-    const long long plane = (long long)KC * ctx->G_pad;
+    const long long plane = (long long)b.sched.KC * ctx->G_pad;
+    SweepLaunch s = batch_sweep(ctx, b.sched.nslots, b.max_k, tiers);
+    s.V = ctx->bat.H; s.ldv = ctx->G_pad; s.L = b.G; s.P = ctx->bat.XtW; s.gram = ctx->bat.gramW; s.l1 = b.l1H;
+    s.chunks = b.chunksH; s.parts = b.partsH; s.want_gram = 1;
+    if (ps.use2h) { s.rmax_part = ctx->bat.rmaxH; s.rmax_scale = ps.dsc; }
     if (ps.use2h && !ctx->knobs.no_psum && !(tiers & 8)) {      // (ranks above 64 take the separately reduced product)
-        HIP_TRY(ctx, launch_sweep(st, nslots, ctx->bat.H, ctx->G_pad, b.G, ctx->bat.XtW, ctx->bat.gramW,
-                                  ctx->bat.d_slots, b.l1H, ctx->bat.gram_part, ctx->bat.viol_part, b.chunksH, b.partsH, 1, b.max_k, tiers,
-                                  psum_info(nsB, plane, ps.dsc), ctx->bat.rmaxH, ps.dsc, true));
-    } else {
-        HIP_TRY(ctx, launch_reduce_splits(st, ctx->bat.XtW, nsB, plane, plane, ps.usec ? ps.dsc : nullptr, ctx->G_pad));
-        HIP_TRY(ctx, launch_sweep(st, nslots, ctx->bat.H, ctx->G_pad, b.G, ctx->bat.XtW, ctx->bat.gramW,
-                                  ctx->bat.d_slots, b.l1H, ctx->bat.gram_part, ctx->bat.viol_part, b.chunksH, b.partsH, 1, b.max_k, tiers,
-                                  SplitInfo{nullptr, nullptr, 1, 1, 1}, ps.use2h ? ctx->bat.rmaxH : nullptr,
-                                  ps.use2h ? ps.dsc : nullptr));
-    }
+        s.from = SweepLaunch::SPLIT_SUM; s.sum = SplitSum{nsB, plane, ps.dsc};
+    } else
+        HIP_TRY(ctx, launch_reduce_splits(b.st, ctx->bat.XtW, nsB, plane, plane, ps.usec ? ps.dsc : nullptr, ctx->G_pad));
+    HIP_TRY(ctx, launch_sweep(b.st, s));
     return CNMF_OK;
 }
 
@@ -614,18 +545,20 @@ static int iterate(BatchRun& b, int n_new)
         ev = &b.gev[b.gev.size() - 4];
         hipEventRecord(ev[0], st);
     }
-    SplitInfo spA;
-    if ((rc = launch_pass_a(b, n_new, livemask, ev ? ev[0] : nullptr, &spA))) return rc;
+    SweepLaunch w = batch_sweep(ctx, sc.nslots, b.max_k, tiers);
+    if ((rc = launch_pass_a(b, n_new, livemask, ev ? ev[0] : nullptr, &w.cut))) return rc;
     if (ev) hipEventRecord(ev[1], st);
-    if (!spA.plane1)
-        HIP_TRY(ctx, launch_reduce_splits(st, ctx->bat.XHt, ps.use2h ? gemm2h_splits(ps.KbA, b.nsplitA, ps.nsubA) : b.nsplitA,
+    if (w.cut.plane1) w.from = SweepLaunch::CUT_PLANES;
+    else
+        HIP_TRY(ctx, launch_reduce_splits(st, ctx->bat.XHt, ps.use2h ? gemm2h_splits(ps.KbA, b.plan.nsplitA, ps.nsubA) : b.plan.nsplitA,
                                           (long long)sc.KC * ctx->N_pad, (long long)sc.KC * ctx->N_pad));
     // W half-step                                             (sklearn _nmf.py:500)
-    const bool fuse_now = b.fuseW && ps.use2h;
-    HIP_TRY(ctx, launch_sweep(st, sc.nslots, ctx->bat.Wt, ctx->N_pad, b.N, ctx->bat.XHt, ctx->bat.gramH,
-                              ctx->bat.d_slots, b.l1W, ctx->bat.gram_part, ctx->bat.viol_part, b.chunksW, b.partsW, 1, b.max_k, tiers, spA,
-                              ps.use2h ? ctx->bat.rmaxW : nullptr, nullptr, false,
-                              fuse_now ? PlaneOut{(unsigned short*)ctx->bat.Wt3, b.shW[b.shgen], ps.KbB, G3_MW} : PlaneOut{nullptr, nullptr, 0, 0}));
+    w.V = ctx->bat.Wt; w.ldv = ctx->N_pad; w.L = b.N; w.P = ctx->bat.XHt; w.gram = ctx->bat.gramH; w.l1 = b.l1W;
+    w.chunks = b.chunksW; w.parts = b.partsW; w.want_gram = 1;
+    if (ps.use2h) w.rmax_part = ctx->bat.rmaxW;
+    const PlaneOut wplanes{(unsigned short*)ctx->bat.Wt3, b.shW[b.shgen], ps.KbB, G3_MW};
+    if (b.fuseW && ps.use2h) w.planes = &wplanes;
+    HIP_TRY(ctx, launch_sweep(st, w));
     if ((rc = launch_w_finalize(b))) return rc;
     if (ev) hipEventRecord(ev[2], st);
     int nsB = 1;
@@ -749,7 +682,7 @@ static int pick_batch_width(cnmf_ctx* ctx, const cnmf_cd_params* prm, int64_t to
     // of four 256-column rounds, 17 -> 8 ms per job); CNMF_WIDE_SMALL=0: the round-5 rule (A/B)
     const bool wide_small = total_k >= 512 && kn.wide_small;
     const bool wide_auto = wide_can && ((int64_t)ctx->N_pad * ctx->G_pad >= (1ll << 24) || wide_small);
-    int KC = pick_kc(ctx, total_k, max_k, prm->kc_max, (prm->kc_max > 256 || kn.kc_set) ? wide_can : wide_auto);
+    int KC = pick_kc(kn.kc, kn.kc_limit, total_k, max_k, prm->kc_max, (prm->kc_max > 256 || kn.kc_set) ? wide_can : wide_auto);
     // 65..128 columns of a count-structured matrix: the 256-column integer-plane kernels (half empty) are still
     // faster than 128 columns on the f32 pipe
     if (KC == 128 && prm->kc_max <= 0 && !kn.kc_set && kn.gemm3 >= 3 && gemm3_enabled(ctx, 256) &&
@@ -808,7 +741,6 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
 {
     if (!ctx) { SET_ERR(ctx, "ctx is NULL"); return CNMF_EINVAL; }
     if (int rcd_ = ensure_dense(ctx)) return rcd_;
-    KnobScope knob_scope(ctx);
     const CdKnobs& kn = ctx->knobs;
     int rc = validate_params(ctx, prm);
     if (rc) return rc;
@@ -862,7 +794,7 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
     POOL_TRY(ctx, b.events);
     HIP_TRY(ctx, hipEventRecord(b.ev_begin, b.st));
     if ((rc = plan_passes(b, ctx->bat.nsplit, ctx->bat.nsplitA))) return rc;
-    b.nsplit3_first = b.nsplit3;
+    b.nsplit3_first = b.plan.nsplit3;
 
     while (true) {
         int n_new = 0;
@@ -926,7 +858,6 @@ extern "C" int cnmf_nnls(cnmf_ctx* ctx, int k, const float* Hin, const cnmf_cd_p
                          float* W_out, int32_t* n_iter_out, double* viol_out)
 {
     if (!ctx) { SET_ERR(ctx, "ctx is NULL"); return CNMF_EINVAL; }
-    KnobScope knob_scope(ctx);
     if (int rcd_ = ensure_dense(ctx)) return rcd_;
     int rc = validate_params(ctx, prm);
     if (rc) return rc;
@@ -956,7 +887,9 @@ extern "C" int cnmf_nnls(cnmf_ctx* ctx, int k, const float* Hin, const cnmf_cd_p
     HIP_TRY(ctx, hipMemcpyAsync(ctx->bat.d_slot_list, ctx->bat.h_slot_list, sizeof(int), hipMemcpyHostToDevice, st));
     gram_rows_kernel<<<1, 256, 0, st>>>(ctx->bat.H, ctx->G_pad, G, ctx->bat.d_slots, ctx->bat.d_slot_list, ctx->bat.gramH, (float)prm->l2_reg_W);
     HIP_TRY(ctx, launch_gemm<false>(st, 0, ctx->bat.H, ctx->G_pad, ctx->X, ctx->G_pad, ctx->bat.XHt, ctx->N_pad, 0, KC, ctx->G_pad, ctx->N_pad, 1));
-    const int chunksW = sweep_chunks(ctx, N), partsW = sweep_parts(ctx, N);
+    SweepLaunch sw = batch_sweep(ctx, 1, k, k <= 16 ? 1 : (k <= 32 ? 2 : (k <= KSMALL ? 4 : 8)));
+    sw.V = ctx->bat.Wt; sw.ldv = ctx->N_pad; sw.L = N; sw.P = ctx->bat.XHt; sw.gram = ctx->bat.gramH; sw.l1 = (float)prm->l1_reg_W;
+    sw.chunks = sweep_chunks(ctx, N); sw.parts = sweep_parts(ctx, N);
     DevPool pool;
     EventPool events;
     hipEvent_t ev = events.get(hipEventDisableTiming);
@@ -968,10 +901,8 @@ extern "C" int cnmf_nnls(cnmf_ctx* ctx, int k, const float* Hin, const cnmf_cd_p
     SlotDesc* snap = ctx->bat.h_snap;
     for (int it = 0; it < prm->max_iter && !done; it += burst) {
         for (int b = 0; b < burst; ++b) {
-            HIP_TRY(ctx, launch_sweep(st, 1, ctx->bat.Wt, ctx->N_pad, N, ctx->bat.XHt, ctx->bat.gramH,
-                                      ctx->bat.d_slots, (float)prm->l1_reg_W, ctx->bat.gram_part, ctx->bat.viol_part,
-                                      chunksW, partsW, 0, k, k <= 16 ? 1 : (k <= 32 ? 2 : (k <= KSMALL ? 4 : 8))));
-            finalize_kernel<<<dim3(1, 1), 256, 0, st>>>(ctx->bat.gram_part, ctx->bat.viol_part, partsW, ctx->bat.gramW, 0.f,
+            HIP_TRY(ctx, launch_sweep(st, sw));
+            finalize_kernel<<<dim3(1, 1), 256, 0, st>>>(ctx->bat.gram_part, ctx->bat.viol_part, sw.parts, ctx->bat.gramW, 0.f,
                                                ctx->bat.d_slots, 2, prm->tol, prm->max_iter, 0, k);
         }
         HIP_TRY(ctx, hipMemcpyAsync(snap, ctx->bat.d_slots, sizeof(SlotDesc), hipMemcpyDeviceToHost, st));

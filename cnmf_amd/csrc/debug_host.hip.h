@@ -6,7 +6,6 @@
 extern "C" int cnmf_x_matmul(cnmf_ctx* ctx, int trans, const float* Q, int ncols, float* out)
 {
     if (!ctx || !Q || !out) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
-    KnobScope knob_scope(ctx);
     if (int rcd_ = ensure_dense(ctx)) return rcd_;
     if (ncols < 1 || ncols > 256 || (trans != 0 && trans != 1)) { SET_ERR(ctx, "bad ncols/trans"); return CNMF_EINVAL; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -49,7 +48,6 @@ extern "C" int cnmf_debug_gemm(cnmf_ctx* ctx, int mode, int variant, const float
     if (KC % 32 || K % 32 || J % 32 || nsplit < 1 || (mode != 0 && mode != 1)) {
         SET_ERR(ctx, "debug_gemm needs KC,K,J multiples of 32"); return CNMF_EINVAL;
     }
-    KnobScope knob_scope(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const int Jp = round_up(J, 128);           // J padded like N_pad so any tile shape is addressable
@@ -72,8 +70,8 @@ extern "C" int cnmf_debug_gemm(cnmf_ctx* ctx, int mode, int variant, const float
     for (int i = 0; i < reps + 1; ++i) {
         if (i == 1) hipEventRecord(e0, st);
         hipError_t e = (mode == 0)
-            ? launch_gemm<false>(st, variant, dA, Kp, dB, Kp, dC, Jp, (long long)KC * Jp, KC, Kp, Jp, 1)
-            : launch_gemm<true>(st, variant, dA, Kp, dB, J, dC, Jp, (long long)KC * Jp, KC, Kp, J, nsplit);
+            ? launch_gemm<false>(st, variant, dA, Kp, dB, Kp, dC, Jp, (long long)KC * Jp, KC, Kp, Jp, 1, ctx->knobs.s_mtw2)
+            : launch_gemm<true>(st, variant, dA, Kp, dB, J, dC, Jp, (long long)KC * Jp, KC, Kp, J, nsplit, ctx->knobs.s_mtw2);
         HIP_TRY(ctx, e);
     }
     hipEventRecord(e1, st);
@@ -99,7 +97,6 @@ extern "C" int cnmf_debug_gemm3(cnmf_ctx* ctx, const float* A, const float* B, f
 {
     if (!ctx || !A || !B || !C) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     if (KC % 256 || K % 16 || J < 1 || nsplit < 1) { SET_ERR(ctx, "debug_gemm3 needs KC %% 256 == 0, K %% 16 == 0"); return CNMF_EINVAL; }
-    KnobScope knob_scope(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const int Jp = round_up(J, gemm3_jw()), Kb = K / 16;
@@ -121,7 +118,7 @@ extern "C" int cnmf_debug_gemm3(cnmf_ctx* ctx, const float* A, const float* B, f
     int zs = 1;
     for (int i = 0; i < reps + 1; ++i) {
         if (i == 1) hipEventRecord(e0, st);
-        HIP_TRY(ctx, launch_gemm3(st, dA3, dB3, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit));
+        HIP_TRY(ctx, launch_gemm3(st, dA3, dB3, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit, ctx->knobs.gemm3));
     }
     hipEventRecord(e1, st);
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -262,17 +259,20 @@ extern "C" int cnmf_debug_gemm2h(cnmf_ctx* ctx, const float* A, const float* Bn,
     const int var = (nsub >> 4) & 7;                     // (upper bits of `nsub`: instruction-stream variant, A/B probes)
     nsub &= 15;
     const int ns = (!has_hi && nsub == 2 && Kb % 2 == 0) ? 2 : 1;
+    G2Launch g;                                          // (the instantiation is chosen here, not by g2_form: no knobs)
+    g.A2 = dA2; g.rscale = dInv; g.x = XOperand{dB1, dBh, dFl, nullptr}; g.Kb = Kb;
+    g.C[0] = dC; g.ldc = Jp; g.cstride = (long long)KC * Jp; g.KC = KC; g.Jpad = Jp; g.nsplit = nsplit;
     for (int i = 0; i < reps + 1; ++i) {
         if (i == 1) hipEventRecord(e0, st);
         hipError_t e;
-        if (has_hi) e = launch_gemm2h_t<1, true>(st, dA2, dB1, dBh, dFl, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
-        else if (ns == 2 && var == 2) e = launch_gemm2h_t<2, false, 2>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
-        else if (ns == 2 && var == 3) e = launch_gemm2h_t<2, false, 3>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
-        else if (ns == 2 && var == 4) e = launch_gemm2h_t<2, false, 4>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
-        else if (ns == 2 && var == 6) e = launch_gemm2h_t<2, false, 6>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
-        else if (ns == 2 && var == 7) e = launch_gemm2h_t<2, false, 7>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
-        else if (ns == 2) e = launch_gemm2h_t<2, false, 0>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
-        else e = launch_gemm2h_t<1, false>(st, dA2, dB1, nullptr, nullptr, dInv, Kb, dC, Jp, (long long)KC * Jp, KC, Jp, nsplit);
+        if (has_hi) e = launch_gemm2h_t<1, true>(st, g);
+        else if (ns == 2 && var == 2) e = launch_gemm2h_t<2, false, 2>(st, g);
+        else if (ns == 2 && var == 3) e = launch_gemm2h_t<2, false, 3>(st, g);
+        else if (ns == 2 && var == 4) e = launch_gemm2h_t<2, false, 4>(st, g);
+        else if (ns == 2 && var == 6) e = launch_gemm2h_t<2, false, 6>(st, g);
+        else if (ns == 2 && var == 7) e = launch_gemm2h_t<2, false, 7>(st, g);
+        else if (ns == 2) e = launch_gemm2h_t<2, false, 0>(st, g);
+        else e = launch_gemm2h_t<1, false>(st, g);
         HIP_TRY(ctx, e);
     }
     hipEventRecord(e1, st);

@@ -2,11 +2,12 @@
 // detection (included by cnmf_hip.hip after runtime.hip.h).
 #pragma once
 
+#include "pass_plan.h"
+
 // ------------------------------------------------------------------ GEMM dispatch
 // variant : 0 = auto; 1 = "S" (waves split components, 32 j per workgroup);
 //           2 = "T" (every wave owns all the workgroup's components, 128 j per workgroup)
 //           3 = 2x2 wave grid (64 j per workgroup)
-struct GemmPlan { int variant; int mw; int jw; };
 
 template <int MTW, int WM, int WN, bool NN, int TBK = BK>
 static hipError_t launch_gemm_t(hipStream_t st, const float* A, int lda, const float* B, int ldb,
@@ -25,24 +26,10 @@ static hipError_t launch_gemm_t(hipStream_t st, const float* A, int lda, const f
     return hipGetLastError();
 }
 
-// The launchers and planners below carry no context: they read the switches (CdKnobs, runtime.hip.h) of the context whose
-// call is running on this thread.  Every entry point that reaches one of them holds a KnobScope for the length of the call;
-// between calls the pointer names the built-in defaults, never a context (which may be destroyed from any thread).  Code
-// that has the context in hand reads ctx->knobs and does not depend on this.
-static const CdKnobs k_default_knobs;
-static thread_local const CdKnobs* g_knobs = &k_default_knobs;
-struct KnobScope {
-    const CdKnobs* prev;
-    explicit KnobScope(const cnmf_ctx* ctx) : prev(g_knobs) { g_knobs = &ctx->knobs; }
-    ~KnobScope() { g_knobs = prev; }
-    KnobScope(const KnobScope&) = delete;
-    KnobScope& operator=(const KnobScope&) = delete;
-};
-
 template <bool NN>
 static hipError_t launch_gemm(hipStream_t st, int variant, const float* A, int lda, const float* B,
                               int ldb, float* C, int ldc, long long cstride, int KC, int Ktot,
-                              int J, int nsplit)
+                              int J, int nsplit, bool s_mtw2 = false)   // s_mtw2: CNMF_S_MTW2 (the diagnostic "S" layout only)
 {
 #define GO(MTW, WM, WN) \
     return launch_gemm_t<MTW, WM, WN, NN>(st, A, lda, B, ldb, C, ldc, cstride, KC, Ktot, J, nsplit)
@@ -51,7 +38,7 @@ static hipError_t launch_gemm(hipStream_t st, int variant, const float* A, int l
     if (variant == 3 && KC < 64) variant = 2;
     switch (variant) {
         case 1:  // S: 4 waves x (MTW tiles of 32 comps), 32 j
-            if (KC % 256 == 0 && KC >= 256 && g_knobs->s_mtw2) GO(2, 4, 1);
+            if (KC % 256 == 0 && KC >= 256 && s_mtw2) GO(2, 4, 1);
             GO(1, 4, 1);
         case 3:  // 2x2
             if (KC % 128 == 0) GO(2, 2, 2);
@@ -65,138 +52,72 @@ static hipError_t launch_gemm(hipStream_t st, int variant, const float* A, int l
 }
 
 // ------------------------------------------------------------------ sweep dispatch
-// SplitInfo of a PSUM sweep (kernels_sweep.hip.h): `nsplit` partial planes `stride` floats apart, scaled per row by
-// `colscale` (nullable).  The fields are re-used: mgroups = nsplit, tile_rows / tile_cols = stride, split = colscale.
-static SplitInfo psum_info(int nsplit, long long stride, const double* colscale)
-{
-    SplitInfo sp{nullptr, reinterpret_cast<const unsigned char*>(colscale), (int)(stride >> 20), (int)(stride & ((1 << 20) - 1)), nsplit};
-    return sp;
-}
+static constexpr CutPlanes NO_CUT{nullptr, nullptr, 1, 1, 1, nullptr};
+static constexpr PlaneOut NO_PLANES{nullptr, nullptr, 0, 0};
 
-static hipError_t launch_sweep(hipStream_t st, int nslots, float* V, int ldv, int L, const float* P,
-                               const float* gram, const SlotDesc* slots, float l1, float* gram_part,
-                               double* viol_part, int chunks, int parts, int want_gram, int kmax, int tiers,
-                               SplitInfo sp = SplitInfo{nullptr, nullptr, 1, 1, 1},
-                               float* rmax_part = nullptr, const double* rmax_scale = nullptr, bool psum = false,
-                               PlaneOut po = PlaneOut{nullptr, nullptr, 0, 0})
+// One half-step sweep over `nslots` slots.  The form of sweep_kernel it takes follows from the fields (sweep_form,
+// pass_plan.h): where the product comes from, whether the row maxima are wanted exactly, whether planes are written.
+struct SweepLaunch {
+    int nslots = 0;
+    float* V = nullptr; int ldv = 0, L = 0;         // the factor being solved, component-major, L valid entries per row
+    const float* P = nullptr;                       // its product with X, as ...
+    enum { ONE_PLANE, CUT_PLANES, SPLIT_SUM } from = ONE_PLANE;
+    CutPlanes cut = NO_CUT;                         // CUT_PLANES: ... the stream-K planes to add where a tile was cut
+    SplitSum sum{1, 0, nullptr};                    // SPLIT_SUM: ... split-K planes summed (and scaled) in the sweep itself
+    const float* gram = nullptr;
+    const SlotDesc* slots = nullptr;
+    float l1 = 0.f;
+    float* gram_part = nullptr; double* viol_part = nullptr;
+    int chunks = 1, parts = 1;                      // a workgroup walks `chunks` 256-row tiles; `parts` workgroups (= partials) per slot
+    int want_gram = 0, kmax = 0, tiers = 0;         // tiers: bit t = a live slot has a rank of tier t (8: ranks 65..128)
+    float* rmax_part = nullptr;                     // row-maximum report: the bound, or with rmax_scale the exact maximum x scale
+    const double* rmax_scale = nullptr;
+    const PlaneOut* planes = nullptr;               // f16 planes of the result written by the sweep (ranks <= 64)
+};
+
+using SweepFn = void (*)(float*, int, int, const float*, SplitInfo, const float*, const SlotDesc*, float, float*, double*, int, int, int,
+                         int, float*, const double*, PlaneOut);
+static constexpr SweepFn SWEEP_KERNELS[6][3] = {    // [SweepForm][tier]
+    {sweep_kernel<0>, sweep_kernel<1>, sweep_kernel<2>},
+    {sweep_kernel<0, false, false, false, true>, sweep_kernel<1, false, false, false, true>, sweep_kernel<2, false, false, false, true>},
+    {sweep_kernel<0, false, false, true>, sweep_kernel<1, false, false, true>, sweep_kernel<2, false, false, true>},
+    {sweep_kernel<0, false, false, true, true>, sweep_kernel<1, false, false, true, true>, sweep_kernel<2, false, false, true, true>},
+    {sweep_kernel<0, true>, sweep_kernel<1, true>, sweep_kernel<2, true>},
+    {sweep_kernel<0, true, true>, sweep_kernel<1, true, true>, sweep_kernel<2, true, true>}};
+
+static hipError_t launch_sweep(hipStream_t st, const SweepLaunch& s)
 {
-    // `parts` = partials per slot = workgroups per slot; a workgroup walks `chunks` 256-row tiles
-    dim3 grid(parts, nslots);
-    // the W half-step kernels address a slot with 32-bit byte offsets from its first column (sweep_body, B32): the
-    // largest is 64 columns * ldv * 4.  A leading dimension too long for 31 bits takes their flat-address form.
-    const bool a64 = 64ll * ldv * 4 > 0x7fffffffll;
-    if (po.dst) {
-        // the W half-step of the f16 paths, planes written by the sweep itself (ranks <= 64 only: the caller checks)
-        if (psum || (rmax_part && rmax_scale) || (tiers & 8) || po.TR != G3_MW) return hipErrorInvalidValue;
-        const size_t pl = sweep_lds_bytes(kmax, true);
-        const int kgp = sweep_kg(kmax);
-        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<0, false, false, true>, (int)sweep_lds_bytes(KSMALL, true))) return e_;
-        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<1, false, false, true>, (int)sweep_lds_bytes(KSMALL, true))) return e_;
-        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<2, false, false, true>, (int)sweep_lds_bytes(KSMALL, true))) return e_;
-#define CNMF_SWEEP_PLN(T_, A_) sweep_kernel<T_, false, false, true, A_><<<grid, 256, pl, st>>>(V, ldv, L, P, sp, gram, slots, l1, gram_part, viol_part, chunks, want_gram, kgp, kmax, rmax_part, nullptr, po)
-        if (a64) {
-            if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<0, false, false, true, true>, (int)sweep_lds_bytes(KSMALL, true))) return e_;
-            if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<1, false, false, true, true>, (int)sweep_lds_bytes(KSMALL, true))) return e_;
-            if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<2, false, false, true, true>, (int)sweep_lds_bytes(KSMALL, true))) return e_;
-            if (tiers & 1) CNMF_SWEEP_PLN(0, true);
-            if (tiers & 2) CNMF_SWEEP_PLN(1, true);
-            if (tiers & 4) CNMF_SWEEP_PLN(2, true);
-            return hipGetLastError();
-        }
-        if (tiers & 1) CNMF_SWEEP_PLN(0, false);
-        if (tiers & 2) CNMF_SWEEP_PLN(1, false);
-        if (tiers & 4) CNMF_SWEEP_PLN(2, false);
-#undef CNMF_SWEEP_PLN
-        return hipGetLastError();
+    const bool pln = s.planes != nullptr, exact = s.rmax_part && s.rmax_scale;
+    const SweepForm form = sweep_form(pln, s.from == SweepLaunch::SPLIT_SUM, exact, sweep_a64(s.ldv), s.tiers);
+    if (form == SweepForm::INVALID || (pln && s.planes->TR != G3_MW)) return hipErrorInvalidValue;
+    SplitInfo sp;
+    if (form == SweepForm::H_PSUM) sp.sum = s.sum;
+    else sp.cut = s.from == SweepLaunch::CUT_PLANES ? s.cut : NO_CUT;
+    const dim3 grid(s.parts, s.nslots);
+    // one launch per rank tier present among the live slots; a launch skips the slots of other tiers at once
+    // (ranks above 32 need more than the default 64 KB of dynamic LDS)
+    for (int t = 0; t < 3; ++t) {
+        if (!(s.tiers & (1 << t))) continue;
+        const SweepFn fn = SWEEP_KERNELS[(int)form][t];
+        if (hipError_t e_ = dyn_lds_optin((const void*)fn, (int)sweep_lds_bytes(KSMALL, pln))) return e_;
+        fn<<<grid, 256, sweep_lds_bytes(s.kmax, pln), st>>>(s.V, s.ldv, s.L, s.P, sp, s.gram, s.slots, s.l1, s.gram_part, s.viol_part, s.chunks,
+                                                           s.want_gram, sweep_kg(s.kmax), s.kmax, s.rmax_part, pln ? nullptr : s.rmax_scale,
+                                                           pln ? *s.planes : NO_PLANES);
     }
-    {      // ranks above 32 need more than the default 64 KB of dynamic LDS
-        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<0, false>, (int)sweep_lds_bytes(KSMALL))) return e_;
-        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<1, false>, (int)sweep_lds_bytes(KSMALL))) return e_;
-        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<2, false>, (int)sweep_lds_bytes(KSMALL))) return e_;
-        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<0, true>, (int)sweep_lds_bytes(KSMALL))) return e_;
-        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<1, true>, (int)sweep_lds_bytes(KSMALL))) return e_;
-        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<2, true>, (int)sweep_lds_bytes(KSMALL))) return e_;
-    }
-    // one launch per rank tier present among the live slots; a launch skips the slots of other tiers at once.
-    // rmax_scale != nullptr selects the exact row-maximum report (the H half-step of the f16 plane split).
-    const size_t lds = sweep_lds_bytes(kmax);
-    const int kg = sweep_kg(kmax);
-#define CNMF_SWEEP(T_, R_) sweep_kernel<T_, R_><<<grid, 256, lds, st>>>(V, ldv, L, P, sp, gram, slots, l1, gram_part, viol_part, chunks, want_gram, kg, kmax, rmax_part, rmax_scale)
-#define CNMF_SWEEP_PSUM(T_) sweep_kernel<T_, true, true><<<grid, 256, lds, st>>>(V, ldv, L, P, sp, gram, slots, l1, gram_part, viol_part, chunks, want_gram, kg, kmax, rmax_part, rmax_scale)
-    if (psum) {                 // split-K partial planes summed (and column-scaled) inside the sweep: sp = psum_info(...)
-        {
-            if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<0, true, true>, (int)sweep_lds_bytes(KSMALL))) return e_;
-            if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<1, true, true>, (int)sweep_lds_bytes(KSMALL))) return e_;
-            if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<2, true, true>, (int)sweep_lds_bytes(KSMALL))) return e_;
-        }
-        if (tiers & 1) CNMF_SWEEP_PSUM(0);
-        if (tiers & 2) CNMF_SWEEP_PSUM(1);
-        if (tiers & 4) CNMF_SWEEP_PSUM(2);
-    } else if (rmax_part && rmax_scale) {
-        if (tiers & 1) CNMF_SWEEP(0, true);
-        if (tiers & 2) CNMF_SWEEP(1, true);
-        if (tiers & 4) CNMF_SWEEP(2, true);
-    } else if (a64) {
-#define CNMF_SWEEP_A64(T_) sweep_kernel<T_, false, false, false, true><<<grid, 256, lds, st>>>(V, ldv, L, P, sp, gram, slots, l1, gram_part, viol_part, chunks, want_gram, kg, kmax, rmax_part, rmax_scale)
-        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<0, false, false, false, true>, (int)sweep_lds_bytes(KSMALL))) return e_;
-        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<1, false, false, false, true>, (int)sweep_lds_bytes(KSMALL))) return e_;
-        if (hipError_t e_ = dyn_lds_optin((const void*)sweep_kernel<2, false, false, false, true>, (int)sweep_lds_bytes(KSMALL))) return e_;
-        if (tiers & 1) CNMF_SWEEP_A64(0);
-        if (tiers & 2) CNMF_SWEEP_A64(1);
-        if (tiers & 4) CNMF_SWEEP_A64(2);
-#undef CNMF_SWEEP_A64
-    } else {
-        if (tiers & 1) CNMF_SWEEP(0, false);
-        if (tiers & 2) CNMF_SWEEP(1, false);
-        if (tiers & 4) CNMF_SWEEP(2, false);
-    }
-#undef CNMF_SWEEP_PSUM
-#undef CNMF_SWEEP
-    if (tiers & 8) {            // ranks 65..128: sweep_big_kernel (+ the Gram of the updated rows as its own launch)
-        if (psum) return hipErrorInvalidValue;                 // the caller reduces the split-K planes first
+    if (s.tiers & 8) {            // ranks 65..128: sweep_big_kernel (+ the Gram of the updated rows as its own launch)
         const size_t blds = sweep_big_lds_bytes();
-        const int bchunks = chunks;
-        const dim3 gbig(parts, nslots);
-        if (rmax_part && rmax_scale) {
-            if (hipError_t e_ = dyn_lds_optin((const void*)sweep_big_kernel<true>, (int)blds)) return e_;
-            sweep_big_kernel<true><<<gbig, 256, blds, st>>>(V, ldv, L, P, sp, gram, slots, l1, viol_part, bchunks, rmax_part, rmax_scale);
-        } else {
-            if (hipError_t e_ = dyn_lds_optin((const void*)sweep_big_kernel<false>, (int)blds)) return e_;
-            sweep_big_kernel<false><<<gbig, 256, blds, st>>>(V, ldv, L, P, sp, gram, slots, l1, viol_part, bchunks, nullptr, nullptr);
-        }
-        if (want_gram)
-            gram_big_kernel<<<gbig, 256, 0, st>>>(V, ldv, L, slots, gram_part, bchunks, kmax, (rmax_part && !rmax_scale) ? rmax_part : nullptr);
+        const auto big = exact ? sweep_big_kernel<true> : sweep_big_kernel<false>;
+        if (hipError_t e_ = dyn_lds_optin((const void*)big, (int)blds)) return e_;
+        big<<<grid, 256, blds, st>>>(s.V, s.ldv, s.L, s.P, sp, s.gram, s.slots, s.l1, s.viol_part, s.chunks, exact ? s.rmax_part : nullptr,
+                                     exact ? s.rmax_scale : nullptr);
+        if (s.want_gram)
+            gram_big_kernel<<<grid, 256, 0, st>>>(s.V, s.ldv, s.L, s.slots, s.gram_part, s.chunks, s.kmax,
+                                                  (s.rmax_part && !s.rmax_scale) ? s.rmax_part : nullptr);
     }
     return hipGetLastError();
 }
 
-// ---- stream-K pass A (T layout: 128 components x 128 cells per tile)
-struct StreamK {
-    bool on = false;
-    int MG = 1, T = 0, nk = 0, P = 0, mw = 128;      // mw: component rows per workgroup tile
-    std::vector<unsigned char> split;
-};
-
-static StreamK plan_streamk(int KC, int N_pad, int G_pad, int n_wg_slots)
-{
-    StreamK sk;
-    if (KC % 128 != 0 || g_knobs->no_streamk) return sk;
-    sk.MG = KC / sk.mw;
-    sk.T = sk.MG * (N_pad / 128);
-    sk.nk = G_pad / BK;                                    // stages per tile, as the kernel counts them
-    sk.P = n_wg_slots;
-    if (sk.T <= sk.P) sk.P = n_wg_slots / 2;              // one workgroup per CU
-    if (sk.T <= sk.P || sk.T % sk.P == 0) return sk;      // nothing to balance
-    sk.on = true;
-    sk.split.assign(sk.T, 0);
-    const long long U = (long long)sk.T * sk.nk;
-    for (int p = 1; p < sk.P; ++p) {
-        const long long b = U * p / sk.P;                  // first unit of workgroup p
-        if (b % sk.nk) sk.split[b / sk.nk] = 1;            // boundary inside a tile -> that tile is cut
-    }
-    return sk;
-}
-
+// ---- stream-K pass A (T layout: 128 components x 128 cells per tile; the plan: plan_streamk, pass_plan.h)
 static hipError_t launch_streamk_passA(hipStream_t st, const StreamK& sk, const float* A, int lda,
                                        const float* B, int ldb, float* C0, float* C1, int ldc, int Jtot)
 {
@@ -242,17 +163,11 @@ static hipError_t launch_split3(hipStream_t st, const float* src, int ld, int ro
 // 2 MFMAs per product.  Tests switch it between calls (cnmf_reload_env).
 // (Tried and dropped, all within 3 % of variant 2 at the 50k x 2000 shape: the same ping-pong with register
 //  staging; 256 x 256 tiles with the two wave groups half a block apart (2/3 of the DMA bytes per flop).)
-static int gemm3_mode() { return g_knobs->gemm3; }
-// (CNMF_WG_SLOTS: fewer persistent GEMM workgroups than CUs -- leaves whole CUs to the kernels of another stream)
-static int gemm3_wg_slots(const CdKnobs& k)
-{
-    if (k.wg_slots >= 32 && k.gemm3 >= 2) return k.wg_slots;
-    return k.gemm3 >= 2 ? 256 : 512;
-}
+static int gemm3_wg_slots(const CdKnobs& k) { return gemm3_wg_slots(k.gemm3, k.wg_slots); }
 static int gemm3_jw() { return G3_JW; }     // j extent of a tile = row tile of the B planes
 
 static hipError_t launch_gemm3(hipStream_t st, const unsigned char* A3, const unsigned char* B3, int Kb,
-                               float* C, int ldc, long long cstride, int KC, int Jpad, int nsplit)
+                               float* C, int ldc, long long cstride, int KC, int Jpad, int nsplit, int gemm3_mode)
 {
     {
         if (hipError_t e_ = dyn_lds_optin((const void*)gemm3_kernel, G3_LDS_BYTES)) return e_;
@@ -260,7 +175,7 @@ static hipError_t launch_gemm3(hipStream_t st, const unsigned char* A3, const un
     }
     const int kb_per = (Kb + nsplit - 1) / nsplit;
     dim3 grid(Jpad / gemm3_jw(), KC / G3_MW, (Kb + kb_per - 1) / kb_per);
-    if (gemm3_mode() >= 2)
+    if (gemm3_mode >= 2)
         gemm3g_kernel<<<grid, 512, G3G_LDS_BYTES, st>>>(A3, B3, Kb, C, ldc, cstride, kb_per);
     else
         gemm3_kernel<<<grid, 256, G3_LDS_BYTES, st>>>(A3, B3, Kb, C, ldc, cstride, kb_per);
@@ -283,45 +198,16 @@ static hipError_t launch_split2h_finalize(hipStream_t st, const float* src, int 
                                           float* inv_scale, const FinalizeArgs& fa, int nslots, int fin_y,
                                           SplitFused fu = SplitFused{nullptr, nullptr});
 
-// ---- stream-K plan for the split-operand pass A (tile = 256 components x 128 cells, up to 2 cuts per tile)
-struct StreamK3 {
-    bool on = false;
-    int T = 0, Kb = 0, P = 0, MG = 1;     // Kb: work units per tile (16-k blocks / `unit`)
-    std::vector<unsigned char> flags;     // bit 0: >= 1 cut (plane 1 holds the tail), bit 1: 2 cuts (plane 2 the middle)
-};
-
-static StreamK3 plan_streamk3(int KC, int N_pad, int G_pad, int n_wg_slots, int jw, int unit = 1)
-{
-    StreamK3 sk;
-    sk.MG = KC / G3_MW;
-    sk.T = sk.MG * (N_pad / jw);
-    sk.Kb = G_pad / (G3_BK * unit);
-    sk.P = n_wg_slots;
-    if (sk.T < sk.P / 2 + sk.P / 4 || sk.P > 2 * sk.T || g_knobs->no_streamk) return sk;   // few tiles: K split + reduce instead
-    sk.on = true;
-    sk.flags.assign(sk.T, 0);
-    const long long U = (long long)sk.T * sk.Kb;
-    // the kernels walk the tiles component-group-major (o = mg * NJ + jt); the sweep looks the flags up by jt * MG + mg
-    const int NJ = sk.T / sk.MG;
-    for (int p = 1; p < sk.P; ++p) {
-        const long long b = U * p / sk.P;
-        if (b % sk.Kb) {
-            const int o = (int)(b / sk.Kb);
-            unsigned char& f = sk.flags[(o % NJ) * sk.MG + o / NJ];
-            f = f ? 3 : 1;
-        }
-    }
-    return sk;
-}
-
+// ---- stream-K pass A of the split-operand kernels (the plan: plan_streamk3, pass_plan.h)
 static hipError_t launch_gemm3_streamk(hipStream_t st, const StreamK3& sk, const unsigned char* A3,
-                                       const unsigned char* B3, float* C0, float* C1, float* C2, int ldc)
+                                       const unsigned char* B3, float* C0, float* C1, float* C2, int ldc,
+                                       int gemm3_mode)
 {
     {
         if (hipError_t e_ = dyn_lds_optin((const void*)gemm3_streamk_kernel, G3_LDS_BYTES)) return e_;
         if (hipError_t e_ = dyn_lds_optin((const void*)gemm3g_streamk_kernel, G3G_LDS_BYTES)) return e_;
     }
-    if (gemm3_mode() >= 2)
+    if (gemm3_mode >= 2)
         gemm3g_streamk_kernel<<<sk.P, 512, G3G_LDS_BYTES, st>>>(A3, B3, sk.Kb, C0, C1, C2, ldc, sk.MG, sk.T);
     else
         gemm3_streamk_kernel<<<sk.P, 256, G3_LDS_BYTES, st>>>(A3, B3, sk.Kb, C0, C1, C2, ldc, sk.MG, sk.T);
@@ -417,126 +303,94 @@ static hipError_t launch_gemm3c_streamk(hipStream_t st, const StreamK3& sk, cons
 // Instruction streams (the VAR parameter of kernels_gemm2h.hip.h): production launches use 4, the spread stream, and 0,
 // the burst loop, on the two-plane count path; general matrices (GEN) take 0 instead of 4 with CNMF_G2_GVAR=0 (same bits).
 
-static inline unsigned long long g2_full_mask(int KC) { const int t = KC / 32; return t >= 64 ? ~0ull : ((1ull << t) - 1ull); }
+// One GEMM pass on the f16 pipe.  Its kernel instantiation is g2_form's (pass_plan.h) from the operand, the knobs, the
+// live mask and -- stream-K -- the number of component groups.
+struct G2Launch {
+    const unsigned char* A2 = nullptr;      // the factor's two f16 planes ...
+    const float* rscale = nullptr;          // ... and its 2^-s per row
+    XOperand x{};                           // X: the count plane(s), or the two planes and column scale of a general matrix
+    int Kb = 0;                             // 16-k blocks of the contraction
+    float* C[3] = {nullptr, nullptr, nullptr};      // output: K-split partial planes from C[0]; stream-K: the plane and its two cut planes
+    int ldc = 0;
+    // livemask: bit t = the 32 packed columns 32 t .. 32 t + 31 hold a restart that still iterates (all ones: everything)
+    unsigned long long livemask = ~0ull;
+    long long cstride = 0; int KC = 0, Jpad = 0, nsplit = 1;    // K split: `nsplit` planes `cstride` floats apart, KC x Jpad each
+    const StreamK3* sk = nullptr;           // ... or stream-K: the plan, made with unit = gemm2h_nsub(x.hi != nullptr, Kb, g2_nsub)
+    const CdKnobs* kn = nullptr;            // reads g2_gen4, g2_gvar, g2_nsub, g2_xmap
+};
+using G2Fn = hipError_t (*)(hipStream_t, const G2Launch&);
+struct G2Entry { G2Form form; G2Fn fn; };
 
 template <int NSUB, bool HI, int VAR = 0, bool PART = false, bool GEN = false>
-static hipError_t launch_gemm2h_t(hipStream_t st, const unsigned char* A2, const unsigned char* B1,
-                                  const unsigned char* Bhi, const unsigned int* hiflag, const float* rscale, int Kb,
-                                  float* C, int ldc, long long cstride, int KC, int Jpad, int nsplit,
-                                  const float* cscale = nullptr, unsigned long long livemask = ~0ull)
+static hipError_t launch_gemm2h_t(hipStream_t st, const G2Launch& g)
 {
     constexpr int lds = g2_lds_bytes(NSUB, HI);
     {
         if (hipError_t e_ = dyn_lds_optin((const void*)gemm2h_kernel<NSUB, HI, VAR, PART, GEN>, lds)) return e_;
     }
-    int kb_per = (Kb + nsplit - 1) / nsplit;
+    int kb_per = (g.Kb + g.nsplit - 1) / g.nsplit;
     kb_per = ((kb_per + NSUB - 1) / NSUB) * NSUB;            // whole steps
-    dim3 grid(Jpad / G3C_JW, KC / G3_MW, (Kb + kb_per - 1) / kb_per);
-    gemm2h_kernel<NSUB, HI, VAR, PART, GEN><<<grid, 512, lds, st>>>(A2, B1, Bhi, hiflag, rscale, Kb, C, ldc, cstride, kb_per, cscale, livemask);
+    dim3 grid(g.Jpad / G3C_JW, g.KC / G3_MW, (g.Kb + kb_per - 1) / kb_per);
+    gemm2h_kernel<NSUB, HI, VAR, PART, GEN><<<grid, 512, lds, st>>>(g.A2, g.x.plane, HI ? g.x.hi : nullptr, HI ? g.x.flags : nullptr, g.rscale,
+                                                                   g.Kb, g.C[0], g.ldc, g.cstride, kb_per, g.x.colscale,
+                                                                   PART ? g.livemask : ~0ull);
     return hipGetLastError();
 }
 
-// number of K splits the launch above will actually use (the partial planes the reduce must add)
-static int gemm2h_splits(int Kb, int nsplit, int nsub)
-{
-    int kb_per = (Kb + nsplit - 1) / nsplit;
-    kb_per = ((kb_per + nsub - 1) / nsub) * nsub;
-    return (Kb + kb_per - 1) / kb_per;
-}
-
-// 16-k sub-blocks per barrier pair: 2 on the one-plane count path (CNMF_G2_NSUB=1: one), 1 with a second X plane
-static int gemm2h_nsub(bool hi, int Kb) { return (!hi && g_knobs->g2_nsub == 2 && Kb % 2 == 0) ? 2 : 1; }
-
-static hipError_t launch_gemm2h(hipStream_t st, const unsigned char* A2, const unsigned char* B1,
-                                const unsigned char* Bhi, const unsigned int* hiflag, const float* rscale, int Kb,
-                                float* C, int ldc, long long cstride, int KC, int Jpad, int nsplit,
-                                const float* cscale = nullptr, unsigned long long livemask = ~0ull)
-{
-    // livemask: bit t = the 32 packed columns 32 t .. 32 t + 31 hold a restart that still iterates (all ones: everything)
-    const bool part = (livemask & g2_full_mask(KC)) != g2_full_mask(KC);
-    // general matrices (cscale != nullptr: X as two f16 planes) multiply three of the four plane pairs (GEN); CNMF_G2_GEN4=1: all four (A/B)
-    if (Bhi && cscale && !g_knobs->g2_gen4) {
-        if (g_knobs->g2_gvar == 0)                 // (A/B: the burst loop of rounds 3-5; bit-identical results)
-            return part ? launch_gemm2h_t<1, true, 0, true, true>(st, A2, B1, Bhi, hiflag, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, cscale, livemask)
-                        : launch_gemm2h_t<1, true, 0, false, true>(st, A2, B1, Bhi, hiflag, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, cscale);
-        return part ? launch_gemm2h_t<1, true, 4, true, true>(st, A2, B1, Bhi, hiflag, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, cscale, livemask)
-                    : launch_gemm2h_t<1, true, 4, false, true>(st, A2, B1, Bhi, hiflag, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, cscale);
-    }
-    if (Bhi) return part ? launch_gemm2h_t<1, true, 0, true>(st, A2, B1, Bhi, hiflag, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, cscale, livemask)
-                         : launch_gemm2h_t<1, true>(st, A2, B1, Bhi, hiflag, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, cscale);
-    if (cscale) return hipErrorInvalidValue;              // a column scale exists only on the two-plane operand path
-    if (gemm2h_nsub(false, Kb) == 2)
-        return part ? launch_gemm2h_t<2, false, 4, true>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit, nullptr, livemask)
-                    : launch_gemm2h_t<2, false, 4>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit);
-    return launch_gemm2h_t<1, false, 4>(st, A2, B1, nullptr, nullptr, rscale, Kb, C, ldc, cstride, KC, Jpad, nsplit);
-}
-
 template <int NSUB, bool HI, int VAR = 0, bool NTB = true, bool PART = false, bool GEN = false>
-static hipError_t launch_gemm2h_streamk_t(hipStream_t st, const StreamK3& sk, const unsigned char* A2,
-                                          const unsigned char* B1, const unsigned char* Bhi,
-                                          const unsigned int* hiflag, const float* rscale, int Kb, float* C0, float* C1,
-                                          float* C2, int ldc, const float* cscale = nullptr,
-                                          unsigned long long livemask = ~0ull)
+static hipError_t launch_gemm2h_streamk_t(hipStream_t st, const G2Launch& g)
 {
     constexpr int lds = g2_lds_bytes(NSUB, HI);
     {
         if (hipError_t e_ = dyn_lds_optin((const void*)gemm2h_streamk_kernel<NSUB, HI, VAR, NTB, PART, GEN>, lds)) return e_;
     }
-    // XCD mapping of the persistent workgroups (kernel comment).  Count path: every XCD inside ONE component group (1).  General
-    // path (GEN: both X planes, 410 MB at 50 000 x 2 000, re-streamed per component group): the identity order (0) -- the four
-    // groups of a row tile share it in one L2 -- measured +1.3 % (133.7 / 134.1 vs 131.9 / 132.4 restarts/s, round 6); the
-    // count path measured -2 % with it (round 3).  CNMF_G2_XMAP=0|1 forces either.
-    const int xmap = g_knobs->g2_xmap >= 0 ? g_knobs->g2_xmap : (GEN ? 0 : 1);
-    gemm2h_streamk_kernel<NSUB, HI, VAR, NTB, PART, GEN><<<sk.P, 512, lds, st>>>(A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, sk.MG, sk.T, xmap, cscale, livemask);
+    const int xmap = g2_xmap(G2Form{true, NSUB, HI, VAR, NTB, PART, GEN}, g.kn->g2_xmap);
+    gemm2h_streamk_kernel<NSUB, HI, VAR, NTB, PART, GEN><<<g.sk->P, 512, lds, st>>>(g.A2, g.x.plane, HI ? g.x.hi : nullptr,
+                                                                                    HI ? g.x.flags : nullptr, g.rscale, g.Kb, g.C[0], g.C[1],
+                                                                                    g.C[2], g.ldc, g.sk->MG, g.sk->T, xmap, g.x.colscale,
+                                                                                    PART ? g.livemask : ~0ull);
     return hipGetLastError();
 }
 
-// (the plan `sk` must have been made with unit = gemm2h_nsub(Bhi != nullptr, Kb))
-static hipError_t launch_gemm2h_streamk(hipStream_t st, const StreamK3& sk, const unsigned char* A2,
-                                        const unsigned char* B1, const unsigned char* Bhi, const unsigned int* hiflag,
-                                        const float* rscale, int Kb, float* C0, float* C1, float* C2, int ldc,
-                                        const float* cscale = nullptr, unsigned long long livemask = ~0ull)
+template <int NSUB, bool HI, int VAR, bool PART, bool GEN>
+static constexpr G2Entry g2_ksplit() { return {G2Form{true, NSUB, HI, VAR, false, PART, GEN}, launch_gemm2h_t<NSUB, HI, VAR, PART, GEN>}; }
+template <int NSUB, bool HI, int VAR, bool NTB, bool PART, bool GEN>
+static constexpr G2Entry g2_streamk() { return {G2Form{true, NSUB, HI, VAR, NTB, PART, GEN}, launch_gemm2h_streamk_t<NSUB, HI, VAR, NTB, PART, GEN>}; }
+
+// the instantiations production launches take: 9 of gemm2h_kernel, 14 of gemm2h_streamk_kernel
+static constexpr G2Entry G2_KSPLIT[] = {
+    g2_ksplit<1, true, 0, false, true>(),  g2_ksplit<1, true, 0, true, true>(),  g2_ksplit<1, true, 4, false, true>(),
+    g2_ksplit<1, true, 4, true, true>(),   g2_ksplit<1, true, 0, false, false>(), g2_ksplit<1, true, 0, true, false>(),
+    g2_ksplit<2, false, 4, false, false>(), g2_ksplit<2, false, 4, true, false>(), g2_ksplit<1, false, 4, false, false>()};
+static constexpr G2Entry G2_STREAMK[] = {
+    g2_streamk<1, true, 0, false, true, true>(),   g2_streamk<1, true, 0, false, false, true>(),  g2_streamk<1, true, 0, true, false, true>(),
+    g2_streamk<1, true, 4, false, true, true>(),   g2_streamk<1, true, 4, false, false, true>(),  g2_streamk<1, true, 4, true, false, true>(),
+    g2_streamk<1, true, 0, false, true, false>(),  g2_streamk<1, true, 0, false, false, false>(), g2_streamk<1, true, 0, true, false, false>(),
+    g2_streamk<2, false, 4, false, true, false>(), g2_streamk<2, false, 4, false, false, false>(), g2_streamk<2, false, 4, true, false, false>(),
+    g2_streamk<1, false, 4, false, false, false>(), g2_streamk<1, false, 4, true, false, false>()};
+
+static G2Form g2_form_of(const G2Launch& g, int KC, bool shared)
 {
-    const bool part = (livemask & g2_full_mask(sk.MG * G3_MW)) != g2_full_mask(sk.MG * G3_MW);
-    // several component groups share every count-plane tile in the L2: no non-temporal loads then
-    const bool shared = sk.MG > 1;
-    if (Bhi && cscale && !g_knobs->g2_gen4) {          // general matrices: three of the four plane pairs (GEN)
-        if (g_knobs->g2_gvar == 0) {              // (A/B: the burst loop of rounds 3-5; bit-identical results)
-            if (part) return launch_gemm2h_streamk_t<1, true, 0, false, true, true>(st, sk, A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, cscale, livemask);
-            return shared ? launch_gemm2h_streamk_t<1, true, 0, false, false, true>(st, sk, A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, cscale)
-                          : launch_gemm2h_streamk_t<1, true, 0, true, false, true>(st, sk, A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, cscale);
-        }
-        if (part) return launch_gemm2h_streamk_t<1, true, 4, false, true, true>(st, sk, A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, cscale, livemask);
-        return shared ? launch_gemm2h_streamk_t<1, true, 4, false, false, true>(st, sk, A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, cscale)
-                      : launch_gemm2h_streamk_t<1, true, 4, true, false, true>(st, sk, A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, cscale);
-    }
-    if (Bhi) {
-        if (part) return launch_gemm2h_streamk_t<1, true, 0, false, true>(st, sk, A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, cscale, livemask);
-        return shared ? launch_gemm2h_streamk_t<1, true, 0, false>(st, sk, A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, cscale)
-                      : launch_gemm2h_streamk_t<1, true>(st, sk, A2, B1, Bhi, hiflag, rscale, Kb, C0, C1, C2, ldc, cscale);
-    }
-    if (cscale) return hipErrorInvalidValue;
-    if (gemm2h_nsub(false, Kb) == 2) {
-        if (part) return launch_gemm2h_streamk_t<2, false, 4, false, true>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc, nullptr, livemask);
-        return shared ? launch_gemm2h_streamk_t<2, false, 4, false>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc)
-                      : launch_gemm2h_streamk_t<2, false, 4>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc);
-    }
-    // (CNMF_G2_NSUB=1 A/B: the one-block spread stream on the count plane)
-    return shared ? launch_gemm2h_streamk_t<1, false, 4, false>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc)
-                  : launch_gemm2h_streamk_t<1, false, 4, true>(st, sk, A2, B1, nullptr, nullptr, rscale, Kb, C0, C1, C2, ldc);
+    const unsigned long long full = g2_full_mask(KC);
+    return g2_form(g.x.hi != nullptr, g.x.colscale != nullptr, g.kn->g2_gen4, g.kn->g2_gvar, gemm2h_nsub(false, g.Kb, g.kn->g2_nsub),
+                   (g.livemask & full) != full, shared);
 }
 
-// geometry of the split launch: tiles of 16 rows x 256 k when K % 256 == 0 (1 KB contiguous per row), else 64 x 64;
-// every workgroup walks its k tiles with stride `groups`, so that all workgroups are resident at once (<= 7 per CU)
-// and the row scale is reduced once per workgroup
-static bool split2h_wide(int K) { return K % 256 == 0; }
-static int split2h_col_groups(int K, int rows)
+// Instruction streams (the VAR parameter of kernels_gemm2h.hip.h): production launches use 4, the spread stream, and 0,
+// the burst loop, on the two-plane count path; general matrices (GEN) take 0 instead of 4 with CNMF_G2_GVAR=0 (same bits).
+static hipError_t launch_gemm2h(hipStream_t st, const G2Launch& g)
 {
-    const int tk = split2h_wide(K) ? 256 : 64, trows = split2h_wide(K) ? 16 : 64;
-    const int tiles = K / tk, rg = std::max(1, rows / trows);
-    const int cap = std::max(1, (256 * 7) / rg);
-    int per = (tiles + cap - 1) / cap;                     // k tiles per workgroup
-    return (tiles + per - 1) / per;
+    G2Form f = g2_form_of(g, g.KC, false);
+    f.NTB = false;                                           // (the K-split kernel has no such parameter)
+    for (const G2Entry& e : G2_KSPLIT) if (e.form == f) return e.fn(st, g);
+    return hipErrorInvalidValue;
+}
+
+static hipError_t launch_gemm2h_streamk(hipStream_t st, const G2Launch& g)
+{
+    const G2Form f = g2_form_of(g, g.sk->MG * G3_MW, g.sk->MG > 1);
+    for (const G2Entry& e : G2_STREAMK) if (e.form == f) return e.fn(st, g);
+    return hipErrorInvalidValue;
 }
 
 // f16 planes of a packed factor (rows, K multiples of 64) from the sweep's row-maximum partials
@@ -664,16 +518,6 @@ static bool gemm3_enabled(const cnmf_ctx* ctx, int KC)
     //  only because nothing larger has been run; the gene side still rides on grid.y of those builders: G_pad / 256 <= 65 535)
     return ctx->knobs.gemm3 != 0 && KC % G3_MW == 0 && ctx->G_pad % gemm3_jw() == 0 && ctx->N_pad % gemm3_jw() == 0 &&
            ctx->N_pad <= (1 << 24) && ctx->G_pad / 256 <= 65535;
-}
-
-static int pick_nsplit3(const cnmf_ctx* ctx, int KC, int jw)
-{
-    // pass B grid = (G_pad/jw) x (KC/256) x nsplit; aim at one (two) workgroups per CU, >= 16 blocks per split
-    const int tiles = std::max(1, ctx->G_pad / jw) * std::max(1, KC / G3_MW);
-    const int Kb = ctx->N_pad / G3_BK;
-    int s = std::max(1, std::min(gemm3_wg_slots(ctx->knobs) / std::max(1, tiles), Kb / 16));
-    const int kb_per = (Kb + s - 1) / s;
-    return (Kb + kb_per - 1) / kb_per;
 }
 
 static hipError_t launch_split2h_finalize(hipStream_t st, const float* src, int ld, int rows, int K, unsigned char* dst,

@@ -54,11 +54,21 @@ struct SlotDesc {                   // one restart in flight (device + host mirr
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-struct SplitInfo {                  // further partial planes of a stream-K product (or plane1 == nullptr)
+struct CutPlanes {                  // further partial planes of a stream-K product (or plane1 == nullptr)
     const float* plane1;
     const unsigned char* split;     // [tiles] bit 0 = the tile was cut: add plane 1; bit 1 = cut twice: add plane 2 too
     int tile_rows, tile_cols, mgroups;
-    const float* plane2 = nullptr;
+    const float* plane2;
+};
+struct SplitSum {                   // PSUM: `nsplit` split-K partial planes `stride` floats apart, scaled per row by `colscale` (nullable)
+    int nsplit;
+    long long stride;
+    const double* colscale;
+};
+// What a sweep adds to the product plane it is given: `sum` in the PSUM forms, `cut` in all others (one kernel argument
+// either way; the host fills the member the form reads, launch_sweep)
+struct SplitInfo {
+    union { CutPlanes cut; SplitSum sum; };
 };
 
 // PLN (round 3, the W half-step of the f16 paths): the sweep also writes the two f16 planes of the rows it has just
@@ -86,9 +96,9 @@ struct PlaneOut {
 // bound  sqrt(sum_rows w^2)  from the diagonal of the workgroup's Gram partial -- at most sqrt(rows per workgroup)
 // = 32 x the true maximum, which the f16 plane split tolerates (kernels_gemm2h.hip.h: 5 bits of exponent slack only
 // move the threshold below which tiny entries keep an absolute rather than a relative accuracy).
-// PSUM: the products arrive as `sp.mgroups` split-K partial planes (stride sp.tile_rows * 2^20 + sp.tile_cols floats,
-// see psum_info) that are summed here in split order and scaled by the per-row constant sp.split (reinterpreted as
-// const double*) -- the work of reduce_splits_kernel folded into the H half-step (no extra launch, no extra pass).
+// PSUM: the products arrive as `sp.sum.nsplit` split-K partial planes (`sp.sum.stride` floats apart) that are summed here
+// in split order and scaled by the per-row constant sp.sum.colscale -- the work of reduce_splits_kernel folded into the
+// H half-step (no extra launch, no extra pass).
 // EX: the rank IS KP (the W half-step of ranks <= 16): no clamped duplicate loads, no `c < k` selects, no padded
 // multiply-adds, divisions by a constant.  The padded terms it drops are fmaf(0, 0, grad): they can at most turn a -0.0
 // gradient into +0.0, which neither fabsf(pg) nor fmaxf(w - grad / hess, 0) can see -- same bits out.
@@ -157,12 +167,12 @@ __device__ __forceinline__ void sweep_body(
         // so two wave-uniform flags cover every element.
         int cut0 = 0, cut1 = 0;
         int mg_edge = 1 << 30;
-        if (!PSUM && sp.plane1) {
-            const int rt = __builtin_amdgcn_readfirstlane(min(row, L - 1) / sp.tile_rows);
-            const int g0 = off / sp.tile_cols, g1 = (off + k - 1) / sp.tile_cols;
-            mg_edge = (g0 + 1) * sp.tile_cols;
-            cut0 = sp.split[rt * sp.mgroups + g0];
-            cut1 = sp.split[rt * sp.mgroups + g1];
+        if (!PSUM && sp.cut.plane1) {
+            const int rt = __builtin_amdgcn_readfirstlane(min(row, L - 1) / sp.cut.tile_rows);
+            const int g0 = off / sp.cut.tile_cols, g1 = (off + k - 1) / sp.cut.tile_cols;
+            mg_edge = (g0 + 1) * sp.cut.tile_cols;
+            cut0 = sp.cut.split[rt * sp.cut.mgroups + g0];
+            cut1 = sp.cut.split[rt * sp.cut.mgroups + g1];
         }
         float w[KP], p[KP];
         float dsc = 1.0f;                          // per-row scale of the exact row-maximum report (issued with the loads)
@@ -190,8 +200,8 @@ __device__ __forceinline__ void sweep_body(
                 }
             }
             if constexpr (PSUM) {
-                const int nsplit = sp.mgroups;
-                const size_t stride = (size_t)sp.tile_rows * (1u << 20) + (size_t)sp.tile_cols;
+                const int nsplit = sp.sum.nsplit;
+                const size_t stride = (size_t)sp.sum.stride;
                 // U planes' loads in flight at a time; the additions keep the split order (bit-identical to
                 // reduce_splits_kernel)
                 // the remainder of the split count is batched too (clamped plane index, wave-uniform guard on the
@@ -214,7 +224,7 @@ __device__ __forceinline__ void sweep_body(
                             for (int c = 0; c < KP; ++c) p[c] += q[u][c];
                         }
                 }
-                const double* colscale = reinterpret_cast<const double*>(sp.split);
+                const double* colscale = sp.sum.colscale;
                 if (colscale) {
                     const double cs = colscale[rowc];
 #pragma unroll
@@ -224,14 +234,14 @@ __device__ __forceinline__ void sweep_body(
             if ((cut0 | cut1) & 1) {              // wave-uniform: one branch per chunk
                 float qq[KP];
                 if constexpr (B32) {
-                    const auto r1 = CNMF_RSRC(sp.plane1);
+                    const auto r1 = CNMF_RSRC(sp.cut.plane1);
 #pragma unroll
                     for (int c = 0; c < KP; ++c) qq[c] = CNMF_BLD(r1, voff, c);
                 } else {
 #pragma unroll
                     for (int c = 0; c < KP; ++c) {
                         const size_t idx = (size_t)(off + min(c, k - 1)) * ldv + rowc;
-                        qq[c] = sp.plane1[idx];
+                        qq[c] = sp.cut.plane1[idx];
                     }
                 }
 #pragma unroll
@@ -243,14 +253,14 @@ __device__ __forceinline__ void sweep_body(
             if ((cut0 | cut1) & 2) {
                 float qq[KP];
                 if constexpr (B32) {
-                    const auto r2 = CNMF_RSRC(sp.plane2);
+                    const auto r2 = CNMF_RSRC(sp.cut.plane2);
 #pragma unroll
                     for (int c = 0; c < KP; ++c) qq[c] = CNMF_BLD(r2, voff, c);
                 } else {
 #pragma unroll
                     for (int c = 0; c < KP; ++c) {
                         const size_t idx = (size_t)(off + min(c, k - 1)) * ldv + rowc;
-                        qq[c] = sp.plane2[idx];
+                        qq[c] = sp.cut.plane2[idx];
                     }
                 }
 #pragma unroll
@@ -545,12 +555,12 @@ __global__ __launch_bounds__(256) void sweep_big_kernel(
         const bool live = row < L;
         const int rowc = min(row, L - 1);
         int cut0 = 0, cut1 = 0, mg_edge = 1 << 30;
-        if (sp.plane1) {                                    // stream-K pass A: cut flags of this wave's row tile
-            const int rt = __builtin_amdgcn_readfirstlane(rowc / sp.tile_rows);
-            const int g0 = off / sp.tile_cols, g1 = (off + k - 1) / sp.tile_cols;
-            mg_edge = (g0 + 1) * sp.tile_cols;
-            cut0 = sp.split[rt * sp.mgroups + g0];
-            cut1 = sp.split[rt * sp.mgroups + g1];
+        if (sp.cut.plane1) {                                    // stream-K pass A: cut flags of this wave's row tile
+            const int rt = __builtin_amdgcn_readfirstlane(rowc / sp.cut.tile_rows);
+            const int g0 = off / sp.cut.tile_cols, g1 = (off + k - 1) / sp.cut.tile_cols;
+            mg_edge = (g0 + 1) * sp.cut.tile_cols;
+            cut0 = sp.cut.split[rt * sp.cut.mgroups + g0];
+            cut1 = sp.cut.split[rt * sp.cut.mgroups + g1];
         }
         float w[KBIG];
 #pragma unroll
@@ -569,8 +579,8 @@ __global__ __launch_bounds__(256) void sweep_big_kernel(
                     const size_t idx = (size_t)(off + min(c, k - 1)) * ldv + rowc;
                     float pv = P[idx];
                     const int cut = ((off + c) < mg_edge) ? cut0 : cut1;
-                    if (cut & 1) pv += sp.plane1[idx];      // (wave-uniform per component)
-                    if (cut & 2) pv += sp.plane2[idx];
+                    if (cut & 1) pv += sp.cut.plane1[idx];      // (wave-uniform per component)
+                    if (cut & 2) pv += sp.cut.plane2[idx];
                     pl[rr] = (live && c < k) ? pv - l1_reg : 0.f;
                     wl[rr] = w[c];
                 }

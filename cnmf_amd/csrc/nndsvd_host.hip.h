@@ -98,7 +98,6 @@ extern "C" int cnmf_range_finder(cnmf_ctx* ctx, int transpose, int nblocks, cons
 {
     using namespace cnmf;
     if (!ctx || !widths || !Q0 || !Q_out || !B_out || nblocks < 1 || n_iter < 0) { SET_ERR(ctx, "bad argument"); return CNMF_EINVAL; }
-    KnobScope knob_scope(ctx);
     if (int rcd_ = ensure_dense(ctx)) return rcd_;
     int C = 0, cmax = 0;
     for (int b = 0; b < nblocks; ++b) {

@@ -254,7 +254,9 @@ static int nnls_sweep_loop(cnmf_ctx* ctx, int nslots, float* V, int ldv, int L, 
                            float l1, const cnmf_cd_params* prm, int kmax, int tiers)
 {
     hipStream_t st = ctx->stream;
-    const int chunks = sweep_chunks(ctx, L), parts = sweep_parts(ctx, L);
+    const int parts = sweep_parts(ctx, L);
+    SweepLaunch sw = batch_sweep(ctx, nslots, kmax, tiers);
+    sw.V = V; sw.ldv = ldv; sw.L = L; sw.P = P; sw.gram = gram; sw.l1 = l1; sw.chunks = sweep_chunks(ctx, L); sw.parts = parts;
     EventPool events;
     hipEvent_t ev = events.get(hipEventDisableTiming);
     POOL_TRY(ctx, events);
@@ -263,8 +265,7 @@ static int nnls_sweep_loop(cnmf_ctx* ctx, int nslots, float* V, int ldv, int L, 
     bool done = false;
     for (int it = 0; it < prm->max_iter && !done; it += burst) {
         for (int b = 0; b < burst; ++b) {
-            HIP_TRY(ctx, launch_sweep(st, nslots, V, ldv, L, P, gram, ctx->bat.d_slots, l1, ctx->bat.gram_part, ctx->bat.viol_part,
-                                      chunks, parts, 0, kmax, tiers));
+            HIP_TRY(ctx, launch_sweep(st, sw));
             finalize_kernel<<<dim3(nslots, 1), 256, 0, st>>>(ctx->bat.gram_part, ctx->bat.viol_part, parts, ctx->bat.gramW, 0.f,
                                                           ctx->bat.d_slots, 2, prm->tol, prm->max_iter, 0, kmax);
         }
@@ -434,7 +435,6 @@ static int nnls_batch_impl(cnmf_ctx* ctx, int n, const int32_t* ks, const float*
 {
     using namespace cnmf;
     if (!ctx || !ks || !Hin || n < 1) { SET_ERR(ctx, "bad argument"); return CNMF_EINVAL; }
-    KnobScope knob_scope(ctx);
     if (int rcd_ = ensure_dense(ctx)) return rcd_;
     int rc = validate_params(ctx, prm);
     if (rc) return rc;

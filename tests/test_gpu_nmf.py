@@ -12,6 +12,8 @@ restarts that stop within 500 outer iterations; ill-conditioned restarts that ne
 ~1000 sweeps) are held to max-abs <= 5e-4 at the same relative-Frobenius bound.
 |delta n_iter| is bounded too (the stop is a ratio of order-dependent fp sums).
 """
+import functools
+
 import numpy as np
 import pytest
 
@@ -318,6 +320,39 @@ def test_full_width_batch_matches_oracle_in_every_gemm_mode(engine, monkeypatch,
     assert (viol[n_iter < 1000] <= 1e-4).all()
     H2, _, n2, _ = engine.nmf_batch(ks, seeds=seeds)
     assert list(n2) == list(n_iter) and all(np.array_equal(a, b) for a, b in zip(H, H2))
+
+
+@functools.lru_cache(maxsize=None)
+def _full_width_job(general):
+    """The 44-restart job of the two full-width tests above (count-structured C1, or their general matrix) with the float64
+    oracle run of every third restart, computed once for all knob arms below."""
+    rs = np.random.RandomState(17 if general else 11)
+    X64 = synth.make_config("C1", dtype=np.float64)
+    if general:
+        X64 = X64 * np.exp(0.8 * rs.standard_normal((X64.shape[0], 1))) * np.exp(0.8 * rs.standard_normal((1, X64.shape[1])))
+        X64 += 0.01 * np.abs(rs.standard_normal(X64.shape))
+    ks = [int(k) for k in rs.randint(5, 10, size=44)]
+    seeds = [int(s) for s in rs.randint(1, 2**31 - 1, size=44)]
+    refs = [nmf_cd.nmf(X64, k, seed=seed)[1:] for k, seed in list(zip(ks, seeds))[::3]]
+    return X64, ks, seeds, refs
+
+
+@pytest.mark.parametrize("knob,value,mode", [("CNMF_G2_NSUB", "1", 4), ("CNMF_NO_STREAMK", "1", 4), ("CNMF_WG_SLOTS", "32", 4),
+                                             ("CNMF_G2_GEN4", "1", 5), ("CNMF_G2_XMAP", "1", 5)])
+def test_full_width_batch_matches_oracle_under_the_launch_knobs(engine, monkeypatch, knob, value, mode):
+    """The kernel forms only a knob reaches (g2_form / plan_pass_splits, pass_plan.h), each on one 256-column batch at the
+    tolerance of the two tests above: the one-block count stream (CNMF_G2_NSUB=1), pass A as K splits + reduce
+    (CNMF_NO_STREAMK=1), 32 persistent workgroups (CNMF_WG_SLOTS=32) on the f16 count path; all four plane pairs
+    (CNMF_G2_GEN4=1) and the count path's XCD mapping (CNMF_G2_XMAP=1) on a general matrix."""
+    X64, ks, seeds, refs = _full_width_job(mode == 5)
+    monkeypatch.setenv(knob, value)
+    engine.set_matrix(X64)
+    H, _, n_iter, viol = engine.nmf_batch(ks, seeds=seeds)
+    assert engine.last_stats["kc"] == 256 and engine.last_stats["gemm_mode"] == mode
+    for (H_ref, n_ref), h, n in zip(refs, H[::3], n_iter[::3]):
+        _check(H_ref, n_ref, h, n, slack=3)
+    if mode == 4:
+        assert (viol[n_iter < 1000] <= 1e-4).all()
 
 
 @pytest.mark.parametrize("g3mode,kc", [("4", 512), ("4", 768), ("3", 512), ("2", 512), ("4", 1024), ("5", 512), ("5", 1024)])
