@@ -18,7 +18,9 @@
 //   (this file)          lifecycle, upload of the data matrix
 //   batch_host.hip.h     batch buffers, the restart loop (run_batch: operand scheme, installs, launches), NNLS refit;
 //                        includes batch_sched.h, the restart scheduler itself (standard library only, no HIP)
-//   consensus_host / mu_host / comm_host / normalize_host .hip.h   the other entry points
+//   mu_host.hip.h        the multiplicative-update solver: images, launches, one driver for all kernel families;
+//                        includes mu_sched.h, its round scheduler (standard library only, no HIP)
+//   consensus_host / comm_host / normalize_host .hip.h   the other entry points
 //   debug_host.hip.h     products with X for NNDSVD, diagnostics used by the tests
 #include <hip/hip_runtime.h>
 
@@ -107,7 +109,7 @@ static void drop_derived_images(cnmf_ctx* c)
 {
     hipStreamSynchronize(c->stream);
     c->planes.release(); c->counts.release(); c->x2.release();
-    hipFree(c->XtF); c->XtF = nullptr;
+    c->XtF.release();
     for (int i = 0; i < 2; ++i) { c->spA[i].release(); c->spB[i].release(); }
     c->x_nnz = -1;
     free_csr(c);
@@ -286,7 +288,7 @@ extern "C" int cnmf_get_shape(const cnmf_ctx* ctx, int64_t* N, int64_t* G)
 extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
 {
     if (!ctx || !flags) return CNMF_EINVAL;
-    *flags = (ctx->X ? 1 : 0) | (ctx->csr.ptr ? 2 : 0) | (ctx->csc.ptr ? 4 : 0) | (ctx->XtF ? 8 : 0) |
+    *flags = (ctx->X ? 1 : 0) | (ctx->csr.ptr ? 2 : 0) | (ctx->csc.ptr ? 4 : 0) | (ctx->XtF.p ? 8 : 0) |
              ((ctx->spA[0].ent && ctx->spB[0].ent) ? 16 : 0) | ((ctx->spA[1].ent && ctx->spB[1].ent) ? 32 : 0) | (ctx->counts.C1 ? 64 : 0);
     return CNMF_OK;
 }

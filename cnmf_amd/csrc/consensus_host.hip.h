@@ -17,8 +17,6 @@
 
 namespace cnmf {
 
-// (DevPool, the scope-bound device allocator, is defined in cnmf_hip.hip)
-
 static inline bool same_clustering(const std::vector<int>& a, const std::vector<int>& b, int k)
 {   // sklearn _k_means_common.pyx:314-330
     std::vector<int> map(k, -1);

@@ -36,16 +36,8 @@ struct Arena {
     }
 };
 
-// blocked sliced-ELL image of the non-zeros of one orientation of X (kernels_mu_sparse.hip.h); all pointers device memory
-struct SpImage {
-    int R = 0, C = 0, BS = 0, nblk = 0, nslice = 0;
-    int* perm = nullptr; long long* off = nullptr; int* len = nullptr; void* ent = nullptr;
-    size_t n_ent = 0;
-    void release() { hipFree(perm); hipFree(off); hipFree(len); hipFree(ent); *this = SpImage{}; }
-};
-
 // An owning group of device arrays.  F is a plain struct of device pointers (and what describes them) with a free_all().
-// Not copyable, and no destructor: like Arena and SpImage a group is released explicitly, by an owner that has
+// Not copyable, and no destructor: like Arena a group is released explicitly, by an owner that has
 // synchronised the stream that may still use the arrays.
 template <typename F>
 struct Owned : F {
@@ -86,6 +78,20 @@ struct CsrF {
 };
 template <typename V> using DevCsr = Owned<CsrF<V>>;
 template <typename V> using DevCsrLocal = OwnedLocal<CsrF<V>>;
+
+// blocked sliced-ELL image of the non-zeros of one orientation of X (kernels_mu_sparse.hip.h); ent = NULL: none
+struct SpImageF {
+    int R = 0, C = 0, BS = 0, nblk = 0, nslice = 0;
+    int* perm = nullptr; long long* off = nullptr; int* len = nullptr; void* ent = nullptr;
+    size_t n_ent = 0;
+    void free_all() { hipFree(perm); hipFree(off); hipFree(len); hipFree(ent); }
+};
+using SpImage = Owned<SpImageF>;
+// X^T as a dense float32 image [round_up(G_pad, 128)][N_pad] (the matrix-pipe kernels of the multiplicative updates)
+struct DenseTF {
+    float* p = nullptr;
+    void free_all() { hipFree(p); }
+};
 
 // ---- the images of the resident matrix X that the GEMM passes of the coordinate-descent batch read (gemm_host.hip.h)
 // What a GEMM pass reads of X: the plane, an optional second plane with its block flags (one bit per tile row and block),
@@ -235,7 +241,14 @@ struct CdKnobs {
     bool no_streamk = false;           // CNMF_NO_STREAMK: pass A always as K splits + reduce
     bool s_mtw2 = false;               // CNMF_S_MTW2: the "S" f32 GEMM layout with two tiles per wave (diagnostic entry point only)
     bool no_counts = false;            // CNMF_NO_COUNTS: no count-structure detection
-    bool debug = false;                // CNMF_DEBUG: scheduler statistics of the batch path on stderr (consensus and MU read the snapshot themselves)
+    bool debug = false;                // CNMF_DEBUG: scheduler statistics of the batch path on stderr (consensus reads the snapshot itself)
+};
+// ... and those of the multiplicative-update solver (mu_host.hip.h): parse_mu_knobs
+struct MuKnobs {
+    bool valu = false;                 // CNMF_MU_VALU=1: the vector-ALU kernels, one restart at a time (kernels_mu.hip.h)
+    int  sparse = -1;                  // CNMF_MU_SPARSE=0: never the non-zero path, =1: always, else (-1) by density and memory
+    bool sp_order = true;              // CNMF_SP_ORDER=0: the non-zero images keep every row's entries in storage order
+    bool debug = false;                // CNMF_DEBUG: what mu_sparse_prepare decided, on stderr
 };
 
 struct cnmf_ctx {
@@ -247,6 +260,7 @@ struct cnmf_ctx {
     // -- a knob that steers a numerics-affecting path cannot change between two calls on one context behind the caller's back
     std::map<std::string, std::string> env;
     CdKnobs knobs;                                 // ... and the switches of the coordinate-descent batch path, parsed from it
+    MuKnobs mu_knobs;                              // ... and of the multiplicative-update solver
 
     // data matrix
     int64_t N = 0, G = 0;
@@ -258,8 +272,7 @@ struct cnmf_ctx {
     Owned<Bf16PlanesF> planes;                     // ensure_planes
     Owned<CountPlanesF> counts;                    // ensure_counts; counts.state says whether X has the structure at all
     Owned<GeneralPlanesF> x2;                      // ensure_x2planes
-    float* XtF = nullptr;                          // X^T [round_up(G_pad, 64)][N_pad] float32, built on first use by the
-                                                   // Kullback-Leibler solver (kernels_mu_mfma.hip.h)
+    Owned<DenseTF> XtF;                            // mu_ensure_xt (mu_host.hip.h)
     // Kullback-Leibler on the non-zeros (kernels_mu_sparse.hip.h): images for padded ranks 16 and 32, cells x genes (A) and
     // genes x cells (B); x_nnz = -1 until the first Kullback-Leibler call counted the matrix
     SpImage spA[2], spB[2];
@@ -324,6 +337,17 @@ static void parse_cd_knobs(cnmf_ctx* ctx)
     k.debug = ctx_getenv(ctx, "CNMF_DEBUG") != nullptr;
     ctx->knobs = k;
 }
+static void parse_mu_knobs(cnmf_ctx* ctx)
+{
+    MuKnobs m;
+    auto num = [](const char* s, int dflt) { return s ? atoi(s) : dflt; };
+    m.valu = num(ctx_getenv(ctx, "CNMF_MU_VALU"), 0) != 0;
+    const int sp = num(ctx_getenv(ctx, "CNMF_MU_SPARSE"), -1);
+    m.sparse = sp == 0 || sp == 1 ? sp : -1;
+    m.sp_order = num(ctx_getenv(ctx, "CNMF_SP_ORDER"), 1) != 0;
+    m.debug = ctx_getenv(ctx, "CNMF_DEBUG") != nullptr;
+    ctx->mu_knobs = m;
+}
 
 extern char** environ;
 static void ctx_snapshot_env(cnmf_ctx* ctx)
@@ -335,6 +359,7 @@ static void ctx_snapshot_env(cnmf_ctx* ctx)
         if (eq) ctx->env[std::string(*e, eq - *e)] = std::string(eq + 1);
     }
     parse_cd_knobs(ctx);
+    parse_mu_knobs(ctx);
 }
 
 #define SET_ERR(ctx, ...)                                                   \

@@ -84,7 +84,7 @@ def test_mu_batch_matches_single_and_valu_path(engine, X, monkeypatch):
     """Kullback-Leibler restarts run batched on the matrix pipe (kernels_mu_mfma.hip.h): a restart's result must not
     depend on what else is in the batch (bit for bit), and must agree with the vector-ALU path and the oracle."""
     engine.set_matrix(X)
-    ks = [5, 7, 12, 20, 9, 16, 17, 3, 8, 13, 6, 11, 10, 4, 15, 14, 19, 2]          # more than one round of 16 slots
+    ks = [5, 7, 12, 20, 9, 16, 17, 3, 8, 13, 6, 11, 10, 4, 15, 14, 19, 2]          # padded ranks 16 and 32: groups of 15 and 3 (no refill: tests/test_gpu_mu_refill.py)
     seeds = [100 + i for i in range(len(ks))]
     H, W, n_iter, err = engine.nmf_mu_batch(ks, seeds=seeds, max_iter=200, return_W=True, warn=False)
     for i in (0, 3, 6, 17):

@@ -1,9 +1,11 @@
 """Fixed seeded jobs through whichever build of the library CNMF_LIB_PATH names, for bit-identity A/B runs of two builds:
-    CNMF_LIB_PATH=/path/to/libcnmf_hip.so [CNMF_GEMM3=2 ...] python tools/ab_identity.py wide|general|f32|mode|init|streamk|streamk_general|hints|staging
+    CNMF_LIB_PATH=/path/to/libcnmf_hip.so [CNMF_GEMM3=2 ...] python tools/ab_identity.py wide|general|f32|mode|init|streamk|streamk_general|hints|staging|mu
 Prints one JSON line: SHA-256 digests of everything the job's batch calls returned (H, n_iter, viol) and of the
 last_stats fields that describe the schedule.  One process per library and per knob value; the lines must be equal.
 ``staging`` runs no coordinate-descent batch: it digests every array the prepare / preprocess / filter entry points and
-a Kullback-Leibler batch on the non-zeros return for one small count matrix (staging_matrix)."""
+a Kullback-Leibler batch on the non-zeros return for one small count matrix (staging_matrix).  ``mu`` digests H, W, n_iter
+and err of multiplicative-update calls that refill slots, on the dense matrix pipe and on the non-zeros; run it once per
+arm: no knob, CNMF_MU_VALU=1 (then the first 6 restarts of every call), CNMF_MU_SPARSE=0|1, CNMF_SP_ORDER=0."""
 import hashlib
 import json
 import os
@@ -134,11 +136,68 @@ def staging():
     return out
 
 
+def mu():
+    """{name: SHA-256} of what the multiplicative-update calls return: the 70- and 40-restart refill calls of
+    tests/test_gpu_mu_refill.py, Itakura-Saito, padded rank 64 at a max_iter that is no multiple of 10, a caller-initialised
+    regularised restart and the refit with H fixed"""
+    from oracle import nmf_cd
+    out = {}
+    valu = os.environ.get("CNMF_MU_VALU", "0") not in ("", "0")
+
+    def put(name, eng, ks, **kw):
+        n = 6 if valu else len(ks)
+        for key in ("seeds", "W0", "H0"):
+            if kw.get(key) is not None:
+                kw[key] = kw[key][:n]
+        H, W, n_iter, err = eng.nmf_mu_batch(ks[:n], return_W=True, warn=False, **kw)
+        h = hashlib.sha256()
+        for a in list(H) + list(W) + [np.asarray(n_iter, dtype=np.int32), np.asarray(err, dtype=np.float64)]:
+            h.update(np.ascontiguousarray(a).tobytes())
+        out[name] = h.hexdigest()
+        out[name + "_n_iter"] = [int(v) for v in n_iter]
+
+    X = synth.make_config("C1", dtype=np.float64, n_cells=700)
+    eng = Engine(0)
+    eng.set_matrix(X)
+    put("kl_refill_70", eng, [2 + (7 * i) % 15 for i in range(70)], seeds=[1000 + i for i in range(70)], max_iter=200)
+    put("kl_rank_64", eng, [40, 33, 64, 48, 57], seeds=[300 + i for i in range(5)], max_iter=25, tol=0.0)
+    W0, H0 = nmf_cd.random_init(X, 6, 11)
+    put("kl_custom_init", eng, [6], W0=[W0], H0=[H0], max_iter=200, alpha_W=0.001, alpha_H=0.002, l1_ratio=0.5)
+    Hn = H0 / H0.sum(axis=1, keepdims=True)
+    W, n = eng.nnls_mu(Hn, max_iter=100, warn=False)
+    out["nnls_mu"] = hashlib.sha256(np.ascontiguousarray(W).tobytes() + str(int(n)).encode()).hexdigest()
+    # ... and the same refit through cnmf_nmf_mu_batch itself (update_H = 0: W starts at avg, H0 stays), which the engine
+    # does not call any more
+    import ctypes as C
+    from cnmf_amd import _lib
+    ks = np.asarray([6, 6], dtype=np.int32)
+    h0 = np.ascontiguousarray(np.concatenate([Hn, 2.0 * Hn]), dtype=np.float32)
+    avg = np.asarray([eng.init_scale(6)] * 2, dtype=np.float64)
+    prm = _lib.CdParams(1e-4, 100, 0, 0.0, 0.0, 0.0, 0.0, 0, 0)
+    Wf = np.zeros(12 * X.shape[0], dtype=np.float32)
+    n_it, er = np.zeros(2, dtype=np.int32), np.zeros(2, dtype=np.float64)
+    f32p = C.POINTER(C.c_float)
+    eng._check(eng._lib.cnmf_nmf_mu_batch(eng._ctx, 2, ks.ctypes.data_as(C.POINTER(C.c_int32)), 0, None,
+                                          avg.ctypes.data_as(C.POINTER(C.c_double)), None, h0.ctypes.data_as(f32p), 1, 0,
+                                          C.byref(prm), None, Wf.ctypes.data_as(f32p), n_it.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          er.ctypes.data_as(C.POINTER(C.c_double))))
+    out["update_h_0"] = hashlib.sha256(Wf.tobytes() + n_it.tobytes() + er.tobytes()).hexdigest()
+    out["update_h_0_n_iter"] = [int(v) for v in n_it]
+    eng.set_matrix(X + 1e-3)
+    put("is_batch", eng, [5, 3, 16, 17, 9, 24, 7, 40], seeds=[40 + i for i in range(8)], beta_loss="itakura-saito", max_iter=60)
+    C, _ = synth.topic_counts(1200, 900, 6, 4.6, 0.4, 1200)
+    eng.set_matrix(synth.normalise_like_prepare(C, dtype=np.float32))
+    put("kl_sparse_40", eng, [3 + i % 14 for i in range(40)], seeds=[2000 + i for i in range(40)], max_iter=60)
+    out["images"] = {k: v for k, v in eng.matrix_images().items() if k.startswith("non_zero")}
+    eng.close()
+    return out
+
+
 def main():
     job = sys.argv[1]
     env = {k: v for k, v in sorted(os.environ.items()) if k.startswith("CNMF_") and k != "CNMF_LIB_PATH"}
-    if job == "staging":
-        print(json.dumps({"job": job, "env": env, "seen": [], "sha256": staging()}))
+    if job in ("staging", "mu"):
+        print(json.dumps({"job": job, "env": env, "seen": [], "sha256": staging() if job == "staging" else mu()}))
         return
     X, jobs = calls(job)
     eng = Engine(0)

@@ -1,5 +1,5 @@
 """KL multiplicative update at C3 (50000 x 2000): time per restart-iteration, one restart alone and batches
-(the matrix-pipe path batches up to 16 restarts per round of launches); CNMF_MU_VALU=1 selects the vector-ALU path."""
+(the matrix-pipe path batches up to 32 restarts per round of launches); CNMF_MU_VALU=1 selects the vector-ALU path."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
