@@ -32,6 +32,7 @@ SYMBOLS = [
     "cnmf_preprocess_row_sums", "cnmf_preprocess_normalize_dense", "cnmf_preprocess_select_mi",
     "cnmf_preprocess_upload_csr_as_stored", "cnmf_preprocess_gene_detect", "cnmf_preprocess_cell_sums",
     "cnmf_preprocess_subset", "cnmf_preprocess_fetch_counts",
+    "cnmf_preprocess_gene_moments", "cnmf_preprocess_loess_fit", "cnmf_preprocess_clipped_sums",
     "cnmf_nmf_cd_batch", "cnmf_nmf_cd_batch_resident", "cnmf_get_iteration_means", "cnmf_set_iteration_hints", "cnmf_nnls",
     "cnmf_consensus", "cnmf_pairwise_distances", "cnmf_prediction_error", "cnmf_nmf_mu_batch", "cnmf_mu_refit_f64", "cnmf_x_matmul",
     "cnmf_xt_matmul_f64", "cnmf_nnls_spectra", "cnmf_nnls_f64", "cnmf_nnls_gram", "cnmf_nnls_batch", "cnmf_kselect_stats",
@@ -245,6 +246,12 @@ def load():
     lib.cnmf_preprocess_subset.argtypes = [vp, u8p, u8p, i64p_, i64p_, i64p_]
     lib.cnmf_preprocess_fetch_counts.restype = i32
     lib.cnmf_preprocess_fetch_counts.argtypes = [vp, C.c_double, i64p_, i32p, dblp]
+    lib.cnmf_preprocess_gene_moments.restype = i32
+    lib.cnmf_preprocess_gene_moments.argtypes = [vp, i64p_, i64p_, i32p]
+    lib.cnmf_preprocess_loess_fit.restype = i32
+    lib.cnmf_preprocess_loess_fit.argtypes = [vp, i64, dblp, dblp, i64, i64, dblp, dblp, dblp, i32p]
+    lib.cnmf_preprocess_clipped_sums.restype = i32
+    lib.cnmf_preprocess_clipped_sums.argtypes = [vp, dblp, dblp, dblp]
     lib.cnmf_prepare_release.restype = i32
     lib.cnmf_prepare_release.argtypes = [vp]
     lib.cnmf_nmf_cd_batch.restype = i32

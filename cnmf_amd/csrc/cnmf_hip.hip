@@ -60,7 +60,7 @@ extern "C" int cnmf_device_count(void)
     return n;
 }
 
-extern "C" const char* cnmf_version(void) { return "cnmf_hip 0.1.0 (gfx950)"; }
+extern "C" const char* cnmf_version(void) { return "cnmf_hip 0.2.0 (gfx950)"; }
 
 extern "C" const char* cnmf_last_error(const cnmf_ctx* ctx)
 {
@@ -308,6 +308,7 @@ extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
 #include "harmony_host.hip.h"
 #include "harmony_init_host.hip.h"
 #include "filter_host.hip.h"
+#include "hvg_host.hip.h"
 #include "select_mi_host.hip.h"
 #include "tail_host.hip.h"
 

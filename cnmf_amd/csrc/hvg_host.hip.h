@@ -1,0 +1,328 @@
+// The device steps of Preprocess.highly_variable_genes (scanpy's flavor='seurat_v3', one batch) on the staging of
+// preprocess_host.hip.h (ctx->pre: the raw counts as CSR and as their transpose):
+//
+//   * per-gene moments S1 = sum x and S2 = sum x^2 as 64-bit integers over the transpose, a wavefront per column in the
+//     pattern of flt_gene_detect_kernel (lane-strided, a fixed butterfly), with a flag for a value that is no count
+//     (negative, non-integer, not finite) and one for a count above HVG_COUNT_MAX = 2^20; with at most HVG_CELLS_MAX =
+//     2^22 cells S2 <= 2^62 never wraps.  The host forms mean and the ddof=1 variance from the exact integers;
+//   * the local fits of skmisc's loess(degree=2, family gaussian) at m evaluation points over n SORTED abscissae, one
+//     workgroup per point: the q nearest neighbours of x0 in a sorted array are a contiguous window, found by binary
+//     search (the first lo in [0, n - q] with x0 - x[lo] <= x[lo + q] - x0); h = max(x0 - x[lo], x[lo + q - 1] - x0)
+//     is the q-th smallest distance; the workgroup strides the window and accumulates the eight weighted moments in
+//     t = (x - x0) / h -- sum w, w t, w t^2, w t^3, w t^4, w y, w t y, w t^2 y, w = (1 - (|x - x0| / h)^3)^3 where
+//     |x - x0| < h, else 0 -- reduces them in a fixed tree (a butterfly per wavefront, the four wavefronts through LDS),
+//     and one thread solves the 3 x 3 normal equations by an LDL^T factorisation.  Normal equations square the
+//     condition number of the design (about 6 inside the data, more at the end vertices), which a plain float64 sum and
+//     solve pay with 10 to 50 times the rounding error of a least-squares solve on the design itself; so the moments
+//     are COMPENSATED float64 sums (every partial sum a pair hi + lo of doubles, the error of each addition kept by
+//     Knuth's two-sum) and the 3 x 3 solve runs on such pairs as well.  Status per point: HVG_FIT_ZERO_WIDTH when
+//     h <= 0, HVG_FIT_DEFICIENT when a pivot of the factorisation falls below HVG_PIVOT_MIN of its diagonal entry (fewer
+//     than three distinct weighted abscissae, or close to it): the caller redoes those few points on the host with the
+//     minimum-norm formula; the pseudo-inverse's threshold is not emulated here;
+//   * per-gene sums C1 = sum min(x, clip[g]) and C2 = sum min(x, clip[g])^2 over the transpose, float64, a wavefront per
+//     column as above.
+//
+// Integer counters and fixed-order float64 sums only -- no float atomics: two calls on the same input give the same
+// bits.  Included by cnmf_hip.hip (after filter_host.hip.h).
+#pragma once
+
+namespace cnmf {
+
+constexpr double HVG_COUNT_MAX = 1048576.0;              // 2^20: a larger count is refused
+constexpr long long HVG_CELLS_MAX = 1ll << 22;           // so that sum x^2 <= 2^62
+constexpr int HVG_FLAG_NOT_COUNT = 1, HVG_FLAG_TOO_LARGE = 2;
+constexpr int HVG_FIT_OK = 0, HVG_FIT_ZERO_WIDTH = 1, HVG_FIT_DEFICIENT = 2;
+constexpr double HVG_PIVOT_MIN = 1e-6;
+constexpr int HVG_FIT_THREADS = 256;
+
+// one wavefront per column g of the transposed counts: s1[g] = sum x, s2[g] = sum x^2 as integers, flags[g] = what was
+// met that is no count (left out of the sums)
+__global__ __launch_bounds__(256) void hvg_gene_moments_kernel(const long long* __restrict__ cptr, const int* __restrict__ crow,
+                                                               const double* __restrict__ cval, int G, int N,
+                                                               long long* __restrict__ s1, long long* __restrict__ s2,
+                                                               int* __restrict__ flags)
+{
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (g >= G) return;
+    long long a = 0, b = 0;
+    int f = 0;
+    for (long long p = cptr[g] + lane; p < cptr[g + 1]; p += 64) {
+        const int r = crow[p];
+        if (r < 0 || r >= N) continue;
+        const double v = cval[p];
+        if (!(v >= 0.0) || v != floor(v)) { f |= HVG_FLAG_NOT_COUNT; continue; }
+        if (v > HVG_COUNT_MAX) { f |= HVG_FLAG_TOO_LARGE; continue; }
+        const long long iv = (long long)v;
+        a += iv;
+        b += iv * iv;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); f |= __shfl_xor(f, o, 64); }
+    if (lane == 0) { s1[g] = a; s2[g] = b; flags[g] = f; }
+}
+
+// one wavefront per column g: c1[g] = sum min(x, clip[g]), c2[g] = sum of its square (the square rounded, then added)
+__global__ __launch_bounds__(256) void hvg_clipped_sums_kernel(const long long* __restrict__ cptr, const int* __restrict__ crow,
+                                                               const double* __restrict__ cval, int G, int N,
+                                                               const double* __restrict__ clip, double* __restrict__ c1,
+                                                               double* __restrict__ c2)
+{
+#pragma clang fp contract(off)
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (g >= G) return;
+    const double c = clip[g];
+    double a = 0.0, b = 0.0;
+    for (long long p = cptr[g] + lane; p < cptr[g + 1]; p += 64) {
+        const int r = crow[p];
+        if (r < 0 || r >= N) continue;
+        const double m = fmin(cval[p], c);
+        a += m;
+        b += m * m;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+    if (lane == 0) { c1[g] = a; c2[g] = b; }
+}
+
+// ---------------------------------------------------------------- pairs of doubles (hi + lo, |lo| <= ulp(hi) / 2)
+// The error term of a two-sum is exact only when every operation is rounded on its own: a product fused into the
+// following addition (the compiler's default for device code) leaves a wrong error term behind and the pair is worth
+// one double again.  Hence `fp contract(off)` in every function here and in the kernels that call them (the flag stays
+// on the instructions when they are inlined); the one fused operation wanted, the error of a product, is an explicit fma.
+struct hvg_dd { double hi, lo; };
+
+__device__ __forceinline__ hvg_dd hvg_two_sum(double a, double b)
+{
+#pragma clang fp contract(off)
+    const double s = a + b, bb = s - a;
+    return {s, (a - (s - bb)) + (b - bb)};
+}
+
+__device__ __forceinline__ hvg_dd hvg_renorm(double hi, double lo)          // (|hi| >= |lo|)
+{
+#pragma clang fp contract(off)
+    const double s = hi + lo;
+    return {s, lo - (s - hi)};
+}
+
+__device__ __forceinline__ hvg_dd hvg_add_d(hvg_dd a, double b)
+{
+#pragma clang fp contract(off)
+    const hvg_dd s = hvg_two_sum(a.hi, b);
+    return hvg_renorm(s.hi, s.lo + a.lo);
+}
+
+__device__ __forceinline__ hvg_dd hvg_add(hvg_dd a, hvg_dd b)
+{
+#pragma clang fp contract(off)
+    hvg_dd s = hvg_two_sum(a.hi, b.hi);
+    const hvg_dd t = hvg_two_sum(a.lo, b.lo);
+    s = hvg_renorm(s.hi, s.lo + t.hi);
+    return hvg_renorm(s.hi, s.lo + t.lo);
+}
+
+__device__ __forceinline__ hvg_dd hvg_neg(hvg_dd a) { return {-a.hi, -a.lo}; }
+
+__device__ __forceinline__ hvg_dd hvg_mul(hvg_dd a, hvg_dd b)
+{
+#pragma clang fp contract(off)
+    const double p = a.hi * b.hi;
+    double e = fma(a.hi, b.hi, -p);
+    e += a.hi * b.lo + a.lo * b.hi;
+    return hvg_renorm(p, e);
+}
+
+__device__ __forceinline__ hvg_dd hvg_div(hvg_dd a, hvg_dd b)
+{
+#pragma clang fp contract(off)
+    const double q1 = a.hi / b.hi;
+    hvg_dd r = hvg_add(a, hvg_neg(hvg_mul(b, {q1, 0.0})));
+    const double q2 = r.hi / b.hi;
+    r = hvg_add(r, hvg_neg(hvg_mul(b, {q2, 0.0})));
+    const double q3 = r.hi / b.hi;
+    return hvg_add_d(hvg_renorm(q1, q2), q3);
+}
+
+__device__ __forceinline__ hvg_dd hvg_sub(hvg_dd a, hvg_dd b) { return hvg_add(a, hvg_neg(b)); }
+
+// one workgroup per evaluation point e: the local quadratic fit at x0[e] over the q nearest of the n sorted abscissae
+// (see the head of this file); value[e] = c0, slope[e] = c1 / h, status[e]
+__global__ __launch_bounds__(HVG_FIT_THREADS) void hvg_loess_fit_kernel(const double* __restrict__ x, const double* __restrict__ y,
+                                                                        int n, int q, const double* __restrict__ x0s, int m,
+                                                                        double* __restrict__ value, double* __restrict__ slope,
+                                                                        int* __restrict__ status)
+{
+#pragma clang fp contract(off)
+    __shared__ hvg_dd part[HVG_FIT_THREADS / 64][8];
+    const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (e >= m) return;                                  // (uniform over the workgroup)
+    const double x0 = x0s[e];
+    int lo = 0, hi = n - q;                              // the window [lo, lo + q): uniform over the workgroup
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (x0 - x[mid] <= x[mid + q] - x0) hi = mid; else lo = mid + 1;
+    }
+    const double h = fmax(x0 - x[lo], x[lo + q - 1] - x0);
+    if (!(h > 0.0) || !(h < INFINITY)) {
+        if (tid == 0) { value[e] = 0.0; slope[e] = 0.0; status[e] = HVG_FIT_ZERO_WIDTH; }
+        return;
+    }
+    hvg_dd acc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = {0.0, 0.0};
+    for (int i = lo + tid; i < lo + q; i += HVG_FIT_THREADS) {
+        const double dx = x[i] - x0, d = fabs(dx);
+        if (!(d < h)) continue;                          // (a point tied at distance h weighs nothing)
+        const double r = d / h, u = 1.0 - r * r * r;
+        const double w = u * u * u, t = dx / h, yi = y[i];
+        const double wt = w * t, wt2 = wt * t, wt3 = wt2 * t, wt4 = wt3 * t;
+        acc[0] = hvg_add_d(acc[0], w);
+        acc[1] = hvg_add_d(acc[1], wt);
+        acc[2] = hvg_add_d(acc[2], wt2);
+        acc[3] = hvg_add_d(acc[3], wt3);
+        acc[4] = hvg_add_d(acc[4], wt4);
+        acc[5] = hvg_add_d(acc[5], w * yi);
+        acc[6] = hvg_add_d(acc[6], wt * yi);
+        acc[7] = hvg_add_d(acc[7], wt2 * yi);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const hvg_dd other = {__shfl_xor(acc[k].hi, o, 64), __shfl_xor(acc[k].lo, o, 64)};
+            acc[k] = hvg_add(acc[k], other);             // (a + b on both lanes of a pair: the same bits on every lane)
+        }
+        if (lane == 0) part[wave][k] = acc[k];
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    hvg_dd M[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) M[k] = hvg_add(hvg_add(part[0][k], part[1][k]), hvg_add(part[2][k], part[3][k]));
+    // G = [[m0, m1, m2], [m1, m2, m3], [m2, m3, m4]] = L D L^T, rhs (b0, b1, b2) = M[5..7]
+    const hvg_dd m0 = M[0], m1 = M[1], m2 = M[2], m3 = M[3], m4 = M[4];
+    int st = HVG_FIT_OK;
+    double c0 = 0.0, c1 = 0.0;
+    if (!(m0.hi > 0.0)) {
+        st = HVG_FIT_DEFICIENT;
+    } else {
+        const hvg_dd l21 = hvg_div(m1, m0), l31 = hvg_div(m2, m0);
+        const hvg_dd d2 = hvg_sub(m2, hvg_mul(l21, m1));
+        if (!(d2.hi > HVG_PIVOT_MIN * m2.hi)) {
+            st = HVG_FIT_DEFICIENT;
+        } else {
+            const hvg_dd ee = hvg_sub(m3, hvg_mul(l31, m1));
+            const hvg_dd l32 = hvg_div(ee, d2);
+            const hvg_dd d3 = hvg_sub(hvg_sub(m4, hvg_mul(l31, m2)), hvg_mul(l32, ee));
+            if (!(d3.hi > HVG_PIVOT_MIN * m4.hi)) {
+                st = HVG_FIT_DEFICIENT;
+            } else {
+                const hvg_dd z1 = M[5];
+                const hvg_dd z2 = hvg_sub(M[6], hvg_mul(l21, z1));
+                const hvg_dd z3 = hvg_sub(hvg_sub(M[7], hvg_mul(l31, z1)), hvg_mul(l32, z2));
+                const hvg_dd k2 = hvg_div(z3, d3);
+                const hvg_dd k1 = hvg_sub(hvg_div(z2, d2), hvg_mul(l32, k2));
+                const hvg_dd k0 = hvg_sub(hvg_sub(hvg_div(z1, m0), hvg_mul(l21, k1)), hvg_mul(l31, k2));
+                c0 = k0.hi + k0.lo;
+                c1 = (k1.hi + k1.lo) / h;
+            }
+        }
+    }
+    value[e] = c0; slope[e] = c1; status[e] = st;
+}
+
+}  // namespace cnmf
+
+extern "C" int cnmf_preprocess_gene_moments(cnmf_ctx* ctx, int64_t* s1, int64_t* s2, int32_t* flags)
+{
+    using namespace cnmf;
+    if (int rc = flt_staged(ctx)) return rc;
+    if (!s1 || !s2 || !flags) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
+    PreStage& P = ctx->pre;
+    const int N = (int)P.N, G = (int)P.counts.cols;
+    if (P.N > HVG_CELLS_MAX) {
+        SET_ERR(ctx, "gene_moments: %lld cells, more than %lld (sum x^2 must stay an exact int64)", (long long)P.N, HVG_CELLS_MAX);
+        return CNMF_EINVAL;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevPool pool;
+    long long* d1 = pool.get<long long>((size_t)G);
+    long long* d2 = pool.get<long long>((size_t)G);
+    int* df = pool.get<int>((size_t)G);
+    POOL_TRY(ctx, pool);
+    std::vector<int> hf((size_t)G);
+    hvg_gene_moments_kernel<<<(G + 3) / 4, 256, 0, st>>>(P.columns.ptr, P.columns.idx, P.columns.val, G, N, d1, d2, df);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(s1, d1, (size_t)G * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s2, d2, (size_t)G * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(hf.data(), df, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    int all = 0;
+    for (int f : hf) all |= f;
+    *flags = all;
+    return CNMF_OK;
+}
+
+extern "C" int cnmf_preprocess_clipped_sums(cnmf_ctx* ctx, const double* clip, double* c1, double* c2)
+{
+    using namespace cnmf;
+    if (int rc = flt_staged(ctx)) return rc;
+    if (!clip || !c1 || !c2) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
+    PreStage& P = ctx->pre;
+    const int N = (int)P.N, G = (int)P.counts.cols;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevPool pool;
+    double* dc = pool.get<double>((size_t)G);
+    double* d1 = pool.get<double>((size_t)G);
+    double* d2 = pool.get<double>((size_t)G);
+    POOL_TRY(ctx, pool);
+    HIP_TRY(ctx, hipMemcpyAsync(dc, clip, (size_t)G * sizeof(double), hipMemcpyHostToDevice, st));
+    hvg_clipped_sums_kernel<<<(G + 3) / 4, 256, 0, st>>>(P.columns.ptr, P.columns.idx, P.columns.val, G, N, dc, d1, d2);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(c1, d1, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(c2, d2, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return CNMF_OK;
+}
+
+extern "C" int cnmf_preprocess_loess_fit(cnmf_ctx* ctx, int64_t n, const double* x, const double* y, int64_t q, int64_t m,
+                                         const double* x0, double* value, double* slope, int32_t* status)
+{
+    using namespace cnmf;
+    if (!ctx || !x || !y || !x0 || !value || !slope || !status) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
+    if (n < 1 || n > (1ll << 30) || q < 1 || q > n || m < 0 || m > (1ll << 30)) {
+        SET_ERR(ctx, "loess_fit: n = %lld, q = %lld, m = %lld (1 <= q <= n <= 2^30, 0 <= m <= 2^30)", (long long)n, (long long)q,
+                (long long)m);
+        return CNMF_EINVAL;
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(x[i]) || !std::isfinite(y[i]) || (i && x[i] < x[i - 1])) {
+            SET_ERR(ctx, "loess_fit: the abscissae must be finite and sorted, the ordinates finite (entry %lld)", (long long)i);
+            return CNMF_EINVAL;
+        }
+    for (int64_t i = 0; i < m; ++i)
+        if (!std::isfinite(x0[i])) { SET_ERR(ctx, "loess_fit: evaluation point %lld is not finite", (long long)i); return CNMF_EINVAL; }
+    if (m == 0) return CNMF_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevPool pool;
+    double* dx = pool.get<double>((size_t)n);
+    double* dy = pool.get<double>((size_t)n);
+    double* d0 = pool.get<double>((size_t)m);
+    double* dv = pool.get<double>((size_t)m);
+    double* ds = pool.get<double>((size_t)m);
+    int* dst = pool.get<int>((size_t)m);
+    POOL_TRY(ctx, pool);
+    HIP_TRY(ctx, hipMemcpyAsync(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(dy, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d0, x0, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
+    hvg_loess_fit_kernel<<<(unsigned)m, HVG_FIT_THREADS, 0, st>>>(dx, dy, (int)n, (int)q, d0, (int)m, dv, ds, dst);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(value, dv, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(slope, ds, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(status, dst, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return CNMF_OK;
+}

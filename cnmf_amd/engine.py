@@ -697,6 +697,51 @@ class Engine:
             indptr = indptr.astype(np.int32)
         return sp.csr_matrix((data[:nnz], indices[:nnz].astype(indptr.dtype), indptr), shape=(N, G))
 
+    # ---- the device steps of Preprocess.highly_variable_genes (hvg_host.hip.h)
+    def preprocess_gene_moments(self):
+        """Per staged gene, over the staging as it is now: S1 = sum x and S2 = sum x^2 as exact int64.  Returns
+        ``(s1, s2, flags)``: flags bit 0 = a negative, non-integer or non-finite value was met, bit 1 = a count above
+        2^20 (both kinds are left out of the sums)."""
+        self._pre_mask(None, "G", "")
+        G = self._pre["G"]
+        s1, s2, flags = np.empty(G, dtype=np.int64), np.empty(G, dtype=np.int64), C.c_int32(0)
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._lib.cnmf_preprocess_gene_moments(self._ctx, s1.ctypes.data_as(i64p), s2.ctypes.data_as(i64p),
+                                                           C.byref(flags)))
+        return s1, s2, int(flags.value)
+
+    def preprocess_loess_fit(self, x, y, q, x0):
+        """The local quadratic fits of loess(degree=2) at the points ``x0`` over the points (``x`` sorted ascending,
+        ``y``), each over its ``q`` nearest abscissae with tricube weights.  Returns ``(value, slope, status)`` per
+        point: status 0, 1 (zero-width neighbourhood) or 2 (fewer than three distinct weighted abscissae, or nearly so);
+        value and slope are 0 where the status is not 0.  The same bits on every call.  Needs no staging."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        if x.ndim != 1 or y.shape != x.shape or x0.ndim != 1 or not 1 <= int(q) <= x.size:
+            raise ValueError("loess_fit: x %s, y %s, x0 %s, q = %s" % (x.shape, y.shape, x0.shape, q))
+        m = x0.size
+        value, slope, status = np.zeros(m), np.zeros(m), np.zeros(m, dtype=np.int32)
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_preprocess_loess_fit(self._ctx, x.size, x.ctypes.data_as(dblp), y.ctypes.data_as(dblp),
+                                                        int(q), m, x0.ctypes.data_as(dblp), value.ctypes.data_as(dblp),
+                                                        slope.ctypes.data_as(dblp),
+                                                        status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return value, slope, status
+
+    def preprocess_clipped_sums(self, clip):
+        """Per staged gene: ``(C1, C2)``, the sums of min(x, clip[gene]) and of its square over the gene's entries."""
+        self._pre_mask(None, "G", "")
+        G = self._pre["G"]
+        clip = np.ascontiguousarray(clip, dtype=np.float64)
+        if clip.shape != (G,) or not np.isfinite(clip).all():
+            raise ValueError("clip must hold %d finite values (got shape %s)" % (G, clip.shape))
+        c1, c2 = np.empty(G), np.empty(G)
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_preprocess_clipped_sums(self._ctx, clip.ctypes.data_as(dblp), c1.ctypes.data_as(dblp),
+                                                           c2.ctypes.data_as(dblp)))
+        return c1, c2
+
     def preprocess_release(self):
         self._check(self._lib.cnmf_preprocess_release(self._ctx))
         self._pre = None

@@ -69,8 +69,38 @@ scikit-learn's KMeans (tests/test_gpu_harmony_init.py: the best init, its labels
 centres within the rounding of a mean).  With fewer distinct cells than clusters the centres of the surplus clusters are
 unspecified: the restatement and scikit-learn disagree there themselves, and no parity is claimed.
 
-Out of scope: the seurat_v3 HVG selection (``n_top_genes`` / ``n_top_rna_genes``: it needs skmisc's loess), plots
-(``makeplots`` is accepted and nothing is drawn) and ``.h5ad`` writing.
+``Preprocess.highly_variable_genes`` is scanpy's ``highly_variable_genes(flavor='seurat_v3')`` for one batch (the call
+``normalize_batchcorrect(n_top_genes=...)`` makes, :314-315), opt-in through ``hvg="device"`` together with a number for
+``n_top_genes`` / ``n_top_rna_genes`` on ``normalize_batchcorrect`` and ``preprocess_for_cnmf`` (the default,
+``hvg=None``, keeps the NotImplementedError for a number).  On the device (csrc/hvg_host.hip.h), over the staging as it
+is after ``exclude_genes`` went:
+
+* the per-gene moments S1 = sum x, S2 = sum x^2 as 64-bit integers (counts are non-negative integers: exact in any order);
+  mean = S1 / N and var = (N S2 - S1^2) / (N (N - 1)) with the numerator in Python integers and one division;
+* the local fits of skmisc's ``loess(x, y, span=0.3, degree=2)`` (family gaussian: no robustness iterations; no
+  normalisation in one dimension) over the genes with var > 0, x = log10(mean), y = log10(var), n points,
+  q = min(n, floor(n span + 1e-5)).  A local fit at x0: h = the q-th smallest |x_i - x0| (h <= 0: ValueError, skmisc's
+  "zero-width neighborhood"); w_i = (1 - (|x_i - x0| / h)^3)^3 where |x_i - x0| < h, else 0; the weighted least-squares
+  quadratic in t = (x - x0) / h, minimum-norm with the singular values below 100 eps sigma_max dropped; its value c0 and
+  slope c1 / h.  The device finds the neighbourhood by binary search in the sorted abscissae, sums the eight weighted
+  moments (compensated float64 sums, a fixed order) and solves the 3 x 3 normal equations; a neighbourhood with fewer
+  than three distinct weighted abscissae (or nearly so) comes back flagged and is solved on the host
+  (``loess_local_fit_host``).  surface="direct": the fitted value of a gene is the local fit at its own x.
+  surface="interpolate" (skmisc's default): local fits at the vertices of ``loess_vertices`` (about 30), a cubic Hermite
+  blend between the two vertices of a gene's cell (``loess_hermite``);
+* est = 0 on constant genes, the fitted value elsewhere; reg_std = sqrt(10^est); clip = reg_std sqrt(N) + mean; the
+  per-gene sums C1 = sum min(x, clip), C2 = sum min(x, clip)^2; variances_norm = (N mean^2 + C2 - 2 C1 mean) /
+  ((N - 1) reg_std^2); rank by variances_norm descending, ties in gene order.
+
+**The yardstick is the float64 numpy restatement of the above in tests/_seurat_v3_ref.py** (moments, means and variances
+equal bit for bit; the local fits and variances_norm within 16 x the restatement's distance from its own long double run;
+the selected set and the ranks equal).  **Agreement with skmisc's loess and with scanpy itself is unmeasured on this
+project's machines**: neither library is installed on them; tests/test_host_hvg.py compares the restatement with both
+wherever they can be imported.  The vertex rule is written from the published algorithm (Cleveland and Grosse's
+dloess); that test is where a mismatch would show.
+
+Out of scope: ``batch_key`` and the other flavours of highly_variable_genes, loess's robustness iterations and
+``degree != 2``, plots (``makeplots`` is accepted and nothing is drawn) and ``.h5ad`` writing.
 """
 import numpy as np
 import pandas as pd
@@ -79,7 +109,7 @@ HARMONY_IMPORT_ERROR = "harmonypy is not installed. Please install it using 'pip
 HVG_REQUIRED_ERROR = ("If a numeric value for n_top_genes is not provided, you must include a highly_variable column "
                       "in _adata")
 N_TOP_GENES_ERROR = ("n_top_genes (seurat_v3 HVG selection) needs skmisc's loess, which this package does not use: pass "
-                     "highly_variable instead")
+                     "highly_variable instead, or opt into this package's own selection on the device with hvg='device'")
 ADT_CELL_COUNT_ERROR = "ADT and RNA AnnDatas don't have the same number of cells"
 ADT_CELL_INDEX_ERROR = "Inconsistency of the index for the ADT and RNA AnnDatas"
 DATA_FORM_ERROR = 'data should either be an AnnData object or a list of 2 AnnData objects'
@@ -121,11 +151,11 @@ def _data_parts(data):
     return mat, pd.Index([str(c) for c in cells]), pd.Index([str(x) for x in genes]), dense
 
 
-def _to_csr(mat):
+def _to_csr(mat, what="Preprocess"):
     import scipy.sparse as sp
     X = sp.csr_matrix(mat, dtype=np.float64)
     if X.nnz and not (np.isfinite(X.data).all() and (X.data >= 0).all()):
-        raise ValueError("Preprocess expects finite non-negative values")
+        raise ValueError("%s expects finite non-negative values" % what)
     return X
 
 
@@ -280,6 +310,148 @@ def _check_harmony_mode(harmony):
 def _check_kmeans_init(kmeans_init):
     if kmeans_init not in KMEANS_INIT_MODES:
         raise ValueError("kmeans_init must be one of %s, not %r" % (KMEANS_INIT_MODES, kmeans_init))
+
+
+HVG_MODES = (None, "device")
+LOESS_SURFACES = ("interpolate", "direct")
+HVG_COUNT_MAX = 1 << 20
+HVG_CELLS_MAX = 1 << 22
+LOESS_ZERO_WIDTH_ERROR = "loess: zero-width neighborhood; make span bigger"
+LOESS_RCOND = 100 * float(np.finfo(np.float64).eps)
+
+
+def _check_hvg_mode(hvg):
+    if hvg not in HVG_MODES:
+        raise ValueError("hvg must be None or 'device', not %r" % (hvg,))
+
+
+def _check_hvg_args(n_top_genes, span, surface, flavor="seurat_v3"):
+    if flavor != "seurat_v3":
+        raise NotImplementedError("highly_variable_genes: flavor %r is not implemented (only 'seurat_v3')" % (flavor,))
+    if surface not in LOESS_SURFACES:
+        raise ValueError("surface must be one of %s, not %r" % (LOESS_SURFACES, surface))
+    if isinstance(n_top_genes, bool) or int(n_top_genes) != n_top_genes or n_top_genes < 1:
+        raise ValueError("n_top_genes must be a positive integer, not %r" % (n_top_genes,))
+    if not 0.0 < span <= 1.0:
+        raise ValueError("span must be in (0, 1], not %r" % (span,))
+
+
+def loess_neighbours(n, span):
+    """q of skmisc's loess: the points of a neighbourhood among n"""
+    return int(min(n, np.floor(n * span + 1e-5)))
+
+
+def loess_vertices(xs, span):
+    """The vertices of loess's interpolation surface over the SORTED abscissae ``xs`` (Cleveland and Grosse's dloess in
+    one dimension): the ends of [min - mu, max + mu], mu = 0.005 max(max - min, 1e-10 max(|min|, |max|) + 1e-30), and
+    the cuts of every cell that holds more than fc = floor(n span 0.2) points at (x_(m) + x_(m+1)) / 2, m the middle
+    index (l + u) // 2 of the cell's points, moved by +1, -1, +2, ... until x_(m) != x_(m+1); no cut when no such m lies
+    inside the cell or x_(m) equals an end of the cell.  Sorted, strictly increasing."""
+    n = xs.size
+    lo, hi = xs[0], xs[-1]
+    mu = 0.005 * max(hi - lo, 1e-10 * max(abs(lo), abs(hi)) + 1e-30)
+    fc = int(np.floor(n * span * 0.2))
+    cuts, todo = [], [(lo - mu, hi + mu, 0, n - 1)]
+    while todo:
+        a, b, l, u = todo.pop()
+        if u - l + 1 <= fc:
+            continue
+        m, mid = None, (l + u) // 2
+        for k in range(2 * (u - l + 1)):
+            c = mid + ((k + 1) // 2 if k % 2 else -(k // 2))      # offsets 0, +1, -1, +2, -2, ...
+            if l <= c and c + 1 <= u and xs[c] != xs[c + 1]:
+                m = c
+                break
+        if m is None or xs[m] == a or xs[m] == b:
+            continue
+        t = (xs[m] + xs[m + 1]) / 2
+        cuts.append(t)
+        todo += [(a, t, l, m), (t, b, m + 1, u)]
+    return np.array(sorted([lo - mu, hi + mu] + cuts), dtype=np.float64)
+
+
+def loess_local_fit_host(xs, ys, x0, q):
+    """One local fit of loess(degree=2) on the host, as the module docstring states it: (value, slope) at x0 from the
+    minimum-norm weighted least-squares quadratic over the q nearest points (singular values below 100 eps sigma_max
+    dropped).  The device hands the rank-deficient neighbourhoods to this."""
+    d = np.abs(xs - x0)
+    h = np.partition(d, q - 1)[q - 1]
+    if not h > 0:
+        raise ValueError(LOESS_ZERO_WIDTH_ERROR)
+    use = d < h
+    r = d[use] / h
+    sw = np.sqrt((1 - r * r * r) ** 3)
+    t = (xs[use] - x0) / h
+    coef = np.linalg.lstsq(np.stack([sw, sw * t, sw * t * t], axis=1), sw * ys[use], rcond=LOESS_RCOND)[0]
+    return coef[0], coef[1] / h
+
+
+def loess_hermite(v, value, slope, x):
+    """the cubic Hermite interpolant through the vertices ``v`` (values, slopes) at the points ``x`` inside them"""
+    c = np.clip(np.searchsorted(v, x, side="right") - 1, 0, v.size - 2)
+    w = v[c + 1] - v[c]
+    u = (x - v[c]) / w
+    return ((1 - u) ** 2 * (1 + 2 * u) * value[c] + u ** 2 * (3 - 2 * u) * value[c + 1]
+            + (u * (1 - u) ** 2 * slope[c] - u ** 2 * (1 - u) * slope[c + 1]) * w)
+
+
+def loess_fitted(eng, x, y, span=0.3, surface="interpolate"):
+    """The fitted values of skmisc's ``loess(x, y, span=span, degree=2)`` (family gaussian, no robustness iterations)
+    at the points themselves, the local fits on the device (``eng.preprocess_loess_fit``): at the vertices of the
+    interpolation surface (about 30 of them), or with surface="direct" at every point."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    order = np.argsort(x, kind="stable")
+    xs, ys = x[order], y[order]
+    q = loess_neighbours(x.size, span)
+    if q < 1:
+        raise ValueError("span = %g leaves no point in a neighbourhood of %d" % (span, x.size))
+    at = xs if surface == "direct" else loess_vertices(xs, span)
+    value, slope, status = eng.preprocess_loess_fit(xs, ys, q, at)
+    if (status == 1).any():
+        raise ValueError(LOESS_ZERO_WIDTH_ERROR)
+    for i in np.flatnonzero(status != 0):                         # rank-deficient neighbourhoods: the minimum-norm fit
+        value[i], slope[i] = loess_local_fit_host(xs, ys, at[i], q)
+    fitted = np.empty_like(xs)
+    fitted[order] = value if surface == "direct" else loess_hermite(at, value, slope, xs)
+    return fitted
+
+
+def exact_mean_var(s1, s2, N):
+    """mean = S1 / N and the ddof=1 variance (N S2 - S1^2) / (N (N - 1)) from the integer sums: the numerator in Python
+    integers, one division -- correctly rounded, whatever order the sums were taken in"""
+    N = int(N)
+    den = N * (N - 1)
+    mean = np.array([int(a) / N for a in s1], dtype=np.float64)
+    var = np.array([(N * int(b) - int(a) * int(a)) / den for a, b in zip(s1, s2)], dtype=np.float64)
+    return mean, var
+
+
+def seurat_v3_frame(eng, N, genes, n_top_genes=2000, span=0.3, surface="interpolate"):
+    """scanpy's ``highly_variable_genes(flavor='seurat_v3')`` frame (batch_key=None) over the counts ``eng`` has staged
+    (N cells, the genes ``genes``): see Preprocess.highly_variable_genes.  The caller uploads and releases."""
+    if not 2 <= N <= HVG_CELLS_MAX:
+        raise ValueError("flavor='seurat_v3' needs between 2 and %d cells, not %d" % (HVG_CELLS_MAX, N))
+    s1, s2, flags = eng.preprocess_gene_moments()
+    if flags & 1:
+        raise ValueError("flavor='seurat_v3' expects raw counts: a negative or non-integer value was found")
+    if flags & 2:
+        raise ValueError("flavor='seurat_v3': a count above %d cannot be summed exactly and is refused" % HVG_COUNT_MAX)
+    mean, var = exact_mean_var(s1, s2, N)
+    not_const = var > 0
+    est = np.zeros(len(mean))
+    if not_const.any():
+        est[not_const] = loess_fitted(eng, np.log10(mean[not_const]), np.log10(var[not_const]), span, surface)
+    reg_std = np.sqrt(10 ** est)
+    clip = reg_std * np.sqrt(np.float64(N)) + mean
+    c1, c2 = eng.preprocess_clipped_sums(clip)
+    vnorm = (N * mean * mean + c2 - 2 * c1 * mean) / ((N - 1) * reg_std * reg_std)
+    order = np.argsort(-vnorm, kind="stable")                     # ties in gene order
+    rank = np.empty(order.size, dtype=np.float64)
+    rank[order] = np.arange(order.size)
+    hv = rank < n_top_genes
+    rank[~hv] = np.nan
+    return pd.DataFrame({"means": mean, "variances": var, "variances_norm": vnorm, "highly_variable_rank": rank,
+                         "highly_variable": hv}, index=pd.Index(genes))
 
 
 class HarmonyResult:
@@ -528,14 +700,24 @@ class Preprocess:
     # ------------------------------------------------------------------ normalize_batchcorrect (preprocess.py:246-360)
     def normalize_batchcorrect(self, data, obs=None, highly_variable=None, normalize_librarysize=False, harmony_vars=None,
                                n_top_genes=None, librarysize_targetsum=1e4, max_scaled_thresh=None, quantile_thresh=.9999,
-                               theta=1, makeplots=True, max_iter_harmony=20, harmony_res=None, harmony="harmonypy"):
+                               theta=1, makeplots=True, max_iter_harmony=20, harmony_res=None, harmony="harmonypy",
+                               hvg=None):
         """Normalises the high-variance genes of raw counts and optionally corrects them with Harmony.  Returns
         ``(result, hvgs)``: ``result.X`` goes straight into ``cNMF.prepare(counts=(result.X, result.obs_names, hvgs),
         ...)``.  ``harmony``: who runs Harmony when ``harmony_res`` is not given: "harmonypy" (the library), "device"
-        (``self.run_harmony``) or "device_full" (``self.run_harmony(kmeans_init="device")``)."""
-        if n_top_genes is not None:
+        (``self.run_harmony``) or "device_full" (``self.run_harmony(kmeans_init="device")``).
+
+        ``hvg``: None (the default: a number for ``n_top_genes`` raises NotImplementedError and ``highly_variable`` is
+        required) or "device": a number for ``n_top_genes`` then runs ``highly_variable_genes`` (seurat_v3) on the
+        staged counts and its selection replaces ``highly_variable``, as the reference overwrites
+        ``var['highly_variable']``; the frame, restricted to the selected genes, is ``result.var``."""
+        _check_hvg_mode(hvg)
+        if n_top_genes is not None and hvg is None:
             raise NotImplementedError(N_TOP_GENES_ERROR)
-        if highly_variable is None:
+        select = n_top_genes is not None
+        if select:
+            _check_hvg_args(n_top_genes, 0.3, "interpolate")
+        elif highly_variable is None:
             raise Exception(HVG_REQUIRED_ERROR)
         _check_quantile(quantile_thresh)
         _check_harmony_mode(harmony)
@@ -544,22 +726,58 @@ class Preprocess:
                 _import_harmonypy()
             _check_harmony_vars(obs, harmony_vars)
         mat, cells, genes, dense = _data_parts(data)
-        sel = np.flatnonzero(_hv_mask(highly_variable, genes))
-        if sel.size == 0:
-            raise ValueError("highly_variable selects no gene")
-        hvgs = list(genes[sel])
+        if not select:
+            sel = np.flatnonzero(_hv_mask(highly_variable, genes))
+            if sel.size == 0:
+                raise ValueError("highly_variable selects no gene")
         if obs is not None:
             obs = _align_obs(obs, cells)
         X = _to_csr(mat)
+        var = None
         eng = self.engine
         try:
             eng.preprocess_upload(X)
+            if select:
+                var = seurat_v3_frame(eng, X.shape[0], genes, n_top_genes)
+                sel = np.flatnonzero(var["highly_variable"].values)
+                var = var.iloc[sel]
             Xout, obsm = self._batchcorrect_staged(eng, X.shape[0], sel, dense, obs, normalize_librarysize, harmony_vars,
                                                    librarysize_targetsum, max_scaled_thresh, quantile_thresh, theta,
                                                    max_iter_harmony, harmony_res, harmony)
         finally:
             eng.preprocess_release()
-        return PreprocessResult(Xout, cells, pd.Index(hvgs), obs, obsm), hvgs
+        hvgs = list(genes[sel])
+        return PreprocessResult(Xout, cells, pd.Index(hvgs), obs, obsm, var=var), hvgs
+
+    # ------------------------------------------------------------------ highly_variable_genes (scanpy, flavor='seurat_v3')
+    def highly_variable_genes(self, data, n_top_genes=2000, span=0.3, surface="interpolate", flavor="seurat_v3"):
+        """scanpy's ``sc.pp.highly_variable_genes(flavor='seurat_v3', n_top_genes, span)`` for one batch (the call the
+        reference makes, preprocess.py:314-315), over raw counts in any of the forms ``data`` takes.  Returns scanpy's
+        frame, indexed by gene in the data's order: ``means``, ``variances`` (ddof=1), ``variances_norm``,
+        ``highly_variable_rank`` (float; NaN from ``n_top_genes`` on) and ``highly_variable``.
+
+        The two O(nnz) passes (per-gene integer moments; per-gene sums of the counts clipped at
+        ``reg_std sqrt(N) + mean``) and the local fits of the loess of log10(variance) on log10(mean) run on the device;
+        the sort of the abscissae, the vertices, the Hermite blend, the few rank-deficient fits and the ranking run on
+        the host (module docstring).  ``surface``: "interpolate" (skmisc's default: local fits at about 30 vertices, a
+        cubic Hermite blend between them) or "direct" (a local fit at every gene); the two differ by up to about 5e-3 in
+        log10 variance and by a gene or two in the selected set.  Ties of ``variances_norm`` are ranked in gene order (a
+        stable sort; scanpy's own ``np.argsort`` leaves them unspecified).  Two calls on the same input give the same
+        bits.
+
+        Deliberate difference from scanpy, which warns on non-integer data and goes on: a negative or non-integer value
+        raises ValueError, and so does a count above 2^20 or more than 2^22 cells (the bound under which the integer
+        sums stay exact; nothing is ever wrapped).  Any other ``flavor`` raises NotImplementedError; there is no
+        ``batch_key``."""
+        _check_hvg_args(n_top_genes, span, surface, flavor)
+        mat, cells, genes, dense = _data_parts(data)
+        X = _to_csr(mat, what="flavor='seurat_v3'")
+        eng = self.engine
+        try:
+            eng.preprocess_upload(X)
+            return seurat_v3_frame(eng, X.shape[0], genes, n_top_genes, span, surface)
+        finally:
+            eng.preprocess_release()
 
     def _batchcorrect_staged(self, eng, N, sel, dense, obs, normalize_librarysize, harmony_vars, librarysize_targetsum,
                              max_scaled_thresh, quantile_thresh, theta, max_iter_harmony, harmony_res,
@@ -655,7 +873,7 @@ class Preprocess:
                             adt_feature_name='Antibody Capture', harmony_vars=None, n_top_rna_genes=None,
                             librarysize_targetsum=1e4, max_scaled_thresh=None, quantile_thresh=.9999, makeplots=True,
                             theta=1, save_output_base=None, max_iter_harmony=20, exclude_genes=None, harmony_res=None,
-                            harmony="harmonypy"):
+                            harmony="harmonypy", hvg=None):
         """The reference's minimal preprocessing: the HVG-filtered, variance-normalised, optionally Harmony-corrected RNA
         matrix (the ``counts`` input of cNMF) and the library-size-normalised matrix over all genes, ADT features
         appended and normalised on their own (the ``tpm`` input).
@@ -665,9 +883,13 @@ class Preprocess:
         ``[rna, adt]`` over the same cells.  A single-modality input gets anndata's ``var_names_make_unique``.
 
         Deliberate difference from the reference: ``n_top_rna_genes`` defaults to None (the reference: 2000) and
-        ``highly_variable`` -- a boolean mask or a list of names over the RNA genes -- takes its place, because the
-        seurat_v3 selection needs skmisc's loess; a number raises normalize_batchcorrect's NotImplementedError, None
-        without ``highly_variable`` the reference's "you must include a highly_variable column".
+        ``highly_variable`` -- a boolean mask or a list of names over the RNA genes -- takes its place: the seurat_v3
+        selection is opt-in.  With ``hvg=None`` (the default) a number raises normalize_batchcorrect's
+        NotImplementedError, and None without ``highly_variable`` the reference's "you must include a highly_variable
+        column".  With ``hvg="device"`` a number runs ``highly_variable_genes`` (seurat_v3; its yardstick is this
+        project's restatement of skmisc's loess, see the module docstring) on the staged RNA counts after
+        ``exclude_genes`` went, as the reference does: an excluded gene or an ADT feature is never selected, and the
+        selection replaces ``highly_variable``.  The frame of the selected genes is ``result_rna.var``.
 
         The RNA counts are uploaded once: ``tp10k`` comes from them over all RNA genes before ``exclude_genes`` are taken
         out (on the device), then normalize_batchcorrect's body runs on the same staging.
@@ -683,9 +905,13 @@ class Preprocess:
             rna, adt = data, None
         else:
             raise Exception(DATA_FORM_ERROR)
-        if n_top_rna_genes is not None:
+        _check_hvg_mode(hvg)
+        if n_top_rna_genes is not None and hvg is None:
             raise NotImplementedError(N_TOP_GENES_ERROR)
-        if highly_variable is None:
+        select = n_top_rna_genes is not None
+        if select:
+            _check_hvg_args(n_top_rna_genes, 0.3, "interpolate")
+        elif highly_variable is None:
             raise Exception(HVG_REQUIRED_ERROR)
         _check_quantile(quantile_thresh)
         _check_harmony_mode(harmony)
@@ -695,7 +921,7 @@ class Preprocess:
             _check_harmony_vars(obs, harmony_vars)
         mat, cells, genes, dense = _data_parts(rna)
         types_rna = types_adt = None
-        hv = np.asarray(highly_variable)
+        hv = None if select else np.asarray(highly_variable)
         if adt is not None:
             amat, acells, agenes, _ = _data_parts(adt)
             if amat.shape[0] != mat.shape[0]:
@@ -715,27 +941,27 @@ class Preprocess:
             ft = np.asarray(ft.values)
             X_all = sp.csr_matrix(mat) if not dense else mat
             amat, agenes, types_adt = X_all[:, np.flatnonzero(is_adt)], genes[is_adt], ft[is_adt]
-            if hv.dtype == bool and hv.shape == (len(genes),) and is_adt.any():
+            if not select and hv.dtype == bool and hv.shape == (len(genes),) and is_adt.any():
                 hv = hv[~is_adt]                                  # (a var['highly_variable'] column over all features)
             mat, genes, types_rna = X_all[:, np.flatnonzero(~is_adt)], genes[~is_adt], ft[~is_adt]
             adt = (amat, cells, agenes)
         else:
             genes = make_unique_names(genes)
-        hv_mask = _hv_mask(hv, genes)
         excluded = np.zeros(len(genes), dtype=bool)
         if exclude_genes is not None:
             excluded = np.asarray(genes.isin([str(x) for x in exclude_genes]))
-        sel = np.flatnonzero(hv_mask[~excluded])
-        if sel.size == 0:
-            raise ValueError("highly_variable selects no gene")
+        if not select:
+            sel = np.flatnonzero(_hv_mask(hv, genes)[~excluded])
+            if sel.size == 0:
+                raise ValueError("highly_variable selects no gene")
         if excluded.all():
             raise ValueError("exclude_genes leaves no gene")
-        hvgs = list(genes[~excluded][sel])
         if obs is not None:
             obs = _align_obs(obs, cells)
         X = _to_csr(mat)
         Xa = _to_csr(adt[0]) if adt is not None else None
         target = float(librarysize_targetsum)
+        hvg_var = None
         eng = self.engine
         try:
             eng.preprocess_upload(X)
@@ -747,6 +973,10 @@ class Preprocess:
                     eng.preprocess_subset(keep_genes=~excluded)
                 else:
                     print("exclude_genes provided but none found in adata_RNA.var_names.")
+            if select:                                              # on the RNA genes that are left (preprocess.py:314-315)
+                hvg_var = seurat_v3_frame(eng, X.shape[0], genes[~excluded], n_top_rna_genes)
+                sel = np.flatnonzero(hvg_var["highly_variable"].values)
+                hvg_var = hvg_var.iloc[sel]
             Xout, obsm = self._batchcorrect_staged(eng, X.shape[0], sel, dense, obs, False, harmony_vars, target,
                                                    max_scaled_thresh, quantile_thresh, theta, max_iter_harmony,
                                                    harmony_res, harmony)
@@ -759,6 +989,7 @@ class Preprocess:
                     tp_types = np.concatenate([types_rna, types_adt])
         finally:
             eng.preprocess_release()
+        hvgs = list(genes[~excluded][sel])
         if dense:
             tp10k = tp10k.toarray()
         var = pd.DataFrame(index=tp_genes)
@@ -766,7 +997,7 @@ class Preprocess:
             var["feature_type"] = tp_types
         elif adt is None:
             var["features_renamed"] = tp_genes
-        result = PreprocessResult(Xout, cells, pd.Index(hvgs), obs, obsm)
+        result = PreprocessResult(Xout, cells, pd.Index(hvgs), obs, obsm, var=hvg_var)
         tp = PreprocessResult(tp10k, cells, tp_genes, obs, var=var)
         if save_output_base is not None:
             _save_result(save_output_base + '.Corrected.HVG.Varnorm', result)

@@ -233,7 +233,20 @@ int cnmf_prepare_release(cnmf_ctx* ctx);
  *                                gene is kept; on any error the staging is left as it was.
  *   cnmf_preprocess_fetch_counts the staged CSR: target_sum > 0: values x * target_sum / row sum (0 for a cell without
  *                                counts; the bits of the normalised copy inside cnmf_preprocess_select), target_sum == 0:
- *                                the raw values.  Any of the three arrays may be NULL (skipped). */
+ *                                the raw values.  Any of the three arrays may be NULL (skipped).
+ * The device steps of Preprocess.highly_variable_genes (scanpy's flavor='seurat_v3', one batch; hvg_host.hip.h):
+ *   cnmf_preprocess_gene_moments per gene of the staging as it is now: s1 = sum x, s2 = sum x^2 as exact integers (at most
+ *                                2^22 cells); *flags: bit 0 = some value is negative, non-integer or not finite, bit 1 = some
+ *                                count exceeds 2^20 (such entries are left out of the sums: the caller refuses the data).
+ *   cnmf_preprocess_loess_fit    the local quadratic fits of loess(degree 2, family gaussian) at m evaluation points x0 over
+ *                                the n points (x, y), x SORTED ascending (no staging needed): per point h = the q-th smallest
+ *                                |x_i - x0|, tricube weights where |x_i - x0| < h, the weighted least-squares quadratic in
+ *                                (x - x0) / h from its normal equations (compensated float64 sums in a fixed order: the same
+ *                                bits on every call); value = the fit at x0, slope = its derivative there, status = 0, or
+ *                                1 (h <= 0: a zero-width neighbourhood) or 2 (fewer than three distinct weighted abscissae, or
+ *                                nearly so: the caller solves that point itself); value = slope = 0 where status != 0.
+ *   cnmf_preprocess_clipped_sums per gene of the staging: c1 = sum min(x, clip[g]), c2 = sum min(x, clip[g])^2 (float64,
+ *                                fixed order). */
 int cnmf_preprocess_upload_csr(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data,
                                int data_is_f64, int64_t n_cells, int64_t n_genes);
 int cnmf_preprocess_set_dense(cnmf_ctx* ctx, int32_t slot, const double* X, int64_t n_rows, int64_t n_cols);
@@ -265,6 +278,12 @@ int cnmf_preprocess_subset(cnmf_ctx* ctx, const uint8_t* keep_cells /* [n_cells]
                            const uint8_t* keep_genes /* [n_genes] or NULL */, int64_t* n_cells_out, int64_t* n_genes_out,
                            int64_t* nnz_out);
 int cnmf_preprocess_fetch_counts(cnmf_ctx* ctx, double target_sum, int64_t* indptr, int32_t* indices, double* values);
+int cnmf_preprocess_gene_moments(cnmf_ctx* ctx, int64_t* s1 /* [n_genes] */, int64_t* s2 /* [n_genes] */, int32_t* flags);
+int cnmf_preprocess_loess_fit(cnmf_ctx* ctx, int64_t n, const double* x /* [n] sorted */, const double* y /* [n] */, int64_t q,
+                              int64_t m, const double* x0 /* [m] */, double* value /* [m] */, double* slope /* [m] */,
+                              int32_t* status /* [m] */);
+int cnmf_preprocess_clipped_sums(cnmf_ctx* ctx, const double* clip /* [n_genes] */, double* c1 /* [n_genes] */,
+                                 double* c2 /* [n_genes] */);
 
 /* ---- Harmony's clustering loop (harmony_host.hip.h) -----------------------------------------------------------------
  * The loop of harmonypy's run_harmony over N cells, d components, K clusters and n_vars batch variables with n_levels

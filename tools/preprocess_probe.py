@@ -22,9 +22,15 @@ harmony_begin) -- and the device loop after each (best of --repeats, the centroi
 then the whole device route (run_harmony(kmeans_init="device")), and the loop from scikit-learn's centroids through the
 numpy restatement tests/_harmony_ref.py on this machine's cores.
 
+``--hvg`` times Preprocess.highly_variable_genes (seurat_v3) on the raw counts of ``--filter`` (default 50 000 x 20 000,
+about 6.7 % non-zero, 2 000 genes selected): the whole call with both loess surfaces (upload included, best of
+--repeats), its three device steps on their own (the integer moments, the local fits at the vertices and at every gene,
+the clipped sums), and the numpy restatement tests/_seurat_v3_ref.py on this machine's cores.
+
 Usage:  python tools/preprocess_probe.py [--cells 50000] [--genes 2000] [--K 100] [--batches 4] [--out FILE.json]
         python tools/preprocess_probe.py --filter [--filter-cells 50000] [--filter-genes 20000] [--out FILE.json]
         python tools/preprocess_probe.py --harmony [--cells 50000] [--components 50] [--K 100] [--batches 4] [--out FILE.json]
+        python tools/preprocess_probe.py --hvg [--filter-cells 50000] [--filter-genes 20000] [--out FILE.json]
 """
 import argparse
 import json
@@ -265,10 +271,68 @@ def harmony_leg(a):
     return out
 
 
+def hvg_leg(a):
+    from tests import _seurat_v3_ref as ref
+    X, cells, genes = make_raw_counts(a.filter_cells, a.filter_genes)
+    N, G = X.shape
+    out = {"cells": N, "genes": G, "density": round(X.nnz / (N * G), 4), "n_top_genes": N_HVG, "span": 0.3,
+           "host_threads": os.environ.get("OMP_NUM_THREADS"), "device_call_s": {}, "device_steps_ms": [], "restatement_s": {}}
+    frames = {}
+    with Engine(0) as eng:
+        P = pp.Preprocess(engine=eng)
+        small = make_raw_counts(2000, 500, density=0.3, seed=3)
+        P.highly_variable_genes(small, n_top_genes=50)                              # warm-up (code objects)
+        for surface in pp.LOESS_SURFACES:
+            out["device_call_s"][surface] = []
+            for _ in range(a.repeats):
+                t0 = time.perf_counter()
+                frames[surface] = P.highly_variable_genes((X, cells, genes), n_top_genes=N_HVG, surface=surface)
+                out["device_call_s"][surface].append(round(time.perf_counter() - t0, 3))
+        for _ in range(a.repeats):
+            t, names = [time.perf_counter()], []
+
+            def mark(name):
+                t.append(time.perf_counter())
+                names.append(name)
+
+            eng.preprocess_upload(X); mark("upload_counts")
+            s1, s2, _ = eng.preprocess_gene_moments(); mark("gene_moments")
+            mean, var = pp.exact_mean_var(s1, s2, N)
+            nc = var > 0
+            x, y = np.log10(mean[nc]), np.log10(var[nc])
+            order = np.argsort(x, kind="stable")
+            xs, ys = x[order], y[order]
+            v = pp.loess_vertices(xs, 0.3)
+            q = pp.loess_neighbours(xs.size, 0.3); mark("host_mean_var_sort_vertices")
+            eng.preprocess_loess_fit(xs, ys, q, v); mark("loess_fit_vertices")
+            _, _, status = eng.preprocess_loess_fit(xs, ys, q, xs); mark("loess_fit_every_gene")
+            clip = np.sqrt(10 ** np.zeros(G)) * np.sqrt(np.float64(N)) + mean
+            eng.preprocess_clipped_sums(clip); mark("clipped_sums")
+            eng.preprocess_release()
+            out["device_steps_ms"].append({n: round(1e3 * (b - c), 3) for n, c, b in zip(names, t[:-1], t[1:])})
+        out.update({"loess_points": int(xs.size), "loess_q": int(q), "loess_vertices": int(v.size),
+                    "loess_fits_flagged_for_the_host": int((status != 0).sum())})
+    out["device_call_s_best"] = {k: min(v) for k, v in out["device_call_s"].items()}
+    out["device_steps_ms_best"] = {k: min(r[k] for r in out["device_steps_ms"]) for k in out["device_steps_ms"][0]}
+    for surface in pp.LOESS_SURFACES:
+        t0 = time.perf_counter()
+        want = ref.seurat_v3(X, N_HVG, surface=surface, genes=genes)
+        out["restatement_s"][surface] = round(time.perf_counter() - t0, 3)
+        got = frames[surface]
+        out["same_selected_set_" + surface] = bool(np.array_equal(got["highly_variable"].values, want["highly_variable"].values))
+        out["max_rel_diff_variances_norm_" + surface] = float(np.max(
+            np.abs(got["variances_norm"].values - want["variances_norm"].values) / np.maximum(want["variances_norm"].values, 1e-300)))
+        out["restatement_over_device_" + surface] = round(out["restatement_s"][surface] / out["device_call_s_best"][surface], 2)
+    out["selected_genes_that_differ_between_the_surfaces"] = int(
+        (frames["interpolate"]["highly_variable"].values != frames["direct"]["highly_variable"].values).sum() // 2)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--filter", action="store_true")
     ap.add_argument("--harmony", action="store_true")
+    ap.add_argument("--hvg", action="store_true")
     ap.add_argument("--components", type=int, default=50)
     ap.add_argument("--filter-cells", type=int, default=50000)
     ap.add_argument("--filter-genes", type=int, default=20000)
@@ -280,8 +344,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.filter or a.harmony:
-        out = filter_leg(a) if a.filter else harmony_leg(a)
+    if a.filter or a.harmony or a.hvg:
+        out = filter_leg(a) if a.filter else harmony_leg(a) if a.harmony else hvg_leg(a)
         print(json.dumps(out, indent=1))
         if a.out:
             with open(a.out, "w") as F:
