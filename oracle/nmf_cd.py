@@ -78,8 +78,11 @@ def update_coordinate_descent(X, W, Ht, l1_reg, l2_reg):
 
 
 def fit_coordinate_descent(X, W, H, tol=1e-4, max_iter=200, l1_reg_W=0, l1_reg_H=0,
-                           l2_reg_W=0, l2_reg_H=0, update_H=True, trace=None):
-    """sklearn _nmf.py:406-523.  W is updated in place; returns (W, H, n_iter)."""
+                           l2_reg_W=0, l2_reg_H=0, update_H=True, trace=None, snapshots=None):
+    """sklearn _nmf.py:406-523.  W is updated in place; returns (W, H, n_iter).
+
+    ``snapshots``: a dict whose keys are iteration numbers; the value of every key the run reaches is set to copies
+    ``(W, H)`` of the factors as they stand after that iteration (one run then serves several ``max_iter``)."""
     Ht = np.ascontiguousarray(H.T)
     Xt = X.T
     n_iter = 0
@@ -93,6 +96,8 @@ def fit_coordinate_descent(X, W, H, tol=1e-4, max_iter=200, l1_reg_W=0, l1_reg_H
             violation_init = violation
         if trace is not None:
             trace.append(violation)
+        if snapshots is not None and n_iter in snapshots:
+            snapshots[n_iter] = (W.copy(), Ht.T.copy())
         if violation_init == 0:
             break
         if violation / violation_init <= tol:
@@ -101,7 +106,7 @@ def fit_coordinate_descent(X, W, H, tol=1e-4, max_iter=200, l1_reg_W=0, l1_reg_H
 
 
 def nmf(X, n_components, seed=None, W0=None, H0=None, tol=1e-4, max_iter=1000,
-        alpha_W=0.0, alpha_H=0.0, l1_ratio=0.0, trace=None):
+        alpha_W=0.0, alpha_H=0.0, l1_ratio=0.0, trace=None, snapshots=None):
     """CD NMF with both factors free: ``non_negative_factorization(X, n_components=k,
     init='random', solver='cd', beta_loss='frobenius', ...)``.
 
@@ -112,10 +117,10 @@ def nmf(X, n_components, seed=None, W0=None, H0=None, tol=1e-4, max_iter=1000,
     else:
         W, H = np.array(W0, dtype=X.dtype), np.array(H0, dtype=X.dtype)
     l1W, l1H, l2W, l2H = regularization(X.shape[0], X.shape[1], alpha_W, alpha_H, l1_ratio)
-    return fit_coordinate_descent(X, W, H, tol, max_iter, l1W, l1H, l2W, l2H, True, trace)
+    return fit_coordinate_descent(X, W, H, tol, max_iter, l1W, l1H, l2W, l2H, True, trace, snapshots)
 
 
-def nnls(X, H, tol=1e-4, max_iter=1000, alpha_W=0.0, l1_ratio=0.0):
+def nnls(X, H, tol=1e-4, max_iter=1000, alpha_W=0.0, l1_ratio=0.0, snapshots=None):
     """``update_H=False`` refit (sklearn _nmf.py:1210-1233: W0 = zeros for 'cd').
 
     Returns (W, n_iter)."""
@@ -123,7 +128,7 @@ def nnls(X, H, tol=1e-4, max_iter=1000, alpha_W=0.0, l1_ratio=0.0):
     H = np.asarray(H, dtype=X.dtype)
     W = np.zeros((X.shape[0], H.shape[0]), dtype=X.dtype)
     l1W, _, l2W, _ = regularization(X.shape[0], X.shape[1], alpha_W, 0.0, l1_ratio)
-    W, _, n_iter = fit_coordinate_descent(X, W, H, tol, max_iter, l1W, 0, l2W, 0, False)
+    W, _, n_iter = fit_coordinate_descent(X, W, H, tol, max_iter, l1W, 0, l2W, 0, False, None, snapshots)
     return W, n_iter
 
 

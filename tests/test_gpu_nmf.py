@@ -11,6 +11,7 @@ restarts that stop within 500 outer iterations; ill-conditioned restarts that ne
 (rank far above the data's true rank -> a flat objective; fp32 round-off accumulates over
 ~1000 sweeps) are held to max-abs <= 5e-4 at the same relative-Frobenius bound.
 |delta n_iter| is bounded too (the stop is a ratio of order-dependent fp sums).
+Parity iteration by iteration (W, H and the violation ratio after 1, 2, 3 sweeps): tests/test_gpu_cd_steps.py.
 """
 import functools
 

@@ -11,6 +11,8 @@ matched by best cosine, max-abs <= 1e-4 and relative Frobenius <= 1e-3, |delta n
   * stream-K cut tiles (the plane1 / plane2 loads): 12 500 cells x 1024 columns, the smallest shape at which the launcher
     cuts tiles, ranks 5..13 with slots straddling every component-group edge;
   * two runs of the first batch in one process return the same bytes.
+
+Parity iteration by iteration (W, H and the violation ratio after 1, 2, 3 sweeps): tests/test_gpu_cd_steps.py.
 """
 import numpy as np
 import pytest
