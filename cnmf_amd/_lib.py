@@ -33,6 +33,7 @@ SYMBOLS = [
     "cnmf_preprocess_upload_csr_as_stored", "cnmf_preprocess_gene_detect", "cnmf_preprocess_cell_sums",
     "cnmf_preprocess_subset", "cnmf_preprocess_fetch_counts",
     "cnmf_preprocess_gene_moments", "cnmf_preprocess_loess_fit", "cnmf_preprocess_clipped_sums",
+    "cnmf_preprocess_gene_moments_batched", "cnmf_preprocess_clipped_sums_batched",
     "cnmf_nmf_cd_batch", "cnmf_nmf_cd_batch_resident", "cnmf_get_iteration_means", "cnmf_set_iteration_hints", "cnmf_nnls",
     "cnmf_consensus", "cnmf_pairwise_distances", "cnmf_prediction_error", "cnmf_nmf_mu_batch", "cnmf_mu_refit_f64", "cnmf_x_matmul",
     "cnmf_xt_matmul_f64", "cnmf_nnls_spectra", "cnmf_nnls_f64", "cnmf_nnls_gram", "cnmf_nnls_batch", "cnmf_kselect_stats",
@@ -54,6 +55,8 @@ CNMF_MU_KMAX = 64
 CNMF_RIDGE_MAX = 4096
 CNMF_HARMONY_KMAX = 128
 CNMF_HARMONY_DMAX = 64
+CNMF_HVG_BATCHES_MAX = 4096
+CNMF_HVG_PAIRS_MAX = 1 << 26
 
 
 class CdParams(C.Structure):
@@ -252,6 +255,10 @@ def load():
     lib.cnmf_preprocess_loess_fit.argtypes = [vp, i64, dblp, dblp, i64, i64, dblp, dblp, dblp, i32p]
     lib.cnmf_preprocess_clipped_sums.restype = i32
     lib.cnmf_preprocess_clipped_sums.argtypes = [vp, dblp, dblp, dblp]
+    lib.cnmf_preprocess_gene_moments_batched.restype = i32
+    lib.cnmf_preprocess_gene_moments_batched.argtypes = [vp, i32p, i32, i64p_, i64p_, i32p]
+    lib.cnmf_preprocess_clipped_sums_batched.restype = i32
+    lib.cnmf_preprocess_clipped_sums_batched.argtypes = [vp, i32p, i32, dblp, dblp, dblp]
     lib.cnmf_prepare_release.restype = i32
     lib.cnmf_prepare_release.argtypes = [vp]
     lib.cnmf_nmf_cd_batch.restype = i32

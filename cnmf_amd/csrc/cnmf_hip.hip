@@ -309,6 +309,7 @@ extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
 #include "harmony_init_host.hip.h"
 #include "filter_host.hip.h"
 #include "hvg_host.hip.h"
+#include "hvg_batch_host.hip.h"
 #include "select_mi_host.hip.h"
 #include "tail_host.hip.h"
 

@@ -164,7 +164,16 @@ struct PreStage : CountStage {
     double *Rt = nullptr, *Pt = nullptr;             // [N][K], [N][B1]
     int K = 0, B1 = 0;
     void release_ridge() { hipFree(Rt); hipFree(Pt); Rt = Pt = nullptr; K = B1 = 0; }
-    void release() { release_counts(); release_ridge(); slot[0].release(); slot[1].release(); N = 0; }
+    // the batch-grouped transpose of the counts (hvg_batch_host.hip.h), cached for the batch codes it was built for:
+    // genes x cells with the cells in the stable order of their batch code, so that column g lists the entries of
+    // batch b as one run of rows [gstart[b], gstart[b + 1]); gB = 0: none.  It speaks of the staged cells and genes,
+    // so whatever replaces or restricts the staging goes through release() and drops it
+    DevCsr<double> grouped;
+    int* gstart = nullptr;                           // [gB + 1] (device)
+    std::vector<int32_t> gcodes;                     // [N] (host): the codes the cache answers to
+    int gB = 0;
+    void release_grouped() { grouped.release(); hipFree(gstart); gstart = nullptr; gcodes.clear(); gB = 0; }
+    void release() { release_counts(); release_ridge(); release_grouped(); slot[0].release(); slot[1].release(); N = 0; }
 };
 
 // state of the cnmf_harmony_* entry points (harmony_host.hip.h): Harmony's soft clustering of N cells over d components

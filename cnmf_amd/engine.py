@@ -742,6 +742,56 @@ class Engine:
                                                            c2.ctypes.data_as(dblp)))
         return c1, c2
 
+    # ---- the same two passes per batch (hvg_batch_host.hip.h): Preprocess.highly_variable_genes(batch_key=...)
+    def _pre_batches(self, codes, n_batches):
+        """(int32 codes over the staged cells, B) after the checks the library would refuse them with"""
+        self._pre_mask(None, "G", "")
+        N, G, B = self._pre["N"], self._pre["G"], int(n_batches)
+        codes = np.asarray(codes)
+        if codes.shape != (N,) or codes.dtype.kind not in "iu":
+            raise ValueError("codes must hold %d integers (got %s of shape %s)" % (N, codes.dtype, codes.shape))
+        if not 1 <= B <= _lib.CNMF_HVG_BATCHES_MAX:
+            raise NotImplementedError("%d batches: between 1 and %d are supported" % (B, _lib.CNMF_HVG_BATCHES_MAX))
+        if G * B > _lib.CNMF_HVG_PAIRS_MAX:
+            raise NotImplementedError("%d genes x %d batches: more than %d (gene, batch) pairs"
+                                      % (G, B, _lib.CNMF_HVG_PAIRS_MAX))
+        if codes.min() < 0 or codes.max() >= B:
+            raise ValueError("batch codes outside [0, %d)" % B)
+        empty = np.flatnonzero(np.bincount(codes, minlength=B) == 0)
+        if empty.size:
+            raise ValueError("batch %d has no cell" % empty[0])
+        return np.ascontiguousarray(codes, dtype=np.int32), B
+
+    def preprocess_gene_moments_batched(self, codes, n_batches):
+        """``preprocess_gene_moments`` per batch: ``codes`` [N] the batch of every staged cell, in [0, n_batches), every
+        batch with at least one cell.  Returns ``(s1 [B][G], s2 [B][G], flags [B])``: row b is what
+        ``preprocess_gene_moments`` gives on the staging restricted to the cells of batch b.  The staging is not
+        changed.  More than 4096 batches, or more than 2^26 (gene, batch) pairs: NotImplementedError."""
+        codes, B = self._pre_batches(codes, n_batches)
+        G = self._pre["G"]
+        s1, s2 = np.empty((B, G), dtype=np.int64), np.empty((B, G), dtype=np.int64)
+        flags = np.zeros(B, dtype=np.int32)
+        i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        self._check(self._lib.cnmf_preprocess_gene_moments_batched(self._ctx, codes.ctypes.data_as(i32p), B,
+                                                                   s1.ctypes.data_as(i64p), s2.ctypes.data_as(i64p),
+                                                                   flags.ctypes.data_as(i32p)))
+        return s1, s2, flags
+
+    def preprocess_clipped_sums_batched(self, codes, n_batches, clip):
+        """``preprocess_clipped_sums`` per batch with ``clip`` [B][G]: ``(C1 [B][G], C2 [B][G])``, row b with the bits
+        ``preprocess_clipped_sums(clip[b])`` gives on the staging restricted to the cells of batch b."""
+        codes, B = self._pre_batches(codes, n_batches)
+        G = self._pre["G"]
+        clip = np.ascontiguousarray(clip, dtype=np.float64)
+        if clip.shape != (B, G) or not np.isfinite(clip).all():
+            raise ValueError("clip must hold %d x %d finite values (got shape %s)" % (B, G, clip.shape))
+        c1, c2 = np.empty((B, G)), np.empty((B, G))
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_preprocess_clipped_sums_batched(self._ctx, codes.ctypes.data_as(C.POINTER(C.c_int32)), B,
+                                                                   clip.ctypes.data_as(dblp), c1.ctypes.data_as(dblp),
+                                                                   c2.ctypes.data_as(dblp)))
+        return c1, c2
+
     def preprocess_release(self):
         self._check(self._lib.cnmf_preprocess_release(self._ctx))
         self._pre = None

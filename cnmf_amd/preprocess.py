@@ -69,8 +69,8 @@ scikit-learn's KMeans (tests/test_gpu_harmony_init.py: the best init, its labels
 centres within the rounding of a mean).  With fewer distinct cells than clusters the centres of the surplus clusters are
 unspecified: the restatement and scikit-learn disagree there themselves, and no parity is claimed.
 
-``Preprocess.highly_variable_genes`` is scanpy's ``highly_variable_genes(flavor='seurat_v3')`` for one batch (the call
-``normalize_batchcorrect(n_top_genes=...)`` makes, :314-315), opt-in through ``hvg="device"`` together with a number for
+``Preprocess.highly_variable_genes`` is scanpy's ``highly_variable_genes(flavor='seurat_v3')``, for one batch (the call
+``normalize_batchcorrect(n_top_genes=...)`` makes, :314-315) or per batch with ``batch_key`` (below), opt-in through ``hvg="device"`` together with a number for
 ``n_top_genes`` / ``n_top_rna_genes`` on ``normalize_batchcorrect`` and ``preprocess_for_cnmf`` (the default,
 ``hvg=None``, keeps the NotImplementedError for a number).  On the device (csrc/hvg_host.hip.h), over the staging as it
 is after ``exclude_genes`` went:
@@ -99,8 +99,32 @@ project's machines**: neither library is installed on them; tests/test_host_hvg.
 wherever they can be imported.  The vertex rule is written from the published algorithm (Cleveland and Grosse's
 dloess); that test is where a mismatch would show.
 
-Out of scope: ``batch_key`` and the other flavours of highly_variable_genes, loess's robustness iterations and
-``degree != 2``, plots (``makeplots`` is accepted and nothing is drawn) and ``.h5ad`` writing.
+With ``batch_key`` (``hvg_batch_key`` on ``normalize_batchcorrect`` and ``preprocess_for_cnmf``) the selection is
+scanpy's per-batch one (Seurat's SelectIntegrationFeatures).  The batches are the values of ``np.unique`` of the
+column, in that order; every batch needs at least two cells and a label for every cell; at most 4096 batches and 2^26
+(gene, batch) pairs.  For every batch b with N_b cells the computation above runs on that batch's cells alone --
+S1_b, S2_b, mean_b, var_b, the loess over the genes with var_b > 0, reg_std_b, clip_b = reg_std_b sqrt(N_b) + mean_b,
+C1_b, C2_b, variances_norm_b.  On the device (csrc/hvg_batch_host.hip.h) the two O(nnz) passes run for all batches at
+once over a second transpose of the staged counts whose cells are grouped by batch: the entries of batch b in the
+column of gene g are one run, found by binary search, and a wavefront per (gene, batch) pair sums it in the order the
+one-batch kernel uses on that batch alone -- the clipped sums have the bits of ``preprocess_clipped_sums`` on the staging
+restricted to the batch.  The staging itself keeps its cell order.  The loess fits are one ``preprocess_loess_fit`` call
+per batch.  The host combines (``seurat_v3_combine``): a gene's rank in a batch is its position in the stable
+descending sort of variances_norm_b (float32, as scanpy holds it); ``highly_variable_nbatches`` counts the batches with
+rank < n_top_genes; ``highly_variable_rank`` is the median of those ranks (NaN when there is none); ``variances_norm``
+is the mean over the batches; ``means`` and ``variances`` are those of the whole data (S1 = sum_b S1_b, S2 = sum_b S2_b:
+the bits of a call without batches); ``highly_variable`` marks the first n_top_genes genes of a stable sort by (rank
+ascending with NaN last, nbatches descending), ties in gene order.  With one batch every shared column equals the
+one-batch frame.  **Its yardstick is tests/_seurat_v3_batch_ref.py**, the same restatement run per batch with scanpy's
+combination written out (moments, means, variances, nbatches, ranks and the selected set equal; variances_norm within
+16 x the restatement's distance from its long double run).  **Agreement with scanpy's ``batch_key`` result is unmeasured
+on this project's machines**; tests/test_host_hvg_batch.py compares the restatement with it wherever scanpy and skmisc
+can be imported.  No time is claimed for the batched passes: they have not been measured against B runs of the one-batch
+entry points.
+
+Out of scope: the other flavours of highly_variable_genes, scanpy's ``subset`` and ``inplace``, loess's robustness
+iterations and ``degree != 2``, a batched loess entry point, plots (``makeplots`` is accepted and nothing is drawn) and
+``.h5ad`` writing.
 """
 import numpy as np
 import pandas as pd
@@ -316,6 +340,8 @@ HVG_MODES = (None, "device")
 LOESS_SURFACES = ("interpolate", "direct")
 HVG_COUNT_MAX = 1 << 20
 HVG_CELLS_MAX = 1 << 22
+HVG_BATCHES_MAX = 4096
+HVG_PAIRS_MAX = 1 << 26
 LOESS_ZERO_WIDTH_ERROR = "loess: zero-width neighborhood; make span bigger"
 LOESS_RCOND = 100 * float(np.finfo(np.float64).eps)
 
@@ -323,6 +349,23 @@ LOESS_RCOND = 100 * float(np.finfo(np.float64).eps)
 def _check_hvg_mode(hvg):
     if hvg not in HVG_MODES:
         raise ValueError("hvg must be None or 'device', not %r" % (hvg,))
+
+
+def _check_batch_key(obs, batch_key):
+    if obs is None:
+        raise KeyError("obs is required for batch_key %r" % (batch_key,))
+    if batch_key not in obs.columns:
+        raise KeyError("batch_key %r is not a column of obs" % (batch_key,))
+
+
+def _check_hvg_batch_key(hvg_batch_key, select, obs):
+    """hvg_batch_key goes with hvg='device' and a number only (never ignored); its column must be there"""
+    if hvg_batch_key is None:
+        return
+    if not select:
+        raise ValueError("hvg_batch_key is used only with hvg='device' and a number of top genes: without them no "
+                         "selection is computed")
+    _check_batch_key(obs, hvg_batch_key)
 
 
 def _check_hvg_args(n_top_genes, span, surface, flavor="seurat_v3"):
@@ -426,22 +469,120 @@ def exact_mean_var(s1, s2, N):
     return mean, var
 
 
-def seurat_v3_frame(eng, N, genes, n_top_genes=2000, span=0.3, surface="interpolate"):
-    """scanpy's ``highly_variable_genes(flavor='seurat_v3')`` frame (batch_key=None) over the counts ``eng`` has staged
-    (N cells, the genes ``genes``): see Preprocess.highly_variable_genes.  The caller uploads and releases."""
-    if not 2 <= N <= HVG_CELLS_MAX:
-        raise ValueError("flavor='seurat_v3' needs between 2 and %d cells, not %d" % (HVG_CELLS_MAX, N))
-    s1, s2, flags = eng.preprocess_gene_moments()
+def _check_hvg_flags(flags):
     if flags & 1:
         raise ValueError("flavor='seurat_v3' expects raw counts: a negative or non-integer value was found")
     if flags & 2:
         raise ValueError("flavor='seurat_v3': a count above %d cannot be summed exactly and is refused" % HVG_COUNT_MAX)
-    mean, var = exact_mean_var(s1, s2, N)
+
+
+def _regularised_std(eng, mean, var, span, surface):
+    """reg_std = sqrt(10^est), est = the loess of log10 var on log10 mean over the genes with var > 0, 0 elsewhere"""
     not_const = var > 0
     est = np.zeros(len(mean))
     if not_const.any():
         est[not_const] = loess_fitted(eng, np.log10(mean[not_const]), np.log10(var[not_const]), span, surface)
-    reg_std = np.sqrt(10 ** est)
+    return np.sqrt(10 ** est)
+
+
+def seurat_v3_combine(vnorm, n_top_genes):
+    """The combination rule of scanpy's seurat_v3 with ``batch_key`` (Seurat's SelectIntegrationFeatures) over the
+    per-batch ``vnorm`` [B][G].  Returns ``(variances_norm, highly_variable_rank, highly_variable_nbatches,
+    highly_variable)`` per gene:
+
+    * the rank of a gene in a batch: its position in the stable descending sort of that batch's row (ties in gene
+      order), held as float32 as scanpy holds it; ranks >= n_top_genes count as NaN;
+    * highly_variable_nbatches: the batches in which the rank is < n_top_genes;
+    * highly_variable_rank: the median of the ranks that are not NaN -- the float32 sum of the two middle ones (the
+      middle one twice when their number is odd) halved, as ``np.ma.median`` forms it -- NaN when all are NaN; returned
+      as float64 (the value is the same), the dtype of the one-batch frame;
+    * variances_norm: the mean over the batches (``np.mean(vnorm, axis=0)``);
+    * highly_variable: the first n_top_genes genes of a stable sort by (rank ascending with NaN last, nbatches
+      descending), ties in gene order."""
+    vnorm = np.asarray(vnorm, dtype=np.float64)
+    if vnorm.ndim != 2 or vnorm.shape[0] < 1:
+        raise ValueError("vnorm must be [batches][genes], not of shape %s" % (vnorm.shape,))
+    B, G = vnorm.shape
+    ranks = np.empty((B, G), dtype=np.float32)
+    for b in range(B):
+        ranks[b, np.argsort(-vnorm[b], kind="stable")] = np.arange(G, dtype=np.float32)
+    top = ranks < n_top_genes
+    nbatches = top.sum(axis=0).astype(np.int64)
+    s = np.sort(np.where(top, ranks, np.float32(np.inf)), axis=0)              # per gene: its ranks, then the dropped ones
+    k = np.maximum(nbatches, 1)
+    cols = np.arange(G)
+    median = ((s[(k - 1) // 2, cols] + s[k // 2, cols]) / np.float32(2)).astype(np.float64)
+    median[nbatches == 0] = np.nan
+    order = np.lexsort((-nbatches, np.where(nbatches > 0, median, np.inf)))    # (a stable sort: ties in gene order)
+    hv = np.zeros(G, dtype=bool)
+    hv[order[:int(n_top_genes)]] = True
+    return np.mean(vnorm, axis=0), median, nbatches, hv
+
+
+def batch_codes(obs, batch_key):
+    """(codes [N] int32, labels): the batches are the values of ``np.unique(obs[batch_key])``, in that order.  KeyError
+    for a missing ``obs`` or column, ValueError for a missing label or a batch with fewer than two cells -- all of it
+    before any device work."""
+    _check_batch_key(obs, batch_key)
+    values = np.asarray(obs[batch_key])
+    if pd.isna(values).any():
+        raise ValueError("batch_key %r: %d cells have no label (NaN / None)" % (batch_key, int(pd.isna(values).sum())))
+    labels, codes = np.unique(values, return_inverse=True)
+    sizes = np.bincount(codes.reshape(-1), minlength=len(labels))
+    if (sizes < 2).any():
+        b = int(np.flatnonzero(sizes < 2)[0])
+        raise ValueError("batch_key %r: batch %r has %d cell, flavor='seurat_v3' needs at least 2 per batch"
+                         % (batch_key, labels[b], sizes[b]))
+    if len(labels) > HVG_BATCHES_MAX:
+        raise NotImplementedError("batch_key %r: %d batches, more than the %d supported" % (batch_key, len(labels),
+                                                                                          HVG_BATCHES_MAX))
+    return codes.reshape(-1).astype(np.int32), labels
+
+
+def _seurat_v3_frame_batched(eng, N, genes, n_top_genes, span, surface, codes):
+    """seurat_v3_frame with ``batch_key``: the one-batch computation per batch over the two batched device passes, the
+    batches combined by ``seurat_v3_combine``; means and variances are those of the whole data (the integer moments of
+    the batches added up: the bits of a call without batches)"""
+    codes = np.asarray(codes)
+    sizes = np.bincount(codes)
+    B = sizes.size
+    if B > HVG_BATCHES_MAX or B * len(genes) > HVG_PAIRS_MAX:
+        raise NotImplementedError("%d batches x %d genes: at most %d batches and %d (gene, batch) pairs are supported"
+                                  % (B, len(genes), HVG_BATCHES_MAX, HVG_PAIRS_MAX))
+    if codes.shape != (N,) or (sizes < 2).any():
+        raise ValueError("flavor='seurat_v3' needs one batch code per cell and at least 2 cells in every batch")
+    s1, s2, flags = eng.preprocess_gene_moments_batched(codes, B)
+    _check_hvg_flags(int(np.bitwise_or.reduce(np.asarray(flags).reshape(-1))))
+    mean, var = exact_mean_var(s1.sum(axis=0), s2.sum(axis=0), N)
+    G = len(mean)
+    mean_b, reg_std, clip = np.empty((B, G)), np.empty((B, G)), np.empty((B, G))
+    for b in range(B):
+        n = int(sizes[b])
+        mean_b[b], var_b = exact_mean_var(s1[b], s2[b], n)
+        reg_std[b] = _regularised_std(eng, mean_b[b], var_b, span, surface)
+        clip[b] = reg_std[b] * np.sqrt(np.float64(n)) + mean_b[b]
+    c1, c2 = eng.preprocess_clipped_sums_batched(codes, B, clip)
+    vnorm = np.empty((B, G))
+    for b in range(B):
+        n = int(sizes[b])
+        vnorm[b] = (n * mean_b[b] * mean_b[b] + c2[b] - 2 * c1[b] * mean_b[b]) / ((n - 1) * reg_std[b] * reg_std[b])
+    vn, rank, nbatches, hv = seurat_v3_combine(vnorm, n_top_genes)
+    return pd.DataFrame({"means": mean, "variances": var, "variances_norm": vn, "highly_variable_rank": rank,
+                         "highly_variable": hv, "highly_variable_nbatches": nbatches}, index=pd.Index(genes))
+
+
+def seurat_v3_frame(eng, N, genes, n_top_genes=2000, span=0.3, surface="interpolate", batch=None):
+    """scanpy's ``highly_variable_genes(flavor='seurat_v3')`` frame over the counts ``eng`` has staged (N cells, the genes
+    ``genes``): see Preprocess.highly_variable_genes.  ``batch``: None (batch_key=None), or the batch code of every
+    staged cell (``batch_codes``): the per-batch route.  The caller uploads and releases."""
+    if not 2 <= N <= HVG_CELLS_MAX:
+        raise ValueError("flavor='seurat_v3' needs between 2 and %d cells, not %d" % (HVG_CELLS_MAX, N))
+    if batch is not None:
+        return _seurat_v3_frame_batched(eng, N, genes, n_top_genes, span, surface, batch)
+    s1, s2, flags = eng.preprocess_gene_moments()
+    _check_hvg_flags(flags)
+    mean, var = exact_mean_var(s1, s2, N)
+    reg_std = _regularised_std(eng, mean, var, span, surface)
     clip = reg_std * np.sqrt(np.float64(N)) + mean
     c1, c2 = eng.preprocess_clipped_sums(clip)
     vnorm = (N * mean * mean + c2 - 2 * c1 * mean) / ((N - 1) * reg_std * reg_std)
@@ -701,7 +842,7 @@ class Preprocess:
     def normalize_batchcorrect(self, data, obs=None, highly_variable=None, normalize_librarysize=False, harmony_vars=None,
                                n_top_genes=None, librarysize_targetsum=1e4, max_scaled_thresh=None, quantile_thresh=.9999,
                                theta=1, makeplots=True, max_iter_harmony=20, harmony_res=None, harmony="harmonypy",
-                               hvg=None):
+                               hvg=None, hvg_batch_key=None):
         """Normalises the high-variance genes of raw counts and optionally corrects them with Harmony.  Returns
         ``(result, hvgs)``: ``result.X`` goes straight into ``cNMF.prepare(counts=(result.X, result.obs_names, hvgs),
         ...)``.  ``harmony``: who runs Harmony when ``harmony_res`` is not given: "harmonypy" (the library), "device"
@@ -710,8 +851,12 @@ class Preprocess:
         ``hvg``: None (the default: a number for ``n_top_genes`` raises NotImplementedError and ``highly_variable`` is
         required) or "device": a number for ``n_top_genes`` then runs ``highly_variable_genes`` (seurat_v3) on the
         staged counts and its selection replaces ``highly_variable``, as the reference overwrites
-        ``var['highly_variable']``; the frame, restricted to the selected genes, is ``result.var``."""
+        ``var['highly_variable']``; the frame, restricted to the selected genes, is ``result.var``.
+        ``hvg_batch_key``: a column of ``obs``; that selection is then made per batch and the ranks combined
+        (``highly_variable_genes(batch_key=...)``; ``result.var`` carries ``highly_variable_nbatches``).  Given without
+        ``hvg="device"`` and a number it raises ValueError."""
         _check_hvg_mode(hvg)
+        _check_hvg_batch_key(hvg_batch_key, hvg == "device" and n_top_genes is not None, obs)
         if n_top_genes is not None and hvg is None:
             raise NotImplementedError(N_TOP_GENES_ERROR)
         select = n_top_genes is not None
@@ -732,13 +877,14 @@ class Preprocess:
                 raise ValueError("highly_variable selects no gene")
         if obs is not None:
             obs = _align_obs(obs, cells)
+        batch = None if hvg_batch_key is None else batch_codes(obs, hvg_batch_key)[0]
         X = _to_csr(mat)
         var = None
         eng = self.engine
         try:
             eng.preprocess_upload(X)
             if select:
-                var = seurat_v3_frame(eng, X.shape[0], genes, n_top_genes)
+                var = seurat_v3_frame(eng, X.shape[0], genes, n_top_genes, batch=batch)
                 sel = np.flatnonzero(var["highly_variable"].values)
                 var = var.iloc[sel]
             Xout, obsm = self._batchcorrect_staged(eng, X.shape[0], sel, dense, obs, normalize_librarysize, harmony_vars,
@@ -750,9 +896,11 @@ class Preprocess:
         return PreprocessResult(Xout, cells, pd.Index(hvgs), obs, obsm, var=var), hvgs
 
     # ------------------------------------------------------------------ highly_variable_genes (scanpy, flavor='seurat_v3')
-    def highly_variable_genes(self, data, n_top_genes=2000, span=0.3, surface="interpolate", flavor="seurat_v3"):
-        """scanpy's ``sc.pp.highly_variable_genes(flavor='seurat_v3', n_top_genes, span)`` for one batch (the call the
-        reference makes, preprocess.py:314-315), over raw counts in any of the forms ``data`` takes.  Returns scanpy's
+    def highly_variable_genes(self, data, n_top_genes=2000, span=0.3, surface="interpolate", flavor="seurat_v3",
+                              batch_key=None, obs=None):
+        """scanpy's ``sc.pp.highly_variable_genes(flavor='seurat_v3', n_top_genes, span, batch_key)`` (without
+        ``batch_key`` the call the reference makes, preprocess.py:314-315), over raw counts in any of the forms
+        ``data`` takes.  Returns scanpy's
         frame, indexed by gene in the data's order: ``means``, ``variances`` (ddof=1), ``variances_norm``,
         ``highly_variable_rank`` (float; NaN from ``n_top_genes`` on) and ``highly_variable``.
 
@@ -767,15 +915,30 @@ class Preprocess:
 
         Deliberate difference from scanpy, which warns on non-integer data and goes on: a negative or non-integer value
         raises ValueError, and so does a count above 2^20 or more than 2^22 cells (the bound under which the integer
-        sums stay exact; nothing is ever wrapped).  Any other ``flavor`` raises NotImplementedError; there is no
-        ``batch_key``."""
+        sums stay exact; nothing is ever wrapped).  Any other ``flavor`` raises NotImplementedError.
+
+        ``batch_key``: a column of ``obs`` (a DataFrame over the cells, aligned by name or by position); ``obs`` is not
+        read without it.  The batches are the values of ``np.unique`` of that column.  The computation above then runs
+        on every batch's cells alone -- the two O(nnz) passes for all batches at once, over a second transpose of the
+        staged counts whose cells are grouped by batch; one loess per batch -- and the batches are combined as scanpy
+        combines them (``seurat_v3_combine``): ``highly_variable_rank`` is the median over the batches of a gene's ranks
+        below ``n_top_genes``, ``variances_norm`` the mean over the batches, ``highly_variable`` the first
+        ``n_top_genes`` genes by (rank ascending, NaN last; ``highly_variable_nbatches`` descending; gene order), and
+        the frame gains the int column ``highly_variable_nbatches``.  ``means`` and ``variances`` are those of the
+        whole data, with the bits of a call without ``batch_key``.  KeyError for a missing ``obs`` or column,
+        ValueError for a missing label (NaN / None) or a batch with fewer than 2 cells, NotImplementedError for more
+        than 4096 batches, all before any device work; more than 2^26 (gene, batch) pairs raise NotImplementedError
+        before the first batched pass; the count and span errors arise per batch."""
         _check_hvg_args(n_top_genes, span, surface, flavor)
+        if batch_key is not None:
+            _check_batch_key(obs, batch_key)
         mat, cells, genes, dense = _data_parts(data)
+        batch = None if batch_key is None else batch_codes(_align_obs(obs, cells), batch_key)[0]
         X = _to_csr(mat, what="flavor='seurat_v3'")
         eng = self.engine
         try:
             eng.preprocess_upload(X)
-            return seurat_v3_frame(eng, X.shape[0], genes, n_top_genes, span, surface)
+            return seurat_v3_frame(eng, X.shape[0], genes, n_top_genes, span, surface, batch)
         finally:
             eng.preprocess_release()
 
@@ -873,7 +1036,7 @@ class Preprocess:
                             adt_feature_name='Antibody Capture', harmony_vars=None, n_top_rna_genes=None,
                             librarysize_targetsum=1e4, max_scaled_thresh=None, quantile_thresh=.9999, makeplots=True,
                             theta=1, save_output_base=None, max_iter_harmony=20, exclude_genes=None, harmony_res=None,
-                            harmony="harmonypy", hvg=None):
+                            harmony="harmonypy", hvg=None, hvg_batch_key=None):
         """The reference's minimal preprocessing: the HVG-filtered, variance-normalised, optionally Harmony-corrected RNA
         matrix (the ``counts`` input of cNMF) and the library-size-normalised matrix over all genes, ADT features
         appended and normalised on their own (the ``tpm`` input).
@@ -890,6 +1053,8 @@ class Preprocess:
         project's restatement of skmisc's loess, see the module docstring) on the staged RNA counts after
         ``exclude_genes`` went, as the reference does: an excluded gene or an ADT feature is never selected, and the
         selection replaces ``highly_variable``.  The frame of the selected genes is ``result_rna.var``.
+        ``hvg_batch_key`` (a column of ``obs``) makes that selection per batch, as in normalize_batchcorrect; given
+        without ``hvg="device"`` and a number it raises ValueError.
 
         The RNA counts are uploaded once: ``tp10k`` comes from them over all RNA genes before ``exclude_genes`` are taken
         out (on the device), then normalize_batchcorrect's body runs on the same staging.
@@ -906,6 +1071,7 @@ class Preprocess:
         else:
             raise Exception(DATA_FORM_ERROR)
         _check_hvg_mode(hvg)
+        _check_hvg_batch_key(hvg_batch_key, hvg == "device" and n_top_rna_genes is not None, obs)
         if n_top_rna_genes is not None and hvg is None:
             raise NotImplementedError(N_TOP_GENES_ERROR)
         select = n_top_rna_genes is not None
@@ -958,6 +1124,7 @@ class Preprocess:
             raise ValueError("exclude_genes leaves no gene")
         if obs is not None:
             obs = _align_obs(obs, cells)
+        batch = None if hvg_batch_key is None else batch_codes(obs, hvg_batch_key)[0]
         X = _to_csr(mat)
         Xa = _to_csr(adt[0]) if adt is not None else None
         target = float(librarysize_targetsum)
@@ -974,7 +1141,7 @@ class Preprocess:
                 else:
                     print("exclude_genes provided but none found in adata_RNA.var_names.")
             if select:                                              # on the RNA genes that are left (preprocess.py:314-315)
-                hvg_var = seurat_v3_frame(eng, X.shape[0], genes[~excluded], n_top_rna_genes)
+                hvg_var = seurat_v3_frame(eng, X.shape[0], genes[~excluded], n_top_rna_genes, batch=batch)
                 sel = np.flatnonzero(hvg_var["highly_variable"].values)
                 hvg_var = hvg_var.iloc[sel]
             Xout, obsm = self._batchcorrect_staged(eng, X.shape[0], sel, dense, obs, False, harmony_vars, target,

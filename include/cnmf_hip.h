@@ -246,7 +246,18 @@ int cnmf_prepare_release(cnmf_ctx* ctx);
  *                                1 (h <= 0: a zero-width neighbourhood) or 2 (fewer than three distinct weighted abscissae, or
  *                                nearly so: the caller solves that point itself); value = slope = 0 where status != 0.
  *   cnmf_preprocess_clipped_sums per gene of the staging: c1 = sum min(x, clip[g]), c2 = sum min(x, clip[g])^2 (float64,
- *                                fixed order). */
+ *                                fixed order).
+ * The same two passes per batch (flavor='seurat_v3' with batch_key; hvg_batch_host.hip.h).  codes [n_cells]: the batch of
+ * every staged cell, in [0, n_batches); limits: 1 <= n_batches <= 4096, no batch without a cell, n_genes * n_batches <=
+ * 2^26, at most 2^22 cells in all -- CNMF_EINVAL otherwise, before anything is launched.  Both work on a second transpose
+ * of the staged counts whose cells are grouped by batch (built on first use, cached for these codes, dropped by release,
+ * subset and every upload); the staging itself is not touched.  Results are [n_batches][n_genes], row b over the cells of
+ * batch b alone:
+ *   cnmf_preprocess_gene_moments_batched  s1, s2 as cnmf_preprocess_gene_moments gives them on the staging restricted to
+ *                                the cells of batch b; flags [n_batches]: its flags, per batch.
+ *   cnmf_preprocess_clipped_sums_batched  c1, c2 with clip [n_batches][n_genes]: the BITS cnmf_preprocess_clipped_sums
+ *                                gives with clip[b] on the staging restricted to the cells of batch b (the same additions
+ *                                in the same order). */
 int cnmf_preprocess_upload_csr(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* indices, const void* data,
                                int data_is_f64, int64_t n_cells, int64_t n_genes);
 int cnmf_preprocess_set_dense(cnmf_ctx* ctx, int32_t slot, const double* X, int64_t n_rows, int64_t n_cols);
@@ -284,6 +295,12 @@ int cnmf_preprocess_loess_fit(cnmf_ctx* ctx, int64_t n, const double* x /* [n] s
                               int32_t* status /* [m] */);
 int cnmf_preprocess_clipped_sums(cnmf_ctx* ctx, const double* clip /* [n_genes] */, double* c1 /* [n_genes] */,
                                  double* c2 /* [n_genes] */);
+int cnmf_preprocess_gene_moments_batched(cnmf_ctx* ctx, const int32_t* codes /* [n_cells] */, int32_t n_batches,
+                                         int64_t* s1 /* [n_batches][n_genes] */, int64_t* s2 /* [n_batches][n_genes] */,
+                                         int32_t* flags /* [n_batches] */);
+int cnmf_preprocess_clipped_sums_batched(cnmf_ctx* ctx, const int32_t* codes /* [n_cells] */, int32_t n_batches,
+                                         const double* clip /* [n_batches][n_genes] */, double* c1 /* [n_batches][n_genes] */,
+                                         double* c2 /* [n_batches][n_genes] */);
 
 /* ---- Harmony's clustering loop (harmony_host.hip.h) -----------------------------------------------------------------
  * The loop of harmonypy's run_harmony over N cells, d components, K clusters and n_vars batch variables with n_levels
