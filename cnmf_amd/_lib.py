@@ -35,7 +35,7 @@ SYMBOLS = [
     "cnmf_preprocess_gene_moments", "cnmf_preprocess_loess_fit", "cnmf_preprocess_clipped_sums",
     "cnmf_preprocess_gene_moments_batched", "cnmf_preprocess_clipped_sums_batched",
     "cnmf_nmf_cd_batch", "cnmf_nmf_cd_batch_resident", "cnmf_get_iteration_means", "cnmf_set_iteration_hints", "cnmf_nnls",
-    "cnmf_consensus", "cnmf_pairwise_distances", "cnmf_prediction_error", "cnmf_nmf_mu_batch", "cnmf_mu_refit_f64", "cnmf_x_matmul",
+    "cnmf_consensus", "cnmf_pairwise_distances", "cnmf_prediction_error", "cnmf_nmf_mu_batch", "cnmf_mu_refit_f64", "cnmf_mu2_refit_f64", "cnmf_x_matmul",
     "cnmf_xt_matmul_f64", "cnmf_nnls_spectra", "cnmf_nnls_f64", "cnmf_nnls_gram", "cnmf_nnls_batch", "cnmf_kselect_stats",
     "cnmf_comm_unique_id", "cnmf_comm_init", "cnmf_comm_finalize", "cnmf_comm_rank", "cnmf_comm_world",
     "cnmf_allgather_bytes", "cnmf_allgather_spectra",
@@ -299,6 +299,8 @@ def load():
     lib.cnmf_xt_matmul_f64.argtypes = [vp, i32, dblp, i32, dblp, dblp, dblp]
     lib.cnmf_nnls_spectra.restype = i32
     lib.cnmf_nnls_spectra.argtypes = [vp, i32, dblp, C.POINTER(CdParams), dblp, i32p, dblp]
+    lib.cnmf_mu2_refit_f64.restype = i32
+    lib.cnmf_mu2_refit_f64.argtypes = [vp, i32, dblp, C.c_double, C.POINTER(CdParams), dblp, i32p, dblp]
     lib.cnmf_nnls_f64.restype = i32
     lib.cnmf_nnls_f64.argtypes = [vp, i32, dblp, dblp, C.POINTER(CdParams), dblp, i32p, dblp]
     lib.cnmf_nnls_gram.restype = i32

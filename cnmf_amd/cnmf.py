@@ -3,9 +3,11 @@
 Same method names, argument meaning, on-disk artefacts and error behaviour as
 /root/reference/src/cnmf/cnmf.py for ``factorize`` (:692-745), ``combine`` / ``combine_nmf``
 (:462-483, :748-773), ``refit_usage`` / ``refit_spectra`` (:776-820), ``consensus``
-(:823-985, without the plotting block) and the statistics loop of ``k_selection_plot``
-(:1119-1135) -- but every numerical step runs on the MI355X through ``Engine``
-(libcnmf_hip.so).  There is no CPU fallback.
+(:823-985, without the plotting block), ``build_reference`` (:1085-1116), the statistics loop of
+``k_selection_plot`` (:1119-1135) and ``load_results`` (:1161-1210) -- but every numerical step runs on
+the MI355X through ``Engine`` (libcnmf_hip.so).  There is no CPU fallback.  The consumer of
+``build_reference``'s output, the projection of new cells onto the reference programs, is
+``cnmf_amd.starcat.StarCAT``.
 
 What is different by design
 * all restarts of a worker run as ONE batched device call (X is uploaded once, not re-read
@@ -277,6 +279,28 @@ def select_highvar_genes(mean, var, numgenes=None, expected_fano_threshold=None,
     return np.asarray(mask, dtype=bool), dict(A=A, B=B, T=T, minimal_mean=minimal_mean, fano_ratio=ratio.values)
 
 
+def _as_text_would_read(frame):
+    """A float frame as ``pd.read_csv`` returns it from the text ``save_df_to_text`` writes: float64 values survive the
+    round trip unchanged (shortest round-trip repr), float32 values come back as the float64 nearest to their float32
+    repr -- not as their exact widening."""
+    vals = frame.values
+    if vals.dtype == np.float64:
+        return frame
+    return pd.DataFrame(vals.astype(str).astype(np.float64), index=frame.index, columns=frame.columns)
+
+
+def _starcat_reference(spectra_tpm, tpm_stats, hvgs, target_sum=1e6):
+    """The arithmetic of ``build_reference`` (cnmf.py:1103-1113): the TPM spectra (programs x all genes) with every row
+    scaled to sum to ``target_sum``, divided by the genes' TPM standard deviation (``tpm_stats['__std']``, taken in the
+    column order of ``spectra_tpm``; a zero std gives inf / NaN as in the reference), the columns ``hvgs`` in list order,
+    the rows labelled ``GEP<label>``."""
+    std = pd.Series(np.asarray(tpm_stats["__std"].values), index=spectra_tpm.columns)
+    renorm = spectra_tpm.div(spectra_tpm.sum(axis=1), axis=0) * target_sum
+    ref = renorm.div(std)[hvgs].copy()
+    ref.index = "GEP" + ref.index.astype("str")
+    return ref
+
+
 class SparseFrame:
     """A cells x genes scipy CSR matrix with its labels -- what the reference holds in ``norm_counts`` (an AnnData with a
     sparse ``.X``, cnmf.py:537-556 sparse branch) when the counts were stored sparse and not densified.  Only what the
@@ -355,6 +379,8 @@ class cNMF:
                 "gene_spectra_score__txt": o(".gene_spectra_score.k_%d.dt_%s.txt"),
                 "gene_spectra_tpm": t(".gene_spectra_tpm.k_%d.dt_%s.df.npz"),
                 "gene_spectra_tpm__txt": o(".gene_spectra_tpm.k_%d.dt_%s.txt"),
+                "starcat_spectra": t(".starcat_spectra.k_%d.dt_%s.df.npz"),
+                "starcat_spectra__txt": o(".starcat_spectra.k_%d.dt_%s.txt"),
             }
 
     # ------------------------------------------------------------------ engine plumbing
@@ -674,14 +700,18 @@ class cNMF:
     # ------------------------------------------------------------------ the NMF call-site
     def _check_kwargs(self, kw):
         """The two solver configurations the reference can produce (cnmf.py:618-631):
-        ('cd','frobenius') and ('mu', 'kullback-leibler' | 'itakura-saito')."""
+        ('cd','frobenius') and ('mu', 'kullback-leibler' | 'itakura-saito'); and ('mu','frobenius') as a REFIT
+        (``update_H=False``), which is how starCAT projects query cells onto fixed programs."""
         solver, beta = kw.get("solver", "cd"), kw.get("beta_loss", "frobenius")
         ok = (solver == "cd" and beta in ("frobenius", 2)) or \
-             (solver == "mu" and beta in ("kullback-leibler", "itakura-saito", 1, 0))
+             (solver == "mu" and beta in ("kullback-leibler", "itakura-saito", 1, 0)) or \
+             (solver == "mu" and beta in ("frobenius", 2) and kw.get("update_H", True) is False)
         if not ok:
-            raise NotImplementedError("the device engine implements solver='cd'/beta_loss='frobenius' and "
-                                      "solver='mu'/beta_loss in ('kullback-leibler','itakura-saito'); "
-                                      "got solver=%r beta_loss=%r" % (solver, beta))
+            raise NotImplementedError("the device engine implements solver='cd'/beta_loss='frobenius', "
+                                      "solver='mu'/beta_loss in ('kullback-leibler','itakura-saito'), and "
+                                      "solver='mu'/beta_loss='frobenius' only as a refit (update_H=False), not as a "
+                                      "full factorization; got solver=%r beta_loss=%r update_H=%r"
+                                      % (solver, beta, kw.get("update_H", True)))
         if kw.get("init", "random") not in ("random", "custom", "nndsvd", None) and "H" not in kw:
             raise NotImplementedError("init=%r is not implemented on the device (random / nndsvd / custom)" % kw.get("init"))
 
@@ -702,7 +732,11 @@ class cNMF:
             xdt = Xv.dtype if Xv.dtype in (np.float32, np.float64) else np.dtype(np.float64)
             if H.dtype != xdt:
                 raise TypeError("H should have the same dtype as X. Got H.dtype = {}.".format(H.dtype))
-            if mu:
+            if mu and kw.get("beta_loss", "frobenius") in ("frobenius", 2):
+                # the refit starCAT projects query cells with: multiplicative Frobenius updates in float64
+                W, _, _ = eng.mu_frobenius_refit(H, tol=kw.get("tol", 1e-4), max_iter=kw.get("max_iter", 200),
+                                                 alpha_W=kw.get("alpha_W", 0.0), l1_ratio=kw.get("l1_ratio", 0.0))
+            elif mu:
                 # float64 on the stored entries, like scikit-learn on the reference's float64 matrices (cnmf.py:534); both
                 # beta losses (Itakura-Saito: a strictly positive matrix -- scikit-learn's rule -- stores every entry)
                 W, _, _ = eng.mu_refit_f64(H, tol=kw.get("tol", 1e-4), max_iter=kw.get("max_iter", 200),
@@ -939,11 +973,13 @@ class cNMF:
     def consensus(self, k, density_threshold=0.5, local_neighborhood_size=0.30, show_clustering=True,
                   build_ref=True, skip_density_and_return_after_stats=False, close_clustergram_fig=False,
                   refit_usage=True, normalize_tpm_spectra=False, norm_counts=None):
-        """cnmf.py:823-985 without the plotting block and ``build_reference`` (out of scope, SURVEY section 2
-        #10/#11): same signature and defaults as the reference, so positional (cnmf.py:1290) and keyword-less
-        calls bind alike.  With ``show_clustering=True`` AND ``self.materialize_topics_dist`` the distance matrix
-        is fetched as ``self.topics_dist`` for the reference's unchanged plotting code (integration/hip_backend.py);
-        ``build_ref`` and ``close_clustergram_fig`` have nothing to act on here and are ignored."""
+        """cnmf.py:823-985 and :1081-1082 without the plotting block (out of scope): same signature
+        and defaults as the reference, so positional (cnmf.py:1290) and keyword-less calls bind alike.  With
+        ``show_clustering=True`` AND ``self.materialize_topics_dist`` the distance matrix is fetched as
+        ``self.topics_dist`` for the reference's unchanged plotting code (integration/hip_backend.py);
+        ``close_clustergram_fig`` has nothing to act on here and is ignored.  ``build_ref`` (default on, as in the
+        reference): also write ``starcat_spectra`` (:meth:`build_reference`) when the TPM tail ran -- without a TPM file
+        there are no TPM spectra to build it from, and it is skipped with them."""
         cached = self.merged_cache.get(k)
         if cached is not None and cached[0] == os.path.getmtime(self.paths["merged_spectra"] % k):
             merged_spectra = cached[1].copy()                # this process wrote that very file
@@ -1122,11 +1158,53 @@ class cNMF:
                        (save_df_to_text, spectra_tpm, self.paths["gene_spectra_tpm__txt"] % rep),
                        (save_df_to_npz, usage_coef, self.paths["gene_spectra_score"] % rep),
                        (save_df_to_text, usage_coef, self.paths["gene_spectra_score__txt"] % rep)]
+            if build_ref:
+                # build_reference (cnmf.py:1081-1082, 1085-1116) from the frames at hand instead of the text just written
+                ref_spectra = _starcat_reference(_as_text_would_read(spectra_tpm), tpm_stats,
+                                                 open(self.paths["nmf_genes_list"]).read().split("\n"))
+                writes += [(save_df_to_npz, ref_spectra, self.paths["starcat_spectra"] % rep),
+                           (save_df_to_text, ref_spectra, self.paths["starcat_spectra__txt"] % rep)]
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=4) as pool:
             for fut in [pool.submit(fn, obj, path) for fn, obj, path in writes]:
                 fut.result()                                   # a failed write raises here, as it would have inline
         return median_spectra, rf_usages
+
+    # ------------------------------------------------------------------ starCAT reference (cnmf.py:1085-1116)
+    def build_reference(self, k, density_threshold=0.5, target_sum=1e6):
+        """cnmf.py:1085-1116: the reference programs starCAT projects query cells onto (``cnmf_amd.starcat.StarCAT``), from
+        the files a finished ``consensus(k, density_threshold)`` left: ``gene_spectra_tpm`` (text) with every program scaled
+        to ``target_sum``, divided by the genes' TPM standard deviation (``tpm_stats``), the high-variance genes in list
+        order, rows ``GEP1..``.  Writes ``starcat_spectra`` (.df.npz and text) and returns the frame."""
+        density_threshold_repl = str(density_threshold).replace(".", "_")
+        spectra_tpm = pd.read_csv(self.paths["gene_spectra_tpm__txt"] % (k, density_threshold_repl), index_col=0, sep="\t")
+        hvgs = open(self.paths["nmf_genes_list"]).read().split("\n")
+        tpm_stats = load_df_from_npz(self.paths["tpm_stats"])
+        ref_spectra = _starcat_reference(spectra_tpm, tpm_stats, hvgs, target_sum)
+        save_df_to_npz(ref_spectra, self.paths["starcat_spectra"] % (k, density_threshold_repl))
+        save_df_to_text(ref_spectra, self.paths["starcat_spectra__txt"] % (k, density_threshold_repl))
+        return ref_spectra
+
+    # ------------------------------------------------------------------ reading a finished run (cnmf.py:1161-1210)
+    def load_results(self, K, density_threshold, n_top_genes=100, norm_usage=True):
+        """cnmf.py:1161-1210: ``(usage, spectra_scores, spectra_tpm, top_genes)`` of a finished ``consensus(K,
+        density_threshold)`` from its text files -- the usages (cells x K, rows summing to 1 with ``norm_usage``), the
+        z-score and TPM spectra transposed to genes x K, and per program its ``n_top_genes`` genes of largest score."""
+        rep = (K, str(density_threshold).replace(".", "_"))
+        spectra_scores = pd.read_csv(self.paths["gene_spectra_score__txt"] % rep, sep="\t", index_col=0).T
+        spectra_tpm = pd.read_csv(self.paths["gene_spectra_tpm__txt"] % rep, sep="\t", index_col=0).T
+        usage = pd.read_csv(self.paths["consensus_usages__txt"] % rep, sep="\t", index_col=0)
+        if norm_usage:
+            usage = usage.div(usage.sum(axis=1), axis=0)
+        try:
+            usage.columns = [int(x) for x in usage.columns]
+        except (ValueError, TypeError):
+            print("Usage matrix columns include non integer values")
+        top_genes = []
+        for gep in spectra_scores.columns:
+            top_genes.append(list(spectra_scores.sort_values(by=gep, ascending=False).index[:n_top_genes]))
+        top_genes = pd.DataFrame(top_genes, index=spectra_scores.columns).T
+        return usage, spectra_scores, spectra_tpm, top_genes
 
     # ------------------------------------------------------------------ k selection (cnmf.py:1119-1135)
     def k_selection_stats(self, batched=True):

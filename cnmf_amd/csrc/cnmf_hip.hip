@@ -312,6 +312,7 @@ extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
 #include "hvg_batch_host.hip.h"
 #include "select_mi_host.hip.h"
 #include "tail_host.hip.h"
+#include "mu2_refit_host.hip.h"
 
 #include "debug_host.hip.h"
 #include "nndsvd_host.hip.h"

@@ -573,6 +573,17 @@ int cnmf_nnls_spectra(cnmf_ctx* ctx, int k, const double* W, const cnmf_cd_param
  * (float32) matrix.  gram (nullable) [k][k]: used INSTEAD of H.H^T, as in cnmf_nnls_gram below.              */
 int cnmf_nnls_f64(cnmf_ctx* ctx, int k, const double* H, const double* gram, const cnmf_cd_params* prm,
                   double* W_out, int32_t* n_iter_out, double* viol_out);
+/* non_negative_factorization(X, H=H, update_H=False, solver='mu', beta_loss='frobenius') -- the refit starCAT projects
+ * query cells with -- in FLOAT64 over the dense (float32) image of the resident matrix: scikit-learn's
+ * _fit_multiplicative_update with beta_loss = 2 (sklearn:_nmf.py:731-893).  H [k][G] fixed, 1 <= k <= CNMF_KMAX
+ * (CNMF_EUNSUPPORTED above); W_out [N][k] starts from w_init everywhere (scikit-learn: sqrt(X.mean() / k)).  The product
+ * X.H^T, the Gram matrix and sum x^2 are formed once; every iteration is w_t *= P_t / (sum_r w_r Gram[r][t] + l1_reg_W +
+ * l2_reg_W w_t) from the row's old values (a zero denominator -> float32 epsilon); the error
+ * sqrt(sum x^2 + sum W.(W Gram) - 2 sum P.W) is evaluated at the start and after every 10th iteration when tol > 0 and
+ * stops the loop when (previous - error) / error_at_start < tol.  n_iter_out: iterations run; err_out: the last error
+ * evaluated.  Sums run in an order fixed by the shapes: two calls give the same bits.                          */
+int cnmf_mu2_refit_f64(cnmf_ctx* ctx, int k, const double* H, double w_init, const cnmf_cd_params* prm,
+                       double* W_out, int32_t* n_iter_out, double* err_out);
 /* cnmf_nnls with a caller-supplied Gram matrix gram[k][k] = H.H^T: the rows H_prod [k][G] only enter the product
  * X.H_prod^T.  Lets the final usage refit of consensus() (cnmf.py:960-975: X = tpm[:, hvgs] / std) run on the
  * resident TPM matrix: H_prod = spectra / std on the HVG columns and 0 elsewhere, gram from the HVG block.    */
