@@ -102,7 +102,9 @@ def mu_update_h(X, W, H, beta, l1, l2, gamma):
     return H
 
 
-def fit_mu(X, W, H, beta, tol=1e-4, max_iter=200, l1W=0, l1H=0, l2W=0, l2H=0, update_H=True):
+def fit_mu(X, W, H, beta, tol=1e-4, max_iter=200, l1W=0, l1H=0, l2W=0, l2H=0, update_H=True, snapshots=None):
+    """``snapshots``: a dict whose keys are iteration numbers; it receives copies ``(W, H)`` of the factors as they stand
+    after that iteration (what a run with max_iter = that number and tol = 0 returns)."""
     gamma = 1.0 / (2.0 - beta) if beta < 1 else 1.0
     err0 = beta_divergence(X, W, H, beta, square_root=True)
     prev = err0
@@ -115,6 +117,8 @@ def fit_mu(X, W, H, beta, tol=1e-4, max_iter=200, l1W=0, l1H=0, l2W=0, l2H=0, up
             H = mu_update_h(X, W, H, beta, l1H, l2H, gamma)
             if beta <= 1:
                 H[H < np.finfo(np.float64).eps] = 0.0
+        if snapshots is not None and n_iter in snapshots:
+            snapshots[n_iter] = (W.copy(), H.copy())
         if tol > 0 and n_iter % 10 == 0:
             err = beta_divergence(X, W, H, beta, square_root=True)
             if (prev - err) / err0 < tol:
@@ -127,14 +131,14 @@ BETA = {"kullback-leibler": 1, "itakura-saito": 0, 1: 1, 0: 0}
 
 
 def nmf_mu(X, n_components, seed=None, W0=None, H0=None, beta_loss="kullback-leibler", tol=1e-4,
-           max_iter=1000, alpha_W=0.0, alpha_H=0.0, l1_ratio=0.0):
+           max_iter=1000, alpha_W=0.0, alpha_H=0.0, l1_ratio=0.0, snapshots=None):
     X = np.asarray(X)
     if W0 is None:
         W, H = random_init(X, n_components, seed)
     else:
         W, H = np.array(W0, dtype=X.dtype), np.array(H0, dtype=X.dtype)
     l1W, l1H, l2W, l2H = regularization(X.shape[0], X.shape[1], alpha_W, alpha_H, l1_ratio)
-    return fit_mu(X, W, H, BETA[beta_loss], tol, max_iter, l1W, l1H, l2W, l2H, True)
+    return fit_mu(X, W, H, BETA[beta_loss], tol, max_iter, l1W, l1H, l2W, l2H, True, snapshots)
 
 
 def nnls_mu(X, H, beta_loss="kullback-leibler", tol=1e-4, max_iter=1000, alpha_W=0.0, l1_ratio=0.0):
