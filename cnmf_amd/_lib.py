@@ -34,6 +34,8 @@ SYMBOLS = [
     "cnmf_preprocess_subset", "cnmf_preprocess_fetch_counts",
     "cnmf_preprocess_gene_moments", "cnmf_preprocess_loess_fit", "cnmf_preprocess_clipped_sums",
     "cnmf_preprocess_gene_moments_batched", "cnmf_preprocess_clipped_sums_batched",
+    "cnmf_symmetric_tridiagonalize", "cnmf_tridiagonal_back_transform", "cnmf_preprocess_pca_tridiag",
+    "cnmf_preprocess_pca_finish",
     "cnmf_nmf_cd_batch", "cnmf_nmf_cd_batch_resident", "cnmf_get_iteration_means", "cnmf_set_iteration_hints", "cnmf_nnls",
     "cnmf_consensus", "cnmf_pairwise_distances", "cnmf_prediction_error", "cnmf_nmf_mu_batch", "cnmf_mu_refit_f64", "cnmf_mu2_refit_f64", "cnmf_x_matmul",
     "cnmf_xt_matmul_f64", "cnmf_nnls_spectra", "cnmf_nnls_f64", "cnmf_nnls_gram", "cnmf_nnls_batch", "cnmf_kselect_stats",
@@ -53,6 +55,7 @@ COMM_ID_BYTES = 128
 CNMF_KMAX = 128
 CNMF_MU_KMAX = 64
 CNMF_RIDGE_MAX = 4096
+CNMF_PCA_NMAX = 8192
 CNMF_HARMONY_KMAX = 128
 CNMF_HARMONY_DMAX = 64
 CNMF_HVG_BATCHES_MAX = 4096
@@ -255,6 +258,14 @@ def load():
     lib.cnmf_preprocess_loess_fit.argtypes = [vp, i64, dblp, dblp, i64, i64, dblp, dblp, dblp, i32p]
     lib.cnmf_preprocess_clipped_sums.restype = i32
     lib.cnmf_preprocess_clipped_sums.argtypes = [vp, dblp, dblp, dblp]
+    lib.cnmf_symmetric_tridiagonalize.restype = i32
+    lib.cnmf_symmetric_tridiagonalize.argtypes = [vp, i64, dblp, dblp, dblp]
+    lib.cnmf_tridiagonal_back_transform.restype = i32
+    lib.cnmf_tridiagonal_back_transform.argtypes = [vp, i64, i32, dblp, i32, dblp]
+    lib.cnmf_preprocess_pca_tridiag.restype = i32
+    lib.cnmf_preprocess_pca_tridiag.argtypes = [vp, i32, dblp, dblp, dblp]
+    lib.cnmf_preprocess_pca_finish.restype = i32
+    lib.cnmf_preprocess_pca_finish.argtypes = [vp, i32, i32, dblp, dblp, dblp]
     lib.cnmf_preprocess_gene_moments_batched.restype = i32
     lib.cnmf_preprocess_gene_moments_batched.argtypes = [vp, i32p, i32, i64p_, i64p_, i32p]
     lib.cnmf_preprocess_clipped_sums_batched.restype = i32

@@ -9,7 +9,8 @@
 //     ceiling's order statistics come from a radix select over the float64 bit patterns (all values >= 0, so the bit
 //     order is the value order; -0.0 is taken as +0.0) with integer counters only, the implicit zeros of a CSR slot counted analytically;
 //   * PCA (sc.pp.pca(zero_center=True)): column means and the G x G scatter matrix, then the scores (X - mean) V, on the
-//     float64 MFMA pipe; the eigendecomposition runs on the host;
+//     float64 MFMA pipe; the eigendecomposition runs on the host (or, opt-in, as a Householder tridiagonalisation on the
+//     device with only the tridiagonal problem on the host: pca_host.hip.h);
 //   * Harmony's ridge correction (moe_correct_ridge, :9-18): every cluster's W_k = (Phi_Rk Phi^T + lamb)^-1 Phi_Rk X is
 //     formed from the UNcorrected X, so the K updates are independent.  With A[(k,b), n] = R[k,n] Phi[b,n] (formed on
 //     the fly from R^T / Phi^T, never stored): one moments pass M = A X and Gram_k = A Phi^T (split-K over the cells,
@@ -458,6 +459,25 @@ extern "C" int cnmf_preprocess_fetch(cnmf_ctx* ctx, int32_t slot, int64_t* indpt
     return CNMF_OK;
 }
 
+// the column means mu [n] and the scatter matrix out [n][n] of a dense slot, both on the device
+static int pre_scatter_device(cnmf_ctx* ctx, int slot, double* mu, double* out)
+{
+    using namespace cnmf;
+    hipStream_t st = ctx->stream;
+    PreSlot& S = ctx->pre.slot[slot];
+    const int N = (int)ctx->pre.N, C = (int)S.n;
+    const int rpc = std::max(64, (N + 63) / 64), nch = (N + rpc - 1) / rpc;
+    DevPool pool;
+    double* part = pool.get<double>((size_t)nch * C);
+    POOL_TRY(ctx, pool);
+    pre_colsum_partial_kernel<<<dim3((C + 63) / 64, nch), 256, 0, st>>>(S.dense, N, C, rpc, part);
+    pre_colmean_kernel<<<(C + 255) / 256, 256, 0, st>>>(part, nch, N, C, mu);
+    HIP_TRY(ctx, hipGetLastError());
+    PreGemm g{};
+    g.M = C; g.Nn = C; g.K = N; g.X = S.dense; g.ldx = C; g.mu = mu;
+    return pre_product<0, 1>(ctx, g, out);
+}
+
 extern "C" int cnmf_preprocess_scatter(cnmf_ctx* ctx, int32_t slot, double* mean, double* scatter)
 {
     using namespace cnmf;
@@ -465,20 +485,12 @@ extern "C" int cnmf_preprocess_scatter(cnmf_ctx* ctx, int32_t slot, double* mean
     if (!mean || !scatter) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    PreSlot& S = ctx->pre.slot[slot];
-    const int N = (int)ctx->pre.N, C = (int)S.n;
-    const int rpc = std::max(64, (N + 63) / 64), nch = (N + rpc - 1) / rpc;
+    const int C = (int)ctx->pre.slot[slot].n;
     DevPool pool;
-    double* part = pool.get<double>((size_t)nch * C);
     double* mu = pool.get<double>(C);
     double* out = pool.get<double>((size_t)C * C);
     POOL_TRY(ctx, pool);
-    pre_colsum_partial_kernel<<<dim3((C + 63) / 64, nch), 256, 0, st>>>(S.dense, N, C, rpc, part);
-    pre_colmean_kernel<<<(C + 255) / 256, 256, 0, st>>>(part, nch, N, C, mu);
-    HIP_TRY(ctx, hipGetLastError());
-    PreGemm g{};
-    g.M = C; g.Nn = C; g.K = N; g.X = S.dense; g.ldx = C; g.mu = mu;
-    if (int rc = pre_product<0, 1>(ctx, g, out)) return rc;
+    if (int rc = pre_scatter_device(ctx, slot, mu, out)) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(mean, mu, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(scatter, out, (size_t)C * C * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));

@@ -173,7 +173,19 @@ struct PreStage : CountStage {
     std::vector<int32_t> gcodes;                     // [N] (host): the codes the cache answers to
     int gB = 0;
     void release_grouped() { grouped.release(); hipFree(gstart); gstart = nullptr; gcodes.clear(); gB = 0; }
-    void release() { release_counts(); release_ridge(); release_grouped(); slot[0].release(); slot[1].release(); N = 0; }
+    // the last Householder tridiagonalisation (pca_host.hip.h): the working matrix and the reflector store [tri_n][tri_n],
+    // tau [tri_n] and, for the scatter of a slot (tri_slot; -1: a host-supplied matrix), that slot's column means;
+    // replaced by the next tridiagonalisation; triR = NULL: none
+    double *triA = nullptr, *triR = nullptr, *tri_tau = nullptr, *tri_mu = nullptr;
+    int tri_n = 0, tri_slot = -1;
+    void release_tridiag() {
+        hipFree(triA); hipFree(triR); hipFree(tri_tau); hipFree(tri_mu);
+        triA = triR = tri_tau = tri_mu = nullptr; tri_n = 0; tri_slot = -1;
+    }
+    void release() {
+        release_counts(); release_ridge(); release_grouped(); release_tridiag();
+        slot[0].release(); slot[1].release(); N = 0;
+    }
 };
 
 // state of the cnmf_harmony_* entry points (harmony_host.hip.h): Harmony's soft clustering of N cells over d components

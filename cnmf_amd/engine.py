@@ -449,6 +449,80 @@ class Engine:
         else:
             self._check(self._lib.cnmf_preprocess_ridge_apply_mode(self._ctx, int(slot), W.ctypes.data_as(dblp), 0))
 
+    # ------------------------------------------------------------------ top eigenpairs through the tridiagonal form (pca_host.hip.h)
+    # The reflectors of the last tridiagonalisation stay staged beside the preprocess slots: the next one replaces them,
+    # preprocess_release (and every preprocess_upload) frees them.
+    @staticmethod
+    def pca_check_limit(n):
+        """NotImplementedError above the device limit of the tridiagonalisation entry points (nothing is allocated)"""
+        if n > _lib.CNMF_PCA_NMAX:
+            raise NotImplementedError("n = %d is above the device limit %d of the tridiagonalisation (Preprocess: use "
+                                      "pca=\"lapack\")" % (n, _lib.CNMF_PCA_NMAX))
+
+    def symmetric_tridiagonalize(self, A):
+        """Householder tridiagonalisation of the symmetric float64 matrix ``A`` [n][n] (both triangles are read; symmetry
+        is not checked) on the device: returns ``(d [n], e [n - 1])`` with Q^T A Q = tridiag(e, d, e).  Q stays staged
+        for :meth:`tridiagonal_back_transform`."""
+        if np.ndim(A) != 2 or np.shape(A)[0] != np.shape(A)[1] or np.shape(A)[0] < 1:
+            raise ValueError("a square matrix is expected, not shape %s" % (np.shape(A),))
+        n = int(np.shape(A)[0])
+        self.pca_check_limit(n)
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        d, e = np.empty(n), np.empty(max(n - 1, 1))
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_symmetric_tridiagonalize(self._ctx, n, A.ctypes.data_as(dblp), d.ctypes.data_as(dblp),
+                                                            e.ctypes.data_as(dblp)))
+        return d, e[:n - 1]
+
+    def tridiagonal_back_transform(self, Z, sign_rule=False):
+        """``Q Z`` for ``Z`` [n][n_comp] (1 <= n_comp <= n; eigenvectors of the tridiagonal matrix give eigenvectors of
+        A), Q of the last tridiagonalisation.  ``sign_rule``: every column then has its entry of largest magnitude
+        positive (the first index on ties).  ValueError when nothing is staged or n differs."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        if Z.ndim != 2 or Z.shape[1] < 1:
+            raise ValueError("Z [n][n_comp] is expected, not shape %s" % (Z.shape,))
+        V = np.empty_like(Z)
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_tridiagonal_back_transform(self._ctx, Z.shape[0], Z.shape[1], Z.ctypes.data_as(dblp),
+                                                              int(bool(sign_rule)), V.ctypes.data_as(dblp)))
+        return V
+
+    def symmetric_eigh_top(self, A, k):
+        """The ``k`` largest eigenvalues of the symmetric matrix ``A`` (descending) and their eigenvectors [n][k] (the
+        sign rule applied): tridiagonalisation on the device, the tridiagonal problem on the host
+        (``preprocess.tridiagonal_top``), back-transformation on the device."""
+        from .preprocess import tridiagonal_top
+        n = int(np.shape(A)[0]) if np.ndim(A) == 2 else 0
+        if not 1 <= int(k) <= max(n, 1):
+            raise ValueError("k = %s outside [1, %d]" % (k, n))
+        d, e = self.symmetric_tridiagonalize(A)
+        w, Z = tridiagonal_top(d, e, int(k))
+        return w, self.tridiagonal_back_transform(Z, sign_rule=True)
+
+    def preprocess_pca_tridiag(self, slot):
+        """The scatter matrix of a dense slot (as :meth:`preprocess_scatter` forms it), tridiagonalised where it is:
+        returns ``(mean [n], d [n], e [n - 1])``."""
+        n = self._pre[int(slot)][0]
+        self.pca_check_limit(n)
+        mean, d, e = np.empty(n), np.empty(n), np.empty(max(n - 1, 1))
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_preprocess_pca_tridiag(self._ctx, int(slot), mean.ctypes.data_as(dblp),
+                                                          d.ctypes.data_as(dblp), e.ctypes.data_as(dblp)))
+        return mean, d, e[:n - 1]
+
+    def preprocess_pca_finish(self, slot, Z):
+        """After :meth:`preprocess_pca_tridiag` on ``slot``: ``V = Q Z`` [n][n_comp] with the sign rule, and the scores
+        ``(X - mean) V`` [n_cells][n_comp]; V stays on the device in between.  Returns ``(V, scores)``."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        n = self._pre[int(slot)][0]
+        if Z.ndim != 2 or Z.shape[0] != n or Z.shape[1] < 1:
+            raise ValueError("Z [%d][n_comp] is expected, not shape %s" % (n, Z.shape))
+        V, scores = np.empty_like(Z), np.empty((self._pre["N"], Z.shape[1]))
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_preprocess_pca_finish(self._ctx, int(slot), Z.shape[1], Z.ctypes.data_as(dblp),
+                                                         V.ctypes.data_as(dblp), scores.ctypes.data_as(dblp)))
+        return V, scores
+
     # ------------------------------------------------------------------ harmony (cnmf_harmony_*, harmony_host.hip.h)
     # Harmony's clustering loop with a state of its own: the preprocess staging stays as it is.
     @staticmethod

@@ -10,7 +10,17 @@ defaults and error texts; every O(N G) step runs on the device (csrc/preprocess_
   (``np.quantile([lo, hi], frac)``), so the ceiling is the one ``np.quantile`` gives for the same matrix, bit for bit;
 * the PCA of ``sc.pp.pca(zero_center=True)``: min(50, min(N, G) - 1) components; the column means, the G x G covariance
   and the scores ``(X - mean) V`` on the device, ``np.linalg.eigh`` on the host.  Sign rule: the loading of largest
-  magnitude of every component is positive (scanpy's sign depends on its solver; Harmony's result does not depend on it);
+  magnitude of every component is positive (scanpy's sign depends on its solver; Harmony's result does not depend on it).
+  Opt-in, ``pca="device"`` on ``normalize_batchcorrect`` and ``preprocess_for_cnmf`` (the default, ``"lapack"``, is the
+  route above): the covariance stays on the device and is reduced to tridiagonal form there by Householder reflections
+  (csrc/pca_host.hip.h; LAPACK's dsytd2 convention, one launch per column), ``tridiagonal_top`` finds the kept
+  eigenpairs of the tridiagonal matrix on the host (``scipy.linalg.eigh_tridiagonal`` by index, 'stebz'), and the
+  back-transformation, the sign rule and the scores run on the device: the covariance is never fetched and the loadings
+  never uploaded.  At most 8192 genes (``NotImplementedError`` above).  **The yardstick is the float64 numpy restatement
+  in tests/_tridiag_ref.py** and gap-free contracts against ``np.linalg.eigh`` (residual and eigenvalues within
+  8 n eps |A|_inf, orthogonality within 8 n eps); the loadings of the two routes agree only as far as the eigenvalue
+  gaps allow.  **Agreement with scanpy's own ``sc.pp.pca`` solver is unmeasured on this project's machines**, for both
+  routes;
 * Harmony's mixture-of-experts ridge correction: every cluster's ``W_k`` is formed from the uncorrected X (as in the
   reference), so the moments ``M_k = (R_k Phi) X`` and ``Gram_k = (R_k Phi) Phi^T`` of all K clusters come from one
   device pass, ``W_k = inv(Gram_k + lamb) @ M_k`` (``W_k[0] = 0``) runs in numpy, so that ``lamb`` broadcasts exactly as
@@ -261,10 +271,54 @@ def _ceiling(eng, slot, n_rows, n_cols, quantile_thresh):
     return thresh
 
 
-def _pca(eng, slot, n_rows, n_cols, n_comps=None):
+PCA_MODES = ("lapack", "device")
+PCA_NMAX = 8192                     # (include/cnmf_hip.h: CNMF_PCA_NMAX)
+
+
+def _check_pca_mode(pca):
+    if pca not in PCA_MODES:
+        raise ValueError("pca must be one of %s, not %r" % (PCA_MODES, pca))
+
+
+def tridiagonal_top(d, e, n_comps):
+    """The ``n_comps`` largest eigenvalues of the symmetric tridiagonal matrix with diagonal ``d`` [n] and off-diagonal
+    ``e`` [n - 1], descending, and their eigenvectors ``Z`` [n][n_comps]: ``scipy.linalg.eigh_tridiagonal`` by index
+    with bisection and inverse iteration ('stebz': its vectors stay orthogonal through clustered eigenvalues), O(n n_comps).
+    Host only.  ValueError on non-finite input."""
+    from scipy.linalg import eigh_tridiagonal
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    e = np.ascontiguousarray(e, dtype=np.float64)
+    n = d.size
+    if d.ndim != 1 or n < 1 or e.shape != (n - 1,):
+        raise ValueError("d [n] and e [n - 1] are expected, not shapes %s and %s" % (d.shape, e.shape))
+    if not 1 <= n_comps <= n:
+        raise ValueError("n_comps = %s outside [1, %d]" % (n_comps, n))
+    if not (np.isfinite(d).all() and np.isfinite(e).all()):
+        raise ValueError("the tridiagonal matrix holds non-finite values")
+    if n == 1:
+        return d.copy(), np.ones((1, 1))
+    w, Z = eigh_tridiagonal(d, e, select='i', select_range=(n - int(n_comps), n - 1), lapack_driver='stebz')
+    return w[::-1].copy(), np.ascontiguousarray(Z[:, ::-1])
+
+
+def _pca_components(n_rows, n_cols):
+    return 50 if 50 < min(n_rows, n_cols) else min(n_rows, n_cols) - 1
+
+
+def _check_pca_size(pca, n_cols):
+    if pca == "device" and n_cols > PCA_NMAX:
+        raise NotImplementedError("pca=\"device\" takes at most %d genes, not %d: use pca=\"lapack\"" % (PCA_NMAX, n_cols))
+
+
+def _pca(eng, slot, n_rows, n_cols, n_comps=None, pca="lapack"):
     """sc.pp.pca(zero_center=True) of a dense device slot: scores [n_rows][n_comps] (see the module docstring)."""
     if n_comps is None:
-        n_comps = 50 if 50 < min(n_rows, n_cols) else min(n_rows, n_cols) - 1
+        n_comps = _pca_components(n_rows, n_cols)
+    if pca == "device":
+        _check_pca_size(pca, n_cols)
+        _, d, e = eng.preprocess_pca_tridiag(slot)
+        _, Z = tridiagonal_top(d, e, n_comps)
+        return eng.preprocess_pca_finish(slot, Z)[1]
     mean, scatter = eng.preprocess_scatter(slot)
     w, V = np.linalg.eigh(scatter / (n_rows - 1))
     order = np.argsort(-w, kind="stable")[:n_comps]
@@ -842,7 +896,7 @@ class Preprocess:
     def normalize_batchcorrect(self, data, obs=None, highly_variable=None, normalize_librarysize=False, harmony_vars=None,
                                n_top_genes=None, librarysize_targetsum=1e4, max_scaled_thresh=None, quantile_thresh=.9999,
                                theta=1, makeplots=True, max_iter_harmony=20, harmony_res=None, harmony="harmonypy",
-                               hvg=None, hvg_batch_key=None):
+                               hvg=None, hvg_batch_key=None, pca="lapack"):
         """Normalises the high-variance genes of raw counts and optionally corrects them with Harmony.  Returns
         ``(result, hvgs)``: ``result.X`` goes straight into ``cNMF.prepare(counts=(result.X, result.obs_names, hvgs),
         ...)``.  ``harmony``: who runs Harmony when ``harmony_res`` is not given: "harmonypy" (the library), "device"
@@ -854,7 +908,13 @@ class Preprocess:
         ``var['highly_variable']``; the frame, restricted to the selected genes, is ``result.var``.
         ``hvg_batch_key``: a column of ``obs``; that selection is then made per batch and the ranks combined
         (``highly_variable_genes(batch_key=...)``; ``result.var`` carries ``highly_variable_nbatches``).  Given without
-        ``hvg="device"`` and a number it raises ValueError."""
+        ``hvg="device"`` and a number it raises ValueError.
+
+        ``pca``: who solves the PCA's eigenproblem in the Harmony branch: "lapack" (the default: the gene covariance is
+        fetched and ``np.linalg.eigh`` finds all its eigenpairs on the host) or "device" (Householder tridiagonalisation
+        on the device, the tridiagonal problem for the kept components on the host, back-transformation and scores on
+        the device; at most 8192 selected genes, NotImplementedError above).  Anything else raises ValueError."""
+        _check_pca_mode(pca)
         _check_hvg_mode(hvg)
         _check_hvg_batch_key(hvg_batch_key, hvg == "device" and n_top_genes is not None, obs)
         if n_top_genes is not None and hvg is None:
@@ -889,7 +949,7 @@ class Preprocess:
                 var = var.iloc[sel]
             Xout, obsm = self._batchcorrect_staged(eng, X.shape[0], sel, dense, obs, normalize_librarysize, harmony_vars,
                                                    librarysize_targetsum, max_scaled_thresh, quantile_thresh, theta,
-                                                   max_iter_harmony, harmony_res, harmony)
+                                                   max_iter_harmony, harmony_res, harmony, pca)
         finally:
             eng.preprocess_release()
         hvgs = list(genes[sel])
@@ -944,12 +1004,13 @@ class Preprocess:
 
     def _batchcorrect_staged(self, eng, N, sel, dense, obs, normalize_librarysize, harmony_vars, librarysize_targetsum,
                              max_scaled_thresh, quantile_thresh, theta, max_iter_harmony, harmony_res,
-                             harmony="harmonypy"):
+                             harmony="harmonypy", pca="lapack"):
         """normalize_batchcorrect (preprocess.py:314-358) over the counts ``eng`` has staged (N cells), for the staged
         genes ``sel``: returns ``(X, obsm)``.  The caller uploads and releases."""
         n = int(sel.size)
         obsm = {}
         if harmony_vars is not None:
+            _check_pca_size(pca, n)
             # anorm: normalize_total(copy=True) -> HVG subset -> scale + ceiling (preprocess.py:316-318)
             eng.preprocess_select(0, sel, float(librarysize_targetsum), max_scaled_thresh)
             _ceiling(eng, 0, N, n, quantile_thresh)
@@ -958,7 +1019,7 @@ class Preprocess:
                 eng.preprocess_select(1, sel, 0.0, max_scaled_thresh)
                 _ceiling(eng, 1, N, n, quantile_thresh)
             eng.preprocess_densify(0)
-            obsm["X_pca"] = _pca(eng, 0, N, n)                     # (:326)
+            obsm["X_pca"] = _pca(eng, 0, N, n, pca=pca)            # (:326)
             slot = 0 if normalize_librarysize else 1
             eng.preprocess_densify(slot)
             if harmony_res is None:
@@ -1036,7 +1097,7 @@ class Preprocess:
                             adt_feature_name='Antibody Capture', harmony_vars=None, n_top_rna_genes=None,
                             librarysize_targetsum=1e4, max_scaled_thresh=None, quantile_thresh=.9999, makeplots=True,
                             theta=1, save_output_base=None, max_iter_harmony=20, exclude_genes=None, harmony_res=None,
-                            harmony="harmonypy", hvg=None, hvg_batch_key=None):
+                            harmony="harmonypy", hvg=None, hvg_batch_key=None, pca="lapack"):
         """The reference's minimal preprocessing: the HVG-filtered, variance-normalised, optionally Harmony-corrected RNA
         matrix (the ``counts`` input of cNMF) and the library-size-normalised matrix over all genes, ADT features
         appended and normalised on their own (the ``tpm`` input).
@@ -1054,7 +1115,8 @@ class Preprocess:
         ``exclude_genes`` went, as the reference does: an excluded gene or an ADT feature is never selected, and the
         selection replaces ``highly_variable``.  The frame of the selected genes is ``result_rna.var``.
         ``hvg_batch_key`` (a column of ``obs``) makes that selection per batch, as in normalize_batchcorrect; given
-        without ``hvg="device"`` and a number it raises ValueError.
+        without ``hvg="device"`` and a number it raises ValueError.  ``pca``: "lapack" (the default) or "device", as in
+        normalize_batchcorrect.
 
         The RNA counts are uploaded once: ``tp10k`` comes from them over all RNA genes before ``exclude_genes`` are taken
         out (on the device), then normalize_batchcorrect's body runs on the same staging.
@@ -1070,6 +1132,7 @@ class Preprocess:
             rna, adt = data, None
         else:
             raise Exception(DATA_FORM_ERROR)
+        _check_pca_mode(pca)
         _check_hvg_mode(hvg)
         _check_hvg_batch_key(hvg_batch_key, hvg == "device" and n_top_rna_genes is not None, obs)
         if n_top_rna_genes is not None and hvg is None:
@@ -1146,7 +1209,7 @@ class Preprocess:
                 hvg_var = hvg_var.iloc[sel]
             Xout, obsm = self._batchcorrect_staged(eng, X.shape[0], sel, dense, obs, False, harmony_vars, target,
                                                    max_scaled_thresh, quantile_thresh, theta, max_iter_harmony,
-                                                   harmony_res, harmony)
+                                                   harmony_res, harmony, pca)
             tp_genes, tp_types = genes, types_rna
             if adt is not None:
                 eng.preprocess_upload(Xa)                           # normalised on its own (:254)

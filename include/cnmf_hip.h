@@ -38,6 +38,7 @@ extern "C" {
 #define CNMF_HARMONY_KMAX 128  /* most clusters of cnmf_harmony_begin (CNMF_EUNSUPPORTED above)                             */
 #define CNMF_HARMONY_DMAX 64   /* most components of cnmf_harmony_begin                                                     */
 #define CNMF_RIDGE_MAX 4096    /* largest K * (B + 1) of cnmf_preprocess_ridge_moments (CNMF_EUNSUPPORTED above)      */
+#define CNMF_PCA_NMAX 8192     /* largest matrix of the tridiagonalisation entry points (CNMF_EUNSUPPORTED above)            */
 #define CNMF_KMAX 128          /* largest rank of the coordinate-descent / NNLS / consensus entry points
                                   (<= 64: register-resident sweep; 65..128: sweep_big_kernel)              */
 
@@ -301,6 +302,29 @@ int cnmf_preprocess_gene_moments_batched(cnmf_ctx* ctx, const int32_t* codes /* 
 int cnmf_preprocess_clipped_sums_batched(cnmf_ctx* ctx, const int32_t* codes /* [n_cells] */, int32_t n_batches,
                                          const double* clip /* [n_batches][n_genes] */, double* c1 /* [n_batches][n_genes] */,
                                          double* c2 /* [n_batches][n_genes] */);
+
+/* ---- the top eigenpairs of a symmetric matrix through its tridiagonal form (pca_host.hip.h) ------------------------------
+ * Householder tridiagonalisation on the device (LAPACK's dsytd2 / dlarfg convention, one launch per column), the
+ * tridiagonal eigenproblem left to the caller (O(n n_comp) on the host), back-transformation of the kept vectors on the
+ * device.  The reflectors of the LAST tridiagonalisation stay staged beside the preprocess slots: the next one replaces
+ * them, cnmf_preprocess_release (and every cnmf_preprocess_upload_csr) frees them.  n > CNMF_PCA_NMAX: CNMF_EUNSUPPORTED,
+ * before anything is allocated.
+ *   cnmf_symmetric_tridiagonalize    A [n][n] symmetric (both triangles; not checked) -> d [n], e [n - 1] (e may be NULL
+ *                                    for n = 1) with Q^T A Q = tridiag(e, d, e).
+ *   cnmf_tridiagonal_back_transform  V [n][n_comp] = Q Z for Z [n][n_comp], 1 <= n_comp <= n; sign_rule != 0: every column
+ *                                    then negated when its entry of largest magnitude (the first on ties) is negative.
+ *                                    Nothing staged, or n not the staged one: CNMF_EINVAL.
+ *   cnmf_preprocess_pca_tridiag      the same for the scatter matrix of a dense slot, formed as cnmf_preprocess_scatter forms
+ *                                    it and left on the device: mean [n] (the bits of cnmf_preprocess_scatter), d, e.
+ *   cnmf_preprocess_pca_finish       after cnmf_preprocess_pca_tridiag on the same slot (else CNMF_EINVAL): V = Q Z with the
+ *                                    sign rule and scores [n_cells][n_comp] = (X - mean) V, V taken where it is.        */
+int cnmf_symmetric_tridiagonalize(cnmf_ctx* ctx, int64_t n, const double* A, double* d /* [n] */, double* e /* [n-1] */);
+int cnmf_tridiagonal_back_transform(cnmf_ctx* ctx, int64_t n, int32_t n_comp, const double* Z /* [n][n_comp] */,
+                                    int32_t sign_rule, double* V /* [n][n_comp] */);
+int cnmf_preprocess_pca_tridiag(cnmf_ctx* ctx, int32_t slot, double* mean /* [n] */, double* d /* [n] */,
+                                double* e /* [n-1] */);
+int cnmf_preprocess_pca_finish(cnmf_ctx* ctx, int32_t slot, int32_t n_comp, const double* Z /* [n][n_comp] */,
+                               double* V /* [n][n_comp] */, double* scores /* [n_cells][n_comp] */);
 
 /* ---- Harmony's clustering loop (harmony_host.hip.h) -----------------------------------------------------------------
  * The loop of harmonypy's run_harmony over N cells, d components, K clusters and n_vars batch variables with n_levels

@@ -27,7 +27,15 @@ about 6.7 % non-zero, 2 000 genes selected): the whole call with both loess surf
 --repeats), its three device steps on their own (the integer moments, the local fits at the vertices and at every gene,
 the clipped sums), and the numpy restatement tests/_seurat_v3_ref.py on this machine's cores.
 
-Usage:  python tools/preprocess_probe.py [--cells 50000] [--genes 2000] [--K 100] [--batches 4] [--out FILE.json]
+``--pca`` times the PCA of the Harmony branch both ways on one staged slot of --cells x --genes (the normalised,
+scaled and ceilinged counts of the default leg), the median of --repeats, every step between two synchronising calls:
+``pca="device"`` (scatter + Householder tridiagonalisation on the device; ``tridiagonal_top`` on the host;
+back-transformation + sign rule + scores on the device) and ``pca="lapack"`` (scatter + fetch; ``np.linalg.eigh`` on
+this machine's cores; upload + scores), the contracts of tests/_tridiag_ref.py for the device's eigenpairs at that size,
+and writes profiles/preprocess_probe_pca_<N>x<G>.json unless --out says otherwise.
+
+Usage:  python tools/preprocess_probe.py --pca [--cells 50000] [--genes 2000] [--repeats 3] [--out FILE.json]
+        python tools/preprocess_probe.py [--cells 50000] [--genes 2000] [--K 100] [--batches 4] [--out FILE.json]
         python tools/preprocess_probe.py --filter [--filter-cells 50000] [--filter-genes 20000] [--out FILE.json]
         python tools/preprocess_probe.py --harmony [--cells 50000] [--components 50] [--K 100] [--batches 4] [--out FILE.json]
         python tools/preprocess_probe.py --hvg [--filter-cells 50000] [--filter-genes 20000] [--out FILE.json]
@@ -328,8 +336,69 @@ def hvg_leg(a):
     return out
 
 
+def pca_leg(a):
+    """the PCA of normalize_batchcorrect's Harmony branch both ways on the same staged slot, every step between two
+    synchronising calls, the median of --repeats"""
+    from tests import _tridiag_ref as ref
+    N, G = a.cells, a.genes
+    C = make_inputs(N, G, 1, 1)[0]
+    n_comps = pp._pca_components(N, G)
+    steps = {"device": {"scatter_and_tridiagonalise_ms": [], "host_tridiagonal_solve_ms": [],
+                        "back_transform_and_scores_ms": []},
+             "lapack": {"scatter_and_fetch_ms": [], "host_eigh_ms": [], "upload_and_project_ms": []}}
+    free = []
+    with Engine(0) as eng:
+        eng.symmetric_eigh_top(np.eye(8), 2)                         # warm-up (code objects)
+        eng.preprocess_upload(C)
+        eng.preprocess_select(0, np.arange(G), 1e4, None)
+        pp._ceiling(eng, 0, N, G, .9999)
+        eng.preprocess_densify(0)
+        eng.preprocess_scatter(0)
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            mean, d, e = eng.preprocess_pca_tridiag(0)
+            t1 = time.perf_counter()
+            w, Z = pp.tridiagonal_top(d, e, n_comps)
+            t2 = time.perf_counter()
+            Vd, scores_d = eng.preprocess_pca_finish(0, Z)
+            t3 = time.perf_counter()
+            for k, v in zip(steps["device"], (t1 - t0, t2 - t1, t3 - t2)):
+                steps["device"][k].append(1e3 * v)
+            t0 = time.perf_counter()
+            mean_l, S = eng.preprocess_scatter(0)
+            t1 = time.perf_counter()
+            lam, V = np.linalg.eigh(S / (N - 1))
+            V = ref.sign_rule(V[:, np.argsort(-lam, kind="stable")[:n_comps]])
+            t2 = time.perf_counter()
+            scores_l = eng.preprocess_project(0, mean_l, V)
+            t3 = time.perf_counter()
+            for k, v in zip(steps["lapack"], (t1 - t0, t2 - t1, t3 - t2)):
+                steps["lapack"][k].append(1e3 * v)
+        eng.preprocess_release()
+        for _ in range(a.repeats):                                   # the tridiagonalisation of a host matrix: upload + n launches
+            t0 = time.perf_counter()
+            eng.symmetric_tridiagonalize(S)
+            free.append(1e3 * (time.perf_counter() - t0))
+        eng.preprocess_release()
+    out = {"cells": N, "genes": G, "n_comps": n_comps, "repeats": a.repeats, "host_threads": os.environ.get("OMP_NUM_THREADS"),
+           "form": "one launch per column (deferred rank-2 update)"}
+    for route, r in steps.items():
+        out[route] = {k: round(float(np.median(v)), 3) for k, v in r.items()}
+        out[route]["total_ms"] = round(sum(out[route].values()), 3)
+        out[route + "_all_ms"] = {k: [round(x, 3) for x in v] for k, v in r.items()}
+    out["upload_and_tridiagonalise_host_matrix_ms"] = round(float(np.median(free)), 3)
+    out["lapack_over_device"] = round(out["lapack"]["total_ms"] / out["device"]["total_ms"], 2)
+    res, eig, orth, desc = ref.contracts(S, w, Vd)
+    out["device_contracts"] = {"residual_over_u": float(res), "eigenvalues_over_u": float(eig),
+                               "orthogonality_over_n_eps": float(orth), "descending": desc}
+    out["max_abs_diff_scores_over_max_abs"] = float(np.abs(scores_d - scores_l).max() / np.abs(scores_l).max())
+    out["relative_gap_of_the_last_kept_component"] = float((lam[-n_comps] - lam[-n_comps - 1]) / lam[-1])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--pca", action="store_true")
     ap.add_argument("--filter", action="store_true")
     ap.add_argument("--harmony", action="store_true")
     ap.add_argument("--hvg", action="store_true")
@@ -344,8 +413,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.filter or a.harmony or a.hvg:
-        out = filter_leg(a) if a.filter else harmony_leg(a) if a.harmony else hvg_leg(a)
+    if a.pca and not a.out:
+        a.out = os.path.join(ROOT, "profiles", "preprocess_probe_pca_%dx%d.json" % (a.cells, a.genes))
+    if a.pca or a.filter or a.harmony or a.hvg:
+        out = pca_leg(a) if a.pca else filter_leg(a) if a.filter else harmony_leg(a) if a.harmony else hvg_leg(a)
         print(json.dumps(out, indent=1))
         if a.out:
             with open(a.out, "w") as F:
