@@ -42,7 +42,7 @@ SYMBOLS = [
     "cnmf_comm_unique_id", "cnmf_comm_init", "cnmf_comm_finalize", "cnmf_comm_rank", "cnmf_comm_world",
     "cnmf_allgather_bytes", "cnmf_allgather_spectra",
     "cnmf_spectra_rows", "cnmf_spectra_reset", "cnmf_spectra_fetch", "cnmf_spectra_fetch_rows", "cnmf_spectra_genes", "cnmf_spectra_append",
-    "cnmf_consensus_store", "cnmf_kselect_stats_store",
+    "cnmf_consensus_store", "cnmf_kselect_stats_store", "cnmf_clustergram", "cnmf_clustergram_step_ms",
     "cnmf_range_finder", "cnmf_format_rows_f64",
 ]
 # test hooks (include/cnmf_hip_debug.h): present only in a library built with -DCNMF_DEBUG_ABI -- the in-tree default,
@@ -56,6 +56,7 @@ CNMF_KMAX = 128
 CNMF_MU_KMAX = 64
 CNMF_RIDGE_MAX = 4096
 CNMF_PCA_NMAX = 8192
+CNMF_LINKAGE_MAX = 4096
 CNMF_HARMONY_KMAX = 128
 CNMF_HARMONY_DMAX = 64
 CNMF_HVG_BATCHES_MAX = 4096
@@ -349,6 +350,10 @@ def load():
     lib.cnmf_kselect_stats_store.restype = i32
     lib.cnmf_kselect_stats_store.argtypes = [vp, i32, i32p, i32p, i64p, C.POINTER(ConsensusParams), dblp,
                                              C.POINTER(CdParams), dblp, dblp, dblp, i32p]
+    lib.cnmf_clustergram.restype = i32
+    lib.cnmf_clustergram.argtypes = [vp, dblp, i64p, i32, i32, i32p, i32, i32p, dblp, i32p, dblp]
+    lib.cnmf_clustergram_step_ms.restype = i32
+    lib.cnmf_clustergram_step_ms.argtypes = [vp, dblp]
     lib.cnmf_spectra_reset.restype = i32
     lib.cnmf_spectra_reset.argtypes = [vp]
     lib.cnmf_spectra_fetch.restype = i32

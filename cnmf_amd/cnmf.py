@@ -315,6 +315,10 @@ class cNMF:
     # the R x R distance matrix only leaves the device when a consumer exists (the reference's plotting block,
     # integration/hip_backend.py sets this): 8 R^2 bytes of host memory otherwise bought nothing
     materialize_topics_dist = False
+    # "device": consensus(show_clustering=True) also produces the clustergram (cnmf.py:986-1079) -- the kept spectra's
+    # distance matrix ordered by cluster and average-linkage leaf order on the device (Engine.clustergram) as
+    # self.spectra_order / self.topics_dist_ordered, and the figure at paths["clustering_plot"].  None: no clustergram.
+    clustergram = None
 
     def __init__(self, output_dir=".", name=None, device=0, engine=None, compress_merged=True, detect_counts=True):
         """Same constructor semantics as the reference (cnmf.py:268-296) plus the GPU index.
@@ -381,6 +385,7 @@ class cNMF:
                 "gene_spectra_tpm__txt": o(".gene_spectra_tpm.k_%d.dt_%s.txt"),
                 "starcat_spectra": t(".starcat_spectra.k_%d.dt_%s.df.npz"),
                 "starcat_spectra__txt": o(".starcat_spectra.k_%d.dt_%s.txt"),
+                "clustering_plot": o(".clustering.k_%d.dt_%s.png"),
             }
 
     # ------------------------------------------------------------------ engine plumbing
@@ -977,9 +982,19 @@ class cNMF:
         and defaults as the reference, so positional (cnmf.py:1290) and keyword-less calls bind alike.  With
         ``show_clustering=True`` AND ``self.materialize_topics_dist`` the distance matrix is fetched as
         ``self.topics_dist`` for the reference's unchanged plotting code (integration/hip_backend.py);
-        ``close_clustergram_fig`` has nothing to act on here and is ignored.  ``build_ref`` (default on, as in the
+        ``close_clustergram_fig`` has nothing to act on then and is ignored.  ``build_ref`` (default on, as in the
         reference): also write ``starcat_spectra`` (:meth:`build_reference`) when the TPM tail ran -- without a TPM file
-        there are no TPM spectra to build it from, and it is skipped with them."""
+        there are no TPM spectra to build it from, and it is skipped with them.
+
+        ``self.clustergram = "device"`` (opt-in; default None) with ``show_clustering=True``: the clustergram is made here
+        after all -- ``Engine.clustergram`` orders the kept spectra on the device (``self.spectra_order``, indices into
+        the kept rows, and ``self.topics_dist_ordered``), also when the local density came from its cache file, and the
+        figure (cnmf_amd/clustergram.py) is written to ``paths["clustering_plot"]``; ``close_clustergram_fig`` closes it,
+        otherwise it stays at ``self.clustergram_fig``."""
+        if self.clustergram not in (None, "device"):
+            raise ValueError("cNMF.clustergram must be None or 'device', not %r" % (self.clustergram,))
+        want_clustergram = (self.clustergram == "device" and show_clustering
+                            and not skip_density_and_return_after_stats)
         cached = self.merged_cache.get(k)
         if cached is not None and cached[0] == os.path.getmtime(self.paths["merged_spectra"] % k):
             merged_spectra = cached[1].copy()                # this process wrote that very file
@@ -1051,6 +1066,13 @@ class cNMF:
         kept = out["density_filter"]
         self.kmeans_cluster_labels = pd.Series(out["labels"][kept] + 1, index=merged_spectra.index[kept])
         self.local_density = out["local_density"]
+        if want_clustergram:
+            # cnmf.py:986-1009, 1028 on the device: distances of the kept spectra, per-cluster average linkage, leaf order,
+            # the permuted matrix -- from the store rows when the merged spectra are resident (nothing is uploaded)
+            cg = eng.clustergram(None if srows is not None else merged_spectra.values, out["labels"], k,
+                                 **({"store_rows": srows} if srows is not None else {}))
+            self.spectra_order = cg["spectra_order"]
+            self.topics_dist_ordered = cg["topics_dist_ordered"]
         median_spectra = pd.DataFrame(out["median_spectra"], index=np.arange(1, k + 1), columns=merged_spectra.columns)
         xdt = norm_counts.values.dtype
         rf_usages = self.refit_usage(norm_counts, median_spectra.astype(xdt))
@@ -1168,6 +1190,12 @@ class cNMF:
         with ThreadPoolExecutor(max_workers=4) as pool:
             for fut in [pool.submit(fn, obj, path) for fn, obj, path in writes]:
                 fut.result()                                   # a failed write raises here, as it would have inline
+        if want_clustergram:
+            from .clustergram import save_clustergram
+            self.clustergram_fig = save_clustergram(
+                self.paths["clustering_plot"] % rep, self.topics_dist_ordered,
+                self.kmeans_cluster_labels.values[self.spectra_order], np.asarray(self.local_density, dtype=np.float64),
+                density_threshold, int((~np.asarray(out["density_filter"])).sum()), close=close_clustergram_fig)
         return median_spectra, rf_usages
 
     # ------------------------------------------------------------------ starCAT reference (cnmf.py:1085-1116)

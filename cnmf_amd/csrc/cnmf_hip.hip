@@ -297,6 +297,7 @@ extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
 
 // ------------------------------------------------------------------ consensus step
 #include "consensus_host.hip.h"
+#include "linkage_host.hip.h"
 
 // ------------------------------------------------------------------ multiplicative-update solver
 #include "mu_host.hip.h"

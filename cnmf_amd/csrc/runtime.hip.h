@@ -319,6 +319,7 @@ struct cnmf_ctx {
     Arena cons_ws;                    // consensus workspace (consensus_host.hip.h)
     void* cons_pinned = nullptr;      // pinned host block of the consensus calls (k-means state read-backs)
     size_t cons_pinned_bytes = 0;
+    double clustergram_ms[5] = {0, 0, 0, 0, 0};   // steps of the last cnmf_clustergram (linkage_host.hip.h)
 
     cnmf_comm* comm = nullptr;        // RCCL communicator (comm_host.hip.h); NULL = single GPU
 

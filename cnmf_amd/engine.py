@@ -1615,6 +1615,57 @@ class Engine:
                                                       C.byref(sil) if sil is not None else None))
         return D, (float(sil.value) if sil is not None else None)
 
+    def clustergram(self, spectra, labels, k, store_rows=None, return_image=True, return_linkage=False):
+        """``cnmf_clustergram``: what ``consensus(show_clustering=True)`` orders before it draws (cnmf.py:986-1009, :1028),
+        on the device in float64.  ``spectra`` (R x G, as merged: they are L2-normalised on the device) or ``None`` with
+        ``store_rows`` (R rows of the resident spectra store); ``labels`` (R,) with -1 = removed by the density filter,
+        else the 0-based k-means cluster.  Returns a dict with
+
+        ``spectra_order``        indices into the KEPT rows: the clusters in ascending label, each in the leaf order of the
+                                 average-linkage dendrogram of its own distance block (``tests/_upgma_ref.py`` is the
+                                 definition; with distinct merge heights it is scipy's ``leaves_list(linkage(., 'average'))``)
+        ``segments``             (k + 1,): cluster c is ``spectra_order[segments[c]:segments[c + 1]]``
+        ``topics_dist_ordered``  distances of the kept rows, ``D[order][:, order]`` (``None`` without ``return_image``)
+        ``linkage``              the k linkage matrices (``None`` without ``return_linkage``)
+
+        A cluster above ``CNMF_LINKAGE_MAX`` members raises NotImplementedError; a label outside -1..k-1 or a cluster
+        without a member raises ValueError."""
+        self._sync_env()
+        k = int(k)
+        lab = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+        R = int(lab.size)
+        dblp, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        if store_rows is not None:
+            rows = np.ascontiguousarray(store_rows, dtype=np.int64).ravel()
+            if rows.size != R:
+                raise ValueError("labels must have one entry per store row")
+            G, sp, rp = int(self.spectra_genes), None, rows.ctypes.data_as(C.POINTER(C.c_int64))
+        else:
+            S = np.ascontiguousarray(spectra, dtype=np.float64)
+            if S.ndim != 2 or S.shape[0] != R:
+                raise ValueError("spectra must be 2-D with one label per row")
+            G, sp, rp = int(S.shape[1]), S.ctypes.data_as(dblp), None
+        Rk = int((lab >= 0).sum())
+        order = np.zeros(Rk, dtype=np.int32)
+        seg = np.zeros(max(k, 0) + 1, dtype=np.int32)
+        Z = np.zeros((max(Rk - k, 0), 4), dtype=np.float64) if return_linkage else None
+        image = np.empty((Rk, Rk), dtype=np.float64) if return_image else None
+        self._check(self._lib.cnmf_clustergram(self._ctx, sp, rp, R, G, lab.ctypes.data_as(i32p), k,
+                                               order.ctypes.data_as(i32p),
+                                               Z.ctypes.data_as(dblp) if Z is not None else None,
+                                               seg.ctypes.data_as(i32p),
+                                               image.ctypes.data_as(dblp) if image is not None else None))
+        linkage = None
+        if return_linkage:
+            linkage = [Z[seg[c] - c:seg[c + 1] - c - 1].copy() for c in range(k)]
+        return dict(spectra_order=order.astype(np.int64), segments=seg, topics_dist_ordered=image, linkage=linkage)
+
+    def clustergram_step_ms(self):
+        """Device milliseconds of the last :meth:`clustergram` by step (HIP events)."""
+        out = np.zeros(5, dtype=np.float64)
+        self._check(self._lib.cnmf_clustergram_step_ms(self._ctx, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return dict(zip(("distances", "cluster_blocks", "linkage_and_order", "ordered_image", "download"), out.tolist()))
+
     def prediction_error(self, W, H):
         """``((X - W @ H)**2).sum()`` over the resident matrix (cnmf.py:926-930)."""
         if self.shape is None:

@@ -39,6 +39,7 @@ extern "C" {
 #define CNMF_HARMONY_DMAX 64   /* most components of cnmf_harmony_begin                                                     */
 #define CNMF_RIDGE_MAX 4096    /* largest K * (B + 1) of cnmf_preprocess_ridge_moments (CNMF_EUNSUPPORTED above)      */
 #define CNMF_PCA_NMAX 8192     /* largest matrix of the tridiagonalisation entry points (CNMF_EUNSUPPORTED above)            */
+#define CNMF_LINKAGE_MAX 4096  /* largest cluster of cnmf_clustergram: 20 bytes of LDS per member (CNMF_EUNSUPPORTED above)        */
 #define CNMF_KMAX 128          /* largest rank of the coordinate-descent / NNLS / consensus entry points
                                   (<= 64: register-resident sweep; 65..128: sweep_big_kernel)              */
 
@@ -574,6 +575,27 @@ int cnmf_consensus_store(cnmf_ctx* ctx, const int64_t* store_rows, int R, int G,
 int cnmf_kselect_stats_store(cnmf_ctx* ctx, int n, const int32_t* ks, const int32_t* R, const int64_t* store_rows,
                              const cnmf_consensus_params* cprm, const double* uniforms, const cnmf_cd_params* prm,
                              double* silhouette_out, double* pred_err_out, double* median_out, int32_t* nnls_iter_out);
+
+/* ---- consensus clustergram (cnmf.py:986-1009, :1028) ------------------------------------------------------------
+ * What consensus(show_clustering=True) draws, without the drawing: the distance matrix of the KEPT spectra (labels[r]
+ * >= 0), reordered so that every k-means cluster is contiguous (ascending label) and its members stand in the leaf order
+ * of an average-linkage dendrogram of the cluster's own distance block.
+ *   spectra [R][G] float64 (host) or store_rows [R] into the resident spectra store -- exactly one of them; the kept rows
+ *   are L2-normalised and their all-pairs distances computed on the device, as cnmf.py:882 / :988 do;
+ *   labels [R]: -1 = filtered out, else the cluster 0..k-1 (a value outside, or a cluster without a member: CNMF_EINVAL);
+ *   order_out [Rk]: indices INTO THE KEPT ROWS (cnmf.py:995-1009), seg_out [k+1]: cluster c is order_out[seg[c]..seg[c+1]);
+ *   Z_out (NULL ok) [Rk - k][4]: the linkage rows (id, id, height, size) of the clusters in label order, m_c - 1 each;
+ *   image_out (NULL ok) [Rk][Rk]: D[order][:, order].
+ * The agglomeration is defined by tests/_upgma_ref.py: the closest live pair merges, ties to the smallest first slot and
+ * then the smallest second; d(a,t) = (n_a d(a,t) + n_b d(b,t)) / (n_a + n_b) rounded four times; entries < 0 count as 0.
+ * With distinct heights this is scipy.cluster.hierarchy.linkage(..., 'average') row for row.  A cluster of more than
+ * CNMF_LINKAGE_MAX members: CNMF_EUNSUPPORTED, before anything is launched.                                        */
+int cnmf_clustergram(cnmf_ctx* ctx, const double* spectra, const int64_t* store_rows, int R, int G,
+                     const int32_t* labels, int k, int32_t* order_out, double* Z_out, int32_t* seg_out,
+                     double* image_out);
+/* device milliseconds of the last cnmf_clustergram by step (HIP events), out[5]: distances of the kept rows | cluster
+ * blocks | agglomeration and leaf order | ordered image | downloads                                                  */
+int cnmf_clustergram_step_ms(const cnmf_ctx* ctx, double* out);
 
 /* ---- consensus tail + k selection on the device ------------------------------------------------------------ */
 /* out[k][G] (float64) = W^T . X, or W^T . zscore(X) with z = (x - mean[g]) * inv_std[g]: the X^T Y accumulation of
