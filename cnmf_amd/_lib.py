@@ -36,6 +36,8 @@ SYMBOLS = [
     "cnmf_preprocess_gene_moments_batched", "cnmf_preprocess_clipped_sums_batched",
     "cnmf_symmetric_tridiagonalize", "cnmf_tridiagonal_back_transform", "cnmf_preprocess_pca_tridiag",
     "cnmf_preprocess_pca_finish",
+    "cnmf_tridiagonal_eigh_top", "cnmf_symmetric_eigh_top", "cnmf_preprocess_pca_device", "cnmf_tridiagonal_fetch",
+    "cnmf_tridiagonal_eigh_step_ms",
     "cnmf_nmf_cd_batch", "cnmf_nmf_cd_batch_resident", "cnmf_get_iteration_means", "cnmf_set_iteration_hints", "cnmf_nnls",
     "cnmf_consensus", "cnmf_pairwise_distances", "cnmf_prediction_error", "cnmf_nmf_mu_batch", "cnmf_mu_refit_f64", "cnmf_mu2_refit_f64", "cnmf_x_matmul",
     "cnmf_xt_matmul_f64", "cnmf_nnls_spectra", "cnmf_nnls_f64", "cnmf_nnls_gram", "cnmf_nnls_batch", "cnmf_kselect_stats",
@@ -56,6 +58,7 @@ CNMF_KMAX = 128
 CNMF_MU_KMAX = 64
 CNMF_RIDGE_MAX = 4096
 CNMF_PCA_NMAX = 8192
+CNMF_NOT_ACCEPTED = 1           # (no error: the device's check of its tridiagonal solve failed; the caller falls back)
 CNMF_LINKAGE_MAX = 4096
 CNMF_HARMONY_KMAX = 128
 CNMF_HARMONY_DMAX = 64
@@ -267,6 +270,16 @@ def load():
     lib.cnmf_preprocess_pca_tridiag.argtypes = [vp, i32, dblp, dblp, dblp]
     lib.cnmf_preprocess_pca_finish.restype = i32
     lib.cnmf_preprocess_pca_finish.argtypes = [vp, i32, i32, dblp, dblp, dblp]
+    lib.cnmf_tridiagonal_eigh_top.restype = i32
+    lib.cnmf_tridiagonal_eigh_top.argtypes = [vp, i64, i32, dblp, dblp, dblp, dblp, dblp]
+    lib.cnmf_symmetric_eigh_top.restype = i32
+    lib.cnmf_symmetric_eigh_top.argtypes = [vp, i64, i32, dblp, dblp, dblp, dblp]
+    lib.cnmf_preprocess_pca_device.restype = i32
+    lib.cnmf_preprocess_pca_device.argtypes = [vp, i32, i32, dblp, dblp, dblp, dblp, dblp]
+    lib.cnmf_tridiagonal_fetch.restype = i32
+    lib.cnmf_tridiagonal_fetch.argtypes = [vp, i64, dblp, dblp]
+    lib.cnmf_tridiagonal_eigh_step_ms.restype = i32
+    lib.cnmf_tridiagonal_eigh_step_ms.argtypes = [vp, dblp]
     lib.cnmf_preprocess_gene_moments_batched.restype = i32
     lib.cnmf_preprocess_gene_moments_batched.argtypes = [vp, i32p, i32, i64p_, i64p_, i32p]
     lib.cnmf_preprocess_clipped_sums_batched.restype = i32

@@ -307,6 +307,7 @@ extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
 #include "prepare_host.hip.h"
 #include "preprocess_host.hip.h"
 #include "pca_host.hip.h"
+#include "tridiag_eig_host.hip.h"
 #include "harmony_host.hip.h"
 #include "harmony_init_host.hip.h"
 #include "filter_host.hip.h"

@@ -204,27 +204,28 @@ static int tri_alloc(cnmf_ctx* ctx, int n)
     if (e == hipSuccess) e = hipMalloc((void**)&P.triR, nn);
     if (e == hipSuccess) e = hipMalloc((void**)&P.tri_tau, (size_t)n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&P.tri_mu, (size_t)n * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&P.tri_d, (size_t)n * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&P.tri_e, (size_t)n * sizeof(double));
     if (e != hipSuccess) P.release_tridiag();
     HIP_TRY(ctx, e);
     P.tri_n = n;
     return CNMF_OK;
 }
 
-// P.triA (filled) -> tridiagonal: the reflectors into P.triR / P.tri_tau, d [n] and e [n - 1] to the host
-static int tri_reduce(cnmf_ctx* ctx, double* d, double* e)
+// P.triA (filled) -> tridiagonal: the reflectors into P.triR / P.tri_tau, d [n] and e [n - 1] into P.tri_d / P.tri_e (they
+// stay staged for tridiag_eig_host.hip.h).  Launches only; p is released when the launches have run
+static int tri_reduce_launch(cnmf_ctx* ctx)
 {
     using namespace cnmf;
     PreStage& P = ctx->pre;
     hipStream_t st = ctx->stream;
     const int n = P.tri_n;
     DevPool pool;
-    double* dd = pool.get<double>(n);
-    double* de = pool.get<double>(std::max(n - 1, 1));
     double* p = pool.get<double>(2 * (size_t)n);
     POOL_TRY(ctx, pool);
     HIP_TRY(ctx, dyn_lds_optin((const void*)tri_column_kernel, TRI_COLUMN_LDS_MAX));
     TriArgs a{};
-    a.n = n; a.A = P.triA; a.R = P.triR; a.tau = P.tri_tau; a.d = dd; a.e = de;
+    a.n = n; a.A = P.triA; a.R = P.triR; a.tau = P.tri_tau; a.d = P.tri_d; a.e = P.tri_e;
     for (int k = 0; k < n; ++k) {
         const int m = n - k;
         a.k = k; a.p_prev = p + (size_t)((k + 1) & 1) * n; a.p_cur = p + (size_t)(k & 1) * n;
@@ -232,24 +233,45 @@ static int tri_reduce(cnmf_ctx* ctx, double* d, double* e)
         tri_column_kernel<<<grid, 256, (2 * (size_t)m + 8) * sizeof(double), st>>>(a);
     }
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(d, dd, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (n > 1) HIP_TRY(ctx, hipMemcpyAsync(e, de, (size_t)(n - 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+    return CNMF_OK;
+}
+
+// the staged d [n] and e [n - 1] to the host
+static int tri_fetch(cnmf_ctx* ctx, double* d, double* e)
+{
+    PreStage& P = ctx->pre;
+    hipStream_t st = ctx->stream;
+    const int n = P.tri_n;
+    HIP_TRY(ctx, hipMemcpyAsync(d, P.tri_d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (n > 1) HIP_TRY(ctx, hipMemcpyAsync(e, P.tri_e, (size_t)(n - 1) * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return CNMF_OK;
 }
 
-// dV [n][n_comp] (device) = the back-transformed columns of the host's Z [n][n_comp]; dZ: device scratch of that size
-static int tri_back(cnmf_ctx* ctx, int n_comp, const double* Z, int sign_rule, double* dZ, double* dV)
+static int tri_reduce(cnmf_ctx* ctx, double* d, double* e)
+{
+    if (int rc = tri_reduce_launch(ctx)) return rc;
+    return tri_fetch(ctx, d, e);
+}
+
+// dV [n][n_comp] (device) = the back-transformed columns of dZ [n][n_comp] (device)
+static int tri_back_launch(cnmf_ctx* ctx, int n_comp, const double* dZ, int sign_rule, double* dV)
 {
     using namespace cnmf;
     PreStage& P = ctx->pre;
-    hipStream_t st = ctx->stream;
     const int n = P.tri_n;
     HIP_TRY(ctx, dyn_lds_optin((const void*)tri_back_kernel, TRI_BACK_LDS_MAX));
-    HIP_TRY(ctx, hipMemcpyAsync(dZ, Z, (size_t)n * n_comp * sizeof(double), hipMemcpyHostToDevice, st));
-    tri_back_kernel<<<n_comp, 256, ((size_t)n + 16) * sizeof(double), st>>>(n, n_comp, P.triR, P.tri_tau, dZ, sign_rule, dV);
+    tri_back_kernel<<<n_comp, 256, ((size_t)n + 16) * sizeof(double), ctx->stream>>>(n, n_comp, P.triR, P.tri_tau, dZ, sign_rule, dV);
     HIP_TRY(ctx, hipGetLastError());
     return CNMF_OK;
+}
+
+// the same for the host's Z [n][n_comp]; dZ: device scratch of that size
+static int tri_back(cnmf_ctx* ctx, int n_comp, const double* Z, int sign_rule, double* dZ, double* dV)
+{
+    PreStage& P = ctx->pre;
+    HIP_TRY(ctx, hipMemcpyAsync(dZ, Z, (size_t)P.tri_n * n_comp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    return tri_back_launch(ctx, n_comp, dZ, sign_rule, dV);
 }
 
 extern "C" int cnmf_symmetric_tridiagonalize(cnmf_ctx* ctx, int64_t n, const double* A, double* d, double* e)

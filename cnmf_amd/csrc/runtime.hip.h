@@ -177,10 +177,11 @@ struct PreStage : CountStage {
     // tau [tri_n] and, for the scatter of a slot (tri_slot; -1: a host-supplied matrix), that slot's column means;
     // replaced by the next tridiagonalisation; triR = NULL: none
     double *triA = nullptr, *triR = nullptr, *tri_tau = nullptr, *tri_mu = nullptr;
+    double *tri_d = nullptr, *tri_e = nullptr;       // the tridiagonal form itself [tri_n] (tridiag_eig_host.hip.h reads it)
     int tri_n = 0, tri_slot = -1;
     void release_tridiag() {
-        hipFree(triA); hipFree(triR); hipFree(tri_tau); hipFree(tri_mu);
-        triA = triR = tri_tau = tri_mu = nullptr; tri_n = 0; tri_slot = -1;
+        hipFree(triA); hipFree(triR); hipFree(tri_tau); hipFree(tri_mu); hipFree(tri_d); hipFree(tri_e);
+        triA = triR = tri_tau = tri_mu = tri_d = tri_e = nullptr; tri_n = 0; tri_slot = -1;
     }
     void release() {
         release_counts(); release_ridge(); release_grouped(); release_tridiag();
@@ -320,6 +321,7 @@ struct cnmf_ctx {
     void* cons_pinned = nullptr;      // pinned host block of the consensus calls (k-means state read-backs)
     size_t cons_pinned_bytes = 0;
     double clustergram_ms[5] = {0, 0, 0, 0, 0};   // steps of the last cnmf_clustergram (linkage_host.hip.h)
+    double teig_ms[5] = {0, 0, 0, 0, 0};          // steps of the last device tridiagonal solve (tridiag_eig_host.hip.h)
 
     cnmf_comm* comm = nullptr;        // RCCL communicator (comm_host.hip.h); NULL = single GPU
 

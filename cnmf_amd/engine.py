@@ -487,17 +487,106 @@ class Engine:
                                                               int(bool(sign_rule)), V.ctypes.data_as(dblp)))
         return V
 
-    def symmetric_eigh_top(self, A, k):
+    def symmetric_eigh_top(self, A, k, solver="host"):
         """The ``k`` largest eigenvalues of the symmetric matrix ``A`` (descending) and their eigenvectors [n][k] (the
         sign rule applied): tridiagonalisation on the device, the tridiagonal problem on the host
-        (``preprocess.tridiagonal_top``), back-transformation on the device."""
+        (``preprocess.tridiagonal_top``; ``solver="host"``, the default) or on the device as well (``solver="device"``:
+        one library call, see :meth:`tridiagonal_eigh_top`; a result its check does not accept is replaced through the
+        host solve, and ``last_tridiagonal_solver`` says which of the two it was), back-transformation on the device."""
         from .preprocess import tridiagonal_top
+        if solver not in ("host", "device"):
+            raise ValueError("solver must be \"host\" or \"device\", not %r" % (solver,))
         n = int(np.shape(A)[0]) if np.ndim(A) == 2 else 0
         if not 1 <= int(k) <= max(n, 1):
             raise ValueError("k = %s outside [1, %d]" % (k, n))
-        d, e = self.symmetric_tridiagonalize(A)
-        w, Z = tridiagonal_top(d, e, int(k))
-        return w, self.tridiagonal_back_transform(Z, sign_rule=True)
+        if solver == "host":
+            d, e = self.symmetric_tridiagonalize(A)
+            w, Z = tridiagonal_top(d, e, int(k))
+            return w, self.tridiagonal_back_transform(Z, sign_rule=True)
+        if np.ndim(A) != 2 or np.shape(A)[0] != np.shape(A)[1]:
+            raise ValueError("a square matrix is expected, not shape %s" % (np.shape(A),))
+        self.pca_check_limit(n)
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        w, V, info = np.empty(int(k)), np.empty((n, int(k))), np.empty(4)
+        dblp = C.POINTER(C.c_double)
+        rc = self._lib.cnmf_symmetric_eigh_top(self._ctx, n, int(k), A.ctypes.data_as(dblp), w.ctypes.data_as(dblp),
+                                               V.ctypes.data_as(dblp), info.ctypes.data_as(dblp))
+        if not self._tridiagonal_accepted(rc, info):
+            w, Z = tridiagonal_top(*self.tridiagonal_fetch(n), int(k))
+            V = self.tridiagonal_back_transform(Z, sign_rule=True)
+        return w, V
+
+    # The tridiagonal problem on the device (tridiag_eig_host.hip.h).  last_tridiagonal_solver: "device", or
+    # "host_fallback" when the device's own check of its result (residual within 2 n eps |T|_1, orthogonality within
+    # 2 n eps, every entry finite) did not accept it; last_tridiagonal_check: the measured (residual / u_T,
+    # |rayleigh quotient - w| / u_T, orthogonality / (n eps)).
+    last_tridiagonal_solver = None
+    last_tridiagonal_check = None
+
+    def _tridiagonal_accepted(self, rc, info):
+        if rc != _lib.CNMF_NOT_ACCEPTED:
+            self._check(rc)
+        ok = rc == 0 and info[0] == 1.0
+        self.last_tridiagonal_solver = "device" if ok else "host_fallback"
+        self.last_tridiagonal_check = tuple(float(x) for x in info[1:4])
+        return ok
+
+    def tridiagonal_eigh_top(self, d, e, k):
+        """The ``k`` largest eigenpairs of the symmetric tridiagonal matrix with diagonal ``d`` [n] and off-diagonal ``e``
+        [n - 1], on the device: multisection on Sturm counts (the eigenvalues are those of the float64 restatement in
+        tests/_tridiag_eig_ref.py, bit for bit), three steps of inverse iteration per vector, CGS2, and a check of the
+        result.  Returns ``(w [k] descending, Z [n][k], accepted)``; ``accepted`` False: ``w`` is valid and ``Z`` is not
+        (inverse iteration without orthogonalisation inside fails on some large tight clusters) -- take
+        ``preprocess.tridiagonal_top`` then.  ValueError on non-finite input or ``k`` outside [1, n]."""
+        d = np.ascontiguousarray(d, dtype=np.float64)
+        e = np.ascontiguousarray(e, dtype=np.float64)
+        n = d.size
+        if d.ndim != 1 or n < 1 or e.shape != (n - 1,):
+            raise ValueError("d [n] and e [n - 1] are expected, not shapes %s and %s" % (d.shape, e.shape))
+        if not 1 <= int(k) <= n:
+            raise ValueError("k = %s outside [1, %d]" % (k, n))
+        self.pca_check_limit(n)
+        e1 = e if n > 1 else np.zeros(1)
+        w, Z, info = np.empty(int(k)), np.empty((n, int(k))), np.empty(4)
+        dblp = C.POINTER(C.c_double)
+        rc = self._lib.cnmf_tridiagonal_eigh_top(self._ctx, n, int(k), d.ctypes.data_as(dblp), e1.ctypes.data_as(dblp),
+                                                 w.ctypes.data_as(dblp), Z.ctypes.data_as(dblp), info.ctypes.data_as(dblp))
+        return w, Z, self._tridiagonal_accepted(rc, info)
+
+    def tridiagonal_fetch(self, n):
+        """``(d [n], e [n - 1])`` of the staged tridiagonalisation"""
+        d, e = np.empty(n), np.empty(max(n - 1, 1))
+        dblp = C.POINTER(C.c_double)
+        self._check(self._lib.cnmf_tridiagonal_fetch(self._ctx, int(n), d.ctypes.data_as(dblp), e.ctypes.data_as(dblp)))
+        return d, e[:n - 1]
+
+    def tridiagonal_eigh_step_ms(self):
+        """HIP-event milliseconds of the last device tridiagonal solve: bounds, bisection, inverse iteration,
+        orthogonalisation plus check and (after :meth:`preprocess_pca_device`) back-transformation plus scores"""
+        out = np.zeros(5)
+        self._check(self._lib.cnmf_tridiagonal_eigh_step_ms(self._ctx, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def preprocess_pca_device(self, slot, n_comps):
+        """The PCA of a dense slot in one library call: the scatter matrix, its tridiagonalisation, the tridiagonal
+        eigenproblem (:meth:`tridiagonal_eigh_top`), back-transformation, sign rule and scores on the device; only the
+        results cross the bus and the slot is left as it was.  Returns ``(mean [n], w [n_comps] (eigenvalues of the scatter
+        matrix, descending), V [n][n_comps], scores [n_cells][n_comps])``.  A solve the device's check does not accept is
+        redone by ``preprocess.tridiagonal_top`` on the host (``last_tridiagonal_solver == "host_fallback"``)."""
+        n = self._pre[int(slot)][0]
+        self.pca_check_limit(n)
+        k = int(n_comps)
+        if not 1 <= k <= n:
+            raise ValueError("n_comps = %s outside [1, %d]" % (n_comps, n))
+        mean, w, V, scores, info = np.empty(n), np.empty(k), np.empty((n, k)), np.empty((self._pre["N"], k)), np.empty(4)
+        dblp = C.POINTER(C.c_double)
+        rc = self._lib.cnmf_preprocess_pca_device(self._ctx, int(slot), k, mean.ctypes.data_as(dblp), w.ctypes.data_as(dblp),
+                                                  V.ctypes.data_as(dblp), scores.ctypes.data_as(dblp), info.ctypes.data_as(dblp))
+        if not self._tridiagonal_accepted(rc, info):
+            from .preprocess import tridiagonal_top
+            w, Z = tridiagonal_top(*self.tridiagonal_fetch(n), k)
+            V, scores = self.preprocess_pca_finish(slot, Z)
+        return mean, w, V, scores
 
     def preprocess_pca_tridiag(self, slot):
         """The scatter matrix of a dense slot (as :meth:`preprocess_scatter` forms it), tridiagonalised where it is:

@@ -19,7 +19,14 @@ defaults and error texts; every O(N G) step runs on the device (csrc/preprocess_
   never uploaded.  At most 8192 genes (``NotImplementedError`` above).  **The yardstick is the float64 numpy restatement
   in tests/_tridiag_ref.py** and gap-free contracts against ``np.linalg.eigh`` (residual and eigenvalues within
   8 n eps |A|_inf, orthogonality within 8 n eps); the loadings of the two routes agree only as far as the eigenvalue
-  gaps allow.  **Agreement with scanpy's own ``sc.pp.pca`` solver is unmeasured on this project's machines**, for both
+  gaps allow.  ``pca="device_full"`` (named as ``harmony="device_full"`` is) solves the tridiagonal problem on the
+  device as well (csrc/tridiag_eig_host.hip.h, ``Engine.preprocess_pca_device``: one library call, only the means, the
+  loadings and the scores cross the bus): multisection on Sturm counts, three steps of inverse iteration per vector,
+  CGS2; the float64 restatement is tests/_tridiag_eig_ref.py, and the eigenvalues are its bits.  The device checks its
+  own result (residual within 2 n eps |T|_1, orthogonality within 2 n eps, all finite), because inverse iteration
+  without orthogonalisation inside fails on some large tight clusters; a result that is not accepted is redone by
+  ``tridiagonal_top`` (scipy is imported only then), and ``Engine.last_tridiagonal_solver`` says which of the two
+  ran.  **Agreement with scanpy's own ``sc.pp.pca`` solver is unmeasured on this project's machines**, for all
   routes;
 * Harmony's mixture-of-experts ridge correction: every cluster's ``W_k`` is formed from the uncorrected X (as in the
   reference), so the moments ``M_k = (R_k Phi) X`` and ``Gram_k = (R_k Phi) Phi^T`` of all K clusters come from one
@@ -271,7 +278,7 @@ def _ceiling(eng, slot, n_rows, n_cols, quantile_thresh):
     return thresh
 
 
-PCA_MODES = ("lapack", "device")
+PCA_MODES = ("lapack", "device", "device_full")
 PCA_NMAX = 8192                     # (include/cnmf_hip.h: CNMF_PCA_NMAX)
 
 
@@ -306,8 +313,8 @@ def _pca_components(n_rows, n_cols):
 
 
 def _check_pca_size(pca, n_cols):
-    if pca == "device" and n_cols > PCA_NMAX:
-        raise NotImplementedError("pca=\"device\" takes at most %d genes, not %d: use pca=\"lapack\"" % (PCA_NMAX, n_cols))
+    if pca in ("device", "device_full") and n_cols > PCA_NMAX:
+        raise NotImplementedError("pca=\"%s\" takes at most %d genes, not %d: use pca=\"lapack\"" % (pca, PCA_NMAX, n_cols))
 
 
 def _pca(eng, slot, n_rows, n_cols, n_comps=None, pca="lapack"):
@@ -319,6 +326,9 @@ def _pca(eng, slot, n_rows, n_cols, n_comps=None, pca="lapack"):
         _, d, e = eng.preprocess_pca_tridiag(slot)
         _, Z = tridiagonal_top(d, e, n_comps)
         return eng.preprocess_pca_finish(slot, Z)[1]
+    if pca == "device_full":                             # (scipy is imported on the fallback alone)
+        _check_pca_size(pca, n_cols)
+        return eng.preprocess_pca_device(slot, n_comps)[3]
     mean, scatter = eng.preprocess_scatter(slot)
     w, V = np.linalg.eigh(scatter / (n_rows - 1))
     order = np.argsort(-w, kind="stable")[:n_comps]
@@ -913,7 +923,9 @@ class Preprocess:
         ``pca``: who solves the PCA's eigenproblem in the Harmony branch: "lapack" (the default: the gene covariance is
         fetched and ``np.linalg.eigh`` finds all its eigenpairs on the host) or "device" (Householder tridiagonalisation
         on the device, the tridiagonal problem for the kept components on the host, back-transformation and scores on
-        the device; at most 8192 selected genes, NotImplementedError above).  Anything else raises ValueError."""
+        the device; at most 8192 selected genes, NotImplementedError above) or "device_full" (the tridiagonal problem
+        on the device too, with the host solve as the fallback for a result the device's check does not accept; the same
+        limit).  Anything else raises ValueError."""
         _check_pca_mode(pca)
         _check_hvg_mode(hvg)
         _check_hvg_batch_key(hvg_batch_key, hvg == "device" and n_top_genes is not None, obs)
@@ -1115,8 +1127,8 @@ class Preprocess:
         ``exclude_genes`` went, as the reference does: an excluded gene or an ADT feature is never selected, and the
         selection replaces ``highly_variable``.  The frame of the selected genes is ``result_rna.var``.
         ``hvg_batch_key`` (a column of ``obs``) makes that selection per batch, as in normalize_batchcorrect; given
-        without ``hvg="device"`` and a number it raises ValueError.  ``pca``: "lapack" (the default) or "device", as in
-        normalize_batchcorrect.
+        without ``hvg="device"`` and a number it raises ValueError.  ``pca``: "lapack" (the default), "device" or
+        "device_full", as in normalize_batchcorrect.
 
         The RNA counts are uploaded once: ``tp10k`` comes from them over all RNA genes before ``exclude_genes`` are taken
         out (on the device), then normalize_batchcorrect's body runs on the same staging.

@@ -327,6 +327,38 @@ int cnmf_preprocess_pca_tridiag(cnmf_ctx* ctx, int32_t slot, double* mean /* [n]
 int cnmf_preprocess_pca_finish(cnmf_ctx* ctx, int32_t slot, int32_t n_comp, const double* Z /* [n][n_comp] */,
                                double* V /* [n][n_comp] */, double* scores /* [n_cells][n_comp] */);
 
+/* ---- the tridiagonal eigenproblem on the device as well (tridiag_eig_host.hip.h) ------------------------------------------
+ * The n_comp largest eigenpairs of tridiag(e, d, e): multisection on Sturm counts (a wavefront per eigenvalue), inverse
+ * iteration (a lane per vector, three iterations), CGS2, and a check of the result on the device; the algorithm is stated
+ * in tests/_tridiag_eig_ref.py.  info [4] = {accepted, max |T Z - Z diag(w)| / u_T, max_j |z_j^T T z_j - w_j| / u_T,
+ * max |Z^T Z - I| / (n eps)} with u_T = n eps |T|_1; accepted = 1 iff every entry is finite, the residual is within
+ * 2 u_T and the orthogonality within 2 n eps, else 0: inverse iteration without orthogonalisation inside fails on some
+ * large tight clusters, and then w is valid and the vectors are not.  n > CNMF_PCA_NMAX: CNMF_EUNSUPPORTED before
+ * anything is allocated; n_comp outside [1, n] or non-finite d / e (a non-finite A produces them): CNMF_EINVAL.  The
+ * orthogonalisation is O(n n_comp^2) on one compute unit: meant for n_comp << n.
+ *   cnmf_tridiagonal_eigh_top      the solver alone on a host (d, e): w [n_comp] descending, Z [n][n_comp], CNMF_OK
+ *                                  whether accepted or not (info [0]).
+ *   cnmf_symmetric_eigh_top        upload, tridiagonalise, solve, back-transform with the sign rule: w, V [n][n_comp].
+ *   cnmf_preprocess_pca_device     the PCA of a dense slot (left as it was): mean [n] (the bits of cnmf_preprocess_scatter),
+ *                                  w (of the scatter matrix), V, scores [n_cells][n_comp] = (X - mean) V.
+ *                                  Both return CNMF_NOT_ACCEPTED (no error: w is written, V and scores are not) when the
+ *                                  check fails, with the staging as cnmf_symmetric_tridiagonalize / cnmf_preprocess_pca_tridiag
+ *                                  leave it: fetch (d, e) with cnmf_tridiagonal_fetch, solve on the host, and finish
+ *                                  through cnmf_tridiagonal_back_transform / cnmf_preprocess_pca_finish.
+ *   cnmf_tridiagonal_fetch         d [n], e [n - 1] of the staged tridiagonalisation (none, or another n: CNMF_EINVAL).
+ *   cnmf_tridiagonal_eigh_step_ms  out [5]: milliseconds (HIP events) of the last solve's bounds, bisection, inverse
+ *                                  iteration and orthogonalisation-plus-check launches and, after
+ *                                  cnmf_preprocess_pca_device, of its back-transformation plus scores (else 0).          */
+#define CNMF_NOT_ACCEPTED 1
+int cnmf_tridiagonal_eigh_top(cnmf_ctx* ctx, int64_t n, int32_t n_comp, const double* d /* [n] */, const double* e /* [n-1] */,
+                              double* w /* [n_comp] */, double* Z /* [n][n_comp] */, double* info /* [4] */);
+int cnmf_symmetric_eigh_top(cnmf_ctx* ctx, int64_t n, int32_t n_comp, const double* A /* [n][n] */, double* w /* [n_comp] */,
+                            double* V /* [n][n_comp] */, double* info /* [4] */);
+int cnmf_preprocess_pca_device(cnmf_ctx* ctx, int32_t slot, int32_t n_comp, double* mean /* [n] */, double* w /* [n_comp] */,
+                               double* V /* [n][n_comp] */, double* scores /* [n_cells][n_comp] */, double* info /* [4] */);
+int cnmf_tridiagonal_fetch(cnmf_ctx* ctx, int64_t n, double* d /* [n] */, double* e /* [n-1] */);
+int cnmf_tridiagonal_eigh_step_ms(const cnmf_ctx* ctx, double* out /* [5] */);
+
 /* ---- Harmony's clustering loop (harmony_host.hip.h) -----------------------------------------------------------------
  * The loop of harmonypy's run_harmony over N cells, d components, K clusters and n_vars batch variables with n_levels
  * levels in all (B): float64, state of its own in the context, fixed summation orders, no float atomics -- two runs give

@@ -27,14 +27,18 @@ about 6.7 % non-zero, 2 000 genes selected): the whole call with both loess surf
 --repeats), its three device steps on their own (the integer moments, the local fits at the vertices and at every gene,
 the clipped sums), and the numpy restatement tests/_seurat_v3_ref.py on this machine's cores.
 
-``--pca`` times the PCA of the Harmony branch both ways on one staged slot of --cells x --genes (the normalised,
+``--pca`` times the PCA of the Harmony branch three ways on one staged slot of --cells x --genes (the normalised,
 scaled and ceilinged counts of the default leg), the median of --repeats, every step between two synchronising calls:
 ``pca="device"`` (scatter + Householder tridiagonalisation on the device; ``tridiagonal_top`` on the host;
-back-transformation + sign rule + scores on the device) and ``pca="lapack"`` (scatter + fetch; ``np.linalg.eigh`` on
-this machine's cores; upload + scores), the contracts of tests/_tridiag_ref.py for the device's eigenpairs at that size,
-and writes profiles/preprocess_probe_pca_<N>x<G>.json unless --out says otherwise.
+back-transformation + sign rule + scores on the device), ``pca="device_full"`` (``preprocess_pca_device``: one call,
+its device steps -- bounds, bisection, inverse iteration, orthogonalisation + check, back-transformation + scores -- by
+HIP events; the same (d, e) through ``tridiagonal_eigh_top`` and ``tridiagonal_top`` alone beside it) and
+``pca="lapack"`` (scatter + fetch; ``np.linalg.eigh`` on this machine's cores; upload + scores), the contracts of
+tests/_tridiag_ref.py for the device's eigenpairs at that size, and writes
+profiles/preprocess_probe_pca_full_<N>x<G>.json unless --out says otherwise (profiles/preprocess_probe_pca_<N>x<G>.json
+is the two-arm run from before the third arm).
 
-Usage:  python tools/preprocess_probe.py --pca [--cells 50000] [--genes 2000] [--repeats 3] [--out FILE.json]
+Usage:  python tools/preprocess_probe.py --pca [--cells 50000] [--genes 2000] --repeats 5 [--out FILE.json]
         python tools/preprocess_probe.py [--cells 50000] [--genes 2000] [--K 100] [--batches 4] [--out FILE.json]
         python tools/preprocess_probe.py --filter [--filter-cells 50000] [--filter-genes 20000] [--out FILE.json]
         python tools/preprocess_probe.py --harmony [--cells 50000] [--components 50] [--K 100] [--batches 4] [--out FILE.json]
@@ -345,10 +349,15 @@ def pca_leg(a):
     n_comps = pp._pca_components(N, G)
     steps = {"device": {"scatter_and_tridiagonalise_ms": [], "host_tridiagonal_solve_ms": [],
                         "back_transform_and_scores_ms": []},
+             "device_full": {"one_call_ms": []},
              "lapack": {"scatter_and_fetch_ms": [], "host_eigh_ms": [], "upload_and_project_ms": []}}
+    events = {k: [] for k in ("bounds_ms", "bisection_ms", "inverse_iteration_ms", "orthogonalisation_and_check_ms",
+                              "back_transform_and_scores_ms")}
+    solver_alone = {"device_tridiagonal_eigh_top_ms": [], "host_tridiagonal_top_ms": []}
     free = []
     with Engine(0) as eng:
-        eng.symmetric_eigh_top(np.eye(8), 2)                         # warm-up (code objects)
+        eng.symmetric_eigh_top(np.eye(8), 2)                         # warm-up (code objects), both solvers
+        eng.symmetric_eigh_top(np.eye(8) + np.diag(np.ones(7), 1) + np.diag(np.ones(7), -1), 2, solver="device")
         eng.preprocess_upload(C)
         eng.preprocess_select(0, np.arange(G), 1e4, None)
         pp._ceiling(eng, 0, N, G, .9999)
@@ -364,6 +373,21 @@ def pca_leg(a):
             t3 = time.perf_counter()
             for k, v in zip(steps["device"], (t1 - t0, t2 - t1, t3 - t2)):
                 steps["device"][k].append(1e3 * v)
+            # pca="device_full": one library call; its device steps by HIP events
+            t0 = time.perf_counter()
+            mean_f, w_f, Vf, scores_f = eng.preprocess_pca_device(0, n_comps)
+            steps["device_full"]["one_call_ms"].append(1e3 * (time.perf_counter() - t0))
+            solver_used, check_f = eng.last_tridiagonal_solver, eng.last_tridiagonal_check
+            for k, v in zip(events, eng.tridiagonal_eigh_step_ms()):
+                events[k].append(float(v))
+            # the same (d, e) through both solvers alone (the device one with its transfers of d, e, w and Z)
+            t0 = time.perf_counter()
+            eng.tridiagonal_eigh_top(d, e, n_comps)
+            t1 = time.perf_counter()
+            pp.tridiagonal_top(d, e, n_comps)
+            t2 = time.perf_counter()
+            solver_alone["device_tridiagonal_eigh_top_ms"].append(1e3 * (t1 - t0))
+            solver_alone["host_tridiagonal_top_ms"].append(1e3 * (t2 - t1))
             t0 = time.perf_counter()
             mean_l, S = eng.preprocess_scatter(0)
             t1 = time.perf_counter()
@@ -388,9 +412,19 @@ def pca_leg(a):
         out[route + "_all_ms"] = {k: [round(x, 3) for x in v] for k, v in r.items()}
     out["upload_and_tridiagonalise_host_matrix_ms"] = round(float(np.median(free)), 3)
     out["lapack_over_device"] = round(out["lapack"]["total_ms"] / out["device"]["total_ms"], 2)
+    out["device_full_over_device"] = round(out["device_full"]["total_ms"] / out["device"]["total_ms"], 3)
+    out["device_full_event_ms"] = {k: round(float(np.median(v)), 3) for k, v in events.items()}
+    out["tridiagonal_solver_alone"] = {k: round(float(np.median(v)), 3) for k, v in solver_alone.items()}
+    out["device_full_solver"] = solver_used
+    out["device_full_check"] = {"residual_over_uT": check_f[0], "rayleigh_over_uT": check_f[1],
+                                "orthogonality_over_n_eps": check_f[2]}
     res, eig, orth, desc = ref.contracts(S, w, Vd)
     out["device_contracts"] = {"residual_over_u": float(res), "eigenvalues_over_u": float(eig),
                                "orthogonality_over_n_eps": float(orth), "descending": desc}
+    res, eig, orth, desc = ref.contracts(S, w_f, Vf)
+    out["device_full_contracts"] = {"residual_over_u": float(res), "eigenvalues_over_u": float(eig),
+                                    "orthogonality_over_n_eps": float(orth), "descending": desc}
+    out["max_abs_diff_scores_full_over_max_abs"] = float(np.abs(scores_f - scores_l).max() / np.abs(scores_l).max())
     out["max_abs_diff_scores_over_max_abs"] = float(np.abs(scores_d - scores_l).max() / np.abs(scores_l).max())
     out["relative_gap_of_the_last_kept_component"] = float((lam[-n_comps] - lam[-n_comps - 1]) / lam[-1])
     return out
@@ -414,7 +448,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.pca and not a.out:
-        a.out = os.path.join(ROOT, "profiles", "preprocess_probe_pca_%dx%d.json" % (a.cells, a.genes))
+        a.out = os.path.join(ROOT, "profiles", "preprocess_probe_pca_full_%dx%d.json" % (a.cells, a.genes))
     if a.pca or a.filter or a.harmony or a.hvg:
         out = pca_leg(a) if a.pca else filter_leg(a) if a.filter else harmony_leg(a) if a.harmony else hvg_leg(a)
         print(json.dumps(out, indent=1))
