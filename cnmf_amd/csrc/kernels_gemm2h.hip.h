@@ -23,6 +23,9 @@
 //   counts : 32 B per row and block = two slots, stored at  hf ^ ((row >> 3) & 1)  (same argument).
 // The kernel body is gemm3c's (256 x 256 tile, 8 waves in two groups half a block apart, 4 LDS-DMA images, counted
 // vmcnt, raw barriers) with NSUB 16-k sub-blocks per barrier pair: NSUB = 2 halves the number of barriers per flop.
+// NSUB = 1 (second count plane, general matrices) multiplies with v_mfma_f32_32x32x16_f16, one MFMA per 16-k block;
+// NSUB = 2 (the production count path) with v_mfma_f32_16x16x32_f16, one MFMA per 32-k step (gemm2h_segment_mf16): the
+// same flops per cycle, and the clock the chip holds under this load is higher with the smaller shape.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels_gemm3.hip.h"
@@ -417,14 +420,12 @@ __global__ __launch_bounds__(256) void count_max_base_kernel(const float* __rest
 //   Bhi / hiflag : second count plane and its per-(tile, block) flags (nullptr: none),
 //   rscale : 2^-s_c per component row, applied to the stored product.
 // Timeline exactly as gemm3c_segment, in units of "steps" of NSUB blocks.
-// VAR (A/B knobs of the instruction stream; NSUB = 2 without a second count plane only):
-//   bit 0: the six LDS-DMA pieces of a step are spread through the MFMA stream (one after every 4th MFMA of the step's
-//          first 24) instead of issued in one burst behind the X barrier -- a burst of DMA issues in front of 20
-//          ds_read_b128 is the expensive place for them (MI355X_MICROARCH.md, "LDS-DMA piece issue cost");
-//   VAR 4 (production): that stream with the fragment reads in two batches (see G2_READ_A / G2_READ_B);
-//   VAR 2 / 3 (timing ablations, results meaningless): the spread stream WITHOUT its MFMAs (fill + fragment reads
-//          only) / WITHOUT its steady-state DMA (MFMAs + fragment reads on stale images).  s_setprio around the MFMA
-//          halves was tried and is neutral (profiles/r2_probe_gemm2h_variants.txt).
+// NSUB = 2 (one count plane) is gemm2h_segment_mf16 above; this body multiplies the NSUB = 1 instantiations.
+// VAR (the instruction stream): 0 = the six (NSUB = 1: three or four) LDS-DMA pieces of a step in one burst behind the X
+//   barrier; 4 (production) = the pieces spread through the MFMA stream and the fragment reads in two counted batches -- a
+//   burst of DMA issues in front of 20 ds_read_b128 is the expensive place for them (MI355X_MICROARCH.md, "LDS-DMA piece
+//   issue cost"); 2 / 3 / 6 / 7 (NSUB = 2 only): timing ablations.  s_setprio around the MFMA halves was tried and is
+//   neutral (profiles/r2_probe_gemm2h_variants.txt).
 // NTB: the count plane is loaded non-temporally (every tile is read by ONE workgroup per pass: 256 packed columns, or pass B
 // with its XCD-aware order); with several component groups in pass A the workgroups p, p + P / MG stream the SAME tile at
 // the same time and must find it in their L2: default cache policy (PMC, 1024 columns: 607 -> see profiles/r3_pmc_*).
@@ -439,6 +440,170 @@ __global__ __launch_bounds__(256) void count_max_base_kernel(const float* __rest
 // EPI (round 4): what happens to a WHOLE tile's accumulators instead of the plain store -- the W half-step of the tile's
 // restarts run by the pass-A workgroup itself (kernels_fusedw.hip.h); G2NoEpi: the store below.
 struct G2NoEpi { static constexpr bool enabled = false; };
+
+// ---- NSUB = 2 with ONE count plane (the production count path, counts <= 2048): the same segment on
+// v_mfma_f32_16x16x32_f16.  Images, DMA pieces, barriers and the vmcnt accounting are those of gemm2h_segment below; only
+// the fragments and the MFMA differ.  One 32-k step holds the 16-k blocks u = 0, 1 in one image and one MFMA consumes
+// both: lane (r = lane & 15, g = lane >> 4) holds the eight k  8 g .. 8 g + 7  of the step, that is block u = g >> 1,
+// 8-k half hf = g & 1, of factor row  mt * 16 + r  (mt = 0..7: the wave's 128 rows) and of count row  nt * 16 + r
+// (nt = 0..3: its 64 columns).  The plane swizzles stay conflict-free: the sixteen rows of a lane group with one logical
+// slot c hit the 16-byte bank groups (row % 4) * 4 + (c ^ ((row >> 2) & 3)) of the factor image and
+// (row % 8) * 2 + (hf ^ ((row >> 3) & 1)) of the count image -- sixteen distinct ones each.
+// Per step and wave: 16 + 4 ds_read_b128 (80 fragment registers), 64 MFMAs on acc[8][4] (128 registers); per accumulator
+// the small plane m first, then h.  Element i of acc[mt][nt] is component row mt * 16 + 4 g + i, column nt * 16 + r.
+// VAR: 4 = production (pieces spread through the MFMA stream, fragment reads in two counted batches: 12 + 8), 0 = the
+// same stream with the six pieces in one burst behind the X barrier; 2 / 3 / 6 / 7: the timing ablations (no MFMAs / no
+// steady-state DMA / fragments read once / ... and no barriers; results meaningless).
+template <int VAR, bool NTB, bool PART>
+__device__ __forceinline__ void gemm2h_segment_mf16(const unsigned char* __restrict__ A2, const unsigned char* __restrict__ B1,
+                                                    const float* __restrict__ rscale, int Kb, float* __restrict__ C,
+                                                    int ldc, int m0, int j0, int kb0, int nkb, unsigned char* smem,
+                                                    unsigned live)
+{
+    static_assert(VAR == 0 || VAR == 2 || VAR == 3 || VAR == 4 || VAR == 6 || VAR == 7, "instruction streams 1 and 5 were retired");
+    constexpr int NSUB = 2, IMGS = g2_imgs(NSUB), IMG = g2_img_bytes(NSUB, false);
+    constexpr int OFF_B = NSUB * G2_A;                   // image: [A block 0][A block 1][B block 0][B block 1]
+    constexpr int NA = NSUB * 2, NB = NSUB, AHEAD = IMGS - 1;
+    constexpr bool BURST = VAR == 0, NOMFMA = VAR == 2, NODMA = VAR == 3 || VAR == 6 || VAR == 7;
+    constexpr bool NOREAD = VAR == 6 || VAR == 7, NOBAR = VAR == 7;
+    static_assert(IMGS == 3 && NA + NB == 6, "three images, six pieces per step");
+    const int tid = threadIdx.x;                         // 0..511
+    const int lane = tid & 63, wave = tid >> 6;
+    const int grp = wave >> 2, wn = wave & 3;
+    const int r = lane & 15, g = lane >> 4;
+    const int ub = g >> 1, hf = g & 1;
+    const int nst = nkb / NSUB;                          // steps in this segment
+    // bit m of the live mask = the wave's rows 32 m .. 32 m + 31 = its 16-row tiles 2 m and 2 m + 1
+    const unsigned lv = PART ? (unsigned)__builtin_amdgcn_readfirstlane((int)((live >> (grp * 4)) & 0xfu)) : 0xfu;
+#define G2_LIVE(mt_) (!PART || ((lv >> ((mt_) >> 1)) & 1u))
+
+    const unsigned char* abase = A2 + ((size_t)(m0 / G3_MW) * Kb + kb0) * G2_A + tid * 16;
+    const unsigned char* bbase = B1 + ((size_t)(j0 / G3C_JW) * Kb + kb0) * G2_B + tid * 16;
+
+    f32x4_g acc[8][4];
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[mt][nt][i] = 0.f;
+
+    // fragment addresses inside an image (tile mt / nt: + mt * 16 rows of 64 B / + nt * 16 rows of 32 B)
+    const int a_row = ub * G2_A + (grp * 128 + r) * G2_ROWB;
+    const int a_s0 = ((0 + hf) ^ ((r >> 2) & 3)) * 16, a_s1 = ((2 + hf) ^ ((r >> 2) & 3)) * 16;
+    const int b_off = OFF_B + ub * G2_B + (wn * 64 + r) * 32 + (hf ^ ((r >> 3) & 1)) * 16;
+
+#define G2_PIECE(s_, i_)                                                                           \
+    {                                                                                              \
+        unsigned char* d_ = smem + ((s_) % IMGS) * IMG + wave * 1024;                              \
+        if ((i_) < NA)                                                                             \
+            __builtin_amdgcn_global_load_lds(G3_AS1(abase + (size_t)(s_) * (NSUB * G2_A) + (i_) * 8192), \
+                                             G3_AS3(d_ + (i_) * 8192), 16, 0, 0);                  \
+        else   /* the count plane is read once per pass: non-temporal */                           \
+            __builtin_amdgcn_global_load_lds(G3_AS1(bbase + (size_t)(s_) * (NSUB * G2_B) + ((i_) - NA) * 8192), \
+                                             G3_AS3(d_ + OFF_B + ((i_) - NA) * 8192), 16, 0, NTB ? 2 : 0); \
+        __builtin_amdgcn_sched_barrier(0);                                                         \
+    }
+#define G2_ISSUE(s_) { _Pragma("unroll") for (int i = 0; i < NA + NB; ++i) G2_PIECE(s_, i) }
+#define G2_FRAG(ptr_) __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(ptr_))
+#define G2_AFRAG(bb_, mt_, q_) G2_FRAG((bb_) + a_row + (mt_) * 16 * G2_ROWB + ((q_) ? a_s1 : a_s0))
+// fragment reads in two batches: the 12 the first half of the step needs, then -- behind its first 16 MFMAs -- the 8 of the
+// second half: at most 12 LDS reads are outstanding, so the waits in front of the MFMAs can be counted (lgkmcnt is a
+// 4-bit counter: behind 20 reads the compiler can only wait for all of them)
+#define G2_READ_A(s_)                                                                              \
+    {                                                                                              \
+        const unsigned char* bb = smem + ((s_) % IMGS) * IMG;                                      \
+        _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) bq[nt] = G2_FRAG(bb + b_off + nt * 16 * 32); \
+        _Pragma("unroll") for (int mp = 0; mp < 4; mp += 2) {                                      \
+            aq[mp][1] = G2_AFRAG(bb, mp, 1); aq[mp + 1][1] = G2_AFRAG(bb, mp + 1, 1);              \
+            aq[mp][0] = G2_AFRAG(bb, mp, 0); aq[mp + 1][0] = G2_AFRAG(bb, mp + 1, 0);              \
+        }                                                                                          \
+        __builtin_amdgcn_sched_barrier(0);                                                         \
+    }
+#define G2_READ_B(s_)                                                                              \
+    {                                                                                              \
+        const unsigned char* bb = smem + ((s_) % IMGS) * IMG;                                      \
+        _Pragma("unroll") for (int mp = 4; mp < 8; mp += 2) {                                      \
+            aq[mp][1] = G2_AFRAG(bb, mp, 1); aq[mp + 1][1] = G2_AFRAG(bb, mp + 1, 1);              \
+            aq[mp][0] = G2_AFRAG(bb, mp, 0); aq[mp + 1][0] = G2_AFRAG(bb, mp + 1, 0);              \
+        }                                                                                          \
+        __builtin_amdgcn_sched_barrier(0);                                                         \
+    }
+// one factor tile and plane against the wave's four count tiles
+#define G2_MF(mt_, q_)                                                                             \
+    if constexpr (NOMFMA) { asm volatile("" :: "v"(aq[mt_][q_]), "v"(bq[0]), "v"(bq[1]), "v"(bq[2]), "v"(bq[3])); } \
+    else if (G2_LIVE(mt_)) {                                                                       \
+        _Pragma("unroll") for (int nt = 0; nt < 4; ++nt)                                           \
+            acc[mt_][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aq[mt_][q_], bq[nt], acc[mt_][nt], 0, 0, 0); \
+    }
+// eight MFMAs on eight accumulators; G2_MF8(.., 1) then G2_MF8(.., 0): small plane first
+#define G2_MF8(ma_, mb_, q_) G2_MF(ma_, q_) G2_MF(mb_, q_)
+#define G2_STEP(MORE_)                                                                             \
+    {                                                                                              \
+        if constexpr (!NOBAR) G3_RAW_BARRIER()                  /* X_s: image (s + 2) % 3 = (s - 1) % 3 is free */ \
+        if (BURST && MORE_) G2_ISSUE(s + AHEAD)                                                    \
+        if constexpr (NOREAD) { if (s == 0) { G2_READ_A(s) G2_READ_B(s) } } else { G2_READ_A(s) }  \
+        G2_MF8(0, 1, 1)                                                                            \
+        if (!BURST && MORE_) G2_PIECE(s + AHEAD, 0)                                                \
+        G2_MF8(0, 1, 0)                                                                            \
+        if constexpr (!NOREAD) { G2_READ_B(s) }                                                    \
+        if (!BURST && MORE_) G2_PIECE(s + AHEAD, 1)                                                \
+        G2_MF8(2, 3, 1)                                                                            \
+        if (!BURST && MORE_) G2_PIECE(s + AHEAD, 2)                                                \
+        G2_MF8(2, 3, 0)                                                                            \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      /* this image is free once both groups pass here */ \
+        /* step s+1 must have landed before Y_s; what was issued for step s+2 since X_s (three pieces, or the burst's six) may stay in flight */ \
+        if (s + 1 < nst) { if (MORE_) { if constexpr (BURST) G3_WAIT_VM(6); else G3_WAIT_VM(3); } else G3_WAIT_VM(0); } \
+        if constexpr (!NOBAR) G3_RAW_BARRIER()                  /* Y_s */                          \
+        G2_MF8(4, 5, 1)                                                                            \
+        if (!BURST && MORE_) G2_PIECE(s + AHEAD, 3)                                                \
+        G2_MF8(4, 5, 0)                                                                            \
+        if (!BURST && MORE_) G2_PIECE(s + AHEAD, 4)                                                \
+        G2_MF8(6, 7, 1)                                                                            \
+        if (!BURST && MORE_) G2_PIECE(s + AHEAD, 5)                                                \
+        G2_MF8(6, 7, 0)                                                                            \
+    }
+
+    f16x8 bq[4], aq[8][2];
+    G3_WAIT_VM(0);                                          // stores of a previous segment
+    G2_ISSUE(0)
+    if (nst > 1) G2_ISSUE(1)
+    // step 0 landed (step 1 may stay in flight)
+    if (nst > 1) G3_WAIT_VM(6); else G3_WAIT_VM(0);
+    if (grp == 1) G3_RAW_BARRIER()
+    {
+        int s = 0;
+        const int n_main = NODMA ? 0 : nst - AHEAD;             // steps that still have a step to request
+        for (; s < n_main; ++s) G2_STEP(true)
+        for (; s < nst; ++s) G2_STEP(false)
+    }
+    if (grp == 0) G3_RAW_BARRIER()
+#undef G2_STEP
+#undef G2_MF8
+#undef G2_MF
+#undef G2_READ_B
+#undef G2_READ_A
+#undef G2_AFRAG
+#undef G2_FRAG
+#undef G2_ISSUE
+#undef G2_PIECE
+
+    if (C == nullptr) return;                                // (a pass without its stores: timing ablation)
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+        if (!G2_LIVE(mt)) continue;                      // nobody reads the products of dead columns
+        const int row0 = m0 + grp * 128 + mt * 16 + 4 * g;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float rs = rscale[row0 + i];
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+                C[(size_t)(row0 + i) * ldc + j0 + wn * 64 + nt * 16 + r] = acc[mt][nt][i] * rs;
+        }
+    }
+#undef G2_LIVE
+}
+
 template <int NSUB, bool HI, int VAR = 0, bool NTB = true, bool PART = false, bool GEN = false, class EPI = G2NoEpi>
 __device__ __forceinline__ void gemm2h_segment(const unsigned char* __restrict__ A2, const unsigned char* __restrict__ B1,
                                                const unsigned char* __restrict__ Bhi,
@@ -448,6 +613,12 @@ __device__ __forceinline__ void gemm2h_segment(const unsigned char* __restrict__
                                                int nkb, unsigned char* smem, const float* __restrict__ cscale = nullptr,
                                                unsigned live = 0xffu, const EPI* epi = nullptr, bool whole_tile = false)
 {
+    static_assert(NSUB == 1 || !HI, "two blocks per step: one count plane only");
+    if constexpr (NSUB == 2) {
+        static_assert(!EPI::enabled, "the 16x16x32 body has no tile epilogue");
+        gemm2h_segment_mf16<VAR, NTB, PART>(A2, B1, rscale, Kb, C, ldc, m0, j0, kb0, nkb, smem, live);
+        return;
+    }
     constexpr int IMGS = g2_imgs(NSUB);
     constexpr int IMG = g2_img_bytes(NSUB, HI);
     constexpr int OFF_B = NSUB * G2_A;                   // image: [A sub-blocks][B sub-blocks][hi sub-blocks]
@@ -550,17 +721,13 @@ __device__ __forceinline__ void gemm2h_segment(const unsigned char* __restrict__
 
     f16x8 bq[NSUB][2], bh[NSUB][2], aq[NSUB][4][2];
     constexpr int AHEAD = IMGS - 1;                      // steps requested ahead of the one being multiplied
-    constexpr bool SPREAD = VAR >= 1 && NSUB == 2 && !HI;
     // round 6, general matrices (GEN: both X planes in every block, flags all set): the count kernels' spread stream for the
     // one-block-per-step instantiation -- the four LDS-DMA pieces of step s + 3 ride between the MFMA groups instead of a
     // burst behind the X barrier, the fragment reads come in two batches (8 + 4).  Same MFMA order per accumulator as the
     // burst loop below: results are bit-identical (tests/test_gpu_nmf.py).
     constexpr bool SPREADG = VAR >= 1 && NSUB == 1 && ((HI && GEN) || !HI);   // (!HI: the count plane alone, A/B via CNMF_G2_NSUB=1)
     constexpr bool PRIO = false;
-    constexpr bool NOMFMA = VAR == 2, NODMA = VAR == 3 || VAR == 6 || VAR == 7, SPLITRD = VAR >= 4;
     static_assert(VAR != 1 && VAR != 5, "instruction streams 1 and 5 were retired");
-    constexpr bool NOREAD = VAR == 6 || VAR == 7;         // timing ablations: fragments read once / ... and no barriers
-    constexpr bool NOBAR = VAR == 7;
     G3_WAIT_VM(0);                                          // stores of a previous segment
     G2_ISSUE(0)
     if (nst > 1) G2_ISSUE(1)
@@ -632,7 +799,7 @@ __device__ __forceinline__ void gemm2h_segment(const unsigned char* __restrict__
 #undef G2G_READ_B
 #undef G2G_READ_A
 #undef G2G_PIECE
-    } else if constexpr (!SPREAD) {
+    } else {
         for (int s = 0; s < nst; ++s) {
             bool hi_blk[NSUB];
 #pragma unroll
@@ -653,83 +820,6 @@ __device__ __forceinline__ void gemm2h_segment(const unsigned char* __restrict__
             G2_HALF(2, 3)
             if (PRIO) __builtin_amdgcn_s_setprio(0);
         }
-    } else {
-        // NSUB = 2, six pieces per step (A 0..3, B 4..5): pieces 0-2 ride in the first half, 3-5 in the second
-#define G2_PIECE(s_, i_)                                                                           \
-        {                                                                                          \
-            unsigned char* d_ = smem + ((s_) % IMGS) * IMG + wave * 1024;                          \
-            if ((i_) < NA)                                                                         \
-                __builtin_amdgcn_global_load_lds(G3_AS1(abase + (size_t)(s_) * (NSUB * G2_A) + (i_) * 8192), \
-                                                 G3_AS3(d_ + (i_) * 8192), 16, 0, 0);              \
-            else                                                                                   \
-                __builtin_amdgcn_global_load_lds(G3_AS1(bbase + (size_t)(s_) * (NSUB * G2_B) + ((i_) - NA) * 8192), \
-                                                 G3_AS3(d_ + OFF_B + ((i_) - NA) * 8192), 16, 0, NTB ? 2 : 0); \
-            __builtin_amdgcn_sched_barrier(0);                                                     \
-        }
-#define G2_MF(u_, m_, q_)                                                                          \
-        if constexpr (NOMFMA) { asm volatile("" :: "v"(aq[u_][m_][q_]), "v"(bq[u_][0]), "v"(bq[u_][1])); }        \
-        else { G2_MFMA(bq, u_, m_, q_) }
-// fragment reads in two batches (VAR 4): the 12 the first half needs, then -- behind the first 8 MFMAs -- the 8 of the
-// second half: at most 12 LDS reads are outstanding, so the waits in front of the MFMAs can be counted (lgkmcnt is a
-// 4-bit counter: behind 20 reads the compiler can only wait for all of them)
-#define G2_READ_A(s_)                                                                              \
-    {                                                                                              \
-        const unsigned char* bb = smem + ((s_) % IMGS) * IMG;                                      \
-        _Pragma("unroll") for (int u = 0; u < NSUB; ++u) {                                         \
-            _Pragma("unroll") for (int n = 0; n < 2; ++n) bq[u][n] = G2_FRAG(bb + b_off + u * G2_B + n * 32 * 32); \
-            _Pragma("unroll") for (int m = 0; m < 2; ++m) {                                        \
-                aq[u][m][1] = G2_FRAG(bb + u * G2_A + a_row + m * 32 * G2_ROWB + a_s1);            \
-                aq[u][m][0] = G2_FRAG(bb + u * G2_A + a_row + m * 32 * G2_ROWB + a_s0);            \
-            }                                                                                      \
-        }                                                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-    }
-#define G2_READ_B(s_)                                                                              \
-    {                                                                                              \
-        const unsigned char* bb = smem + ((s_) % IMGS) * IMG;                                      \
-        _Pragma("unroll") for (int u = 0; u < NSUB; ++u)                                           \
-            _Pragma("unroll") for (int m = 2; m < 4; ++m) {                                        \
-                aq[u][m][1] = G2_FRAG(bb + u * G2_A + a_row + m * 32 * G2_ROWB + a_s1);            \
-                aq[u][m][0] = G2_FRAG(bb + u * G2_A + a_row + m * 32 * G2_ROWB + a_s0);            \
-            }                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-    }
-#define G2_STEP(MORE_)                                                                             \
-        {                                                                                          \
-            if constexpr (!NOBAR) G3_RAW_BARRIER()                  /* X_s */                      \
-            if constexpr (NOREAD) { if (s == 0) { G2_READ(s) } }                                   \
-            else if constexpr (SPLITRD) { G2_READ_A(s) } else { G2_READ(s) }                       \
-            G2_MF(0, 0, 1) G2_MF(0, 1, 1)                                                          \
-            if (MORE_) G2_PIECE(s + AHEAD, 0)                                                      \
-            G2_MF(0, 0, 0) G2_MF(0, 1, 0)                                                          \
-            if constexpr (SPLITRD && !NOREAD) { G2_READ_B(s) }                                     \
-            if (MORE_) G2_PIECE(s + AHEAD, 1)                                                      \
-            G2_MF(1, 0, 1) G2_MF(1, 1, 1)                                                          \
-            if (MORE_) G2_PIECE(s + AHEAD, 2)                                                      \
-            G2_MF(1, 0, 0) G2_MF(1, 1, 0)                                                          \
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                     \
-            /* step s+1 must have landed before Y_s; the three pieces of step s+2 just issued may stay in flight */ \
-            if (s + 1 < nst) { if (MORE_) G3_WAIT_VM(3); else G3_WAIT_VM(0); }                     \
-            if constexpr (!NOBAR) G3_RAW_BARRIER()                  /* Y_s */                      \
-            G2_MF(0, 2, 1) G2_MF(0, 3, 1)                                                          \
-            if (MORE_) G2_PIECE(s + AHEAD, 3)                                                      \
-            G2_MF(0, 2, 0) G2_MF(0, 3, 0)                                                          \
-            if (MORE_) G2_PIECE(s + AHEAD, 4)                                                      \
-            G2_MF(1, 2, 1) G2_MF(1, 3, 1)                                                          \
-            if (MORE_) G2_PIECE(s + AHEAD, 5)                                                      \
-            G2_MF(1, 2, 0) G2_MF(1, 3, 0)                                                          \
-        }
-        {
-            int s = 0;
-            const int n_main = NODMA ? 0 : nst - AHEAD;             // steps that still have a step to request
-            for (; s < n_main; ++s) G2_STEP(true)
-            for (; s < nst; ++s) G2_STEP(false)
-        }
-#undef G2_STEP
-#undef G2_READ_B
-#undef G2_READ_A
-#undef G2_MF
-#undef G2_PIECE
     }
     if (grp == 0) G3_RAW_BARRIER()
 #undef G2_WAIT_AHEAD
