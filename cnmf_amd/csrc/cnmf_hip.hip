@@ -42,6 +42,7 @@
 #include "kernels_gemm.hip.h"
 #include "kernels_gemm3.hip.h"
 #include "kernels_counts.hip.h"
+#include "kernels_planes.hip.h"
 #include "kernels_gemm2h.hip.h"
 #include "kernels_rng.hip.h"
 #include "kernels_sweep.hip.h"

@@ -165,12 +165,7 @@ extern "C" int cnmf_debug_gemm3c(cnmf_ctx* ctx, const float* A, const float* Bn,
     HIP_TRY(ctx, hipMemcpyAsync(dB, Bn, (size_t)J * K * sizeof(float), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(dUnit, ones.data(), (size_t)K * sizeof(float), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, launch_split3(st, dA, K, KC, K, dA3, G3_MW));
-    {
-        const long long total = (long long)Jp * Kb;
-        count_planes_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(dB, K, J, K, Jp, K, G3C_JW, dUnit,
-                                                                           (unsigned short*)dB1, (unsigned short*)dBh, dFl);
-        HIP_TRY(ctx, hipGetLastError());
-    }
+    HIP_TRY(ctx, launch_x_planes(st, XPlaneFormat::COUNT_BF16, false, dB, K, J, K, Jp, K, dUnit, dB1, dBh, dFl));
     reps = std::max(1, reps);
     for (int i = 0; i < reps + 1; ++i) {
         if (i == 1) hipEventRecord(e0, st);
@@ -249,12 +244,7 @@ extern "C" int cnmf_debug_gemm2h(cnmf_ctx* ctx, const float* A, const float* Bn,
     } else
         HIP_TRY(ctx, launch_rowmax_part(st, dA, K, K, KC, K, nullptr, 1, dRmax));
     HIP_TRY(ctx, launch_split2h(st, dA, K, KC, K, dA2, G3_MW, nullptr, dRmax, bparts, dInv));
-    {
-        const long long total = (long long)Jp * Kb;
-        count_planes_f16_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(dB, K, J, K, Jp, K, G3C_JW, dUnit,
-                                                                               (unsigned short*)dB1, (unsigned short*)dBh, dFl);
-        HIP_TRY(ctx, hipGetLastError());
-    }
+    HIP_TRY(ctx, launch_x_planes(st, XPlaneFormat::COUNT_F16, false, dB, K, J, K, Jp, K, dUnit, dB1, dBh, dFl));
     reps = std::max(1, reps);
     const int var = (nsub >> 4) & 7;                     // (upper bits of `nsub`: instruction-stream variant, A/B probes)
     nsub &= 15;

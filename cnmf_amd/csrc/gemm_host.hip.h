@@ -146,6 +146,7 @@ static hipError_t launch_split3(hipStream_t st, const float* src, int ld, int ro
                                 const double* kscale = nullptr)
 {
     if (rows % 64 == 0 && K % 64 == 0 && TR % 64 == 0) {        // tiled through LDS: both sides coalesced
+        if (rows / 64 > PLAN_GRID_YZ) return hipErrorInvalidValue;
         dim3 grid(K / 64, rows / 64);
         split3_tiled_kernel<<<grid, 256, 0, st>>>(src, ld, K, TR, (unsigned short*)dst, kscale);
         return hipGetLastError();
@@ -214,6 +215,43 @@ static hipError_t launch_gemm3_streamk(hipStream_t st, const StreamK3& sk, const
     return hipGetLastError();
 }
 
+// ---- X-side planes of the count and general paths (x_planes_kernel, kernels_planes.hip.h): the one place that knows the
+// two grid shapes.  X is N x G with leading dimension ld; the planes have rows_pad rows of K k (row tiles of G3C_JW):
+// transpose = false, rows = cells and k = genes, or transpose = true, rows = genes and k = cells.
+//   COUNT_BF16 / COUNT_F16 : aux = the per-gene unit (float), plane1 / flags = the second plane and its block flags or nullptr
+//   SPLIT_F16              : aux = the per-row exponent (int), plane0 / plane1 = the h and m planes
+enum class XPlaneFormat { COUNT_BF16, COUNT_F16, SPLIT_F16 };
+
+template <class F>
+static hipError_t launch_x_planes_t(hipStream_t st, bool transpose, const float* X, int ld, int N, int G, int rows_pad, int K,
+                                    const void* aux, unsigned char* plane0, unsigned char* plane1, unsigned int* flags)
+{
+    const auto* a = static_cast<const typename F::Aux*>(aux);
+    auto* p0 = reinterpret_cast<unsigned short*>(plane0);
+    auto* p1 = reinterpret_cast<unsigned short*>(plane1);
+    if (transpose) {                // lanes along the output row; the 16-k blocks (the long dimension: cells) on grid.x
+        const int groups = (rows_pad + 255) / 256;
+        if (groups > PLAN_GRID_YZ) return hipErrorInvalidValue;
+        x_planes_kernel<F, true><<<dim3(K / 16, groups), 256, 0, st>>>(X, ld, N, G, rows_pad, K, G3C_JW, a, p0, p1, flags);
+    } else {                        // one thread per (row, block), flat
+        const long long blocks = ((long long)rows_pad * (K / 16) + 255) / 256;
+        if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+        x_planes_kernel<F, false><<<(unsigned)blocks, 256, 0, st>>>(X, ld, N, G, rows_pad, K, G3C_JW, a, p0, p1, flags);
+    }
+    return hipGetLastError();
+}
+
+static hipError_t launch_x_planes(hipStream_t st, XPlaneFormat fmt, bool transpose, const float* X, int ld, int N, int G,
+                                  int rows_pad, int K, const void* aux, unsigned char* plane0, unsigned char* plane1,
+                                  unsigned int* flags = nullptr)
+{
+    switch (fmt) {
+        case XPlaneFormat::COUNT_BF16: return launch_x_planes_t<CountBf16>(st, transpose, X, ld, N, G, rows_pad, K, aux, plane0, plane1, flags);
+        case XPlaneFormat::COUNT_F16: return launch_x_planes_t<CountF16>(st, transpose, X, ld, N, G, rows_pad, K, aux, plane0, plane1, flags);
+        default: return launch_x_planes_t<SplitF16>(st, transpose, X, ld, N, G, rows_pad, K, aux, plane0, plane1, flags);
+    }
+}
+
 // planes of X (pass A) and of X^T (pass B), built once per matrix on first use
 static int ensure_planes(cnmf_ctx* ctx)
 {
@@ -236,7 +274,7 @@ static int ensure_planes(cnmf_ctx* ctx)
     return CNMF_OK;
 }
 
-// planes of a general (not count-structured) matrix for the f16 pipe (gemm_mode 5, kernels_gemm2h.hip.h)
+// planes of a general (not count-structured) matrix for the f16 pipe (gemm_mode 5, SplitF16 of kernels_planes.hip.h)
 static int ensure_x2planes(cnmf_ctx* ctx)
 {
     if (ctx->x2.X2h) return CNMF_OK;
@@ -261,12 +299,9 @@ static int ensure_x2planes(cnmf_ctx* ctx)
     HIP_TRY(ctx, hipMemsetAsync(L.onesB, 0xff, fb, st));
     x2h_rowshift_kernel<<<(Np + 3) / 4, 256, 0, st>>>(ctx->X, Gp, N, G, 0, Np, shA, L.sA);
     x2h_rowshift_kernel<<<(Gp + 255) / 256, 256, 0, st>>>(ctx->X, Gp, N, G, 1, Gp, shB, L.sB);
-    const long long total = (long long)Np * (Gp / 16);
-    x2h_planes_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(ctx->X, Gp, N, G, Np, Gp, G3C_JW, shA,
-                                                                        (unsigned short*)L.X2h, (unsigned short*)L.X2m);
-    x2h_planes_transpose_kernel<<<dim3(Np / 16, (Gp + 255) / 256), 256, 0, st>>>(ctx->X, Gp, N, G, Gp, Np, G3C_JW, shB,
-                                                                                (unsigned short*)L.Xt2h, (unsigned short*)L.Xt2m);
     HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, launch_x_planes(st, XPlaneFormat::SPLIT_F16, false, ctx->X, Gp, N, G, Np, Gp, shA, L.X2h, L.X2m));
+    HIP_TRY(ctx, launch_x_planes(st, XPlaneFormat::SPLIT_F16, true, ctx->X, Gp, N, G, Gp, Np, shB, L.Xt2h, L.Xt2m));
     HIP_TRY(ctx, hipStreamSynchronize(st));                // the shift scratch is freed on return
     ctx->x2.take(L);
     return CNMF_OK;
@@ -324,7 +359,7 @@ struct G2Entry { G2Form form; G2Fn fn; };
 template <int NSUB, bool HI, int VAR = 0, bool PART = false, bool GEN = false>
 static hipError_t launch_gemm2h_t(hipStream_t st, const G2Launch& g)
 {
-    constexpr int lds = g2_lds_bytes(NSUB, HI);
+    constexpr int lds = G2Geom<NSUB, HI>::LDS_BYTES;
     {
         if (hipError_t e_ = dyn_lds_optin((const void*)gemm2h_kernel<NSUB, HI, VAR, PART, GEN>, lds)) return e_;
     }
@@ -340,7 +375,7 @@ static hipError_t launch_gemm2h_t(hipStream_t st, const G2Launch& g)
 template <int NSUB, bool HI, int VAR = 0, bool NTB = true, bool PART = false, bool GEN = false>
 static hipError_t launch_gemm2h_streamk_t(hipStream_t st, const G2Launch& g)
 {
-    constexpr int lds = g2_lds_bytes(NSUB, HI);
+    constexpr int lds = G2Geom<NSUB, HI>::LDS_BYTES;
     {
         if (hipError_t e_ = dyn_lds_optin((const void*)gemm2h_streamk_kernel<NSUB, HI, VAR, NTB, PART, GEN>, lds)) return e_;
     }
@@ -417,7 +452,7 @@ static hipError_t launch_rowmax_part(hipStream_t st, const float* V, int ld, int
 }
 
 // Examine the resident matrix once: is every column (integers <= 256) x one constant?  If so build the
-// integer planes of X and X^T and the per-gene scale (kernels_counts.hip.h).  counts.state leaves "not examined" at two
+// integer planes of X and X^T and the per-gene scale (kernels_counts.hip.h, kernels_planes.hip.h).  counts.state leaves "not examined" at two
 // points only: `absent`, where the examination has decided so, and the commit after the last synchronisation -- a
 // failed call leaves it "not examined", and the next call on this matrix examines it again.
 static int ensure_counts(cnmf_ctx* ctx)
@@ -433,7 +468,8 @@ static int ensure_counts(cnmf_ctx* ctx)
     const int N = (int)ctx->N, G = (int)ctx->G;
     if (ctx->N_pad % G3C_JW || ctx->G_pad % G3C_JW || ctx->knobs.no_counts || !ctx->count_detect) return absent();
     hipStream_t st = ctx->stream;
-    const int chunks = (N + CNT_ROWS - 1) / CNT_ROWS;
+    const int chunks = (N + CNT_ROWS - 1) / CNT_ROWS;      // on grid.y of the column passes
+    if (chunks > PLAN_GRID_YZ) { SET_ERR(ctx, "count detection: too many rows for one launch"); return CNMF_EINVAL; }
     DevPool pool;
     float* part = pool.get<float>((size_t)chunks * G);
     float* vmin = pool.get<float>(G);
@@ -484,25 +520,9 @@ static int ensure_counts(cnmf_ctx* ctx)
         HIP_TRY(ctx, hipMemsetAsync(L.hiA, 0, nfA, st));
         HIP_TRY(ctx, hipMemsetAsync(L.hiB, 0, nfB, st));
     }
-    {
-        const long long total = (long long)ctx->N_pad * (ctx->G_pad / 16);
-        dim3 gt(ctx->N_pad / 16, (ctx->G_pad + 255) / 256);
-        if (fmt == 4) {
-            count_planes_f16_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(
-                ctx->X, ctx->G_pad, N, G, ctx->N_pad, ctx->G_pad, G3C_JW, unit, (unsigned short*)L.C1,
-                (unsigned short*)L.C1h, L.hiA);
-            count_planes_f16_transpose_kernel<<<gt, 256, 0, st>>>(
-                ctx->X, ctx->G_pad, N, G, ctx->G_pad, ctx->N_pad, G3C_JW, unit, (unsigned short*)L.Ct1,
-                (unsigned short*)L.Ct1h, L.hiB);
-        } else {
-            count_planes_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(
-                ctx->X, ctx->G_pad, N, G, ctx->N_pad, ctx->G_pad, G3C_JW, unit, (unsigned short*)L.C1,
-                (unsigned short*)L.C1h, L.hiA);
-            count_planes_transpose_kernel<<<gt, 256, 0, st>>>(
-                ctx->X, ctx->G_pad, N, G, ctx->G_pad, ctx->N_pad, G3C_JW, unit, (unsigned short*)L.Ct1,
-                (unsigned short*)L.Ct1h, L.hiB);
-        }
-    }
+    const XPlaneFormat pf = fmt == 4 ? XPlaneFormat::COUNT_F16 : XPlaneFormat::COUNT_BF16;
+    HIP_TRY(ctx, launch_x_planes(st, pf, false, ctx->X, ctx->G_pad, N, G, ctx->N_pad, ctx->G_pad, unit, L.C1, L.C1h, L.hiA));
+    HIP_TRY(ctx, launch_x_planes(st, pf, true, ctx->X, ctx->G_pad, N, G, ctx->G_pad, ctx->N_pad, unit, L.Ct1, L.Ct1h, L.hiB));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));                // the pool's scratch is freed on return
     L.state = 1;
@@ -513,11 +533,11 @@ static int ensure_counts(cnmf_ctx* ctx)
 // the split-operand path needs whole 256 x 128 tiles
 static bool gemm3_enabled(const cnmf_ctx* ctx, int KC)
 {
-    // (round 6: the plane builders carry the 16-cell blocks on grid.x, so matrices beyond 65 535 x 16 = 1 048 560 cells keep the
-    //  matrix-pipe path -- probed at 1 100 000 x 2 000, 2.25e9 padded elements: tools/probe_big_matrix.py; bounded at 2^24 cells
-    //  only because nothing larger has been run; the gene side still rides on grid.y of those builders: G_pad / 256 <= 65 535)
+    // (the plane builders carry the 16-cell blocks on grid.x, so matrices beyond 65 535 x 16 = 1 048 560 cells keep the
+    //  matrix-pipe path -- probed at 1 100 000 x 2 000, 2.25e9 padded elements: tools/probe_big_matrix.py; a shape one of
+    //  whose builder or detection launches would not fit its grid takes the f32 pipe: x_launches_fit, pass_plan.h)
     return ctx->knobs.gemm3 != 0 && KC % G3_MW == 0 && ctx->G_pad % gemm3_jw() == 0 && ctx->N_pad % gemm3_jw() == 0 &&
-           ctx->N_pad <= (1 << 24) && ctx->G_pad / 256 <= 65535;
+           x_launches_fit(PadShape{ctx->N_pad, ctx->G_pad}, ctx->knobs.gemm3);
 }
 
 static hipError_t launch_split2h_finalize(hipStream_t st, const float* src, int ld, int rows, int K, unsigned char* dst,

@@ -11,10 +11,10 @@
 // 6, every partial product is exact, and X costs 2 bytes per element instead of 6.
 // The structure is DETECTED on the device from the resident float32 matrix (so it also applies to a
 // matrix that arrives already normalised, as the reference hands it to scikit-learn); a matrix without
-// it simply keeps the general three-plane path.  Included by cnmf_hip.hip.
+// it simply keeps the general three-plane path.  This header holds the detection; the planes themselves are built by
+// x_planes_kernel (kernels_planes.hip.h).  Included by cnmf_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "kernels_gemm3.hip.h"
 
 namespace cnmf {
 
@@ -92,103 +92,6 @@ __global__ __launch_bounds__(256) void count_scale_kernel(const double* __restri
     double sx = 0.0, sn = 0.0;
     if (g < G) for (int c = 0; c < chunks; ++c) { sx += psx[(size_t)c * G + g]; sn += psn[(size_t)c * G + g]; }
     scale[g] = sn > 0.0 ? sx / sn : 0.0;
-}
-
-// ---- integer planes (ONE bf16 plane), block-major with row tiles of TR rows:
-//      [row tile][16-k block][row][16 bf16] = 32 contiguous bytes per row and block
-// rows = cells, k = genes (pass A's operand).  One thread per (row, block).
-// n = lo + 256 hi: lo in [0, 256] (256 itself stays in lo), hi in [0, 255]
-__device__ __forceinline__ void count_lo_hi(float n, float& lo, float& hi)
-{
-    if (n <= 256.f) { lo = n; hi = 0.f; }
-    else { hi = floorf(n * (1.0f / 256.0f)); lo = n - 256.f * hi; hi *= 256.f; }      // hi plane holds 256 hi
-}
-
-__device__ __forceinline__ void store_plane_row(unsigned short* d, const unsigned short* p)
-{
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-        u32x4 w;
-        w.x = p[8 * hf + 0] | ((unsigned)p[8 * hf + 1] << 16); w.y = p[8 * hf + 2] | ((unsigned)p[8 * hf + 3] << 16);
-        w.z = p[8 * hf + 4] | ((unsigned)p[8 * hf + 5] << 16); w.w = p[8 * hf + 6] | ((unsigned)p[8 * hf + 7] << 16);
-        *reinterpret_cast<u32x4*>(d + hf * 8) = w;
-    }
-}
-
-__global__ __launch_bounds__(256) void count_planes_kernel(const float* __restrict__ X, int ld, int N, int G, int rows_pad,
-                                                           int K, int TR, const float* __restrict__ unit,
-                                                           unsigned short* __restrict__ dst,
-                                                           unsigned short* __restrict__ dst_hi,
-                                                           unsigned int* __restrict__ hiflag)
-{
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int Kb = K / 16;
-    if (t >= (long long)rows_pad * Kb) return;
-    const int row = (int)(t / Kb), kb = (int)(t % Kb);
-    unsigned short p[16], ph[16];
-    bool any_hi = false;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int g = kb * 16 + i;
-        float n = 0.f, lo, hi;
-        if (row < N && g < G) { const float u = unit[g]; if (u > 0.f) n = rintf(X[(size_t)row * ld + g] / u); }
-        count_lo_hi(n, lo, hi);
-        p[i] = bf16_rne(lo); ph[i] = bf16_rne(hi);           // both exact
-        any_hi |= hi != 0.f;
-    }
-    const size_t blk = (size_t)(row / TR) * Kb + kb;
-    store_plane_row(dst + (blk * TR + (row % TR)) * 16, p);
-    if (dst_hi) {
-        store_plane_row(dst_hi + (blk * TR + (row % TR)) * 16, ph);
-        // (tile, block) has a non-zero second plane: one bit per block, (Kb + 31) / 32 words per tile row
-        if (any_hi) atomicOr(&hiflag[(size_t)(row / TR) * ((Kb + 31) / 32) + (kb >> 5)], 1u << (kb & 31));
-    }
-}
-
-// rows = genes, k = cells (pass B's operand).  One thread per (gene row j, block); lanes run along j.
-__global__ __launch_bounds__(256) void count_planes_transpose_kernel(const float* __restrict__ X, int ld, int N, int G,
-                                                                     int rows_pad, int K, int TR,
-                                                                     const float* __restrict__ unit,
-                                                                     unsigned short* __restrict__ dst,
-                                                                     unsigned short* __restrict__ dst_hi,
-                                                                     unsigned int* __restrict__ hiflag)
-{
-    const int j = blockIdx.y * 256 + threadIdx.x;       // (grid = (16-k blocks, row groups): the long dimension on x -- no 65 535 limit)
-    const int kb = blockIdx.x;
-    if (j >= rows_pad) return;
-    const int Kb = K / 16;
-    const float u = (j < G) ? unit[j] : 0.f;
-    unsigned short p[16], ph[16];
-    bool any_hi = false;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int c = kb * 16 + i;
-        float n = 0.f, lo, hi;
-        if (u > 0.f && c < N) n = rintf(X[(size_t)c * ld + j] / u);
-        count_lo_hi(n, lo, hi);
-        p[i] = bf16_rne(lo); ph[i] = bf16_rne(hi);
-        any_hi |= hi != 0.f;
-    }
-    const size_t blk = (size_t)(j / TR) * Kb + kb;
-    store_plane_row(dst + (blk * TR + (j % TR)) * 16, p);
-    if (dst_hi) {
-        store_plane_row(dst_hi + (blk * TR + (j % TR)) * 16, ph);
-        if (any_hi) atomicOr(&hiflag[(size_t)(j / TR) * ((Kb + 31) / 32) + (kb >> 5)], 1u << (kb & 31));
-    }
-}
-
-// does any column need the second plane?  (max n > 256)
-__global__ __launch_bounds__(256) void count_max_kernel(const float* __restrict__ X, int ld, int N, int G,
-                                                        const float* __restrict__ unit, unsigned* __restrict__ any_big)
-{
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    if (g >= G) return;
-    const float u = unit[g];
-    if (u <= 0.f) return;
-    const int r0 = blockIdx.y * CNT_ROWS, r1 = min(N, r0 + CNT_ROWS);
-    bool big = false;
-    for (int r = r0; r < r1; ++r) big |= rintf(X[(size_t)r * ld + g] / u) > 256.f;
-    if (big) atomicOr(any_big, 1u);
 }
 
 }  // namespace cnmf

@@ -17,7 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels_gemm.hip.h"
-#include "kernels_gemm2h.hip.h"
+#include "kernels_planes.hip.h"
 
 namespace cnmf {
 

@@ -16,6 +16,31 @@ struct PadShape { int N_pad, G_pad; };        // the resident matrix, cells x ge
 
 static inline int plan_round_up(int64_t v, int m) { return (int)(((v + m - 1) / m) * m); }
 
+// ------------------------------------------------------------------ launches that build the X-side operands
+// Most blocks a launch may put on grid.y or grid.z.
+constexpr int PLAN_GRID_YZ = 65535;
+
+// Does every builder and detection launch of the matrix-pipe path that CNMF_GEMM3 = gemm3 selects fit its grid?  (grid.x
+// carries the long dimension everywhere else.)  What rides on grid.y:
+//   * the column passes of the count detection (ensure_counts, modes 3 and 4): one chunk of 256 rows each;
+//   * the bf16 plane split of X (split3_tiled_kernel, ensure_planes): 64 rows each.  Modes 1 and 2 always take it; mode 3
+//     when the matrix turns out to have no count structure; any mode on a shape that is not whole 256 x 256 tiles, where
+//     neither the count nor the general f16 path applies.  Mode 4 on whole tiles never does: without the structure it
+//     builds the general f16 planes, whose direct builder is flat on grid.x;
+//   * every transposed builder (x_planes_kernel, split3_transpose_kernel): 256 genes each.
+// A shape that does not fit keeps the f32 pipe (gemm3_enabled).
+static inline bool x_launches_fit(PadShape s, int gemm3)
+{
+    if (gemm3 <= 0) return true;
+    const bool whole = s.N_pad % PLAN_G3C_JW == 0 && s.G_pad % PLAN_G3C_JW == 0;
+    const bool detects = gemm3 >= 3 && whole;
+    const bool bf16_planes = gemm3 <= 3 || !whole;
+    if ((s.G_pad + 255) / 256 > PLAN_GRID_YZ) return false;
+    if (detects && (s.N_pad + 255) / 256 > PLAN_GRID_YZ) return false;
+    if (bf16_planes && s.N_pad % 64 == 0 && s.G_pad % 64 == 0 && s.N_pad / 64 > PLAN_GRID_YZ) return false;
+    return true;
+}
+
 // ------------------------------------------------------------------ sweeps
 // a sweep workgroup walks `sweep_chunks` 256-row tiles; parts_knob = CNMF_SWEEP_PARTS, most workgroups per slot
 static inline int sweep_chunks(int parts_knob, int L) { const int64_t m = 256ll * parts_knob; return std::max(1, (int)(((int64_t)L + m - 1) / m)); }

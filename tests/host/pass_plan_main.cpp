@@ -214,6 +214,30 @@ static void check_misc()
           pick_kc(0, 1024, 5, 100, 0, false) == 128 && pick_kc(512, 1024, 1000, 10, 0, true) == 512);
 }
 
+// x_launches_fit at the grid limits of the launches it stands for (65 535 blocks on grid.y):
+//   count detection, 256 rows per block   : 65 535 * 256 = 16 776 960 rows, the next padded shape is 16 777 216
+//   bf16 plane split of X, 64 rows each   : 65 535 * 64  =  4 194 240 rows, the next shape of whole 128-row tiles 4 194 304
+//   transposed builders, 256 genes each   : G_pad = 65 535 * 256, one tile more
+static void check_launch_fit()
+{
+    const int G = 2048;
+    // mode 4 on whole 256 x 256 tiles: the detection's chunks bound the rows (no launch of it carries rows / 64 on grid.y)
+    CHECK(x_launches_fit(PadShape{16776960, G}, 4) && !x_launches_fit(PadShape{16777216, G}, 4));
+    CHECK(x_launches_fit(PadShape{4194304, G}, 4));
+    // modes 1 and 2 always split X into bf16 planes; mode 3 does when the matrix has no count structure
+    for (int mode : {1, 2, 3}) CHECK(x_launches_fit(PadShape{4194240, G}, mode) && !x_launches_fit(PadShape{4194304, G}, mode));
+    // mode 4 off the 256 grid has neither the count nor the general f16 path: the bf16 planes again
+    CHECK(x_launches_fit(PadShape{4194240 - 128, G}, 4) && !x_launches_fit(PadShape{4194304 + 128, G}, 4));
+    // the gene side rides on grid.y of every transposed builder, in every mode
+    for (int mode : {1, 2, 3, 4}) {
+        CHECK(x_launches_fit(PadShape{2048, 65535 * 256}, mode));
+        CHECK(!x_launches_fit(PadShape{2048, 65535 * 256 + 128}, mode) && !x_launches_fit(PadShape{2048, 65536 * 256}, mode));
+    }
+    // nothing to launch on the f32 pipe; the shapes of the recorded plans all fit
+    CHECK(x_launches_fit(PadShape{1 << 30, 1 << 30}, 0));
+    for (int N_pad : SHAPES) for (int G_pad : SHAPES) for (int mode : {1, 2, 3, 4}) CHECK(x_launches_fit(PadShape{N_pad, G_pad}, mode));
+}
+
 // ------------------------------------------------------------------ golden
 // FNV-1a over the integers of a plan and its cut flags: a record keeps one digest per group of stream-K plans
 struct Fnv {
@@ -291,6 +315,7 @@ int main(int argc, char** argv)
     check_g2_form();
     check_sweep_form();
     check_misc();
+    check_launch_fit();
     if (g_fail) { fprintf(stderr, "%d checks failed\n", g_fail); return 1; }
     printf("ok\n");
     return 0;

@@ -78,7 +78,7 @@ def test_split_operand_gemm_is_f32_accurate(engine, monkeypatch, g3mode):
 
 @pytest.mark.parametrize("big", [False, True])
 def test_count_path_gemm_is_exact_product_accurate(engine, big):
-    """Count-structured operand (kernels_counts.hip.h): B holds integers <= 256 as ONE bf16 plane (big: a few
+    """Count-structured operand (kernels_counts.hip.h, kernels_planes.hip.h): B holds integers <= 256 as ONE bf16 plane (big: a few
     entries up to 65 535 -> a second, block-flagged plane), A three planes -- every partial product is exact,
     so the only error is the f32 accumulation."""
     rs = np.random.RandomState(3)
@@ -218,6 +218,37 @@ def test_count_structure_is_detected_only_where_it_exists(engine):
         engine.set_count_detection(True)
 
 
+def test_second_count_plane_on_a_ragged_matrix_in_both_count_formats(engine, monkeypatch):
+    """Both builders of the flagged second count plane (x_planes_kernel, kernels_planes.hip.h: direct and transposed) on a
+    matrix that fills neither its last row tile nor its last gene tile: 1000 x 500 Poisson counts of the topic model over
+    the column std (padded to 1024 x 512) with counts of 300, 2500 and 5000 in three places -- above the base of the bf16
+    planes (256, CNMF_GEMM3=3) and of the f16 planes (2048, CNMF_GEMM3=4).  Each H is held to the exact-f32 pipe
+    (CNMF_GEMM3=0) at the bound test_count_structure_is_detected_only_where_it_exists uses for this comparison; measured
+    5.1e-5 of it in either mode, with the six builders this kernel replaced and with it.
+    The counts are that test's (synth.topic_counts, its parameters, at this shape), not independent Poisson draws: on a
+    matrix without low-rank structure 20 iterations on two pipes that round differently drift further apart than the
+    bound allows whatever builds the planes (independent Poisson(2) counts: 2.2e-4 in mode 3, 2.4e-4 in mode 4, the same
+    figures before and after the builders were merged)."""
+    C = synth.topic_counts(1000, 500, 6, 5.0, 0.3, 2)[0].astype(np.float64)
+    assert (C.sum(axis=0) > 0).all() and (C.sum(axis=1) > 0).all()
+    std = C.std(axis=0, ddof=1)
+    X = C / std
+    for (i, g, c) in ((3, 5, 300), (700, 400, 2500), (11, 17, 5000)):
+        X[i, g] = c / std[g]
+    ks, seeds = [9] * 29, list(range(1, 30))
+    H = {}
+    for mode in ("0", "3", "4"):
+        monkeypatch.setenv("CNMF_GEMM3", mode)
+        engine.set_matrix(X)
+        H[mode], _, _, _ = engine.nmf_batch(ks, seeds=seeds, max_iter=20, warn=False)
+        assert engine.last_stats["kc"] == 256 and engine.last_stats["gemm_mode"] == int(mode), engine.last_stats
+    for mode in ("3", "4"):
+        worst = max(float(np.abs(a - b).max() / max(1.0, np.abs(b).max())) for a, b in zip(H[mode], H["0"]))
+        print("CNMF_GEMM3=%s: largest |H - H0| / max(1, |H0|.max()) = %.3e" % (mode, worst))
+        for a, b in zip(H[mode], H["0"]):
+            assert np.abs(a - b).max() <= 1e-4 * max(1.0, np.abs(b).max()), mode
+
+
 def test_column_scaling_drops_the_general_f16_planes(engine):
     """scale_genes_unit_variance() rewrites the resident matrix in place, so every image derived from it must go: a batch
     on the general f16 path (gemm_mode 5) after the scaling equals, bit for bit, the same batch after a fresh upload of
@@ -271,7 +302,7 @@ def test_general_matrix_on_the_f16_pipe_matches_oracle(engine):
 
 def test_general_path_spread_stream_is_bit_identical_to_the_burst_loop(engine, monkeypatch):
     """Round 6: the general-matrix GEMMs (gemm_mode 5) issue their LDS-DMA pieces between the MFMA groups and read their
-    fragments in two batches (the count kernels' spread stream, kernels_gemm2h.hip.h SPREADG) -- the MFMA order per accumulator
+    fragments in two batches (the count kernels' spread stream, kernels_gemm2h.hip.h SPREAD) -- the MFMA order per accumulator
     is the burst loop's, so every bit of every result must be (CNMF_G2_GVAR=0: the burst loop).  A 256-column batch (pass B
     split-K, pass A stream-K with cut tiles) and a 1024-column one (four component groups, the identity XCD mapping), with
     refill, narrowing and partial tiles in the tail."""

@@ -5,7 +5,9 @@ tests/host/pass_plan_main.cpp, compiled with the address and undefined-behaviour
 flags count the boundaries inside a tile, flags sit at ``jt * MG + mg``), the "off" rules, split counts never above what
 was asked, no planned launch writing more partial planes than ``size_splits`` sized, ``g2_form`` over its 128 inputs
 against the two if-ladders it replaced (typed out in the program; 9 and 14 distinct kernel instantiations), ``sweep_form``
-over its 16 inputs and the flat-address predicate at its threshold.
+over its 16 inputs and the flat-address predicate at its threshold, and ``x_launches_fit`` on both sides of the three
+grid.y limits of the X-side builder and detection launches (16 776 960 / 16 777 216 rows where the count detection runs,
+4 194 240 / 4 194 304 rows where X is split into bf16 planes, ``G_pad`` = 65 535 * 256 and one tile more).
 
 ``golden``: every planner over padded shapes {256, 512, 2 048, 50 176, 1 100 032}^2, widths {32 ... 256, 512, 1 024} and the
 knobs ``no_streamk`` in {0, 1}, ``wg_slots`` in {0, 32, 128}, ``g2_nsub`` in {1, 2}, against tests/golden/pass_plans.json

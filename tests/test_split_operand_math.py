@@ -68,7 +68,7 @@ def test_six_partial_products_are_float32_accurate():
 
 
 def test_count_planes_are_exact():
-    """The count path (kernels_counts.hip.h): every integer n <= 65 535 is lo + hi256 with lo <= 256 and
+    """The count path (count_lo_hi, kernels_planes.hip.h): every integer n <= 65 535 is lo + hi256 with lo <= 256 and
     hi256 a multiple of 256 <= 65 280 -- both exactly representable in bfloat16 -- so (ah + am + al) * n is
     formed from exact partial products."""
     n = np.arange(0, 65536, dtype=np.float32)

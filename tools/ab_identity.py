@@ -1,7 +1,9 @@
 """Fixed seeded jobs through whichever build of the library CNMF_LIB_PATH names, for bit-identity A/B runs of two builds:
-    CNMF_LIB_PATH=/path/to/libcnmf_hip.so [CNMF_GEMM3=2 ...] python tools/ab_identity.py wide|general|f32|mode|init|streamk|streamk_general|hints|staging|mu
+    CNMF_LIB_PATH=/path/to/libcnmf_hip.so [CNMF_GEMM3=2 ...] python tools/ab_identity.py wide|general|f32|mode|hi|init|streamk|streamk_general|hints|staging|mu
 Prints one JSON line: SHA-256 digests of everything the job's batch calls returned (H, n_iter, viol) and of the
 last_stats fields that describe the schedule.  One process per library and per knob value; the lines must be equal.
+``hi`` is ``mode`` with three counts raised above the bases of both count formats: under CNMF_GEMM3=3 and 4 both builders
+write a flagged second plane and the GEMM passes take their two-plane count stream.
 ``staging`` runs no coordinate-descent batch: it digests every array the prepare / preprocess / filter entry points and
 a Kullback-Leibler batch on the non-zeros return for one small count matrix (staging_matrix).  ``mu`` digests H, W, n_iter
 and err of multiplicative-update calls that refill slots, on the dense matrix pipe and on the non-zeros; run it once per
@@ -29,7 +31,7 @@ def draw(rs, n, lo=5, hi=14):
 def calls(job):
     """(matrix, [keyword arguments of one nmf_batch call, ...]) of a job"""
     rs = np.random.RandomState(5)
-    if job in ("wide", "mode", "init", "hints"):            # count path; 150 restarts: 1024 columns, refill, defragmentation, 768 / 512 / 256, f32 tail
+    if job in ("wide", "mode", "hi", "init", "hints"):            # count path; 150 restarts: 1024 columns, refill, defragmentation, 768 / 512 / 256, f32 tail
         X = synth.make_config("C3", dtype=np.float32, n_cells=6000)
         if job == "init":                           # caller-supplied factors of very different size (the exponent guess of the W planes)
             ks = [40, 64, 50, 30, 60, 45, 33]
@@ -39,6 +41,13 @@ def calls(job):
         if job == "hints":                          # the same call twice: the second one ordered by what the first one learned
             ks, seeds = draw(rs, 60)
             return X, [dict(ks=ks, seeds=seeds, max_iter=60), dict(ks=ks, seeds=seeds, max_iter=60, hints=True)]
+        if job == "hi":                             # counts of 300, 2500 and 5000 in three places (tests/test_gpu_nmf.py)
+            N, G, K, mu, sg, seed = synth.CONFIGS["C3"]
+            C, _ = synth.topic_counts(X.shape[0], G, K, mu, sg, seed)
+            C = C[:, C.sum(axis=0) > 0]
+            assert C.shape == X.shape
+            for (i, g, c) in ((3, 5, 300), (700, 400, 2500), (11, 17, 5000)):
+                X[i, g] = np.float64(X[:, g][X[:, g] > 0].min()) * c / C[:, g][C[:, g] > 0].min()
         ks, seeds = draw(rs, 150 if job == "wide" else 44)
         return X, [dict(ks=ks, seeds=seeds, max_iter=60)]
     if job == "general":                            # tests/test_gpu_nmf.py: the perturbed matrix, 256 and 1024 columns
