@@ -46,6 +46,7 @@ SYMBOLS = [
     "cnmf_spectra_rows", "cnmf_spectra_reset", "cnmf_spectra_fetch", "cnmf_spectra_fetch_rows", "cnmf_spectra_genes", "cnmf_spectra_append",
     "cnmf_consensus_store", "cnmf_kselect_stats_store", "cnmf_clustergram", "cnmf_clustergram_step_ms",
     "cnmf_range_finder", "cnmf_format_rows_f64",
+    "cnmf_nndsvd_group", "cnmf_init_store_reset", "cnmf_init_store_fetch",
 ]
 # test hooks (include/cnmf_hip_debug.h): present only in a library built with -DCNMF_DEBUG_ABI -- the in-tree default,
 # because tests/ call them; CNMF_PRODUCT_BUILD=1 in the environment of build() leaves them out
@@ -320,6 +321,12 @@ def load():
     lib.cnmf_format_rows_f64.argtypes = [dblp, i64, i64, C.c_char, C.c_char_p, i64, C.c_void_p, i64]
     lib.cnmf_range_finder.restype = i32
     lib.cnmf_range_finder.argtypes = [vp, i32, i32, i32p, f32p, i32, f32p, f32p]
+    lib.cnmf_nndsvd_group.restype = i32
+    lib.cnmf_nndsvd_group.argtypes = [vp, i32, i32, i32p, C.POINTER(C.c_uint32), i32, i32, C.c_double, C.c_double, i32p]
+    lib.cnmf_init_store_reset.restype = i32
+    lib.cnmf_init_store_reset.argtypes = [vp]
+    lib.cnmf_init_store_fetch.restype = i32
+    lib.cnmf_init_store_fetch.argtypes = [vp, f32p, f32p, i64, i32p]
     lib.cnmf_xt_matmul_f64.restype = i32
     lib.cnmf_xt_matmul_f64.argtypes = [vp, i32, dblp, i32, dblp, dblp, dblp]
     lib.cnmf_nnls_spectra.restype = i32

@@ -319,6 +319,10 @@ class cNMF:
     # distance matrix ordered by cluster and average-linkage leaf order on the device (Engine.clustergram) as
     # self.spectra_order / self.topics_dist_ordered, and the figure at paths["clustering_plot"].  None: no clustergram.
     clustergram = None
+    # where the tail of init='nndsvd' / 'nndsvda' / 'nndsvdar' runs (small SVD, sign flip, split): "host" (LAPACK on a thread pool,
+    # factors uploaded per restart) or "device" (opt-in: Engine.nndsvd_init_batch(tail="device"); factorize() starts
+    # the batch from the engine's init store without a transfer).
+    nndsvd = "host"
 
     def __init__(self, output_dir=".", name=None, device=0, engine=None, compress_merged=True, detect_counts=True):
         """Same constructor semantics as the reference (cnmf.py:268-296) plus the GPU index.
@@ -717,8 +721,15 @@ class cNMF:
                                       "solver='mu'/beta_loss='frobenius' only as a refit (update_H=False), not as a "
                                       "full factorization; got solver=%r beta_loss=%r update_H=%r"
                                       % (solver, beta, kw.get("update_H", True)))
-        if kw.get("init", "random") not in ("random", "custom", "nndsvd", None) and "H" not in kw:
-            raise NotImplementedError("init=%r is not implemented on the device (random / nndsvd / custom)" % kw.get("init"))
+        if kw.get("init", "random") not in ("random", "custom", "nndsvd", "nndsvda", "nndsvdar", None) and "H" not in kw:
+            raise NotImplementedError("init=%r is not implemented on the device (random / nndsvd / nndsvda / nndsvdar / "
+                                      "custom)" % kw.get("init"))
+
+    def _nndsvd_tail(self, variant, eng):
+        """The tail ``factorize`` / ``_nmf`` ask the engine for (``self.nndsvd``)."""
+        if self.nndsvd not in ("host", "device"):
+            raise ValueError("cNMF.nndsvd must be 'host' or 'device', not %r" % (self.nndsvd,))
+        return "device" if (self.nndsvd == "device" and hasattr(eng, "init_store_fetch")) else "host"
 
     def _nmf(self, X, nmf_kwargs):
         """Mirror of cNMF._nmf (cnmf.py:661-674): ``(spectra, usages)`` for one restart, or the
@@ -756,7 +767,14 @@ class cNMF:
             return H, W.astype(xdt, copy=False)
         k = int(kw["n_components"])
         if kw.get("init") == "nndsvd":                       # `--init nndsvd` (cnmf.py:1252)
-            W0, H0 = eng.nndsvd_init(k, random_state=int(kw["random_state"]))
+            if self._nndsvd_tail("nndsvd", eng) == "device":
+                W0, H0 = eng.nndsvd_init(k, random_state=int(kw["random_state"]), tail="device")
+            else:
+                W0, H0 = eng.nndsvd_init(k, random_state=int(kw["random_state"]))
+            kw = dict(kw, init="custom", W=W0, H=H0)
+        elif kw.get("init") in ("nndsvda", "nndsvdar"):
+            W0, H0 = eng.nndsvd_init(k, random_state=int(kw["random_state"]), variant=kw["init"],
+                                     tail=self._nndsvd_tail(kw["init"], eng))
             kw = dict(kw, init="custom", W=W0, H=H0)
         if mu:
             common = dict(beta_loss=kw["beta_loss"], tol=kw.get("tol", 1e-4), max_iter=kw.get("max_iter", 200),
@@ -813,9 +831,17 @@ class cNMF:
                       alpha_W=_nmf_kwargs.get("alpha_W", 0.0), alpha_H=_nmf_kwargs.get("alpha_H", 0.0),
                       l1_ratio=_nmf_kwargs.get("l1_ratio", 0.0))
         init_kw = dict(seeds=seeds)
-        if _nmf_kwargs.get("init") == "nndsvd":
+        init = _nmf_kwargs.get("init")
+        if init == "nndsvd" and self._nndsvd_tail(init, eng) == "host":
             inits = eng.nndsvd_init_batch(ks, seeds)           # range finders of up to 13 restarts per pass over X
             init_kw = dict(W0=[w for w, _ in inits], H0=[h for _, h in inits])
+        elif init in ("nndsvd", "nndsvda", "nndsvdar"):
+            tail = self._nndsvd_tail(init, eng)
+            inits = eng.nndsvd_init_batch(ks, seeds, variant=init, tail=tail, keep=tail == "device")
+            if inits is None:                                  # the factors wait in the engine's init store
+                init_kw = dict(init_store=True)
+            else:                                              # host tail, or the device refused a block
+                init_kw = dict(W0=[w for w, _ in inits], H0=[h for _, h in inits])
         if _nmf_kwargs.get("solver", "cd") == "mu":
             H_list, _, n_iter, _ = eng.nmf_mu_batch(ks, beta_loss=_nmf_kwargs["beta_loss"], **init_kw, **common)
             self.last_factorize_stats = dict(n_iter=n_iter)

@@ -188,7 +188,8 @@ struct BatchRun {
     EventPool events;
     struct PinnedInts { int* p = nullptr; ~PinnedInts() { if (p) hipHostFree(p); } } repack_host;
     float *d_Hres = nullptr, *d_Wres = nullptr;      // device result buffers
-    float *d_H0 = nullptr, *d_Wt0 = nullptr;         // init_mode 1: the random factors of every restart, component-major
+    float *d_H0 = nullptr, *d_Wt0 = nullptr;         // init_mode 1: the random factors of every restart, component-major;
+                                                     // init_mode 2: the context's init store (same layout)
     int* d_repack = nullptr;                         // re-packing: column map, moved slot ids, their new offsets
     int n_repack = 0;
     PassScheme ps;
@@ -308,6 +309,7 @@ static int install(BatchRun& b, const Placement& p)
         // re-converts the rows whose first update left the window
         float mx = 0.f;
         if (b.init_mode == 1) mx = 6.0f * (float)b.avg[r];
+        else if (b.init_mode == 2) mx = ctx->inits.maxW[r];
         else for (size_t q = 0; q < (size_t)k * N; ++q) mx = std::max(mx, b.W0[b.woff[r] + q]);
         int e2 = 0;
         if (mx > 0.f) std::frexp(mx, &e2);
@@ -671,6 +673,18 @@ static int generate_inits(BatchRun& b, const uint32_t* seeds)
     return CNMF_OK;
 }
 
+// init_mode 2: the init store must hold exactly the restarts of the call, on this matrix
+static int check_init_store(cnmf_ctx* ctx, int n, const int32_t* kk)
+{
+    const cnmf_ctx::InitStore& is = ctx->inits;
+    if (is.k.empty()) { SET_ERR(ctx, "init_mode 2: the init store is empty"); return CNMF_EINVAL; }
+    if (is.N != ctx->N || is.G != ctx->G) { SET_ERR(ctx, "init_mode 2: the init store belongs to another matrix shape"); return CNMF_EINVAL; }
+    if ((int)is.k.size() != n) { SET_ERR(ctx, "init_mode 2: the init store holds %d restarts, the call has %d", (int)is.k.size(), n); return CNMF_EINVAL; }
+    for (int r = 0; r < n; ++r)
+        if (is.k[r] != kk[r]) { SET_ERR(ctx, "init_mode 2: restart %d has rank %d in the init store, %d in the call", r, is.k[r], (int)kk[r]); return CNMF_EINVAL; }
+    return CNMF_OK;
+}
+
 // Packed columns of the call: pick_kc on the job's total rank, wide where the matrix-pipe kernels can run it
 static int pick_batch_width(cnmf_ctx* ctx, const cnmf_cd_params* prm, int64_t total_k, int max_k, int* KC_out)
 {
@@ -747,7 +761,8 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
     if (n < 0 || (n > 0 && !kk)) { SET_ERR(ctx, "bad restart list"); return CNMF_EINVAL; }
     if (init_mode == 0 && n > 0 && (!W0 || !H0)) { SET_ERR(ctx, "init_mode 0 needs W0 and H0"); return CNMF_EINVAL; }
     if (init_mode == 1 && n > 0 && (!seeds || !avg)) { SET_ERR(ctx, "init_mode 1 needs seeds and avg"); return CNMF_EINVAL; }
-    if (init_mode != 0 && init_mode != 1) { SET_ERR(ctx, "unknown init_mode %d", init_mode); return CNMF_EINVAL; }
+    if (init_mode < 0 || init_mode > 2) { SET_ERR(ctx, "unknown init_mode %d", init_mode); return CNMF_EINVAL; }
+    if (init_mode == 2 && n > 0 && (rc = check_init_store(ctx, n, kk))) return rc;
     if (!resident && n > 0 && !H_out) { SET_ERR(ctx, "H_out is NULL"); return CNMF_EINVAL; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (stats) memset(stats, 0, sizeof *stats);
@@ -787,6 +802,7 @@ static int run_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode, con
     b.time_stride = (stats && prm->profile > 0) ? prm->profile : 0;
     if ((rc = alloc_call_buffers(b, W_out != nullptr))) return rc;
     if (init_mode == 1 && (rc = generate_inits(b, seeds))) return rc;
+    if (init_mode == 2) { b.d_H0 = ctx->inits.H; b.d_Wt0 = ctx->inits.Wt; }
 
     // stamps restart at 1 in every call: forget the ones a previous call left in the ring (nothing is in flight here)
     memset(ctx->bat.h_snap, 0, (size_t)ctx->bat.kc * RING * sizeof(SlotDesc));

@@ -61,7 +61,7 @@ extern "C" int cnmf_device_count(void)
     return n;
 }
 
-extern "C" const char* cnmf_version(void) { return "cnmf_hip 0.2.0 (gfx950)"; }
+extern "C" const char* cnmf_version(void) { return "cnmf_hip 0.3.0 (gfx950)"; }
 
 extern "C" const char* cnmf_last_error(const cnmf_ctx* ctx)
 {
@@ -113,6 +113,7 @@ static void drop_derived_images(cnmf_ctx* c)
     c->XtF.release();
     for (int i = 0; i < 2; ++i) { c->spA[i].release(); c->spB[i].release(); }
     c->x_nnz = -1;
+    c->inits.release();                                  // (start factors computed from the old values)
     free_csr(c);
 }
 
@@ -320,4 +321,5 @@ extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
 
 #include "debug_host.hip.h"
 #include "nndsvd_host.hip.h"
+#include "nndsvd_tail_host.hip.h"
 #include "format_host.hip.h"

@@ -40,6 +40,8 @@ __device__ __forceinline__ uint32_t mt_temper(uint32_t y)
 
 // MODE 0: out_d[o] = z (raw doubles, for the known-answer test)
 // MODE 1: scatter |float(avg*z)| into H_all rows (o < k*G) and Wt_all rows (o >= k*G)
+// MODE 3: out_d[off + o] = z (raw doubles of several jobs side by side: the 'nndsvdar' fill)
+// MODE 2: float(z) of normal(size=(N, k)), row-major, into the component-major rows Wt[off + c][i]  (NNDSVD start blocks)
 struct RngJob {
     uint32_t seed; int k; int off;
     double avg;
@@ -115,7 +117,11 @@ __global__ __launch_bounds__(256) void rng_kernel(const RngJob* __restrict__ job
                 const double z = e ? z1 : z0;
                 if (oidx < job.total) {
                     if (MODE == 0) out_d[oidx] = z;
-                    else {
+                    else if (MODE == 3) out_d[(size_t)job.off + oidx] = z;
+                    else if (MODE == 2) {
+                        const int i = (int)(oidx / job.k), c = (int)(oidx % job.k);
+                        Wt[(size_t)(job.off + c) * ldw + i] = (float)z;
+                    } else {
                         const float v = fabsf((float)(job.avg * z));
                         if (oidx < kG) {
                             const int c = (int)(oidx / G), g = (int)(oidx % G);

@@ -429,6 +429,10 @@ static int install_slots(MuRun& r, const std::vector<MuPlacement>& pl)
             HIP_TRY(ctx, hipMemcpyAsync(cH, c.H0 + jb.hoff, (size_t)k * G * sizeof(float), hipMemcpyHostToDevice, st));
         if (c.update_H && c.init_mode == 0)
             HIP_TRY(ctx, hipMemcpyAsync(cW, c.W0 + jb.woff, (size_t)k * N * sizeof(float), hipMemcpyHostToDevice, st));
+        if (c.update_H && c.init_mode == 2) {                        // the init store: component-major like the seeded factors
+            HIP_TRY(ctx, hipMemcpyAsync(cH, ctx->inits.H + jb.hoff, (size_t)k * G * sizeof(float), hipMemcpyDeviceToDevice, st));
+            HIP_TRY(ctx, hipMemcpyAsync(cW, ctx->inits.Wt + jb.woff, (size_t)k * N * sizeof(float), hipMemcpyDeviceToDevice, st));
+        }
         mu_pack_kernel<<<gHt, 256, 0, st>>>(cH, k, G, d.Ht, KP);
         if (!c.update_H) mu_fill_kernel<<<gWp, 256, 0, st>>>(d.W, k, N, KP, (float)c.avg[jb.restart]);
         else if (c.init_mode == 0) mu_pack_rm_kernel<<<gWp, 256, 0, st>>>(cW, k, N, d.W, KP);
@@ -583,6 +587,8 @@ extern "C" int cnmf_nmf_mu_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int in
     if (!update_H && (!H0 || !avg)) { SET_ERR(ctx, "update_H=0 needs H0 and avg"); return CNMF_EINVAL; }
     if (update_H && init_mode == 0 && n > 0 && (!W0 || !H0)) { SET_ERR(ctx, "init_mode 0 needs W0 and H0"); return CNMF_EINVAL; }
     if (update_H && init_mode == 1 && n > 0 && (!seeds || !avg)) { SET_ERR(ctx, "init_mode 1 needs seeds and avg"); return CNMF_EINVAL; }
+    if (update_H && (init_mode < 0 || init_mode > 2)) { SET_ERR(ctx, "unknown init_mode %d", init_mode); return CNMF_EINVAL; }
+    if (update_H && init_mode == 2 && n > 0 && (rc = check_init_store(ctx, n, kk))) return rc;
     if (update_H && n > 0 && !H_out) { SET_ERR(ctx, "H_out is NULL"); return CNMF_EINVAL; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const MuCall call{init_mode, beta, update_H, seeds, avg, W0, H0, prm, H_out, W_out, n_iter_out, err_out};

@@ -10,7 +10,8 @@
 // host in float64 (c <= 128), Q = Y R^-1 on the device.  Between two passes over X the condition of a block is that of
 // ONE application of X to orthonormal columns, far below the 1/sqrt(eps) limit of Cholesky-QR.  The final basis gets two
 // rounds (CholeskyQR2: orthonormal to float32 round-off), then B = Q^T M comes from one more pass.  The (k + 10) x G SVD,
-// the sign flip and the positive / negative split stay on the host (Engine.nndsvd_init_batch).
+// the sign flip and the positive / negative split follow on the host (cnmf_range_finder -> Engine.nndsvd_init_batch) or,
+// with Q and B left where they are, on the device (range_finder_run -> cnmf_nndsvd_group, nndsvd_tail_host.hip.h).
 #pragma once
 
 namespace cnmf {
@@ -91,13 +92,25 @@ __global__ __launch_bounds__(256) void gram_chunk_reduce_kernel(const double* __
 
 }  // namespace cnmf
 
-// transpose = 0: M = X (rows = cells), 1: M = X^T.  Q0 [M_cols][C] row-major (C = sum of widths <= 256);
-// Q_out [M_rows][C]; B_out [C][M_cols] = Q^T M.
-extern "C" int cnmf_range_finder(cnmf_ctx* ctx, int transpose, int nblocks, const int32_t* widths, const float* Q0,
-                                 int n_iter, float* Q_out, float* B_out)
+namespace cnmf {
+// What one run of the range finder leaves on the device (released with the object): Q component-major [KC][M_rows]
+// (leading dimension Lrp) and B = Q^T M component-major [KC][M_cols] (leading dimension Lcp), the blocks side by side.
+struct RangeFinderRun {
+    DevPool pool;
+    int C = 0, KC = 0, cmax = 0;
+    int Lr = 0, Lrp = 0, Lc = 0, Lcp = 0;           // M_rows / M_cols and their padded lengths
+    float *dIn = nullptr, *dR = nullptr, *dCm = nullptr;
+    SlotDesc* dBlk = nullptr;                       // off / k of every block
+};
+}  // namespace cnmf
+
+// The range finder of one group.  The start blocks: Q0 [M_cols][C] row-major from the host, or (Q0 == NULL) drawn on the
+// device, block b = RandomState(seeds[b]).normal(size=(M_cols, widths[b])) cast to float32.
+static int range_finder_run(cnmf_ctx* ctx, int transpose, int nblocks, const int32_t* widths, const float* Q0,
+                            const uint32_t* seeds, int n_iter, cnmf::RangeFinderRun& run)
 {
     using namespace cnmf;
-    if (!ctx || !widths || !Q0 || !Q_out || !B_out || nblocks < 1 || n_iter < 0) { SET_ERR(ctx, "bad argument"); return CNMF_EINVAL; }
+    if (!ctx || !widths || (!Q0 && !seeds) || nblocks < 1 || n_iter < 0) { SET_ERR(ctx, "bad argument"); return CNMF_EINVAL; }
     if (int rcd_ = ensure_dense(ctx)) return rcd_;
     int C = 0, cmax = 0;
     for (int b = 0; b < nblocks; ++b) {
@@ -112,7 +125,7 @@ extern "C" int cnmf_range_finder(cnmf_ctx* ctx, int transpose, int nblocks, cons
     // M_rows / M_cols and their padded lengths
     const int Lr = transpose ? G : N, Lrp = transpose ? Gp : Np;
     const int Lc = transpose ? N : G, Lcp = transpose ? Np : Gp;
-    DevPool pool;
+    DevPool& pool = run.pool;
     float* dIn = pool.get<float>((size_t)std::max(Lr, Lc) * C);
     float* dR = pool.get<float>((size_t)KC * Lrp, true, st);          // component-major [KC][M_rows]
     float* dCm = pool.get<float>((size_t)KC * Lcp, true, st);         // component-major [KC][M_cols]
@@ -124,7 +137,10 @@ extern "C" int cnmf_range_finder(cnmf_ctx* ctx, int transpose, int nblocks, cons
     float* dRinv = pool.get<float>((size_t)nblocks * cmax * cmax);
     constexpr int GRAM_CHUNKS = 64;
     double* dGpart = pool.get<double>((size_t)nblocks * GRAM_CHUNKS * cmax * cmax);
+    RngJob* dJobs = Q0 ? nullptr : pool.get<RngJob>(nblocks);
     POOL_TRY(ctx, pool);
+    run.C = C; run.KC = KC; run.cmax = cmax; run.Lr = Lr; run.Lrp = Lrp; run.Lc = Lc; run.Lcp = Lcp;
+    run.dIn = dIn; run.dR = dR; run.dCm = dCm; run.dBlk = dBlk;
     std::vector<SlotDesc> blk(nblocks);
     std::vector<int> list(nblocks);
     int off = 0;
@@ -135,10 +151,18 @@ extern "C" int cnmf_range_finder(cnmf_ctx* ctx, int transpose, int nblocks, cons
     }
     HIP_TRY(ctx, hipMemcpyAsync(dBlk, blk.data(), nblocks * sizeof(SlotDesc), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(dList, list.data(), nblocks * sizeof(int), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(dIn, Q0, (size_t)Lc * C * sizeof(float), hipMemcpyHostToDevice, st));
-    {   // row-major [M_cols][C] -> component-major rows (install_kernel's W path transposes)
+    if (Q0) {
+        HIP_TRY(ctx, hipMemcpyAsync(dIn, Q0, (size_t)Lc * C * sizeof(float), hipMemcpyHostToDevice, st));
+        // row-major [M_cols][C] -> component-major rows (install_kernel's W path transposes)
         dim3 gI((Lc + 255) / 256, C);
         install_kernel<<<gI, 256, 0, st>>>(nullptr, dIn, dCm, Lcp, 0, dCm, Lcp, Lc, 0, C);
+        HIP_TRY(ctx, hipGetLastError());
+    } else {   // one workgroup per block walks its Mersenne-twister stream and writes the component-major rows itself
+        std::vector<RngJob> jobs(nblocks);
+        for (int b = 0; b < nblocks; ++b) jobs[b] = RngJob{seeds[b], blk[b].k, blk[b].off, 0.0, (long long)Lc * blk[b].k};
+        HIP_TRY(ctx, hipMemcpyAsync(dJobs, jobs.data(), nblocks * sizeof(RngJob), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));                       // `jobs` is a stack temporary
+        rng_kernel<2><<<nblocks, 256, 0, st>>>(dJobs, nullptr, nullptr, 0, 1, dCm, Lcp, Lc);
         HIP_TRY(ctx, hipGetLastError());
     }
     // dst[KC][rows of M] = src . M^T   (contracts over M's columns)
@@ -239,14 +263,28 @@ extern "C" int cnmf_range_finder(cnmf_ctx* ctx, int transpose, int nblocks, cons
     if ((rc = normalise(dR, Lrp, Lr))) return rc;
     if ((rc = normalise(dR, Lrp, Lr))) return rc;
     if ((rc = mul_Mt(dR, dCm))) return rc;                    // B = Q^T M  (component-major = [C][M_cols])
+    return CNMF_OK;
+}
+
+// transpose = 0: M = X (rows = cells), 1: M = X^T.  Q0 [M_cols][C] row-major (C = sum of widths <= 256);
+// Q_out [M_rows][C]; B_out [C][M_cols] = Q^T M.
+extern "C" int cnmf_range_finder(cnmf_ctx* ctx, int transpose, int nblocks, const int32_t* widths, const float* Q0,
+                                 int n_iter, float* Q_out, float* B_out)
+{
+    using namespace cnmf;
+    if (!ctx || !Q0 || !Q_out || !B_out) { SET_ERR(ctx, "bad argument"); return CNMF_EINVAL; }
+    RangeFinderRun run;
+    if (int rc = range_finder_run(ctx, transpose, nblocks, widths, Q0, nullptr, n_iter, run)) return rc;
+    hipStream_t st = ctx->stream;
+    const int C = run.C, Lr = run.Lr, Lc = run.Lc;
     dim3 gQ((Lr + 255) / 256, C), gB((Lc + 255) / 256, C);
-    extract_kernel<<<gQ, 256, 0, st>>>(dR, Lrp, Lr, 0, C, dIn, 1);                   // -> [M_rows][C]
+    extract_kernel<<<gQ, 256, 0, st>>>(run.dR, run.Lrp, Lr, 0, C, run.dIn, 1);           // -> [M_rows][C]
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(Q_out, dIn, (size_t)Lr * C * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(Q_out, run.dIn, (size_t)Lr * C * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    extract_kernel<<<gB, 256, 0, st>>>(dCm, Lcp, Lc, 0, C, dIn, 0);                  // -> [C][M_cols]
+    extract_kernel<<<gB, 256, 0, st>>>(run.dCm, run.Lcp, Lc, 0, C, run.dIn, 0);          // -> [C][M_cols]
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(B_out, dIn, (size_t)Lc * C * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(B_out, run.dIn, (size_t)Lc * C * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return CNMF_OK;
 }

@@ -311,6 +311,16 @@ struct cnmf_ctx {
     float* spectra = nullptr;
     size_t spectra_cap = 0, spectra_rows = 0;
     int64_t spectra_G = 0;             // gene count of the rows in the store (the matrix they were computed on)
+    // init store (nndsvd_tail_host.hip.h): the NNDSVD start factors of the restarts of cnmf_nndsvd_group calls, appended
+    // group after group in generate_inits()'s layout -- H0 [sum k][G], Wt0 [sum k][N], component-major -- for init_mode 2
+    struct InitStore {
+        float *H = nullptr, *Wt = nullptr;
+        size_t cap_rows = 0, rows = 0;             // component rows allocated / held
+        int64_t N = 0, G = 0;                      // shape of the matrix the factors belong to
+        std::vector<int> k;                        // rank of every stored restart
+        std::vector<float> maxW;                   // max W0 of every stored restart
+        void release() { hipFree(H); hipFree(Wt); H = Wt = nullptr; cap_rows = rows = 0; N = G = 0; k.clear(); maxW.clear(); }
+    } inits;
     // what the batch calls on THIS matrix learned about the restarts' length: mean outer iterations per rank (0 = nothing
     // yet; cnmf_get_iteration_means), and the caller's hints for the NEXT calls (cnmf_set_iteration_hints): with hints the
     // queue starts longest-expected-first instead of learning the order again.  Never applied implicitly: the queue order

@@ -76,6 +76,24 @@ def _nndsvd_finish(k, Q, B, transpose, eps=1e-6):
     return np.ascontiguousarray(W.T), H
 
 
+NNDSVD_VARIANTS = ("nndsvd", "nndsvda", "nndsvdar")
+
+
+def _nndsvd_fill(W, H, variant, x_mean, random_state):
+    """The zeros of an NNDSVD start (in place): ``'nndsvda'`` -> ``X.mean()``, ``'nndsvdar'`` -> small random values from
+    ``check_random_state(random_state)`` (sklearn decomposition/_nmf.py, the end of ``_initialize_nmf``)."""
+    if variant == "nndsvda":
+        W[W == 0] = x_mean
+        H[H == 0] = x_mean
+    elif variant == "nndsvdar":
+        rng = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+        W[W == 0] = abs(x_mean * rng.standard_normal(size=len(W[W == 0])) / 100)
+        H[H == 0] = abs(x_mean * rng.standard_normal(size=len(H[H == 0])) / 100)
+    elif variant != "nndsvd":
+        raise ValueError("Invalid init parameter: got %r instead of one of %r" % (variant, NNDSVD_VARIANTS))
+    return W, H
+
+
 class Engine:
     def __init__(self, device=0, detect_counts=True):
         """``detect_counts=False``: never take the integer-plane (count-structured) GEMM path -- see
@@ -979,11 +997,13 @@ class Engine:
     # ------------------------------------------------------------------ restarts
     def nmf_batch(self, ks, seeds=None, W0=None, H0=None, tol=1e-4, max_iter=1000,
                   alpha_W=0.0, alpha_H=0.0, l1_ratio=0.0, return_W=False, kc_max=0, lag=0,
-                  resident=False, warn=True, profile=False):
+                  resident=False, warn=True, profile=False, init_store=False):
         """Run ``len(ks)`` independent CD-NMF restarts on the resident matrix.
 
         Either ``seeds`` (sklearn ``init='random'`` reproduced on the device) or the lists
-        ``W0`` / ``H0`` of explicit initial factors (sklearn layouts N x k and k x G).
+        ``W0`` / ``H0`` of explicit initial factors (sklearn layouts N x k and k x G), or ``init_store=True``: the start
+        factors ``nndsvd_init_batch(ks, ..., tail="device", keep=True)`` left in the context's init store for the same
+        ``ks`` (no transfer; the restarts run in the store's order, the results come back in the caller's).
         Returns ``(H_list, W_list_or_None, n_iter, violation)``."""
         if self.shape is None:
             raise RuntimeError("set_matrix() has not been called")
@@ -994,7 +1014,12 @@ class Engine:
             raise ValueError("n_components must be >= 1")
         prm = self._params(tol, max_iter, alpha_W, alpha_H, l1_ratio, kc_max, lag, profile)
         i32p, u32p, dblp = C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_double)
-        if seeds is not None:
+        perm = None
+        if init_store:
+            perm = self._init_store_perm(n)
+            ks = np.ascontiguousarray(ks[perm])
+            mode, w0p, h0p, seedp, avgp = 2, None, None, None, None
+        elif seeds is not None:
             seeds_a = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64).astype(np.uint32)).ravel()
             if seeds_a.size != n:
                 raise ValueError("need one seed per restart")
@@ -1031,6 +1056,8 @@ class Engine:
             H_list = W_list = None
             offs = row0 + np.concatenate([[0], np.cumsum(ks)]).astype(np.int64)
             self.last_store_offsets = offs[:-1].copy()
+            if perm is not None:
+                self.last_store_offsets[perm] = offs[:-1]
             self.last_store_gen = self.store_gen
             if resident == "keep":
                 if return_W:
@@ -1053,10 +1080,35 @@ class Engine:
                 W_list = [W_out[offs[r] * N:offs[r + 1] * N].reshape(N, ks[r]) for r in range(n)]
         self.last_stats = stats.as_dict()
         n_iter, viol = n_iter[:n], viol[:n]
+        if perm is not None:                                  # back to the caller's order
+            n_iter, viol = self._unpermute(n_iter, perm), self._unpermute(viol, perm)
+            H_list = self._unpermute(H_list, perm) if H_list is not None else None
+            W_list = self._unpermute(W_list, perm) if W_list is not None else None
         if warn and n and tol > 0 and (n_iter == max_iter).any():
             warnings.warn("Maximum number of iterations %d reached. Increase it to improve convergence."
                           % max_iter, ConvergenceWarning)
         return H_list, W_list, n_iter, viol
+
+    last_init_store_order = None       # restart index of every entry of the init store (nndsvd_init_batch(keep=True))
+
+    def _init_store_perm(self, n):
+        """Order in which a batch call that starts from the init store runs the caller's ``n`` restarts (the library
+        refuses a store that does not hold exactly their ranks: ValueError)."""
+        order = self.last_init_store_order
+        if order is None or len(order) != n:
+            return np.arange(n, dtype=np.int64)
+        return np.asarray(order, dtype=np.int64)
+
+    @staticmethod
+    def _unpermute(vals, perm):
+        if isinstance(vals, np.ndarray):
+            out = np.empty_like(vals)
+            out[perm] = vals
+            return out
+        out = [None] * len(vals)
+        for i, r in enumerate(perm):
+            out[int(r)] = vals[i]
+        return out
 
     def iteration_means(self):
         """``{rank: mean outer iterations}`` of the restarts the batch calls on the resident matrix have run so far."""
@@ -1079,10 +1131,10 @@ class Engine:
     _BETA = {"kullback-leibler": 1, "itakura-saito": 0, 1: 1, 0: 0, 1.0: 1, 0.0: 0}
 
     def nmf_mu_batch(self, ks, seeds=None, W0=None, H0=None, beta_loss="kullback-leibler", tol=1e-4,
-                     max_iter=1000, alpha_W=0.0, alpha_H=0.0, l1_ratio=0.0, return_W=False, warn=True):
+                     max_iter=1000, alpha_W=0.0, alpha_H=0.0, l1_ratio=0.0, return_W=False, warn=True, init_store=False):
         """``solver='mu'`` restarts (the reference's path for beta_loss != 'frobenius',
-        cnmf.py:618-631).  Same arguments / returns as :meth:`nmf_batch`; the last element of the
-        returned tuple is sqrt(2*beta-divergence) at the final evaluation."""
+        cnmf.py:618-631).  Same arguments / returns as :meth:`nmf_batch` (``init_store=True`` included); the last element
+        of the returned tuple is sqrt(2*beta-divergence) at the final evaluation."""
         if self.shape is None:
             raise RuntimeError("set_matrix() has not been called")
         if beta_loss not in self._BETA:
@@ -1093,8 +1145,14 @@ class Engine:
         n = int(ks.size)
         prm = self._params(tol, max_iter, alpha_W, alpha_H, l1_ratio)
         i32p, u32p, dblp = C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+        perm = None
+        if init_store:
+            perm = self._init_store_perm(n)
+            ks = np.ascontiguousarray(ks[perm])
         avg = np.ascontiguousarray([self.init_scale(int(k)) for k in ks], dtype=np.float64)
-        if seeds is not None:
+        if init_store:
+            mode, w0p, h0p, seedp = 2, None, None, None
+        elif seeds is not None:
             seeds_a = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64).astype(np.uint32)).ravel()
             mode, w0p, h0p, seedp = 1, None, None, seeds_a.ctypes.data_as(u32p)
         else:
@@ -1114,6 +1172,10 @@ class Engine:
         H_list = [H_out[offs[r]:offs[r + 1]] for r in range(n)]
         W_list = [W_out[offs[r] * N:offs[r + 1] * N].reshape(N, ks[r]) for r in range(n)] if return_W else None
         n_iter, err = n_iter[:n], err[:n]
+        if perm is not None:                                  # back to the caller's order
+            n_iter, err = self._unpermute(n_iter, perm), self._unpermute(err, perm)
+            H_list = self._unpermute(H_list, perm)
+            W_list = self._unpermute(W_list, perm) if W_list is not None else None
         if warn and n and tol > 0 and (n_iter == max_iter).any():
             warnings.warn("Maximum number of iterations %d reached. Increase it to improve convergence."
                           % max_iter, ConvergenceWarning)
@@ -1507,12 +1569,71 @@ class Engine:
         return ([Q[:, offs[i]:offs[i + 1]] for i in range(len(widths))],
                 [B[offs[i]:offs[i + 1]] for i in range(len(widths))])
 
-    def nndsvd_init(self, n_components, random_state=None, eps=1e-6):
+    def nndsvd_init(self, n_components, random_state=None, eps=1e-6, tail="host", variant="nndsvd"):
         """sklearn's ``init='nndsvd'`` for ONE restart (decomposition/_nmf.py:316-354); see :meth:`nndsvd_init_batch`.
         Returns (W0, H0) in float64 (cast to X's dtype by the caller, like sklearn)."""
-        return self.nndsvd_init_batch([n_components], [random_state], eps=eps)[0]
+        return self.nndsvd_init_batch([n_components], [random_state], eps=eps, tail=tail, variant=variant)[0]
 
-    def nndsvd_init_batch(self, ks, random_states, eps=1e-6, max_cols=256, threads=None, device_range_finder=True):
+    # The tail of the last nndsvd_init_batch(tail="device"): "device", or "host_fallback" when a block was refused (rank
+    # below k, sweep cap, a non-finite value) and the whole call took the host route.
+    last_nndsvd_tail = None
+
+    @staticmethod
+    def _nndsvd_groups(ks, n_rand, n_iters, max_cols):
+        """Groups of restarts whose blocks fit one pass AND that make the same number of power iterations."""
+        order = sorted(range(len(ks)), key=lambda r: (n_iters[r], ks[r]))
+        groups, cur, cols = [], [], 0
+        for r in order:
+            if cur and (cols + n_rand[r] > max_cols or n_iters[r] != n_iters[cur[0]]):
+                groups.append(cur); cur, cols = [], 0
+            cur.append(r); cols += n_rand[r]
+        if cur:
+            groups.append(cur)
+        return groups
+
+    def init_store_reset(self):
+        """Empty the context's init store (the start factors ``nndsvd_init_batch(tail="device", keep=True)`` left)."""
+        self._check(self._lib.cnmf_init_store_reset(self._ctx))
+        self._init_store_ks = []
+        self.last_init_store_order = None
+
+    def init_store_fetch(self):
+        """The init store on the host: the list of (W0 [N, k], H0 [k, G]) in float32, in the order of the batch call
+        that starts from it (``init_store=True``)."""
+        N, G = self.shape
+        ks = list(getattr(self, "_init_store_ks", []))
+        tot = max(int(sum(ks)), 1)
+        W = np.empty(tot * N, dtype=np.float32)
+        H = np.empty((tot, G), dtype=np.float32)
+        n = C.c_int32(0)
+        self._check(self._lib.cnmf_init_store_fetch(self._ctx, _fp(W), _fp(H), tot, C.byref(n)))
+        if n.value != len(ks):
+            raise RuntimeError("the init store holds %d restarts, %d were expected" % (n.value, len(ks)))
+        offs = np.concatenate([[0], np.cumsum(ks)]).astype(np.int64)
+        return [(W[offs[r] * N:offs[r + 1] * N].reshape(N, ks[r]), H[offs[r]:offs[r + 1]]) for r in range(len(ks))]
+
+    def _nndsvd_device_tail(self, ks, seeds, groups, n_iters, transpose, variant, eps):
+        """One ``cnmf_nndsvd_group`` call per group into the (emptied) init store.  The store fills group after group:
+        returns (status per restart, the restart index of every store entry)."""
+        i32p, u32p = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+        self.init_store_reset()
+        status = np.zeros(len(ks), dtype=np.int32)
+        order = []
+        for grp in groups:
+            kk = np.ascontiguousarray([ks[r] for r in grp], dtype=np.int32)
+            sd = np.ascontiguousarray(np.asarray([seeds[r] for r in grp], dtype=np.int64).astype(np.uint32))
+            st = np.zeros(len(grp), dtype=np.int32)
+            self._check(self._lib.cnmf_nndsvd_group(self._ctx, int(bool(transpose)), len(grp), kk.ctypes.data_as(i32p),
+                                                    sd.ctypes.data_as(u32p), int(n_iters[grp[0]]),
+                                                    NNDSVD_VARIANTS.index(variant), float(eps), float(self.x_mean),
+                                                    st.ctypes.data_as(i32p)))
+            status[grp] = st
+            order.extend(grp)
+        self._init_store_ks = [ks[r] for r in order]
+        return status, order
+
+    def nndsvd_init_batch(self, ks, random_states, eps=1e-6, max_cols=256, threads=None, device_range_finder=True,
+                          tail="host", variant="nndsvd", keep=False):
         """sklearn's ``init='nndsvd'`` (decomposition/_nmf.py:316-354) for MANY restarts: ``_randomized_svd``
         (utils/extmath.py:531-602: n_oversamples=10, n_iter 7|4, LU-normalised power iterations, final QR, small
         SVD, svd_flip), then the positive/negative split.
@@ -1524,7 +1645,19 @@ class Engine:
         scikit-learn's pivoted LU -- any normaliser leaves the iterated subspace unchanged).  What remains on the host
         per restart is the (k + 10) x G SVD, the sign flip and the positive / negative split.
         ``device_range_finder=False``: every product on the device, LU / QR on a host thread pool (the round-2 scheme,
-        batched).  Returns a list of (W0, H0) in float64."""
+        batched).  Returns a list of (W0, H0) in float64.
+
+        ``variant``: ``'nndsvd'``, ``'nndsvda'`` or ``'nndsvdar'`` -- what becomes of the zeros (:func:`_nndsvd_fill`).
+
+        ``tail="device"`` (integer seeds, k + 10 <= 128, all three variants): ONE library call per group
+        (``cnmf_nndsvd_group``: the start blocks drawn on the device, the range finder, a float64 one-sided Jacobi SVD of
+        every block, flip, split and threshold); the factors come back as float64 arrays holding the float32 values the
+        device rounded to.  ``keep=True`` leaves them in the context's init store instead, in the order
+        ``last_init_store_order`` (restart indices; the groups are sorted by (n_iter, k)), and returns ``None``:
+        ``nmf_batch(ks_in_that_order, init_store=True)`` then starts from the store without a transfer.  When the device
+        refuses a block (status != 0: rank below k, sweep cap, non-finite value) the store is discarded, the WHOLE call
+        takes the host route with one warning, the list is returned whatever ``keep`` says, and ``last_nndsvd_tail`` is
+        ``"host_fallback"`` instead of ``"device"``."""
         from concurrent.futures import ThreadPoolExecutor
         from scipy import linalg
         import os
@@ -1541,6 +1674,34 @@ class Engine:
         n_iters = [7 if k < 0.1 * min(N, G) else 4 for k in ks]
         if max(n_rand) > max_cols:
             raise NotImplementedError("n_components + 10 = %d columns exceed one device pass (%d)" % (max(n_rand), max_cols))
+        if variant not in NNDSVD_VARIANTS:
+            raise ValueError("Invalid init parameter: got %r instead of one of %r" % (variant, NNDSVD_VARIANTS))
+        if tail not in ("host", "device"):
+            raise ValueError("tail must be 'host' or 'device'")
+        groups = self._nndsvd_groups(ks, n_rand, n_iters, max_cols)
+        if tail == "device":
+            if any(not isinstance(rs, (int, np.integer)) for rs in random_states):
+                raise TypeError("tail='device' draws the start blocks on the device: integer seeds only")
+            if max(n_rand) > _lib.CNMF_KMAX or max_cols != 256:
+                raise NotImplementedError("tail='device' needs n_components + 10 <= %d and max_cols = 256" % _lib.CNMF_KMAX)
+            status, order = self._nndsvd_device_tail(ks, random_states, groups, n_iters, transpose, variant, eps)
+            if not status.any():
+                self.last_nndsvd_tail = "device"
+                self.last_init_store_order = order
+                if keep:
+                    return None
+                got = self.init_store_fetch()
+                self.init_store_reset()
+                results = [None] * len(ks)
+                for r, (W, H) in zip(order, got):
+                    results[r] = (W.astype(np.float64), H.astype(np.float64))
+                return results
+            self.init_store_reset()
+            self.last_nndsvd_tail = "host_fallback"
+            self.last_init_store_order = None
+            warnings.warn("NNDSVD: the device tail refused %d of %d restarts (status %s); the whole call takes the host "
+                          "route" % (int((status != 0).sum()), len(ks), sorted(set(int(v) for v in status[status != 0]))),
+                          RuntimeWarning)
         if threads is None:                                  # CPUs this process may really use (affinity, cgroup quota)
             try:
                 threads = len(os.sched_getaffinity(0))
@@ -1575,15 +1736,6 @@ class Engine:
             return _nndsvd_finish(k, Q, B, transpose, eps)
 
         results = [None] * len(ks)
-        # groups of restarts whose blocks fit one pass AND that make the same number of power iterations
-        order = sorted(range(len(ks)), key=lambda r: (n_iters[r], ks[r]))
-        groups, cur, cols = [], [], 0
-        for r in order:
-            if cur and (cols + n_rand[r] > max_cols or n_iters[r] != n_iters[cur[0]]):
-                groups.append(cur); cur, cols = [], 0
-            cur.append(r); cols += n_rand[r]
-        if cur:
-            groups.append(cur)
         on_device = device_range_finder and max(n_rand) <= _lib.CNMF_KMAX
         pending = []
 
@@ -1619,6 +1771,9 @@ class Engine:
             pool.shutdown(wait=True)
             if blas_limit is not None:
                 blas_limit.restore_original_limits()
+        if variant != "nndsvd":
+            for r, (W, H) in enumerate(results):
+                _nndsvd_fill(W, H, variant, self.x_mean, random_states[r])
         return results
 
     # ------------------------------------------------------------------ consensus core

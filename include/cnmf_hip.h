@@ -420,6 +420,9 @@ int cnmf_harmony_kmeans_init(cnmf_ctx* ctx, int32_t n_init, int32_t max_iter, do
  *   init_mode 1 (random): the library reproduces sklearn's init='random' on the device
  *       from `seeds` (numpy RandomState(seed): MT19937 + legacy polar gauss, H drawn
  *       before W) scaled by avg[r] = sqrt(X.mean()/k[r]); W0/H0 are ignored.
+ *   init_mode 2 (init store): the factors cnmf_nndsvd_group left in the context's init store, no
+ *       transfer; seeds / avg / W0 / H0 are ignored.  CNMF_EINVAL when the store is empty or does
+ *       not hold exactly the ranks k[] of the call on this matrix.
  *
  *   H_out  [sum k][G]   required.   W_out packed [N][k[r]] blocks, may be NULL
  *   (cNMF.factorize drops the usages, cnmf.py:741-745).
@@ -697,6 +700,26 @@ int64_t cnmf_format_rows_f64(const double* vals, int64_t rows, int64_t cols, cha
  * per block, B_out [C][M_cols] = Q^T M.  The small SVD / sign flip / NNDSVD split stay with the caller.           */
 int cnmf_range_finder(cnmf_ctx* ctx, int transpose, int nblocks, const int32_t* widths, const float* Q0, int n_iter,
                       float* Q_out, float* B_out);
+
+/* init='nndsvd' / 'nndsvda' / 'nndsvdar' for one GROUP of restarts ENTIRELY on the device (nndsvd_tail_host.hip.h): `nblocks` restarts
+ * of ranks k[b] (blocks of k[b] + 10 <= CNMF_KMAX columns, sum <= 256).  The start block of restart b is
+ * RandomState(seeds[b]).normal(size=(M_cols, k[b] + 10)) cast to float32, drawn on the device; the range finder is the one
+ * of cnmf_range_finder; the small SVD of every B_b is a float64 one-sided Jacobi (at most 30 sweeps); back-transformation,
+ * svd_flip, the positive / negative split and the `eps` threshold follow in float64.  variant 0: 'nndsvd'; 1: 'nndsvda'
+ * (zeros become x_mean = X.mean()); 2: 'nndsvdar' (zeros become |x_mean z / 100|, z the first normals of a fresh
+ * RandomState(seeds[b]), handed out in row-major order of W [N][k], then of H).  The factors are rounded once to float32 and APPENDED to the context's init store
+ * (H0 [sum k][G], W0^T [sum k][N]) together with max W0 of every restart; init_mode 2 of the batch calls starts from the
+ * store.  status_out[b]: 0 accepted; bit 0: sweep cap hit, bit 1: a value is not finite, bit 2: S_j == 0 for a j < k[b]
+ * (a block of rank below k[b]) -- the caller discards the store then.  Same bits on every run.
+ * A new or rewritten matrix empties the store. */
+int cnmf_nndsvd_group(cnmf_ctx* ctx, int transpose, int nblocks, const int32_t* k, const uint32_t* seeds, int n_iter,
+                      int variant, double eps, double x_mean, int32_t* status_out);
+/* Empty the init store (its memory stays with the context). */
+int cnmf_init_store_reset(cnmf_ctx* ctx);
+/* The init store on the host, restart after restart in the packing of the batch calls: W0 packed [N][k_r] blocks,
+ * H0 [sum k][G]; *n_out = restarts held.  W0 / H0 may be NULL (only the count); rows_cap: the component rows (sum k) the
+ * arrays have room for (CNMF_EINVAL when the store holds more). */
+int cnmf_init_store_fetch(cnmf_ctx* ctx, float* W0, float* H0, int64_t rows_cap, int32_t* n_out);
 /* (the diagnostic entry points the tests use -- cnmf_debug_* -- are declared in cnmf_hip_debug.h and exist only in a
  * library built with -DCNMF_DEBUG_ABI; they are not part of the drop-in boundary) */
 

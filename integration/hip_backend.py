@@ -29,7 +29,7 @@ import yaml
 import cnmf.cnmf as _ref                      # the UNMODIFIED reference module
 from cnmf.cnmf import load_df_from_npz, save_df_to_npz, worker_filter
 
-from cnmf_amd.engine import Engine
+from cnmf_amd.engine import NNDSVD_VARIANTS, Engine
 from cnmf_amd.standins import DeviceKMeans, device_euclidean_distances, device_silhouette_score
 
 _DEVICE_SOLVERS = {("cd", "frobenius"), ("cd", 2), ("mu", "kullback-leibler"), ("mu", "itakura-saito"), ("mu", 1), ("mu", 0)}
@@ -39,6 +39,7 @@ class cNMF(_ref.cNMF):
     _engine = None
     _untransposed = None          # set by refit_spectra around the inherited call
     _resident = None              # STRONG reference to the matrix object that is on the device (identity check)
+    nndsvd = "host"               # "device": the tail of init='nndsvd*' on the device too (cnmf_amd.cnmf.cNMF.nndsvd)
 
     # -- engine plumbing ---------------------------------------------------------------------------
     def __getstate__(self):       # multiprocessing pickles the object (cnmf.py:254-262): a ctypes handle cannot travel
@@ -59,6 +60,11 @@ class cNMF(_ref.cNMF):
         if sp.issparse(X):
             return all(ptr(getattr(X, n)) == ptr(getattr(R, n)) for n in ("data", "indices", "indptr"))
         return isinstance(X, np.ndarray) and ptr(X) == ptr(R)
+
+    def _nndsvd_tail(self, variant):
+        if self.nndsvd not in ("host", "device"):
+            raise ValueError("cNMF.nndsvd must be 'host' or 'device', not %r" % (self.nndsvd,))
+        return "device" if self.nndsvd == "device" else "host"
 
     def _eng(self, X):
         if self._engine is None:
@@ -114,8 +120,8 @@ class cNMF(_ref.cNMF):
                 W, _ = (eng.nnls_f64 if xdt == np.float64 else eng.nnls)(H, **common)
             return H, W.astype(xdt, copy=False)
         k, seed = int(kw["n_components"]), int(kw["random_state"])
-        if kw.get("init") == "nndsvd":
-            W0, H0 = eng.nndsvd_init(k, random_state=seed)
+        if kw.get("init") in NNDSVD_VARIANTS:
+            W0, H0 = eng.nndsvd_init(k, random_state=seed, variant=kw["init"], tail=self._nndsvd_tail(kw["init"]))
             init = dict(W0=[W0], H0=[H0])
         else:
             init = dict(seeds=[seed])
@@ -147,9 +153,11 @@ class cNMF(_ref.cNMF):
         common = dict(tol=kw.get("tol", 1e-4), max_iter=kw.get("max_iter", 1000), alpha_W=kw.get("alpha_W", 0.0),
                       alpha_H=kw.get("alpha_H", 0.0), l1_ratio=kw.get("l1_ratio", 0.0))
         init = dict(seeds=seeds)
-        if kw.get("init") == "nndsvd":
-            inits = eng.nndsvd_init_batch(ks, seeds)           # range finders of up to 13 restarts per pass over X
-            init = dict(W0=[w for w, _ in inits], H0=[h for _, h in inits])
+        if kw.get("init") in NNDSVD_VARIANTS:
+            tail = self._nndsvd_tail(kw["init"])
+            # range finders of up to 13 restarts per pass over X; tail "device": the factors wait in the engine's init store
+            inits = eng.nndsvd_init_batch(ks, seeds, variant=kw["init"], tail=tail, keep=tail == "device")
+            init = dict(init_store=True) if inits is None else dict(W0=[w for w, _ in inits], H0=[h for _, h in inits])
         if kw.get("solver", "cd") == "mu":
             H, _, _, _ = eng.nmf_mu_batch(ks, beta_loss=kw["beta_loss"], **init, **common)
         else:
