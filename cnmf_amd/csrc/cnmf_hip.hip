@@ -14,6 +14,7 @@
 // One translation unit; the pieces, in include order:
 //   kernels_*.hip.h      device code (GEMMs, sweeps, RNG, counts, consensus, MU)
 //   runtime.hip.h        cnmf_ctx, error plumbing, scope-bound device buffers / events
+//   kernels_segments.hip.h   one wavefront per row / column: the indexing, walk and fixed-order butterfly of the staging kernels
 //   gemm_host.hip.h      GEMM / sweep launchers, stream-K plans, operand planes, count-structure detection
 //   (this file)          lifecycle, upload of the data matrix
 //   batch_host.hip.h     batch buffers, the restart loop (run_batch: operand scheme, installs, launches), NNLS refit;
@@ -50,6 +51,7 @@
 using namespace cnmf;
 
 #include "runtime.hip.h"
+#include "kernels_segments.hip.h"
 #include "csr_host.hip.h"
 #include "gemm_host.hip.h"
 

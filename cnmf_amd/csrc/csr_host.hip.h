@@ -9,7 +9,8 @@
 //   * X^T's compressed rows are built ON THE DEVICE from those of X -- no transposed upload: a counting sort whose order
 //     is fixed by construction (row chunks in order, the rows of a chunk one after the other, the entries of a row -- distinct
 //     columns -- side by side), so every column lists its entries by ascending row, run to run identical.
-// Included by cnmf_hip.hip (after runtime.hip.h).
+// Included by cnmf_hip.hip (after runtime.hip.h and kernels_segments.hip.h, whose indexing, walk and butterfly the
+// wavefront-per-row kernels here use; csc_xtw_f64_kernel and csr_residual_rows_kernel still spell theirs out).
 #pragma once
 
 namespace cnmf {
@@ -18,14 +19,13 @@ namespace cnmf {
 __global__ __launch_bounds__(256) void csr_count_dense_kernel(const float* __restrict__ M, int ld, int R, int C,
                                                               long long* __restrict__ cnt)
 {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int row = seg_index();
     if (row >= R) return;
     const float* m = M + (size_t)row * ld;
     int n = 0;
-    for (int c = lane; c < C; c += 64) n += (m[c] != 0.f) ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-    if (lane == 0) cnt[row] = n;
+    seg_for_each(0, C, [&](long long c) { n += (m[c] != 0.f) ? 1 : 0; });
+    n = seg_sum(n);
+    if (seg_lane() == 0) cnt[row] = n;
 }
 
 // Pass 2: a wavefront per row compacts the row in column order
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(256) void csr_fill_dense_kernel(const float* __rest
                                                              const long long* __restrict__ ptr, int* __restrict__ idx,
                                                              float* __restrict__ val)
 {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int row = seg_index(), lane = seg_lane();
     if (row >= R) return;
     const float* m = M + (size_t)row * ld;
     long long base = ptr[row];
@@ -125,23 +125,29 @@ __global__ __launch_bounds__(64) void csr_tr_fill_kernel(const long long* __rest
 // ---- the float64 statistics and products of the consensus tail on the compressed rows of X^T (round 5): a wavefront per
 // gene, its stored entries lane-strided, fixed-order butterfly sums -- so that a Kullback-Leibler run's tail (whose refits
 // walk the stored entries already) never needs the dense N x G_all image of the TPM matrix.
-// mean[g] = sum x / N ;  ssd[g] = sum over ALL cells of (x - mean)^2 = sum_stored (x - mean)^2 + (N - stored) mean^2
-__global__ __launch_bounds__(256) void csc_col_moments_kernel(const long long* __restrict__ tptr, const float* __restrict__ tval,
-                                                              int G, int N, double* __restrict__ mean, double* __restrict__ ssd)
+
+// Per-column moments, a wavefront per output column j (column sel[j] of the transpose, or j), for the float64 staging
+// (prepare_host.hip.h) and the float32 resident matrix alike: with v = x * scale[cell] (scale == nullptr: v = x),
+// mean[j] = sum v / N and ssd[j] = sum over ALL N cells of (v - mean)^2 = sum_stored (v - mean)^2 + (N - stored) mean^2.
+// Two passes, float64, in the order of kernels_segments.hip.h.
+template <typename V>
+__global__ __launch_bounds__(256) void col_moments_kernel(const long long* __restrict__ cptr, const int* __restrict__ crow,
+                                                          const V* __restrict__ cval, const int* __restrict__ sel,
+                                                          int n_out, int N, const double* __restrict__ scale,
+                                                          double* __restrict__ mean, double* __restrict__ ssd)
 {
-    const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (g >= G) return;
-    const long long b = tptr[g], e = tptr[g + 1];
+    const int j = seg_index();
+    if (j >= n_out) return;
+    const int g = sel ? sel[j] : j;
+    const long long b = cptr[g], e = cptr[g + 1];
+    auto value = [&](long long p) { return scale ? (double)cval[p] * scale[crow[p]] : (double)cval[p]; };
     double s = 0.0;
-    for (long long p = b + lane; p < e; p += 64) s += (double)tval[p];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    const double mu = s / (double)N;
+    seg_for_each(b, e, [&](long long p) { s += value(p); });
+    const double mu = seg_sum(s) / (double)N;
     double q = 0.0;
-    for (long long p = b + lane; p < e; p += 64) { const double d = (double)tval[p] - mu; q += d * d; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-    if (lane == 0) { mean[g] = mu; ssd[g] = q + (double)(N - (e - b)) * mu * mu; }
+    seg_for_each(b, e, [&](long long p) { const double d = value(p) - mu; q += d * d; });
+    q = seg_sum(q);
+    if (seg_lane() == 0) { mean[j] = mu; ssd[j] = q + (double)(N - (e - b)) * mu * mu; }
 }
 
 // column sums of W [N][k] (float64), one workgroup per component, fixed order

@@ -3,8 +3,8 @@
 // as their transpose, float64 values, 64-bit row pointers):
 //
 //   * per-gene detection counts (value > 0; a stored zero is no detection) and totals walk the transpose, a wavefront per
-//     column (sc.pp.filter_genes, the mitochondrial share); per-cell sums over a gene mask walk the rows in the order of
-//     prep_row_sums_kernel (n_counts, the mitochondrial totals) -- with no mask they ARE cnmf_preprocess_row_sums;
+//     column (sc.pp.filter_genes, the mitochondrial share); per-cell sums over a gene mask are prep_row_sums_kernel
+//     with that mask (n_counts, the mitochondrial totals) -- with no mask they ARE cnmf_preprocess_row_sums, one body;
 //   * the restriction of the staging to a subset of cells and genes never leaves the device: the kept entries of every
 //     kept row are counted, an exclusive scan (FLT_SCAN_BLOCK items per workgroup: block sums, a scan of the block sums,
 //     the blocks again) makes the new row pointers and the old -> new maps of rows and columns, and a wavefront per row
@@ -13,7 +13,8 @@
 //   * the staged CSR comes back raw or library-size normalised (x * scale[row], the scale of prep_row_scale_kernel: the
 //     product cnmf_preprocess_select forms, bit for bit).
 //
-// Integer counters and fixed-order float64 sums only -- no float atomics: two calls on the same input give the same bits.
+// Integer counters and fixed-order float64 sums only (the order: kernels_segments.hip.h) -- no float atomics: two calls on
+// the same input give the same bits.
 // Included by cnmf_hip.hip (after preprocess_host.hip.h).
 #pragma once
 
@@ -23,46 +24,25 @@ constexpr int FLT_SCAN_ITEMS = 4;                        // consecutive items pe
 constexpr int FLT_SCAN_BLOCK = 256 * FLT_SCAN_ITEMS;     // items one scan workgroup covers
 
 // one wavefront per column g of the transposed counts: n_cells[g] = stored entries > 0, totals[g] = their sum, over the
-// cells with mask[cell] != 0 (mask == nullptr: all cells); lane-strided, fixed butterfly
+// cells with mask[cell] != 0 (mask == nullptr: all cells), in the order of kernels_segments.hip.h
 __global__ __launch_bounds__(256) void flt_gene_detect_kernel(const long long* __restrict__ cptr, const int* __restrict__ crow,
-                                                              const double* __restrict__ cval, int G, int N,
+                                                              const double* __restrict__ cval, int G,
                                                               const unsigned char* __restrict__ mask,
                                                               long long* __restrict__ n_cells, double* __restrict__ totals)
 {
-    const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int g = seg_index();
     if (g >= G) return;
     int n = 0;
     double s = 0.0;
-    for (long long p = cptr[g] + lane; p < cptr[g + 1]; p += 64) {
-        const int r = crow[p];
-        if (r < 0 || r >= N || (mask && !mask[r])) continue;
+    seg_for_each(cptr[g], cptr[g + 1], [&](long long p) {
+        if (mask && !mask[crow[p]]) return;
         const double v = cval[p];
         n += v > 0.0 ? 1 : 0;
         s += v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { n += __shfl_xor(n, o, 64); s += __shfl_xor(s, o, 64); }
-    if (lane == 0) { n_cells[g] = n; totals[g] = s; }
-}
-
-// one wavefront per row, in the order of prep_row_sums_kernel: the sum of the entries whose gene has mask[gene] != 0
-__global__ __launch_bounds__(256) void flt_cell_sums_kernel(const long long* __restrict__ ptr, const int* __restrict__ idx,
-                                                            const double* __restrict__ val, int R, int C,
-                                                            const unsigned char* __restrict__ mask, double* __restrict__ out)
-{
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= R) return;
-    double s = 0.0;
-    for (long long p = ptr[row] + lane; p < ptr[row + 1]; p += 64) {
-        if (mask) {
-            const int c = idx[p];
-            if (c < 0 || c >= C || !mask[c]) continue;
-        }
-        s += val[p];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) out[row] = s;
+    });
+    n = seg_sum(n);
+    s = seg_sum(s);
+    if (seg_lane() == 0) { n_cells[g] = n; totals[g] = s; }
 }
 
 // ---------------------------------------------------------------- exclusive scan over n items, 64-bit sums
@@ -144,23 +124,19 @@ __global__ __launch_bounds__(256) void flt_scan_write_kernel(const T* in, long l
 // one wavefront per row: cnt[new row] = its entries whose gene is kept; rowmap [R + 1] (the scan of keep_rows) names the
 // new row, keep_rows == nullptr: every row stays where it is
 __global__ __launch_bounds__(256) void flt_row_count_kernel(const long long* __restrict__ ptr, const int* __restrict__ idx,
-                                                            int R, int C, const unsigned char* __restrict__ keep_rows,
+                                                            int R, const unsigned char* __restrict__ keep_rows,
                                                             const long long* __restrict__ rowmap,
                                                             const unsigned char* __restrict__ keep_cols, long long R_new,
                                                             long long* __restrict__ cnt)
 {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int row = seg_index();
     if (row >= R || (keep_rows && !keep_rows[row])) return;
     const long long nr = keep_rows ? rowmap[row] : row;
     if (nr < 0 || nr >= R_new) return;
     int n = 0;
-    for (long long p = ptr[row] + lane; p < ptr[row + 1]; p += 64) {
-        const int c = idx[p];
-        n += (c >= 0 && c < C && (!keep_cols || keep_cols[c])) ? 1 : 0;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-    if (lane == 0) cnt[nr] = n;
+    seg_for_each(ptr[row], ptr[row + 1], [&](long long p) { n += (!keep_cols || keep_cols[idx[p]]) ? 1 : 0; });
+    n = seg_sum(n);
+    if (seg_lane() == 0) cnt[nr] = n;
 }
 
 // one wavefront per row compacts it in stored order: every step of 64 entries takes the ballot of "gene kept", an entry's
@@ -175,7 +151,7 @@ __global__ __launch_bounds__(256) void flt_compact_kernel(const long long* __res
                                                           const long long* __restrict__ nptr, int* __restrict__ nidx,
                                                           double* __restrict__ nval)
 {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int row = seg_index(), lane = seg_lane();
     if (row >= R || (keep_rows && !keep_rows[row])) return;
     const long long nr = keep_rows ? rowmap[row] : row;
     if (nr < 0 || nr >= R_new) return;
@@ -240,20 +216,20 @@ extern "C" int cnmf_preprocess_gene_detect(cnmf_ctx* ctx, const uint8_t* cell_ma
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevPool pool;
-    unsigned char* dm = cell_mask ? pool.get<unsigned char>((size_t)N) : nullptr;
+    unsigned char* dm = cell_mask ? pool.put<unsigned char>(cell_mask, (size_t)N, st) : nullptr;
     long long* dn = pool.get<long long>((size_t)G);
     double* dt = pool.get<double>((size_t)G);
     POOL_TRY(ctx, pool);
-    if (dm) HIP_TRY(ctx, hipMemcpyAsync(dm, cell_mask, (size_t)N, hipMemcpyHostToDevice, st));
-    flt_gene_detect_kernel<<<(G + 3) / 4, 256, 0, st>>>(P.columns.ptr, P.columns.idx, P.columns.val, G, N, dm, dn, dt);
+    flt_gene_detect_kernel<<<seg_grid(G), 256, 0, st>>>(P.columns.ptr, P.columns.idx, P.columns.val, G, dm, dn, dt);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(n_cells, dn, (size_t)G * sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(totals, dt, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, dev_fetch(st, n_cells, dn, (size_t)G));
+    HIP_TRY(ctx, dev_fetch(st, totals, dt, (size_t)G));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return CNMF_OK;
 }
 
-extern "C" int cnmf_preprocess_cell_sums(cnmf_ctx* ctx, const uint8_t* gene_mask, double* sums)
+// the one body of cnmf_preprocess_cell_sums and cnmf_preprocess_row_sums (select_mi_host.hip.h: no mask)
+static int pre_cell_sums(cnmf_ctx* ctx, const uint8_t* gene_mask, double* sums)
 {
     using namespace cnmf;
     if (int rc = flt_staged(ctx)) return rc;
@@ -263,15 +239,19 @@ extern "C" int cnmf_preprocess_cell_sums(cnmf_ctx* ctx, const uint8_t* gene_mask
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevPool pool;
-    unsigned char* dm = gene_mask ? pool.get<unsigned char>((size_t)G) : nullptr;
+    unsigned char* dm = gene_mask ? pool.put<unsigned char>(gene_mask, (size_t)G, st) : nullptr;
     double* ds = pool.get<double>((size_t)N);
     POOL_TRY(ctx, pool);
-    if (dm) HIP_TRY(ctx, hipMemcpyAsync(dm, gene_mask, (size_t)G, hipMemcpyHostToDevice, st));
-    flt_cell_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.idx, P.counts.val, N, G, dm, ds);
+    prep_row_sums_kernel<<<seg_grid(N), 256, 0, st>>>(P.counts.ptr, P.counts.idx, P.counts.val, N, dm, ds);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(sums, ds, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, dev_fetch(st, sums, ds, (size_t)N));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return CNMF_OK;
+}
+
+extern "C" int cnmf_preprocess_cell_sums(cnmf_ctx* ctx, const uint8_t* gene_mask, double* sums)
+{
+    return pre_cell_sums(ctx, gene_mask, sums);
 }
 
 extern "C" int cnmf_preprocess_subset(cnmf_ctx* ctx, const uint8_t* keep_cells, const uint8_t* keep_genes,
@@ -285,21 +265,19 @@ extern "C" int cnmf_preprocess_subset(cnmf_ctx* ctx, const uint8_t* keep_cells, 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevPool pool;
-    unsigned char* dkc = keep_cells ? pool.get<unsigned char>((size_t)N) : nullptr;
-    unsigned char* dkg = keep_genes ? pool.get<unsigned char>((size_t)G) : nullptr;
+    unsigned char* dkc = keep_cells ? pool.put<unsigned char>(keep_cells, (size_t)N, st) : nullptr;
+    unsigned char* dkg = keep_genes ? pool.put<unsigned char>(keep_genes, (size_t)G, st) : nullptr;
     long long* rowmap = keep_cells ? pool.get<long long>((size_t)N + 1) : nullptr;
     long long* colmap = keep_genes ? pool.get<long long>((size_t)G + 1) : nullptr;
     long long* bsum = pool.get<long long>((size_t)flt_scan_blocks(std::max(N, G)));
     POOL_TRY(ctx, pool);
     long long Nn = N, Gn = G;
     if (dkc) {
-        HIP_TRY(ctx, hipMemcpyAsync(dkc, keep_cells, (size_t)N, hipMemcpyHostToDevice, st));
         flt_scan<unsigned char>(st, dkc, N, bsum, rowmap);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(&Nn, rowmap + N, sizeof(long long), hipMemcpyDeviceToHost, st));
     }
     if (dkg) {
-        HIP_TRY(ctx, hipMemcpyAsync(dkg, keep_genes, (size_t)G, hipMemcpyHostToDevice, st));
         flt_scan<unsigned char>(st, dkg, G, bsum, colmap);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(&Gn, colmap + G, sizeof(long long), hipMemcpyDeviceToHost, st));
@@ -312,7 +290,7 @@ extern "C" int cnmf_preprocess_subset(cnmf_ctx* ctx, const uint8_t* keep_cells, 
     DevCsrLocal<double> counts, columns;
     long long nnz = 0;
     HIP_TRY(ctx, counts.alloc_ptr(Nn, Gn));
-    flt_row_count_kernel<<<(N + 3) / 4, 256, 0, st>>>(old.ptr, old.idx, N, G, dkc, rowmap, dkg, Nn, counts.ptr);
+    flt_row_count_kernel<<<seg_grid(N), 256, 0, st>>>(old.ptr, old.idx, N, dkc, rowmap, dkg, Nn, counts.ptr);
     flt_scan<long long>(st, counts.ptr, Nn, bsum, counts.ptr);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(&nnz, counts.ptr + Nn, sizeof(long long), hipMemcpyDeviceToHost, st));
@@ -322,7 +300,7 @@ extern "C" int cnmf_preprocess_subset(cnmf_ctx* ctx, const uint8_t* keep_cells, 
         return CNMF_EHIP;
     }
     HIP_TRY(ctx, counts.alloc_entries(nnz));
-    flt_compact_kernel<<<(N + 3) / 4, 256, 0, st>>>(old.ptr, old.idx, old.val, N, G, dkc, rowmap, dkg, colmap, Nn, counts.ptr,
+    flt_compact_kernel<<<seg_grid(N), 256, 0, st>>>(old.ptr, old.idx, old.val, N, G, dkc, rowmap, dkg, colmap, Nn, counts.ptr,
                                                     counts.idx, counts.val);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -346,15 +324,12 @@ extern "C" int cnmf_preprocess_fetch_counts(cnmf_ctx* ctx, double target_sum, in
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevPool pool;
-    const bool scaled = target_sum > 0.0 && values && P.counts.nnz > 0;
-    double* rs = scaled ? pool.get<double>((size_t)N) : nullptr;
-    double* scale = scaled ? pool.get<double>((size_t)N) : nullptr;
-    double* sval = scaled ? pool.get<double>((size_t)P.counts.nnz) : nullptr;
-    POOL_TRY(ctx, pool);
-    if (scaled) {
-        prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, rs);
-        prep_row_scale_kernel<<<(N + 255) / 256, 256, 0, st>>>(rs, N, target_sum, scale);
-        prep_tpm_values_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, scale, sval);
+    double* sval = nullptr;
+    if (target_sum > 0.0 && values && P.counts.nnz > 0) {
+        double *rs, *scale;
+        sval = pool.get<double>((size_t)P.counts.nnz);
+        if (int rc = stage_row_scale(ctx, P, target_sum, pool, &rs, &scale)) return rc;
+        prep_tpm_values_kernel<<<seg_grid(N), 256, 0, st>>>(P.counts.ptr, P.counts.val, N, scale, sval);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (int rc = csr_fetch<double>(ctx, P.counts, indptr, indices, values, sval)) return rc;

@@ -2,7 +2,7 @@
 // preprocess_host.hip.h (ctx->pre: the raw counts as CSR and as their transpose):
 //
 //   * per-gene moments S1 = sum x and S2 = sum x^2 as 64-bit integers over the transpose, a wavefront per column in the
-//     pattern of flt_gene_detect_kernel (lane-strided, a fixed butterfly), with a flag for a value that is no count
+//     order of kernels_segments.hip.h (lane-strided, a fixed butterfly), with a flag for a value that is no count
 //     (negative, non-integer, not finite) and one for a count above HVG_COUNT_MAX = 2^20; with at most HVG_CELLS_MAX =
 //     2^22 cells S2 <= 2^62 never wraps.  The host forms mean and the ddof=1 variance from the exact integers;
 //   * the local fits of skmisc's loess(degree=2, family gaussian) at m evaluation points over n SORTED abscissae, one
@@ -22,8 +22,8 @@
 //   * per-gene sums C1 = sum min(x, clip[g]) and C2 = sum min(x, clip[g])^2 over the transpose, float64, a wavefront per
 //     column as above.
 //
-// Integer counters and fixed-order float64 sums only -- no float atomics: two calls on the same input give the same
-// bits.  Included by cnmf_hip.hip (after filter_host.hip.h).
+// Integer counters and fixed-order float64 sums only (the order: kernels_segments.hip.h) -- no float atomics: two calls
+// on the same input give the same bits.  Included by cnmf_hip.hip (after filter_host.hip.h).
 #pragma once
 
 namespace cnmf {
@@ -35,53 +35,59 @@ constexpr int HVG_FIT_OK = 0, HVG_FIT_ZERO_WIDTH = 1, HVG_FIT_DEFICIENT = 2;
 constexpr double HVG_PIVOT_MIN = 1e-6;
 constexpr int HVG_FIT_THREADS = 256;
 
-// one wavefront per column g of the transposed counts: s1[g] = sum x, s2[g] = sum x^2 as integers, flags[g] = what was
-// met that is no count (left out of the sums)
+// Both O(nnz) kernels serve the one-batch and the per-batch entry points (hvg_batch_host.hip.h).  One wavefront per pair
+// w = b G + g of a batch b = blockIdx.y and a column g of the transposed counts (kernels_segments.hip.h).  start == nullptr:
+// one batch, the whole column.  Otherwise the column is one of the GROUPED transpose and the pair's entries are its run of
+// the rows [start[b], start[b + 1]): the walk begins at the run's first entry, so the additions of a pair are the very
+// sequence the one-batch call performs on the staging restricted to the cells of b.  An empty run gives zeros.
+
+// s1[w] = sum x, s2[w] = sum x^2 as integers, flags[w] = what was met that is no count (left out of the sums)
 __global__ __launch_bounds__(256) void hvg_gene_moments_kernel(const long long* __restrict__ cptr, const int* __restrict__ crow,
-                                                               const double* __restrict__ cval, int G, int N,
-                                                               long long* __restrict__ s1, long long* __restrict__ s2,
-                                                               int* __restrict__ flags)
+                                                               const double* __restrict__ cval, int G,
+                                                               const int* __restrict__ start, long long* __restrict__ s1,
+                                                               long long* __restrict__ s2, int* __restrict__ flags)
 {
-    const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int g = seg_index(), bt = blockIdx.y;
     if (g >= G) return;
+    long long p0 = cptr[g], p1 = cptr[g + 1];
+    if (start) seg_row_run(crow, start[bt], start[bt + 1], &p0, &p1);
     long long a = 0, b = 0;
     int f = 0;
-    for (long long p = cptr[g] + lane; p < cptr[g + 1]; p += 64) {
-        const int r = crow[p];
-        if (r < 0 || r >= N) continue;
+    seg_for_each(p0, p1, [&](long long p) {
         const double v = cval[p];
-        if (!(v >= 0.0) || v != floor(v)) { f |= HVG_FLAG_NOT_COUNT; continue; }
-        if (v > HVG_COUNT_MAX) { f |= HVG_FLAG_TOO_LARGE; continue; }
+        if (!(v >= 0.0) || v != floor(v)) { f |= HVG_FLAG_NOT_COUNT; return; }
+        if (v > HVG_COUNT_MAX) { f |= HVG_FLAG_TOO_LARGE; return; }
         const long long iv = (long long)v;
         a += iv;
         b += iv * iv;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); f |= __shfl_xor(f, o, 64); }
-    if (lane == 0) { s1[g] = a; s2[g] = b; flags[g] = f; }
+    });
+    a = seg_sum(a); b = seg_sum(b); f = seg_or(f);
+    const size_t w = (size_t)bt * G + g;
+    if (seg_lane() == 0) { s1[w] = a; s2[w] = b; flags[w] = f; }
 }
 
-// one wavefront per column g: c1[g] = sum min(x, clip[g]), c2[g] = sum of its square (the square rounded, then added)
+// c1[w] = sum min(x, clip[w]), c2[w] = sum of its square (the square rounded, then added)
 __global__ __launch_bounds__(256) void hvg_clipped_sums_kernel(const long long* __restrict__ cptr, const int* __restrict__ crow,
-                                                               const double* __restrict__ cval, int G, int N,
-                                                               const double* __restrict__ clip, double* __restrict__ c1,
-                                                               double* __restrict__ c2)
+                                                               const double* __restrict__ cval, int G,
+                                                               const int* __restrict__ start, const double* __restrict__ clip,
+                                                               double* __restrict__ c1, double* __restrict__ c2)
 {
 #pragma clang fp contract(off)
-    const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int g = seg_index(), bt = blockIdx.y;
     if (g >= G) return;
-    const double c = clip[g];
+    long long p0 = cptr[g], p1 = cptr[g + 1];
+    if (start) seg_row_run(crow, start[bt], start[bt + 1], &p0, &p1);
+    const size_t w = (size_t)bt * G + g;
+    const double c = clip[w];
     double a = 0.0, b = 0.0;
-    for (long long p = cptr[g] + lane; p < cptr[g + 1]; p += 64) {
-        const int r = crow[p];
-        if (r < 0 || r >= N) continue;
+    seg_for_each(p0, p1, [&](long long p) {
+#pragma clang fp contract(off)
         const double m = fmin(cval[p], c);
         a += m;
         b += m * m;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-    if (lane == 0) { c1[g] = a; c2[g] = b; }
+    });
+    a = seg_sum(a); b = seg_sum(b);
+    if (seg_lane() == 0) { c1[w] = a; c2[w] = b; }
 }
 
 // ---------------------------------------------------------------- pairs of doubles (hi + lo, |lo| <= ulp(hi) / 2)
@@ -187,11 +193,11 @@ __global__ __launch_bounds__(HVG_FIT_THREADS) void hvg_loess_fit_kernel(const do
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
+        seg_butterfly([&](int o) {
+#pragma clang fp contract(off)
             const hvg_dd other = {__shfl_xor(acc[k].hi, o, 64), __shfl_xor(acc[k].lo, o, 64)};
             acc[k] = hvg_add(acc[k], other);             // (a + b on both lanes of a pair: the same bits on every lane)
-        }
+        });
         if (lane == 0) part[wave][k] = acc[k];
     }
     __syncthreads();
@@ -233,35 +239,69 @@ __global__ __launch_bounds__(HVG_FIT_THREADS) void hvg_loess_fit_kernel(const do
 
 }  // namespace cnmf
 
+// The launch and the read-backs of the gene moments over the transpose T: B batches with their row runs in `start`
+// (device, [B + 1]), or one batch over whole columns (B = 1, start == nullptr).  s1, s2 [B][G], flags [B] (host)
+static int hvg_gene_moments(cnmf_ctx* ctx, const DevCsr<double>& T, int B, const int* start, int64_t* s1, int64_t* s2,
+                            int32_t* flags)
+{
+    using namespace cnmf;
+    const int G = (int)T.rows;
+    const size_t W = (size_t)G * B;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevPool pool;
+    long long* d1 = pool.get<long long>(W);
+    long long* d2 = pool.get<long long>(W);
+    int* df = pool.get<int>(W);
+    POOL_TRY(ctx, pool);
+    std::vector<int> hf(W);
+    hvg_gene_moments_kernel<<<dim3(seg_grid(G), B), 256, 0, st>>>(T.ptr, T.idx, T.val, G, start, d1, d2, df);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, dev_fetch(st, s1, d1, W));
+    HIP_TRY(ctx, dev_fetch(st, s2, d2, W));
+    HIP_TRY(ctx, dev_fetch(st, hf.data(), df, W));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b) {
+        int all = 0;
+        for (int g = 0; g < G; ++g) all |= hf[(size_t)b * G + g];
+        flags[b] = all;
+    }
+    return CNMF_OK;
+}
+
+// the same for the clipped sums: clip, c1, c2 [B][G] (host)
+static int hvg_clipped_sums(cnmf_ctx* ctx, const DevCsr<double>& T, int B, const int* start, const double* clip, double* c1,
+                            double* c2)
+{
+    using namespace cnmf;
+    const int G = (int)T.rows;
+    const size_t W = (size_t)G * B;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    DevPool pool;
+    double* dc = pool.put<double>(clip, W, st);
+    double* d1 = pool.get<double>(W);
+    double* d2 = pool.get<double>(W);
+    POOL_TRY(ctx, pool);
+    hvg_clipped_sums_kernel<<<dim3(seg_grid(G), B), 256, 0, st>>>(T.ptr, T.idx, T.val, G, start, dc, d1, d2);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, dev_fetch(st, c1, d1, W));
+    HIP_TRY(ctx, dev_fetch(st, c2, d2, W));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return CNMF_OK;
+}
+
 extern "C" int cnmf_preprocess_gene_moments(cnmf_ctx* ctx, int64_t* s1, int64_t* s2, int32_t* flags)
 {
     using namespace cnmf;
     if (int rc = flt_staged(ctx)) return rc;
     if (!s1 || !s2 || !flags) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     PreStage& P = ctx->pre;
-    const int N = (int)P.N, G = (int)P.counts.cols;
     if (P.N > HVG_CELLS_MAX) {
         SET_ERR(ctx, "gene_moments: %lld cells, more than %lld (sum x^2 must stay an exact int64)", (long long)P.N, HVG_CELLS_MAX);
         return CNMF_EINVAL;
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    DevPool pool;
-    long long* d1 = pool.get<long long>((size_t)G);
-    long long* d2 = pool.get<long long>((size_t)G);
-    int* df = pool.get<int>((size_t)G);
-    POOL_TRY(ctx, pool);
-    std::vector<int> hf((size_t)G);
-    hvg_gene_moments_kernel<<<(G + 3) / 4, 256, 0, st>>>(P.columns.ptr, P.columns.idx, P.columns.val, G, N, d1, d2, df);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(s1, d1, (size_t)G * sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(s2, d2, (size_t)G * sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(hf.data(), df, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    int all = 0;
-    for (int f : hf) all |= f;
-    *flags = all;
-    return CNMF_OK;
+    return hvg_gene_moments(ctx, P.columns, 1, nullptr, s1, s2, flags);
 }
 
 extern "C" int cnmf_preprocess_clipped_sums(cnmf_ctx* ctx, const double* clip, double* c1, double* c2)
@@ -269,22 +309,7 @@ extern "C" int cnmf_preprocess_clipped_sums(cnmf_ctx* ctx, const double* clip, d
     using namespace cnmf;
     if (int rc = flt_staged(ctx)) return rc;
     if (!clip || !c1 || !c2) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
-    PreStage& P = ctx->pre;
-    const int N = (int)P.N, G = (int)P.counts.cols;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    DevPool pool;
-    double* dc = pool.get<double>((size_t)G);
-    double* d1 = pool.get<double>((size_t)G);
-    double* d2 = pool.get<double>((size_t)G);
-    POOL_TRY(ctx, pool);
-    HIP_TRY(ctx, hipMemcpyAsync(dc, clip, (size_t)G * sizeof(double), hipMemcpyHostToDevice, st));
-    hvg_clipped_sums_kernel<<<(G + 3) / 4, 256, 0, st>>>(P.columns.ptr, P.columns.idx, P.columns.val, G, N, dc, d1, d2);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(c1, d1, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(c2, d2, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return CNMF_OK;
+    return hvg_clipped_sums(ctx, ctx->pre.columns, 1, nullptr, clip, c1, c2);
 }
 
 extern "C" int cnmf_preprocess_loess_fit(cnmf_ctx* ctx, int64_t n, const double* x, const double* y, int64_t q, int64_t m,
@@ -308,21 +333,18 @@ extern "C" int cnmf_preprocess_loess_fit(cnmf_ctx* ctx, int64_t n, const double*
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevPool pool;
-    double* dx = pool.get<double>((size_t)n);
-    double* dy = pool.get<double>((size_t)n);
-    double* d0 = pool.get<double>((size_t)m);
+    double* dx = pool.put<double>(x, (size_t)n, st);
+    double* dy = pool.put<double>(y, (size_t)n, st);
+    double* d0 = pool.put<double>(x0, (size_t)m, st);
     double* dv = pool.get<double>((size_t)m);
     double* ds = pool.get<double>((size_t)m);
     int* dst = pool.get<int>((size_t)m);
     POOL_TRY(ctx, pool);
-    HIP_TRY(ctx, hipMemcpyAsync(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(dy, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d0, x0, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
     hvg_loess_fit_kernel<<<(unsigned)m, HVG_FIT_THREADS, 0, st>>>(dx, dy, (int)n, (int)q, d0, (int)m, dv, ds, dst);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(value, dv, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(slope, ds, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(status, dst, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, dev_fetch(st, value, dv, (size_t)m));
+    HIP_TRY(ctx, dev_fetch(st, slope, ds, (size_t)m));
+    HIP_TRY(ctx, dev_fetch(st, status, dst, (size_t)m));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return CNMF_OK;
 }

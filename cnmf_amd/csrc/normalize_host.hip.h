@@ -78,7 +78,8 @@ extern "C" int cnmf_col_moments(cnmf_ctx* ctx, double* mean_out, double* ssd_out
         double* m_ = pool_.get<double>(G_);
         double* s_ = pool_.get<double>(G_);
         POOL_TRY(ctx, pool_);
-        csc_col_moments_kernel<<<(G_ + 3) / 4, 256, 0, ctx->stream>>>(ctx->csc.ptr, ctx->csc.val, G_, N_, m_, s_);
+        col_moments_kernel<float><<<seg_grid(G_), 256, 0, ctx->stream>>>(ctx->csc.ptr, ctx->csc.idx, ctx->csc.val, nullptr, G_, N_,
+                                                                          nullptr, m_, s_);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(mean_out, m_, (size_t)G_ * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(ssd_out, s_, (size_t)G_ * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

@@ -5,8 +5,8 @@
 //   * the counts arrive as CSR with 64-bit row pointers; values are kept in float64 on the device;
 //   * per-gene statistics walk the columns: the CSR is transposed on the device by the counting sort of csr_host.hip.h
 //     (row chunks in order, one wavefront per chunk, integer counters only), so every column lists its cells in
-//     ascending order and a wavefront per gene sums them lane-strided with a fixed butterfly -- no float atomics, two
-//     calls give the same bits;
+//     ascending order and a wavefront per gene sums them in the fixed order of kernels_segments.hip.h (lane-strided,
+//     one butterfly) -- no float atomics, two calls give the same bits;
 //   * the column subset is the same counting sort run the other way over the chosen columns, in list order: the rows of
 //     the result list their new columns in ascending order by construction (scipy's canonical CSR), whatever the order
 //     of the gene list.
@@ -25,32 +25,36 @@ __global__ __launch_bounds__(256) void prep_widen_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void prep_check_kernel(const long long* __restrict__ ptr, const int* __restrict__ idx,
                                                          const double* __restrict__ val, int R, int C, int* __restrict__ bad)
 {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int row = seg_index();
     if (row >= R) return;
     const long long b = ptr[row], e = ptr[row + 1];
     int flag = 0;
-    for (long long p = b + lane; p < e; p += 64) {
+    seg_for_each(b, e, [&](long long p) {
         const int c = idx[p];
         if (c < 0 || c >= C) flag |= 2;
         if (p > b && idx[p - 1] >= c) flag |= 1;
         const double v = val[p];
         if (!(v > 0.0) || !isfinite(v)) flag |= 4;
         if (!(v >= 0.0) || !isfinite(v)) flag |= 8;
-    }
+    });
     if (flag) atomicOr(bad, flag);
 }
 
-// one wavefront per row: float64 sum of the stored values (lane-strided, fixed butterfly order)
-__global__ __launch_bounds__(256) void prep_row_sums_kernel(const long long* __restrict__ ptr, const double* __restrict__ val,
-                                                            int R, double* __restrict__ out)
+// one wavefront per row: the float64 sum of the stored values whose column has mask[column] != 0 (mask == nullptr: of
+// all of them; idx is read only under a mask), in the order of kernels_segments.hip.h
+__global__ __launch_bounds__(256) void prep_row_sums_kernel(const long long* __restrict__ ptr, const int* __restrict__ idx,
+                                                            const double* __restrict__ val, int R,
+                                                            const unsigned char* __restrict__ mask, double* __restrict__ out)
 {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int row = seg_index();
     if (row >= R) return;
     double s = 0.0;
-    for (long long p = ptr[row] + lane; p < ptr[row + 1]; p += 64) s += val[p];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) out[row] = s;
+    seg_for_each(ptr[row], ptr[row + 1], [&](long long p) {
+        if (mask && !mask[idx[p]]) return;
+        s += val[p];
+    });
+    s = seg_sum(s);
+    if (seg_lane() == 0) out[row] = s;
 }
 
 // TPM factor of every cell: target / total, 0 for a cell without counts (sc.pp.normalize_total)
@@ -65,37 +69,10 @@ __global__ __launch_bounds__(256) void prep_row_scale_kernel(const double* __res
 __global__ __launch_bounds__(256) void prep_tpm_values_kernel(const long long* __restrict__ ptr, const double* __restrict__ val,
                                                               int R, const double* __restrict__ scale, double* __restrict__ out)
 {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int row = seg_index();
     if (row >= R) return;
     const double f = scale ? scale[row] : 1.0;
-    for (long long p = ptr[row] + lane; p < ptr[row + 1]; p += 64) out[p] = scale ? val[p] * f : val[p];
-}
-
-// Per-column moments over the transposed counts, a wavefront per output column j (gene sel[j], or j): with
-// v = x * scale[cell] (scale == nullptr: v = x), mean[j] = sum v / N and ssd[j] = sum over ALL N cells of (v - mean)^2
-// = sum_stored (v - mean)^2 + (N - stored) mean^2.  Two passes, float64, fixed order.
-__global__ __launch_bounds__(256) void prep_col_moments_kernel(const long long* __restrict__ cptr, const int* __restrict__ crow,
-                                                               const double* __restrict__ cval, const int* __restrict__ sel,
-                                                               int n_out, int N, const double* __restrict__ scale,
-                                                               double* __restrict__ mean, double* __restrict__ ssd)
-{
-    const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (j >= n_out) return;
-    const int g = sel ? sel[j] : j;
-    const long long b = cptr[g], e = cptr[g + 1];
-    double s = 0.0;
-    for (long long p = b + lane; p < e; p += 64) s += scale ? cval[p] * scale[crow[p]] : cval[p];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    const double mu = s / (double)N;
-    double q = 0.0;
-    for (long long p = b + lane; p < e; p += 64) {
-        const double d = (scale ? cval[p] * scale[crow[p]] : cval[p]) - mu;
-        q += d * d;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-    if (lane == 0) { mean[j] = mu; ssd[j] = q + (double)(N - (e - b)) * mu * mu; }
+    seg_for_each(ptr[row], ptr[row + 1], [&](long long p) { out[p] = scale ? val[p] * f : val[p]; });
 }
 
 // the images of the selected matrix, a wavefront per row: the float32 dense image (X, leading dimension ld), the float32
@@ -104,18 +81,33 @@ __global__ __launch_bounds__(256) void prep_store_kernel(const long long* __rest
                                                          const double* __restrict__ val, int R, int C, int ld,
                                                          float* __restrict__ X, float* __restrict__ v32, double* __restrict__ d64)
 {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int row = seg_index();
     if (row >= R) return;
-    for (long long p = ptr[row] + lane; p < ptr[row + 1]; p += 64) {
+    seg_for_each(ptr[row], ptr[row + 1], [&](long long p) {
         const double v = val[p];
         const int c = idx[p];
         if (X) X[(size_t)row * ld + c] = (float)v;
         if (v32) v32[p] = (float)v;
         if (d64) d64[(size_t)row * C + c] = v;
-    }
+    });
 }
 
 }  // namespace cnmf
+
+// The row sums of the staged counts S (*rs) and, when target_sum > 0, normalize_total's factor of every cell (*scale, else
+// nullptr): both allocated from `pool`, both launches queued on the stream
+static int stage_row_scale(cnmf_ctx* ctx, const CountStage& S, double target_sum, DevPool& pool, double** rs, double** scale)
+{
+    using namespace cnmf;
+    const int N = (int)S.counts.rows;
+    *rs = pool.get<double>(N);
+    *scale = target_sum > 0.0 ? pool.get<double>(N) : nullptr;
+    POOL_TRY(ctx, pool);
+    prep_row_sums_kernel<<<seg_grid(N), 256, 0, ctx->stream>>>(S.counts.ptr, S.counts.idx, S.counts.val, N, nullptr, *rs);
+    if (*scale) prep_row_scale_kernel<<<(N + 255) / 256, 256, 0, ctx->stream>>>(*rs, N, target_sum, *scale);
+    HIP_TRY(ctx, hipGetLastError());
+    return CNMF_OK;
+}
 
 // the transpose of the staging paths: float64 values, at least one row chunk (csr_host.hip.h)
 static int prep_transpose(cnmf_ctx* ctx, const DevCsr<double>& in, const int* sel, const double* div, int64_t n_rows,
@@ -179,8 +171,7 @@ static int stage_counts(cnmf_ctx* ctx, const int64_t* indptr, const int32_t* ind
         }
     }
     int bad = 0;
-    prep_check_kernel<<<(unsigned)((n_cells + 3) / 4), 256, 0, st>>>(counts.ptr, counts.idx, counts.val, (int)n_cells,
-                                                                    (int)n_genes, d_bad);
+    prep_check_kernel<<<seg_grid(n_cells), 256, 0, st>>>(counts.ptr, counts.idx, counts.val, (int)n_cells, (int)n_genes, d_bad);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -233,22 +224,18 @@ extern "C" int cnmf_prepare_tpm_stats(cnmf_ctx* ctx, double target_sum, double* 
     const int N = (int)P.counts.rows, G = (int)P.counts.cols;
     if (int rc = prep_ensure_columns(ctx)) return rc;
     DevPool pool;
-    double* rs = pool.get<double>(N);
-    double* scale = target_sum > 0.0 ? pool.get<double>(N) : nullptr;
+    double *rs, *scale;
     double* m = pool.get<double>(G);
     double* q = pool.get<double>(G);
     double* tv = tpm_data ? pool.get<double>((size_t)std::max<long long>(P.counts.nnz, 1)) : nullptr;
-    POOL_TRY(ctx, pool);
-    prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, rs);
-    if (scale) prep_row_scale_kernel<<<(N + 255) / 256, 256, 0, st>>>(rs, N, target_sum, scale);
-    prep_col_moments_kernel<<<(G + 3) / 4, 256, 0, st>>>(P.columns.ptr, P.columns.idx, P.columns.val, nullptr, G, N, scale, m, q);
-    if (tv) prep_tpm_values_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, scale, tv);
+    if (int rc = stage_row_scale(ctx, P, target_sum, pool, &rs, &scale)) return rc;
+    col_moments_kernel<double><<<seg_grid(G), 256, 0, st>>>(P.columns.ptr, P.columns.idx, P.columns.val, nullptr, G, N, scale, m, q);
+    if (tv) prep_tpm_values_kernel<<<seg_grid(N), 256, 0, st>>>(P.counts.ptr, P.counts.val, N, scale, tv);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(row_sums, rs, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(mean, m, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(var, q, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (tv && P.counts.nnz > 0)
-        HIP_TRY(ctx, hipMemcpyAsync(tpm_data, tv, (size_t)P.counts.nnz * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, dev_fetch(st, row_sums, rs, (size_t)N));
+    HIP_TRY(ctx, dev_fetch(st, mean, m, (size_t)G));
+    HIP_TRY(ctx, dev_fetch(st, var, q, (size_t)G));
+    if (tv && P.counts.nnz > 0) HIP_TRY(ctx, dev_fetch(st, tpm_data, tv, (size_t)P.counts.nnz));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     for (int g = 0; g < G; ++g) var[g] /= (double)N;
     return CNMF_OK;
@@ -278,19 +265,18 @@ static int select_scaled_columns(cnmf_ctx* ctx, const CountStage& S, const doubl
     hipStream_t st = ctx->stream;
     const int N = (int)S.counts.rows, G = (int)S.counts.cols;
     DevPool pool;
-    int* d_genes = pool.get<int>(n_sel);
+    int* d_genes = pool.put<int>(genes, (size_t)n_sel, st);
     double* m = pool.get<double>(n_sel);
     double* q = pool.get<double>(n_sel);
     double* d_div = pool.get<double>(n_sel);
     POOL_TRY(ctx, pool);
-    HIP_TRY(ctx, hipMemcpyAsync(d_genes, genes, (size_t)n_sel * sizeof(int), hipMemcpyHostToDevice, st));
-    prep_col_moments_kernel<<<(n_sel + 3) / 4, 256, 0, st>>>(S.columns.ptr, S.columns.idx, cval, d_genes, n_sel, N, nullptr, m, q);
+    col_moments_kernel<double><<<seg_grid(n_sel), 256, 0, st>>>(S.columns.ptr, S.columns.idx, cval, d_genes, n_sel, N, nullptr, m, q);
     HIP_TRY(ctx, hipGetLastError());
     // one wait for both read-backs: the column pointers (the stored entries of the chosen columns) and the moments
     std::vector<long long> hc((size_t)G + 1);
     std::vector<double> hq(n_sel), div(n_sel);
-    HIP_TRY(ctx, hipMemcpyAsync(hc.data(), S.columns.ptr, ((size_t)G + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(hq.data(), q, (size_t)n_sel * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, dev_fetch(st, hc.data(), S.columns.ptr, (size_t)G + 1));
+    HIP_TRY(ctx, dev_fetch(st, hq.data(), q, (size_t)n_sel));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     long long nnz_sel = 0;
     for (int j = 0; j < n_sel; ++j) {
@@ -328,10 +314,10 @@ extern "C" int cnmf_prepare_select(cnmf_ctx* ctx, int32_t n_sel, const int32_t* 
     DevPool pool;
     double* rs = pool.get<double>(N);
     POOL_TRY(ctx, pool);
-    const unsigned rows_grid = (unsigned)((N + 3) / 4);
-    prep_row_sums_kernel<<<rows_grid, 256, 0, st>>>(out.ptr, out.val, N, rs);
+    const unsigned rows_grid = seg_grid(N);
+    prep_row_sums_kernel<<<rows_grid, 256, 0, st>>>(out.ptr, out.idx, out.val, N, nullptr, rs);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(row_sums_out, rs, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, dev_fetch(st, row_sums_out, rs, (size_t)N));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     // The staged counts and their transpose go BEFORE the images of the new resident matrix are allocated (alloc_matrix
     // lets go of the old resident matrix first): the peak is the larger of the two, not their sum.

@@ -5,7 +5,8 @@
 //     scale (x * target / row sum) is applied on the fly, so the library-size-normalised copy for the PCA and the raw
 //     copy for the correction come from the same staged counts (preprocess.py:316-321);
 //   * sc.pp.scale(zero_center=False, max_value) + the global quantile ceiling (stdscale_quantile_celing, :21-29): the
-//     column moments and the gather are prepare_host.hip.h's (fixed-order float64 sums, counting-sort transposes); the
+//     column moments and the gather are prepare_host.hip.h's (float64 sums in the order of kernels_segments.hip.h,
+//     counting-sort transposes); the
 //     ceiling's order statistics come from a radix select over the float64 bit patterns (all values >= 0, so the bit
 //     order is the value order; -0.0 is taken as +0.0) with integer counters only, the implicit zeros of a CSR slot counted analytically;
 //   * PCA (sc.pp.pca(zero_center=True)): column means and the G x G scatter matrix, then the scores (X - mean) V, on the
@@ -336,14 +337,12 @@ extern "C" int cnmf_preprocess_select(cnmf_ctx* ctx, int32_t slot, int32_t n_sel
     hipStreamSynchronize(st);
     S.release();
     DevPool pool;
-    double* scale = target_sum > 0.0 ? pool.get<double>(N) : nullptr;
-    double* rs = target_sum > 0.0 ? pool.get<double>(N) : nullptr;
+    double *rs, *scale = nullptr;
     double* sval = target_sum > 0.0 ? pool.get<double>((size_t)std::max<long long>(nnz, 1)) : nullptr;
     POOL_TRY(ctx, pool);
-    if (scale) {
+    if (sval) {
         // normalize_total over ALL genes of the staged counts, then the row-scaled values of the transpose
-        prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, rs);
-        prep_row_scale_kernel<<<(N + 255) / 256, 256, 0, st>>>(rs, N, target_sum, scale);
+        if (int rc = stage_row_scale(ctx, P, target_sum, pool, &rs, &scale)) return rc;
         pre_scale_cols_kernel<<<pre_grid(nnz), 256, 0, st>>>(P.columns.idx, P.columns.val, nnz, scale, sval);
     }
     if (int rc = select_scaled_columns(ctx, P, scale ? sval : P.columns.val, n_sel, genes, std_out, &S.csr)) return rc;
@@ -430,7 +429,7 @@ extern "C" int cnmf_preprocess_densify(cnmf_ctx* ctx, int32_t slot)
     HIP_TRY(ctx, hipMalloc((void**)&d, bytes));
     hipError_t e = hipMemsetAsync(d, 0, bytes, st);
     if (e == hipSuccess) {
-        prep_store_kernel<<<(unsigned)((N + 3) / 4), 256, 0, st>>>(S.csr.ptr, S.csr.idx, S.csr.val, N, C, 0, nullptr, nullptr, d);
+        prep_store_kernel<<<seg_grid(N), 256, 0, st>>>(S.csr.ptr, S.csr.idx, S.csr.val, N, C, 0, nullptr, nullptr, d);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);

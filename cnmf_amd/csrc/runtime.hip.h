@@ -426,8 +426,24 @@ struct DevPool {
         if (zero) hipMemsetAsync(p, 0, std::max<size_t>(n, 1) * sizeof(T), st);
         return (T*)p;
     }
+    // n elements holding a copy of host[0 .. n), queued on st (a failed copy is reported by POOL_TRY like a failed allocation)
+    template <typename T> T* put(const T* host, size_t n, hipStream_t st) {
+        T* p = get<T>(n);
+        if (p && n > 0) {
+            hipError_t e = hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) err = e;
+        }
+        return p;
+    }
     ~DevPool() { for (void* p : ptrs) hipFree(p); }
 };
+
+// queues the copy of n device elements to the host array `host` on st (the caller synchronises)
+template <typename T>
+static inline hipError_t dev_fetch(hipStream_t st, void* host, const T* dev, size_t n)
+{
+    return hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, st);
+}
 
 struct EventPool {
     std::vector<hipEvent_t> evs;

@@ -451,10 +451,9 @@ __global__ __launch_bounds__(256) void mi_store_scaled_kernel(const long long* _
                                                               const double* __restrict__ val, int R, int C,
                                                               const double* __restrict__ scale, double* __restrict__ d)
 {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int row = seg_index();
     if (row >= R) return;
-    for (long long p = ptr[row] + lane; p < ptr[row + 1]; p += 64)
-        d[(size_t)row * C + idx[p]] = scale ? val[p] * scale[row] : val[p];
+    seg_for_each(ptr[row], ptr[row + 1], [&](long long p) { d[(size_t)row * C + idx[p]] = scale ? val[p] * scale[row] : val[p]; });
 }
 
 // the ddof=1 std of every column, as numpy's std(axis=0) of a C-ordered matrix sums: row after row
@@ -592,21 +591,8 @@ static int mi_state_arg(cnmf_ctx* ctx, const cnmf_mt_state* s)
 
 extern "C" int cnmf_preprocess_row_sums(cnmf_ctx* ctx, double* row_sums)
 {
-    using namespace cnmf;
-    if (!ctx || !row_sums) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
-    PreStage& P = ctx->pre;
-    if (!P.staged()) { SET_ERR(ctx, "cnmf_preprocess_upload_csr has not been called"); return CNMF_ESTATE; }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int N = (int)P.N;
-    DevPool pool;
-    double* rs = pool.get<double>(N);
-    POOL_TRY(ctx, pool);
-    prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, rs);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(row_sums, rs, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return CNMF_OK;
+    if (!ctx || !row_sums) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }      // (before "nothing staged", as ever)
+    return pre_cell_sums(ctx, nullptr, row_sums);        // (filter_host.hip.h: the cell sums over all genes)
 }
 
 extern "C" int cnmf_preprocess_normalize_dense(cnmf_ctx* ctx, int32_t slot, double target_sum, double max_value,
@@ -626,19 +612,16 @@ extern "C" int cnmf_preprocess_normalize_dense(cnmf_ctx* ctx, int32_t slot, doub
     hipStreamSynchronize(st);
     S.release();
     DevPool pool;
-    double* scale = target_sum > 0.0 ? pool.get<double>(N) : nullptr;
-    double* rs = target_sum > 0.0 ? pool.get<double>(N) : nullptr;
+    double *rs, *scale = nullptr;
     double* sd = pool.get<double>(G);
     POOL_TRY(ctx, pool);
     const long long n = (long long)N * G;
     HIP_TRY(ctx, hipMalloc((void**)&S.dense, (size_t)n * sizeof(double)));
     S.n = G;
     HIP_TRY(ctx, hipMemsetAsync(S.dense, 0, (size_t)n * sizeof(double), st));
-    if (scale) {
-        prep_row_sums_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.val, N, rs);
-        prep_row_scale_kernel<<<(N + 255) / 256, 256, 0, st>>>(rs, N, target_sum, scale);
-    }
-    mi_store_scaled_kernel<<<(N + 3) / 4, 256, 0, st>>>(P.counts.ptr, P.counts.idx, P.counts.val, N, G, scale, S.dense);
+    if (target_sum > 0.0)
+        if (int rc = stage_row_scale(ctx, P, target_sum, pool, &rs, &scale)) return rc;
+    mi_store_scaled_kernel<<<seg_grid(N), 256, 0, st>>>(P.counts.ptr, P.counts.idx, P.counts.val, N, G, scale, S.dense);
     mi_col_std_kernel<<<(G + 255) / 256, 256, 0, st>>>(S.dense, N, G, sd);
     mi_scale_clip_kernel<<<pre_grid(n), 256, 0, st>>>(S.dense, n, G, sd, max_value);
     HIP_TRY(ctx, hipGetLastError());

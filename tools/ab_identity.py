@@ -4,8 +4,9 @@ Prints one JSON line: SHA-256 digests of everything the job's batch calls return
 last_stats fields that describe the schedule.  One process per library and per knob value; the lines must be equal.
 ``hi`` is ``mode`` with three counts raised above the bases of both count formats: under CNMF_GEMM3=3 and 4 both builders
 write a flagged second plane and the GEMM passes take their two-plane count stream.
-``staging`` runs no coordinate-descent batch: it digests every array the prepare / preprocess / filter entry points and
-a Kullback-Leibler batch on the non-zeros return for one small count matrix (staging_matrix).  ``mu`` digests H, W, n_iter
+``staging`` runs no coordinate-descent batch: it digests every array the prepare / preprocess / filter / HVG entry points,
+the column moments of a CSR-resident matrix and a Kullback-Leibler batch on the non-zeros return for one small count matrix
+(staging_matrix) and for a real-valued copy of it, whose fixed-order float64 sums depend on their order.  ``mu`` digests H, W, n_iter
 and err of multiplicative-update calls that refill slots, on the dense matrix pipe and on the non-zeros; run it once per
 arm: no knob, CNMF_MU_VALU=1 (then the first 6 restarts of every call), CNMF_MU_SPARSE=0|1, CNMF_SP_ORDER=0."""
 import hashlib
@@ -135,7 +136,32 @@ def staging():
         put("select_after_subset_%s" % t, eng.preprocess_select(0, np.arange(int(kept.sum()))[::-1], 1e4, None),
             eng.preprocess_fetch(0))
         eng.preprocess_release()
-    # the resident matrix as CSR, Kullback-Leibler on the non-zeros: the compressed rows of X^T come from ensure_csc
+    # The fixed-order sums.  The counts above are integers, whose float64 sums are exact in any order: a real-valued copy
+    # (every entry times a non-dyadic factor of its own) makes the sums depend on their order.
+    R = X.copy()
+    R.data = R.data * (1.0 + 0.37 * np.sin(1.0 + np.arange(R.nnz)))
+    cells, kept = np.arange(N) % 3 != 1, np.arange(G) % 5 != 2
+    codes = (np.arange(N) * 7 % 11 >= np.array([0, 5, 9])[:, None]).sum(axis=0) - 1      # three batches of unequal size
+    assert len(set(np.bincount(codes, minlength=3))) == 3 and codes.min() == 0 and codes.max() == 2
+    eng.preprocess_upload_as_stored(R)
+    put("real_row_sums", eng.preprocess_row_sums())
+    put("real_gene_detect", *eng.preprocess_gene_detect(), *eng.preprocess_gene_detect(cells))
+    put("real_cell_sums", eng.preprocess_cell_sums(), eng.preprocess_cell_sums(kept))
+    put("real_fetch_counts", eng.preprocess_fetch_counts(1e4))
+    put("real_clipped_sums", *eng.preprocess_clipped_sums(0.9 + 0.613 * np.arange(G)))
+    put("real_normalize_dense", eng.preprocess_normalize_dense(0, 1e4, 2.5), eng.preprocess_fetch(0))
+    eng.preprocess_upload_as_stored(X)
+    put("int_gene_moments", *(np.asarray(a) for a in eng.preprocess_gene_moments()))
+    put("int_clipped_sums", *eng.preprocess_clipped_sums(1.0 + np.arange(G) % 4))
+    put("int_gene_moments_batched", *eng.preprocess_gene_moments_batched(codes, 3))
+    put("int_clipped_sums_batched", *eng.preprocess_clipped_sums_batched(codes, 3, 1.0 + np.arange(3 * G).reshape(3, G) % 5))
+    put("int_normalize_dense", eng.preprocess_normalize_dense(1, 0.0, None), eng.preprocess_fetch(1))
+    eng.preprocess_release()
+    # the resident matrix as CSR: the column moments from the compressed rows of X^T (ensure_csc), then Kullback-Leibler
+    # on the non-zeros
+    eng.set_matrix(R.astype(np.float32))
+    assert not eng.matrix_images()["dense"], eng.matrix_images()
+    put("csc_col_mean_var", *eng.col_mean_var())
     eng.set_matrix(X.astype(np.float32))
     H, W, n_iter, err = eng.nmf_mu_batch([5, 5], seeds=[11, 12], max_iter=10, return_W=True, warn=False)
     images = eng.matrix_images()
