@@ -161,7 +161,7 @@ static int pick_scheme(cnmf_ctx* ctx, int KC, PassScheme* out)
     }
     p.use2g = p.use3 && !p.usec && kn.gemm3 >= 4 && ctx->G_pad % G3C_JW == 0 && ctx->N_pad % G3C_JW == 0;
     if (p.use2g && (rc = ensure_x2planes(ctx))) return rc;
-    p.use2h = (p.usec && ctx->counts.fmt == 4) || p.use2g;
+    p.use2h = (p.usec && ctx->counts.fmt >= 4) || p.use2g;
     p.mode = !p.use3 ? 0 : (p.use2g ? 5 : (p.usec ? (p.use2h ? 4 : 3) : std::min(kn.gemm3, 2)));
     p.KbA = ctx->G_pad / 16; p.KbB = ctx->N_pad / 16;
     p.xA = p.use2g ? ctx->x2.passA() : ctx->counts.passA();

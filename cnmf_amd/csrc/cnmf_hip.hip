@@ -288,12 +288,14 @@ extern "C" int cnmf_get_shape(const cnmf_ctx* ctx, int64_t* N, int64_t* G)
 }
 
 // which images of the matrix are resident (bit 0: dense float32 image, 1: compressed rows of X, 2: compressed rows of X^T,
-// 3: dense X^T copy of the dense multiplicative-update kernels, 4 / 5: non-zero images at padded rank 16 / 32, 6: count planes)
+// 3: dense X^T copy of the dense multiplicative-update kernels, 4 / 5: non-zero images at padded rank 16 / 32, 6: count planes,
+// 7: ... held as one byte per count)
 extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
 {
     if (!ctx || !flags) return CNMF_EINVAL;
     *flags = (ctx->X ? 1 : 0) | (ctx->csr.ptr ? 2 : 0) | (ctx->csc.ptr ? 4 : 0) | (ctx->XtF.p ? 8 : 0) |
-             ((ctx->spA[0].ent && ctx->spB[0].ent) ? 16 : 0) | ((ctx->spA[1].ent && ctx->spB[1].ent) ? 32 : 0) | (ctx->counts.C1 ? 64 : 0);
+             ((ctx->spA[0].ent && ctx->spB[0].ent) ? 16 : 0) | ((ctx->spA[1].ent && ctx->spB[1].ent) ? 32 : 0) | (ctx->counts.C1 ? 64 : 0) |
+             ((ctx->counts.C1 && ctx->counts.bytes) ? 128 : 0);
     return CNMF_OK;
 }
 

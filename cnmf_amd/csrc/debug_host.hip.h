@@ -190,7 +190,8 @@ extern "C" int cnmf_debug_gemm3c(cnmf_ctx* ctx, const float* A, const float* Bn,
 
 // C[KC][J] = A[KC][K] . Bn[J][K]^T through the f16 two-plane count kernel (kernels_gemm2h.hip.h): Bn holds
 // non-negative integers <= 65535, A arbitrary non-negative float32.  KC % 256 == 0, K % 64 == 0.  nsub = 1 | 2 sub-blocks
-// per barrier pair (2 only without a second count plane, K % 32 == 0).
+// per barrier pair (2 only without a second count plane, K % 32 == 0).  Bit 8 of `nsub` (256): the count plane as bytes, on
+// the byte form of the two-block stream (instruction streams 0 and 4); with a count above 255 that is CNMF_EINVAL.
 // The row-scale bound the W half-step reports instead of the exact maximum (kernels_sweep.hip.h, RMX = false):
 // sqrt(sum of w^2 over the <= 1024 cells of one sweep workgroup) * 1.0001, one partial per workgroup.
 // grid = (parts, rows / 4): one wave per row and part.
@@ -210,6 +211,7 @@ extern "C" int cnmf_debug_gemm2h(cnmf_ctx* ctx, const float* A, const float* Bn,
                                  int nsplit, int nsub, double* ms_out, int reps)
 {
     const bool sweep_bound = (nsub & 128) != 0;          // bit 7: scale the rows by the W half-step's BOUND, not the exact maximum
+    const bool u8 = (nsub & 256) != 0;                   // bit 8: the count plane as bytes
     nsub &= 127;
     if (!ctx || !A || !Bn || !C) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     if (KC % 256 || K % 64 || J < 1 || nsplit < 1) { SET_ERR(ctx, "debug_gemm2h needs KC %% 256 == 0, K %% 64 == 0"); return CNMF_EINVAL; }
@@ -218,6 +220,11 @@ extern "C" int cnmf_debug_gemm2h(cnmf_ctx* ctx, const float* A, const float* Bn,
     const int Jp = round_up(J, G3C_JW), Kb = K / 16;
     bool has_hi = false;
     for (size_t i = 0; i < (size_t)J * K && !has_hi; ++i) has_hi = Bn[i] > G2_COUNT_BASE;
+    if (u8) {
+        bool fits = (nsub & 15) == 2 && (((nsub >> 4) & 7) == 0 || ((nsub >> 4) & 7) == 4);
+        for (size_t i = 0; i < (size_t)J * K && fits; ++i) fits = Bn[i] <= 255.0f;
+        if (!fits) { SET_ERR(ctx, "debug_gemm2h: byte planes need nsub 2, stream 0 or 4 and counts <= 255"); return CNMF_EINVAL; }
+    }
     DevPool pool;
     EventPool events;
     float* dA = pool.get<float>((size_t)KC * K);
@@ -244,18 +251,20 @@ extern "C" int cnmf_debug_gemm2h(cnmf_ctx* ctx, const float* A, const float* Bn,
     } else
         HIP_TRY(ctx, launch_rowmax_part(st, dA, K, K, KC, K, nullptr, 1, dRmax));
     HIP_TRY(ctx, launch_split2h(st, dA, K, KC, K, dA2, G3_MW, nullptr, dRmax, bparts, dInv));
-    HIP_TRY(ctx, launch_x_planes(st, XPlaneFormat::COUNT_F16, false, dB, K, J, K, Jp, K, dUnit, dB1, dBh, dFl));
+    HIP_TRY(ctx, launch_x_planes(st, u8 ? XPlaneFormat::COUNT_U8 : XPlaneFormat::COUNT_F16, false, dB, K, J, K, Jp, K, dUnit, dB1, dBh, dFl));
     reps = std::max(1, reps);
     const int var = (nsub >> 4) & 7;                     // (upper bits of `nsub`: instruction-stream variant, A/B probes)
     nsub &= 15;
     const int ns = (!has_hi && nsub == 2 && Kb % 2 == 0) ? 2 : 1;
     G2Launch g;                                          // (the instantiation is chosen here, not by g2_form: no knobs)
-    g.A2 = dA2; g.rscale = dInv; g.x = XOperand{dB1, dBh, dFl, nullptr}; g.Kb = Kb;
+    g.A2 = dA2; g.rscale = dInv; g.x = XOperand{dB1, dBh, dFl, nullptr, u8}; g.Kb = Kb;
     g.C[0] = dC; g.ldc = Jp; g.cstride = (long long)KC * Jp; g.KC = KC; g.Jpad = Jp; g.nsplit = nsplit;
     for (int i = 0; i < reps + 1; ++i) {
         if (i == 1) hipEventRecord(e0, st);
         hipError_t e;
         if (has_hi) e = launch_gemm2h_t<1, true>(st, g);
+        else if (u8 && var == 4) e = launch_gemm2h_t<2, false, 4, false, false, true>(st, g);
+        else if (u8) e = launch_gemm2h_t<2, false, 0, false, false, true>(st, g);
         else if (ns == 2 && var == 2) e = launch_gemm2h_t<2, false, 2>(st, g);
         else if (ns == 2 && var == 3) e = launch_gemm2h_t<2, false, 3>(st, g);
         else if (ns == 2 && var == 4) e = launch_gemm2h_t<2, false, 4>(st, g);

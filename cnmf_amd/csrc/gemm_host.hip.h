@@ -219,8 +219,9 @@ static hipError_t launch_gemm3_streamk(hipStream_t st, const StreamK3& sk, const
 // two grid shapes.  X is N x G with leading dimension ld; the planes have rows_pad rows of K k (row tiles of G3C_JW):
 // transpose = false, rows = cells and k = genes, or transpose = true, rows = genes and k = cells.
 //   COUNT_BF16 / COUNT_F16 : aux = the per-gene unit (float), plane1 / flags = the second plane and its block flags or nullptr
+//   COUNT_U8               : aux = the per-gene unit (float), plane0 = one byte per count (every count <= 255, K % 32 == 0); no second plane
 //   SPLIT_F16              : aux = the per-row exponent (int), plane0 / plane1 = the h and m planes
-enum class XPlaneFormat { COUNT_BF16, COUNT_F16, SPLIT_F16 };
+enum class XPlaneFormat { COUNT_BF16, COUNT_F16, SPLIT_F16, COUNT_U8 };
 
 template <class F>
 static hipError_t launch_x_planes_t(hipStream_t st, bool transpose, const float* X, int ld, int N, int G, int rows_pad, int K,
@@ -248,6 +249,9 @@ static hipError_t launch_x_planes(hipStream_t st, XPlaneFormat fmt, bool transpo
     switch (fmt) {
         case XPlaneFormat::COUNT_BF16: return launch_x_planes_t<CountBf16>(st, transpose, X, ld, N, G, rows_pad, K, aux, plane0, plane1, flags);
         case XPlaneFormat::COUNT_F16: return launch_x_planes_t<CountF16>(st, transpose, X, ld, N, G, rows_pad, K, aux, plane0, plane1, flags);
+        case XPlaneFormat::COUNT_U8:
+            if (K % 32 || plane1) return hipErrorInvalidValue;
+            return launch_x_planes_t<CountU8>(st, transpose, X, ld, N, G, rows_pad, K, aux, plane0, nullptr, nullptr);
         default: return launch_x_planes_t<SplitF16>(st, transpose, X, ld, N, G, rows_pad, K, aux, plane0, plane1, flags);
     }
 }
@@ -353,62 +357,68 @@ struct G2Launch {
     const StreamK3* sk = nullptr;           // ... or stream-K: the plan, made with unit = gemm2h_nsub(x.hi != nullptr, Kb, g2_nsub)
     const CdKnobs* kn = nullptr;            // reads g2_gen4, g2_gvar, g2_nsub, g2_xmap
 };
+// (x.bytes: the count plane as bytes -- the U8 instantiations; what ensure_counts built decides, not a knob read here)
 using G2Fn = hipError_t (*)(hipStream_t, const G2Launch&);
 struct G2Entry { G2Form form; G2Fn fn; };
 
-template <int NSUB, bool HI, int VAR = 0, bool PART = false, bool GEN = false>
+template <int NSUB, bool HI, int VAR = 0, bool PART = false, bool GEN = false, bool U8 = false>
 static hipError_t launch_gemm2h_t(hipStream_t st, const G2Launch& g)
 {
-    constexpr int lds = G2Geom<NSUB, HI>::LDS_BYTES;
+    constexpr int lds = G2Geom<NSUB, HI, U8>::LDS_BYTES;
+    if (g.x.bytes != U8) return hipErrorInvalidValue;
     {
-        if (hipError_t e_ = dyn_lds_optin((const void*)gemm2h_kernel<NSUB, HI, VAR, PART, GEN>, lds)) return e_;
+        if (hipError_t e_ = dyn_lds_optin((const void*)gemm2h_kernel<NSUB, HI, VAR, PART, GEN, U8>, lds)) return e_;
     }
     int kb_per = (g.Kb + g.nsplit - 1) / g.nsplit;
     kb_per = ((kb_per + NSUB - 1) / NSUB) * NSUB;            // whole steps
     dim3 grid(g.Jpad / G3C_JW, g.KC / G3_MW, (g.Kb + kb_per - 1) / kb_per);
-    gemm2h_kernel<NSUB, HI, VAR, PART, GEN><<<grid, 512, lds, st>>>(g.A2, g.x.plane, HI ? g.x.hi : nullptr, HI ? g.x.flags : nullptr, g.rscale,
+    gemm2h_kernel<NSUB, HI, VAR, PART, GEN, U8><<<grid, 512, lds, st>>>(g.A2, g.x.plane, HI ? g.x.hi : nullptr, HI ? g.x.flags : nullptr, g.rscale,
                                                                    g.Kb, g.C[0], g.ldc, g.cstride, kb_per, g.x.colscale,
                                                                    PART ? g.livemask : ~0ull);
     return hipGetLastError();
 }
 
-template <int NSUB, bool HI, int VAR = 0, bool NTB = true, bool PART = false, bool GEN = false>
+template <int NSUB, bool HI, int VAR = 0, bool NTB = true, bool PART = false, bool GEN = false, bool U8 = false>
 static hipError_t launch_gemm2h_streamk_t(hipStream_t st, const G2Launch& g)
 {
-    constexpr int lds = G2Geom<NSUB, HI>::LDS_BYTES;
+    constexpr int lds = G2Geom<NSUB, HI, U8>::LDS_BYTES;
+    if (g.x.bytes != U8) return hipErrorInvalidValue;
     {
-        if (hipError_t e_ = dyn_lds_optin((const void*)gemm2h_streamk_kernel<NSUB, HI, VAR, NTB, PART, GEN>, lds)) return e_;
+        if (hipError_t e_ = dyn_lds_optin((const void*)gemm2h_streamk_kernel<NSUB, HI, VAR, NTB, PART, GEN, U8>, lds)) return e_;
     }
-    const int xmap = g2_xmap(G2Form{true, NSUB, HI, VAR, NTB, PART, GEN}, g.kn->g2_xmap);
-    gemm2h_streamk_kernel<NSUB, HI, VAR, NTB, PART, GEN><<<g.sk->P, 512, lds, st>>>(g.A2, g.x.plane, HI ? g.x.hi : nullptr,
+    const int xmap = g2_xmap(G2Form{true, NSUB, HI, VAR, NTB, PART, GEN, U8}, g.kn->g2_xmap);
+    gemm2h_streamk_kernel<NSUB, HI, VAR, NTB, PART, GEN, U8><<<g.sk->P, 512, lds, st>>>(g.A2, g.x.plane, HI ? g.x.hi : nullptr,
                                                                                     HI ? g.x.flags : nullptr, g.rscale, g.Kb, g.C[0], g.C[1],
                                                                                     g.C[2], g.ldc, g.sk->MG, g.sk->T, xmap, g.x.colscale,
                                                                                     PART ? g.livemask : ~0ull);
     return hipGetLastError();
 }
 
-template <int NSUB, bool HI, int VAR, bool PART, bool GEN>
-static constexpr G2Entry g2_ksplit() { return {G2Form{true, NSUB, HI, VAR, false, PART, GEN}, launch_gemm2h_t<NSUB, HI, VAR, PART, GEN>}; }
-template <int NSUB, bool HI, int VAR, bool NTB, bool PART, bool GEN>
-static constexpr G2Entry g2_streamk() { return {G2Form{true, NSUB, HI, VAR, NTB, PART, GEN}, launch_gemm2h_streamk_t<NSUB, HI, VAR, NTB, PART, GEN>}; }
+template <int NSUB, bool HI, int VAR, bool PART, bool GEN, bool U8 = false>
+static constexpr G2Entry g2_ksplit() { return {G2Form{true, NSUB, HI, VAR, false, PART, GEN, U8}, launch_gemm2h_t<NSUB, HI, VAR, PART, GEN, U8>}; }
+template <int NSUB, bool HI, int VAR, bool NTB, bool PART, bool GEN, bool U8 = false>
+static constexpr G2Entry g2_streamk() { return {G2Form{true, NSUB, HI, VAR, NTB, PART, GEN, U8}, launch_gemm2h_streamk_t<NSUB, HI, VAR, NTB, PART, GEN, U8>}; }
 
-// the instantiations production launches take: 9 of gemm2h_kernel, 14 of gemm2h_streamk_kernel
+// the instantiations production launches take: 11 of gemm2h_kernel, 17 of gemm2h_streamk_kernel (the last rows: the
+// byte forms of the two-block count stream)
 static constexpr G2Entry G2_KSPLIT[] = {
     g2_ksplit<1, true, 0, false, true>(),  g2_ksplit<1, true, 0, true, true>(),  g2_ksplit<1, true, 4, false, true>(),
     g2_ksplit<1, true, 4, true, true>(),   g2_ksplit<1, true, 0, false, false>(), g2_ksplit<1, true, 0, true, false>(),
-    g2_ksplit<2, false, 4, false, false>(), g2_ksplit<2, false, 4, true, false>(), g2_ksplit<1, false, 4, false, false>()};
+    g2_ksplit<2, false, 4, false, false>(), g2_ksplit<2, false, 4, true, false>(), g2_ksplit<1, false, 4, false, false>(),
+    g2_ksplit<2, false, 4, false, false, true>(), g2_ksplit<2, false, 4, true, false, true>()};
 static constexpr G2Entry G2_STREAMK[] = {
     g2_streamk<1, true, 0, false, true, true>(),   g2_streamk<1, true, 0, false, false, true>(),  g2_streamk<1, true, 0, true, false, true>(),
     g2_streamk<1, true, 4, false, true, true>(),   g2_streamk<1, true, 4, false, false, true>(),  g2_streamk<1, true, 4, true, false, true>(),
     g2_streamk<1, true, 0, false, true, false>(),  g2_streamk<1, true, 0, false, false, false>(), g2_streamk<1, true, 0, true, false, false>(),
     g2_streamk<2, false, 4, false, true, false>(), g2_streamk<2, false, 4, false, false, false>(), g2_streamk<2, false, 4, true, false, false>(),
-    g2_streamk<1, false, 4, false, false, false>(), g2_streamk<1, false, 4, true, false, false>()};
+    g2_streamk<1, false, 4, false, false, false>(), g2_streamk<1, false, 4, true, false, false>(),
+    g2_streamk<2, false, 4, false, true, false, true>(), g2_streamk<2, false, 4, false, false, false, true>(), g2_streamk<2, false, 4, true, false, false, true>()};
 
 static G2Form g2_form_of(const G2Launch& g, int KC, bool shared)
 {
     const unsigned long long full = g2_full_mask(KC);
     return g2_form(g.x.hi != nullptr, g.x.colscale != nullptr, g.kn->g2_gen4, g.kn->g2_gvar, gemm2h_nsub(false, g.Kb, g.kn->g2_nsub),
-                   (g.livemask & full) != full, shared);
+                   (g.livemask & full) != full, shared, g.x.bytes);
 }
 
 // Instruction streams (the VAR parameter of kernels_gemm2h.hip.h): production launches use 4, the spread stream, and 0,
@@ -457,7 +467,9 @@ static hipError_t launch_rowmax_part(hipStream_t st, const float* V, int ld, int
 // failed call leaves it "not examined", and the next call on this matrix examines it again.
 static int ensure_counts(cnmf_ctx* ctx)
 {
-    const int fmt = ctx->knobs.gemm3 == 4 ? 4 : 3;      // plane format the current mode multiplies
+    // plane format the current mode multiplies; 5: the f16 pipe with the count plane as bytes where every count fits one
+    // (CNMF_G2_U8; the byte plane is read by the two-block stream only: not with CNMF_G2_NSUB=1)
+    const int fmt = ctx->knobs.gemm3 == 4 ? ((ctx->knobs.g2_u8 && ctx->knobs.g2_nsub == 2) ? 5 : 4) : 3;
     if (ctx->counts.state == 1 && ctx->counts.fmt != fmt) {
         // the mode was switched between two calls on the same matrix (tests, A/B runs): rebuild the planes
         hipStreamSynchronize(ctx->stream);
@@ -501,13 +513,17 @@ static int ensure_counts(cnmf_ctx* ctx)
     count_sums_kernel<<<grid, 256, 0, st>>>(ctx->X, ctx->G_pad, N, G, unit, psx, psn);
     count_scale_kernel<<<(ctx->G_pad + 255) / 256, 256, 0, st>>>(psx, psn, chunks, G, ctx->G_pad, L.d_scale);
     // does any count exceed 256?  then a second plane (256 hi) with per-block flags rides along
-    unsigned* any_big = pool.get<unsigned>(1, true, st);
+    // (fmt 5: and does any exceed 255?  if none does, ONE plane of bytes; else exactly the f16 planes of fmt 4)
+    unsigned* any_big = pool.get<unsigned>(2, true, st);
     POOL_TRY(ctx, pool);
-    count_max_base_kernel<<<grid, 256, 0, st>>>(ctx->X, ctx->G_pad, N, G, unit, fmt == 4 ? G2_COUNT_BASE : 256.0f, any_big);
-    unsigned h_big = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&h_big, any_big, sizeof h_big, hipMemcpyDeviceToHost, st));
+    count_max_base_kernel<<<grid, 256, 0, st>>>(ctx->X, ctx->G_pad, N, G, unit, fmt >= 4 ? G2_COUNT_BASE : 256.0f, any_big);
+    if (fmt == 5) count_max_base_kernel<<<grid, 256, 0, st>>>(ctx->X, ctx->G_pad, N, G, unit, 255.0f, any_big + 1);
+    unsigned h_bigs[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(h_bigs, any_big, sizeof h_bigs, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    const size_t bytes = (size_t)ctx->N_pad * ctx->G_pad * 2;
+    const unsigned h_big = h_bigs[0];
+    L.bytes = fmt == 5 && !h_bigs[1];
+    const size_t bytes = (size_t)ctx->N_pad * ctx->G_pad * (L.bytes ? 1 : 2);
     HIP_TRY(ctx, hipMalloc(&L.C1, bytes));
     HIP_TRY(ctx, hipMalloc(&L.Ct1, bytes));
     if (h_big) {
@@ -520,7 +536,7 @@ static int ensure_counts(cnmf_ctx* ctx)
         HIP_TRY(ctx, hipMemsetAsync(L.hiA, 0, nfA, st));
         HIP_TRY(ctx, hipMemsetAsync(L.hiB, 0, nfB, st));
     }
-    const XPlaneFormat pf = fmt == 4 ? XPlaneFormat::COUNT_F16 : XPlaneFormat::COUNT_BF16;
+    const XPlaneFormat pf = L.bytes ? XPlaneFormat::COUNT_U8 : (fmt >= 4 ? XPlaneFormat::COUNT_F16 : XPlaneFormat::COUNT_BF16);
     HIP_TRY(ctx, launch_x_planes(st, pf, false, ctx->X, ctx->G_pad, N, G, ctx->N_pad, ctx->G_pad, unit, L.C1, L.C1h, L.hiA));
     HIP_TRY(ctx, launch_x_planes(st, pf, true, ctx->X, ctx->G_pad, N, G, ctx->G_pad, ctx->N_pad, unit, L.Ct1, L.Ct1h, L.hiB));
     HIP_TRY(ctx, hipGetLastError());

@@ -38,11 +38,21 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels_gemm3.hip.h"
+#include "kernels_planes.hip.h"
 
 namespace cnmf {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4_g __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2_g __attribute__((ext_vector_type(2)));
+
+// build-time A/B switch of the byte form (CNMF_HIPCC_FLAGS=-DG2_U8_SKIP=n): which of the spread stream's six piece places
+// (0..2 in front of Y_s, 3..5 behind it) carries none of the five pieces.  Measured on the production pass-B launch and on
+// the headline: 0 -- no piece behind the step's first eight MFMAs, where its first fragment batch is
+// still landing -- is the fastest, 1 next, 2 and 4 slower than the f16 plane.
+#ifndef G2_U8_SKIP
+#define G2_U8_SKIP 0
+#endif
 
 constexpr int G2_ROWB = 64;                        // factor bytes per row and 16-k block
 constexpr int G2_A = G3_MW * G2_ROWB;              // 16 384 B of factor planes per 16-k block
@@ -51,19 +61,23 @@ constexpr int G2_B = G3C_JW * 32;                  //  8 192 B of one X plane pe
 // One step = NSUB 16-k blocks = one LDS image [A sub-blocks][B sub-blocks][hi sub-blocks], IMGS of them in flight.
 // The workgroup moves an image in pieces of 8 KB (512 lanes x 16 B, one global_load_lds per wave and piece), numbered
 // A 0 .. NA - 1, B NA .. NA + NB - 1, second plane NA + NB .. NA + 2 NB - 1.
-template <int NSUB, bool HI>
+// U8 (NSUB = 2 only): the count plane as bytes (CountU8, kernels_planes.hip.h) -- the 32 k of a step in ONE 8 KB piece, a
+// 40 KB image.
+template <int NSUB, bool HI, bool U8 = false>
 struct G2Geom {
     static_assert(NSUB == 1 || (NSUB == 2 && !HI), "two blocks per step: one count plane only");
+    static_assert(!U8 || NSUB == 2, "the byte plane is read by the 16x16x32 body only");
     static constexpr int IMGS = NSUB == 1 ? 4 : 3;
-    static constexpr int IMG = NSUB * (G2_A + (HI ? 2 : 1) * G2_B);
+    static constexpr int IMG = U8 ? NSUB * G2_A + G2_B : NSUB * (G2_A + (HI ? 2 : 1) * G2_B);
     static constexpr int OFF_B = NSUB * G2_A, OFF_H = OFF_B + NSUB * G2_B;
-    static constexpr int NA = NSUB * 2, NB = NSUB;       // pieces per step (flagged steps of a second plane: NB more)
+    static constexpr int NA = NSUB * 2, NB = U8 ? 1 : NSUB;  // pieces per step (flagged steps of a second plane: NB more)
     static constexpr int AHEAD = IMGS - 1;               // steps requested ahead of the one being multiplied
     static constexpr int LDS_BYTES = IMGS * IMG;
 };
 
-// gemm2h_segment is overloaded on this tag: the kernels name the body of their NSUB by overload resolution
-template <int NSUB> struct G2Sub {};
+// gemm2h_segment is overloaded on this tag: the kernels name the body of their NSUB by overload resolution (U8: the byte
+// form of the NSUB = 2 body)
+template <int NSUB, bool U8 = false> struct G2Sub {};
 
 // Piece i_ of step s_ into its image: one global_load_lds per wave (no wait, no scheduling fence: the caller's).  Reads
 // abase / bbase / hbase (this lane's 16 bytes of the first step's pieces), smem and wave of the body it is used in.
@@ -135,18 +149,32 @@ __device__ __forceinline__ unsigned g2_wave_live(unsigned live, int grp)
 // Per step and wave: 16 + 4 ds_read_b128 (80 fragment registers), 64 MFMAs on acc[8][4] (128 registers); per accumulator
 // the small plane m first, then h.  Element i of acc[mt][nt] is component row mt * 16 + 4 g + i, column nt * 16 + r.
 // Six pieces per step; spread: fragment reads 12 + 8.
-template <int VAR, bool NTB, bool PART>
+//
+// U8, the count plane as bytes (counts <= 255; CountU8 / g2_u8_chunk, kernels_planes.hip.h): the same operands from half the
+// count bytes.  One step of one tile is one 8 KB piece (FIVE pieces per step, a 40 KB image), in which the 16-byte chunk
+// (wn * 2 + p) * 64 + lane  holds what lane (r, g) of wave wn needs of the count tiles nt = 2 p and 2 p + 1: the bytes
+// k = 8 g .. 8 g + 7 of row nt * 16 + r, tile 2 p in the low eight bytes.  The wave fetches them with TWO ds_read_b128
+// (p = 0, 1) instead of four.  No swizzle is needed: a read is 64 consecutive chunks in lane order, so the sixteen lanes
+// of every ds_read_b128 lane group ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32) read chunks whose indices
+// are all different modulo 16 -- sixteen distinct 16-byte bank groups = all 64 banks once: conflict-free.
+// Conversion in registers, exact: v_perm_b32 puts two bytes n under the high byte 0x64 -- the halves 0x6400 | n are
+// f16(1024 + n), whose ulp is 1 --, v_pk_add_f16 takes the 1024 off again (n = 0 gives +0, like the f16 plane): 4 + 4
+// instructions per fragment, bq[nt] bit for bit what the f16 plane holds, in the same element order.
+// Spread stream: two pieces in front of Y_s (behind the second fragment batch and behind the next eight MFMAs), three behind
+// it (G2_U8_SKIP); fragment reads 10 + 8.
+template <int VAR, bool NTB, bool PART, bool U8 = false>
 __device__ __forceinline__ void gemm2h_segment_mf16(const unsigned char* __restrict__ A2, const unsigned char* __restrict__ B1,
                                                     const float* __restrict__ rscale, int Kb, float* __restrict__ C,
                                                     int ldc, int m0, int j0, int kb0, int nkb, unsigned char* smem,
                                                     unsigned live)
 {
     static_assert(VAR == 0 || VAR == 2 || VAR == 3 || VAR == 4 || VAR == 6 || VAR == 7, "instruction streams 1 and 5 were retired");
-    using GEO = G2Geom<2, false>;
+    static_assert(!U8 || VAR == 0 || VAR == 4, "the byte plane has the burst and the spread stream only");
+    using GEO = G2Geom<2, false, U8>;
     constexpr int NSUB = 2, IMGS = GEO::IMGS, IMG = GEO::IMG, OFF_B = GEO::OFF_B, NA = GEO::NA, NB = GEO::NB, AHEAD = GEO::AHEAD;
     constexpr bool BURST = VAR == 0, NOMFMA = VAR == 2, NODMA = VAR == 3 || VAR == 6 || VAR == 7;
     constexpr bool NOREAD = VAR == 6 || VAR == 7, NOBAR = VAR == 7;
-    static_assert(IMGS == 3 && NA + NB == 6, "three images, six pieces per step");
+    static_assert(IMGS == 3 && NA + NB == (U8 ? 5 : 6), "three images, six pieces per step (bytes: five)");
     const int tid = threadIdx.x;                         // 0..511
     const int lane = tid & 63, wave = tid >> 6;
     const int grp = wave >> 2, wn = wave & 3;
@@ -158,7 +186,9 @@ __device__ __forceinline__ void gemm2h_segment_mf16(const unsigned char* __restr
 #define G2_LIVE(mt_) (!PART || ((lv >> ((mt_) >> 1)) & 1u))
 
     const unsigned char* abase = A2 + ((size_t)(m0 / G3_MW) * Kb + kb0) * G2_A + tid * 16;
-    const unsigned char* bbase = B1 + ((size_t)(j0 / G3C_JW) * Kb + kb0) * G2_B + tid * 16;
+    // (bytes: one G2_B run per STEP of the tile, not per block)
+    const unsigned char* bbase = U8 ? B1 + ((size_t)(j0 / G3C_JW) * (Kb / NSUB) + kb0 / NSUB) * G2_B + tid * 16
+                                    : B1 + ((size_t)(j0 / G3C_JW) * Kb + kb0) * G2_B + tid * 16;
     constexpr const unsigned char* hbase = nullptr;      // (G2_DMA_PIECE names it; no second plane here)
 
     f32x4_g acc[8][4];
@@ -172,9 +202,37 @@ __device__ __forceinline__ void gemm2h_segment_mf16(const unsigned char* __restr
     // fragment addresses inside an image (tile mt / nt: + mt * 16 rows of 64 B / + nt * 16 rows of 32 B)
     const int a_row = ub * G2_A + (grp * 128 + r) * G2_ROWB;
     const int a_s0 = ((0 + hf) ^ ((r >> 2) & 3)) * 16, a_s1 = ((2 + hf) ^ ((r >> 2) & 3)) * 16;
-    const int b_off = OFF_B + ub * G2_B + (wn * 64 + r) * 32 + (hf ^ ((r >> 3) & 1)) * 16;
+    const int b_off = U8 ? OFF_B + wn * 2048 + lane * 16 : OFF_B + ub * G2_B + (wn * 64 + r) * 32 + (hf ^ ((r >> 3) & 1)) * 16;
 
-#define G2_PIECE(s_, i_) { G2_DMA_PIECE(2, false, NTB, s_, i_) __builtin_amdgcn_sched_barrier(0); }
+// bytes: pieces 0..3 the factor planes as ever, piece 4 the whole count run of the step
+#define G2_DMA_PIECE_U8(s_, i_)                                                                    \
+    {                                                                                              \
+        unsigned char* d_ = smem + ((s_) % IMGS) * IMG + wave * 1024;                              \
+        if ((i_) < NA)                                                                             \
+            __builtin_amdgcn_global_load_lds(G3_AS1(abase + (size_t)(s_) * (NSUB * G2_A) + (i_) * 8192), \
+                                             G3_AS3(d_ + (i_) * 8192), 16, 0, 0);                  \
+        else                                                                                       \
+            __builtin_amdgcn_global_load_lds(G3_AS1(bbase + (size_t)(s_) * G2_B), G3_AS3(d_ + OFF_B), 16, 0, NTB ? 2 : 0); \
+    }
+#define G2_PIECE(s_, i_) { if constexpr (U8) G2_DMA_PIECE_U8(s_, i_) else G2_DMA_PIECE(2, false, NTB, s_, i_) __builtin_amdgcn_sched_barrier(0); }
+// the spread stream's six places: piece p_ of the f16 plane's six; of the bytes' five, none at place G2_U8_SKIP
+#define G2_SPOT(MORE_, p_)                                                                         \
+    if (!BURST && MORE_) {                                                                         \
+        if constexpr (!U8) G2_PIECE(s + AHEAD, p_)                                                 \
+        else if constexpr ((p_) != G2_U8_SKIP) G2_PIECE(s + AHEAD, (p_) < G2_U8_SKIP ? (p_) : (p_) - 1) \
+    }
+// two bytes of w_ (selected by sel_) under 0x64: two halves 1024 + n; minus 1024
+#define G2_CVT2(w_, sel_) __builtin_bit_cast(unsigned, __builtin_bit_cast(f16x2_g, __builtin_amdgcn_perm(0x64646464u, (w_), (sel_))) - f16x2_g{(_Float16)1024.0f, (_Float16)1024.0f})
+#define G2_SEL_LO 0x04010400u                              /* bytes 0, 1 of w_ */
+#define G2_SEL_HI 0x04030402u                              /* bytes 2, 3 */
+#define G2_CVT(nt_)                                                                                \
+    {                                                                                              \
+        const unsigned w0_ = braw[(nt_) >> 1][2 * ((nt_) & 1)], w1_ = braw[(nt_) >> 1][2 * ((nt_) & 1) + 1]; \
+        u32x4 c_;                                                                                  \
+        c_.x = G2_CVT2(w0_, G2_SEL_LO); c_.y = G2_CVT2(w0_, G2_SEL_HI);                            \
+        c_.z = G2_CVT2(w1_, G2_SEL_LO); c_.w = G2_CVT2(w1_, G2_SEL_HI);                            \
+        bq[nt_] = __builtin_bit_cast(f16x8, c_);                                                   \
+    }
 #define G2_ISSUE(s_) { _Pragma("unroll") for (int i = 0; i < NA + NB; ++i) G2_PIECE(s_, i) }
 #define G2_FRAG(ptr_) __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(ptr_))
 #define G2_AFRAG(bb_, mt_, q_) G2_FRAG((bb_) + a_row + (mt_) * 16 * G2_ROWB + ((q_) ? a_s1 : a_s0))
@@ -184,12 +242,15 @@ __device__ __forceinline__ void gemm2h_segment_mf16(const unsigned char* __restr
 #define G2_READ_A(s_)                                                                              \
     {                                                                                              \
         const unsigned char* bb = smem + ((s_) % IMGS) * IMG;                                      \
-        _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) bq[nt] = G2_FRAG(bb + b_off + nt * 16 * 32); \
+        if constexpr (U8) { _Pragma("unroll") for (int p = 0; p < 2; ++p) braw[p] = *reinterpret_cast<const u32x4*>(bb + b_off + p * 1024); } \
+        else { _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) bq[nt] = G2_FRAG(bb + b_off + nt * 16 * 32); } \
         _Pragma("unroll") for (int mp = 0; mp < 4; mp += 2) {                                      \
             aq[mp][1] = G2_AFRAG(bb, mp, 1); aq[mp + 1][1] = G2_AFRAG(bb, mp + 1, 1);              \
             aq[mp][0] = G2_AFRAG(bb, mp, 0); aq[mp + 1][0] = G2_AFRAG(bb, mp + 1, 0);              \
         }                                                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                         \
+        /* (no fence behind the conversion: the compiler lays its 32 instructions among the first MFMAs) */ \
+        if constexpr (U8) { _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) G2_CVT(nt) }          \
     }
 #define G2_READ_B(s_)                                                                              \
     {                                                                                              \
@@ -215,32 +276,39 @@ __device__ __forceinline__ void gemm2h_segment_mf16(const unsigned char* __restr
         if (BURST && MORE_) G2_ISSUE(s + AHEAD)                                                    \
         if constexpr (NOREAD) { if (s == 0) { G2_READ_A(s) G2_READ_B(s) } } else { G2_READ_A(s) }  \
         G2_MF8(0, 1, 1)                                                                            \
-        if (!BURST && MORE_) G2_PIECE(s + AHEAD, 0)                                                \
+        G2_SPOT(MORE_, 0)                                                                          \
         G2_MF8(0, 1, 0)                                                                            \
         if constexpr (!NOREAD) { G2_READ_B(s) }                                                    \
-        if (!BURST && MORE_) G2_PIECE(s + AHEAD, 1)                                                \
+        G2_SPOT(MORE_, 1)                                                                          \
         G2_MF8(2, 3, 1)                                                                            \
-        if (!BURST && MORE_) G2_PIECE(s + AHEAD, 2)                                                \
+        G2_SPOT(MORE_, 2)                                                                          \
         G2_MF8(2, 3, 0)                                                                            \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      /* this image is free once both groups pass here */ \
-        /* step s+1 must have landed before Y_s; what was issued for step s+2 since X_s (three pieces, or the burst's six) may stay in flight */ \
-        if (s + 1 < nst) { if (MORE_) { if constexpr (BURST) G3_WAIT_VM(6); else G3_WAIT_VM(3); } else G3_WAIT_VM(0); } \
+        /* step s+1 must have landed before Y_s; what was issued for step s+2 since X_s (three pieces, or the burst's six; \
+           bytes: two, or the burst's five) may stay in flight */                                  \
+        if (s + 1 < nst) {                                                                         \
+            if (MORE_) {                                                                           \
+                if constexpr (U8) { if constexpr (BURST) G3_WAIT_VM(5); else if constexpr (G2_U8_SKIP < 3) G3_WAIT_VM(2); else G3_WAIT_VM(3); } \
+                else { if constexpr (BURST) G3_WAIT_VM(6); else G3_WAIT_VM(3); }                   \
+            } else G3_WAIT_VM(0);                                                                  \
+        }                                                                                          \
         if constexpr (!NOBAR) G3_RAW_BARRIER()                  /* Y_s */                          \
         G2_MF8(4, 5, 1)                                                                            \
-        if (!BURST && MORE_) G2_PIECE(s + AHEAD, 3)                                                \
+        G2_SPOT(MORE_, 3)                                                                          \
         G2_MF8(4, 5, 0)                                                                            \
-        if (!BURST && MORE_) G2_PIECE(s + AHEAD, 4)                                                \
+        G2_SPOT(MORE_, 4)                                                                          \
         G2_MF8(6, 7, 1)                                                                            \
-        if (!BURST && MORE_) G2_PIECE(s + AHEAD, 5)                                                \
+        G2_SPOT(MORE_, 5)                                                                          \
         G2_MF8(6, 7, 0)                                                                            \
     }
 
     f16x8 bq[4], aq[8][2];
+    u32x4 braw[2];                                          // (bytes only: the step's raw counts, two tiles per register quad)
     G3_WAIT_VM(0);                                          // stores of a previous segment
     G2_ISSUE(0)
     if (nst > 1) G2_ISSUE(1)
-    // step 0 landed (step 1 may stay in flight)
-    if (nst > 1) G3_WAIT_VM(6); else G3_WAIT_VM(0);
+    // step 0 landed (step 1, six pieces or five, may stay in flight)
+    if (nst > 1) { if constexpr (U8) G3_WAIT_VM(5); else G3_WAIT_VM(6); } else G3_WAIT_VM(0);
     if (grp == 1) G3_RAW_BARRIER()
     {
         int s = 0;
@@ -257,7 +325,13 @@ __device__ __forceinline__ void gemm2h_segment_mf16(const unsigned char* __restr
 #undef G2_AFRAG
 #undef G2_FRAG
 #undef G2_ISSUE
+#undef G2_CVT
+#undef G2_SEL_HI
+#undef G2_SEL_LO
+#undef G2_CVT2
+#undef G2_SPOT
 #undef G2_PIECE
+#undef G2_DMA_PIECE_U8
 
     if (C == nullptr) return;                                // (kept for the instruction stream: see the head comment)
 #pragma unroll
@@ -486,20 +560,20 @@ __device__ __forceinline__ void gemm2h_segment(G2Sub<1>, const unsigned char* __
 #undef G2_LIVE
 }
 
-// ... and the overload for NSUB = 2: the 16x16x32 body (one X plane: no Bhi, hiflag, cscale)
-template <bool HI, int VAR, bool NTB, bool PART, bool GEN>
-__device__ __forceinline__ void gemm2h_segment(G2Sub<2>, const unsigned char* __restrict__ A2, const unsigned char* __restrict__ B1,
+// ... and the overload for NSUB = 2: the 16x16x32 body (one X plane: no Bhi, hiflag, cscale), U8 deduced from the tag
+template <bool HI, int VAR, bool NTB, bool PART, bool GEN, bool U8>
+__device__ __forceinline__ void gemm2h_segment(G2Sub<2, U8>, const unsigned char* __restrict__ A2, const unsigned char* __restrict__ B1,
                                                const unsigned char* __restrict__, const unsigned int* __restrict__,
                                                const float* __restrict__ rscale, int Kb, float* __restrict__ C, int ldc,
                                                int m0, int j0, int kb0, int nkb, unsigned char* smem, const float* __restrict__,
                                                unsigned live)
 {
     static_assert(!HI && !GEN, "two blocks per step: one count plane only");
-    gemm2h_segment_mf16<VAR, NTB, PART>(A2, B1, rscale, Kb, C, ldc, m0, j0, kb0, nkb, smem, live);
+    gemm2h_segment_mf16<VAR, NTB, PART, U8>(A2, B1, rscale, Kb, C, ldc, m0, j0, kb0, nkb, smem, live);
 }
 
 // pass B (and pass A on few tiles): split-K launch, XCD-aware order as gemm3c_kernel.  kb_per is a multiple of NSUB.
-template <int NSUB, bool HI, int VAR = 0, bool PART = false, bool GEN = false>
+template <int NSUB, bool HI, int VAR = 0, bool PART = false, bool GEN = false, bool U8 = false>
 __global__ __launch_bounds__(512) void gemm2h_kernel(const unsigned char* __restrict__ A2,
                                                      const unsigned char* __restrict__ B1,
                                                      const unsigned char* __restrict__ Bhi,
@@ -523,12 +597,12 @@ __global__ __launch_bounds__(512) void gemm2h_kernel(const unsigned char* __rest
     }
     const int kb0 = z * kb_per;
     const int nkb = min(kb_per, Kb - kb0);
-    gemm2h_segment<HI, VAR, true, PART, GEN>(G2Sub<NSUB>{}, A2, B1, Bhi, hiflag, rscale, Kb, C ? C + (size_t)z * c_split_stride : nullptr, ldc, mg * G3_MW,
+    gemm2h_segment<HI, VAR, true, PART, GEN>(G2Sub<NSUB, U8>{}, A2, B1, Bhi, hiflag, rscale, Kb, C ? C + (size_t)z * c_split_stride : nullptr, ldc, mg * G3_MW,
                                                    jt * G3C_JW, kb0, nkb, smem3, cscale, (unsigned)((livemask >> (8 * mg)) & 0xffu));
 }
 
 // pass A: stream-K over persistent workgroups, unit = one step of NSUB blocks (Kb % NSUB == 0)
-template <int NSUB, bool HI, int VAR = 0, bool NTB = true, bool PART = false, bool GEN = false>
+template <int NSUB, bool HI, int VAR = 0, bool NTB = true, bool PART = false, bool GEN = false, bool U8 = false>
 __global__ __launch_bounds__(512) void gemm2h_streamk_kernel(const unsigned char* __restrict__ A2,
                                                              const unsigned char* __restrict__ B1,
                                                              const unsigned char* __restrict__ Bhi,
@@ -557,7 +631,7 @@ __global__ __launch_bounds__(512) void gemm2h_streamk_kernel(const unsigned char
         const int tile = (int)(u / Ks), ks = (int)(u % Ks);
         const int ke = (int)min((long long)Ks, ks + (u1 - u));
         const int mg = tile / NJ, jt = tile % NJ;
-        gemm2h_segment<HI, VAR, NTB, PART, GEN>(G2Sub<NSUB>{}, A2, B1, Bhi, hiflag, rscale, Kb, (ks == 0) ? C0 : (ke == Ks ? C1 : C2), ldc, mg * G3_MW,
+        gemm2h_segment<HI, VAR, NTB, PART, GEN>(G2Sub<NSUB, U8>{}, A2, B1, Bhi, hiflag, rscale, Kb, (ks == 0) ? C0 : (ke == Ks ? C1 : C2), ldc, mg * G3_MW,
                                                       jt * G3C_JW, ks * NSUB, (ke - ks) * NSUB, smem3, cscale,
                                                       (unsigned)((livemask >> (8 * mg)) & 0xffu));
         u += ke - ks;

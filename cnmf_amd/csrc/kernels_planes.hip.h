@@ -1,7 +1,7 @@
 // Operand planes of the matrix-pipe GEMMs, built outside the GEMM kernels (gfx950 only):
-//   * the X side, once per matrix: ONE builder template (x_planes_kernel) for the three formats the count and general
-//     paths multiply -- bf16 counts (kernels_gemm3.hip.h, gemm3c), f16 counts and the f16 two-plane split of X itself
-//     (kernels_gemm2h.hip.h) -- in both orientations, with the kernels that decide what it needs (a second count plane?
+//   * the X side, once per matrix: ONE builder template (x_planes_kernel) for the four formats the count and general
+//     paths multiply -- bf16 counts (kernels_gemm3.hip.h, gemm3c), f16 counts, counts as bytes and the f16 two-plane split
+//     of X itself (kernels_gemm2h.hip.h) -- in both orientations, with the kernels that decide what it needs (a second count plane?
 //     the per-row exponents of a general matrix);
 //   * the factor side, once per half-step: the f16 two-plane split of a packed factor (split2h_tiled_*), whose body
 //     the sweeps' finalize launch shares (kernels_sweep.hip.h).
@@ -54,11 +54,12 @@ __device__ __forceinline__ void count_lo_hi(float n, float& lo, float& hi)
 //   value()    : the number an element contributes (outside the matrix: 0),
 //   pair()     : the two halfwords it becomes, one per plane,
 //   SWIZZLE    : the two 16-byte slots of a row swapped for rows with bit 3 set (the f16 GEMM's conflict-free LDS image),
+//   BYTES      : one byte per element in the step-major layout of CountU8 (one plane only),
 //   FLAGGED    : a bit per (row tile, block) whose second plane is not all zero ((Kb + 31) / 32 words per tile row).
 template <int BASE>
 struct CountFormat {
     using Aux = float;
-    static constexpr bool FLAGGED = true;
+    static constexpr bool FLAGGED = true, BYTES = false;
     static __device__ __forceinline__ float value(const float* __restrict__ X, size_t at, bool inside,
                                                   const float* __restrict__ unit, int /*row*/, int gene)
     {
@@ -85,13 +86,25 @@ struct CountF16 : CountFormat<(int)G2_COUNT_BASE> {  // gemm2h: integers <= 2048
         a = f16_bits(lo); b = f16_bits(hi);
     }
 };
+// gemm2h, 16x16x32 body: integers <= 255 as ONE BYTE each (exact; the GEMM converts them to f16 in registers).  No second
+// plane, no flags.  One (row tile, 32-k step) is one contiguous 8 KB run, laid out for the wave that reads it (g2_u8_chunk).
+struct CountU8 : CountFormat<255> {
+    static constexpr bool SWIZZLE = false, FLAGGED = false, BYTES = true;
+    static __device__ __forceinline__ void pair(float n, unsigned short& a, unsigned short& b) { a = (unsigned short)n; b = 0; }
+};
+// Byte offset, inside the 8 KB run of a 32-k step, of the eight counts  k = 8 g .. 8 g + 7  (g = 0..3) of tile row rin
+// (0..255).  rin = wn * 64 + nt * 16 + r  (wn: the GEMM wave's 64 columns, nt = 2 p + t its 16-row count tile, r the row in
+// it): the 16-byte chunk  (wn * 2 + p) * 64 + g * 16 + r  holds the eight bytes of tile t = 0 and then those of t = 1 -- what
+// lane g * 16 + r of wave wn fetches with ONE ds_read_b128 per tile pair p (kernels_gemm2h.hip.h, the byte form of mf16).
+__host__ __device__ constexpr int g2_u8_chunk(int rin, int g) { return (rin >> 5) * 1024 + (g * 16 + (rin & 15)) * 16 + ((rin >> 4) & 1) * 8; }
+
 // General (NOT count-structured) X on the f16 pipe, gemm_mode 5: every row r of the operand (a cell for pass A, a gene for
 // pass B) is held as TWO f16 planes of  y = x * 2^s_r  (h = f16(y), m = f16(y - h): within 1 ulp_f32 of x, exactly like
 // the factor planes), s_r from the row maximum (x2h_rowshift_kernel); the GEMM multiplies the plane pairs with the `HI`
 // instantiation, every block flagged, and its epilogue undoes 2^s_r per OUTPUT column.
 struct SplitF16 {
     using Aux = int;
-    static constexpr bool SWIZZLE = true, FLAGGED = false;
+    static constexpr bool SWIZZLE = true, FLAGGED = false, BYTES = false;
     static __device__ __forceinline__ float value(const float* __restrict__ X, size_t at, bool inside,
                                                   const int* __restrict__ shift, int row, int /*gene*/)
     {
@@ -146,6 +159,20 @@ __global__ __launch_bounds__(256) void x_planes_kernel(const float* __restrict__
         const float v = F::value(X, (size_t)cell * ld + gene, cell < N && gene < G, aux, row, gene);
         F::pair(v, p0[i], p1[i]);
         any1 |= p1[i] != 0;                                  // (a hi part is 0 or >= BASE: never a negative zero)
+    }
+    if constexpr (F::BYTES) {
+        // byte plane (TR = 256, Kb even): [row tile][32-k step][8 KB]; this thread's 16-k block is the half kb & 1 of its
+        // step, that is the two 8-k groups g = 2 (kb & 1) + hf
+        const int rin = row % TR;
+        unsigned char* d = reinterpret_cast<unsigned char*>(plane0) + ((size_t)(row / TR) * (Kb / 2) + (kb >> 1)) * ((size_t)TR * 32);
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+            uint2 w;
+            w.x = p0[8 * hf + 0] | ((unsigned)p0[8 * hf + 1] << 8) | ((unsigned)p0[8 * hf + 2] << 16) | ((unsigned)p0[8 * hf + 3] << 24);
+            w.y = p0[8 * hf + 4] | ((unsigned)p0[8 * hf + 5] << 8) | ((unsigned)p0[8 * hf + 6] << 16) | ((unsigned)p0[8 * hf + 7] << 24);
+            *reinterpret_cast<uint2*>(d + g2_u8_chunk(rin, 2 * (kb & 1) + hf)) = w;
+        }
+        return;
     }
     const int rin = row % TR, swz = F::SWIZZLE ? (rin >> 3) & 1 : 0;
     const size_t at = (((size_t)(row / TR) * Kb + kb) * TR + rin) * 16;

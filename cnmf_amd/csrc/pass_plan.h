@@ -218,15 +218,18 @@ static inline int gemm2h_nsub(bool hi, int Kb, int nsub_knob) { return (!hi && n
 //   gvar   : CNMF_G2_GVAR, 0 = general matrices on the burst loop, else the spread stream (VAR 4); same bits
 //   nsub   : gemm2h_nsub of the launch            part   : the live mask has a dead 32-column tile
 //   shared : several component groups share every X tile in the L2 -- no non-temporal loads then (NTB)
+//   u8     : the count plane is held as bytes (ensure_counts; CNMF_G2_U8) -- the byte form (U8) of the two-block count stream
 // A column scale without a second plane does not exist (invalid).  The one-block count stream (nsub 1 without a second
 // plane) has no partial-tile form: it multiplies the dead tiles too.
 struct G2Form {
-    bool valid; int NSUB; bool HI; int VAR; bool NTB, PART, GEN;
-    bool operator==(const G2Form& o) const { return valid == o.valid && NSUB == o.NSUB && HI == o.HI && VAR == o.VAR && NTB == o.NTB && PART == o.PART && GEN == o.GEN; }
+    bool valid; int NSUB; bool HI; int VAR; bool NTB, PART, GEN; bool U8 = false;
+    bool operator==(const G2Form& o) const { return valid == o.valid && NSUB == o.NSUB && HI == o.HI && VAR == o.VAR && NTB == o.NTB && PART == o.PART && GEN == o.GEN && U8 == o.U8; }
 };
 
-static inline G2Form g2_form(bool hi, bool gen, bool gen4, int gvar, int nsub, bool part, bool shared)
+static inline G2Form g2_form(bool hi, bool gen, bool gen4, int gvar, int nsub, bool part, bool shared, bool u8 = false)
 {
+    // (a byte plane exists only where the two-block count stream reads it: no second plane, nsub 2)
+    if (u8) return (hi || gen || nsub != 2) ? G2Form{false, 1, false, 0, false, false, false} : G2Form{true, 2, false, 4, !part && !shared, part, false, true};
     if (gen && !hi) return G2Form{false, 1, false, 0, false, false, false};
     const bool ntb = !part && !shared;
     if (hi && gen && !gen4) return G2Form{true, 1, true, gvar == 0 ? 0 : 4, ntb, part, true};

@@ -96,7 +96,8 @@ struct DenseTF {
 // ---- the images of the resident matrix X that the GEMM passes of the coordinate-descent batch read (gemm_host.hip.h)
 // What a GEMM pass reads of X: the plane, an optional second plane with its block flags (one bit per tile row and block),
 // an optional 2^-s per output column.  Both providers below hand it out for pass A (X) and pass B (X^T).
-struct XOperand { const unsigned char *plane, *hi; const unsigned int* flags; const float* colscale; };
+// bytes: `plane` is a count plane of one byte per element (CountU8, kernels_planes.hip.h), read by the byte form of the kernels.
+struct XOperand { const unsigned char *plane, *hi; const unsigned int* flags; const float* colscale; bool bytes = false; };
 
 // bf16 planes of X and X^T (split-operand GEMM, CNMF_GEMM3=1|2), built on first use
 struct Bf16PlanesF {
@@ -108,14 +109,16 @@ struct Bf16PlanesF {
 // count structure X = n * d (kernels_counts.hip.h)
 struct CountPlanesF {
     int state = 0;                                   // 0 = not examined, 1 = present (the planes below exist), -1 = absent
-    int fmt = 0;                                     // 3 = bf16 planes (base 256), 4 = f16 planes (base 2048, swizzled slots)
+    int fmt = 0;                                     // 3 = bf16 planes (base 256), 4 = f16 planes (base 2048, swizzled slots),
+                                                     // 5 = as 4, built with the byte plane allowed (CNMF_G2_U8) ...
+    bool bytes = false;                              // ... and taken: no count exceeds 255, C1 / Ct1 hold one byte per element
     unsigned char *C1 = nullptr, *Ct1 = nullptr;     // integer planes of n and n^T (one plane, 256-row tiles)
     unsigned char *C1h = nullptr, *Ct1h = nullptr;   // second planes (the high digit) when some count exceeds the base, else NULL
     unsigned int *hiA = nullptr, *hiB = nullptr;     // their flags
     double* d_scale = nullptr;                       // per-gene scale d [G_pad]
     void free_all() { hipFree(C1); hipFree(Ct1); hipFree(C1h); hipFree(Ct1h); hipFree(hiA); hipFree(hiB); hipFree(d_scale); }
-    XOperand passA() const { return {C1, C1h, hiA, nullptr}; }
-    XOperand passB() const { return {Ct1, Ct1h, hiB, nullptr}; }
+    XOperand passA() const { return {C1, C1h, hiA, nullptr, bytes}; }
+    XOperand passB() const { return {Ct1, Ct1h, hiB, nullptr, bytes}; }
 };
 
 // any OTHER matrix on the f16 pipe (gemm_mode 5): two f16 planes of x * 2^s_row for X (rows = cells) and X^T (rows =
@@ -251,6 +254,7 @@ struct CdKnobs {
     bool g2_gen4 = false;              // CNMF_G2_GEN4: general matrices multiply all four f16 plane pairs instead of three
     int  g2_nsub = 2;                  // CNMF_G2_NSUB=1|2: 16-k sub-blocks per barrier pair of the one-plane f16 GEMMs
     int  g2_xmap = -1;                 // CNMF_G2_XMAP=0|1: XCD mapping of the persistent f16 GEMM workgroups (-1: by path)
+    bool g2_u8 = true;                 // CNMF_G2_U8=0: the f16 count plane even where every count fits a byte (same bits)
     bool part = false;                 // CNMF_PART: the tail's GEMM passes skip 32-column tiles without a live restart
     bool no_psum = false;              // CNMF_NO_PSUM: a separate split-K reduce in front of the H sweep
     bool wide_small = true;            // CNMF_WIDE_SMALL=0: a small matrix never runs wider than 256 columns
@@ -356,6 +360,7 @@ static void parse_cd_knobs(cnmf_ctx* ctx)
     k.g2_gen4 = ctx_getenv(ctx, "CNMF_G2_GEN4") != nullptr;
     k.g2_nsub = num(ctx_getenv(ctx, "CNMF_G2_NSUB"), 2) == 1 ? 1 : 2;
     k.g2_xmap = num(ctx_getenv(ctx, "CNMF_G2_XMAP"), -1);
+    k.g2_u8 = num(ctx_getenv(ctx, "CNMF_G2_U8"), 1) != 0;
     k.part = ctx_getenv(ctx, "CNMF_PART") != nullptr;
     k.no_psum = ctx_getenv(ctx, "CNMF_NO_PSUM") != nullptr;
     k.wide_small = num(ctx_getenv(ctx, "CNMF_WIDE_SMALL"), 1) != 0;

@@ -229,7 +229,8 @@ class Engine:
         rows and forms the dense float32 image only when a path that multiplies the dense matrix asks for it."""
         f = C.c_int32(0)
         self._check(self._lib.cnmf_matrix_images(self._ctx, C.byref(f)))
-        names = ("dense", "csr", "csr_of_transpose", "dense_transpose", "non_zero_images_16", "non_zero_images_32", "count_planes")
+        names = ("dense", "csr", "csr_of_transpose", "dense_transpose", "non_zero_images_16", "non_zero_images_32", "count_planes",
+                 "count_planes_bytes")
         return {n: bool(f.value >> i & 1) for i, n in enumerate(names)}
 
     def get_matrix(self):
@@ -2045,11 +2046,12 @@ class Engine:
                                                 C.byref(ms), int(reps)))
         return Cout, ms.value
 
-    def debug_gemm2h(self, A, Bn, nsplit=1, nsub=2, reps=0, sweep_bound=False):
+    def debug_gemm2h(self, A, Bn, nsplit=1, nsub=2, reps=0, sweep_bound=False, count_bytes=False):
         """A [KC, K] . Bn [J, K]^T through the f16 two-plane count kernel (A >= 0, Bn: integers <= 65535);
         returns (C, ms).  ``sweep_bound=True`` scales the rows of A by the bound the W half-step reports
-        (sqrt(sum w^2) per 1024-entry block) instead of the exact row maximum -- the production pass-B scaling."""
-        nsub = int(nsub) | (128 if sweep_bound else 0)
+        (sqrt(sum w^2) per 1024-entry block) instead of the exact row maximum -- the production pass-B scaling.
+        ``count_bytes=True`` holds Bn as one byte per count (integers <= 255, nsub 2, streams 0 and 4; else ValueError)."""
+        nsub = int(nsub) | (128 if sweep_bound else 0) | (256 if count_bytes else 0)
         A = np.ascontiguousarray(A, dtype=np.float32)
         Bn = np.ascontiguousarray(Bn, dtype=np.float32)
         KC, K = A.shape

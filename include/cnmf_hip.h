@@ -102,7 +102,10 @@ const char* cnmf_last_error(const cnmf_ctx* ctx);
 /* The CNMF_* environment variables (INTEGRATION.md "Runtime switches") are read ONCE, when the context is created, into
  * the context; cnmf_reload_env re-reads all of them (A/B tools, tests).  A knob therefore cannot change between two
  * calls on one context unless the caller asks for it.  The one exception is CNMF_RCCL_LIB, the path RCCL is loaded
- * from: read from the process environment the first time a communicator is formed.                                    */
+ * from: read from the process environment the first time a communicator is formed.
+ * CNMF_G2_U8 (default 1): a count-structured matrix none of whose counts exceeds 255 keeps its integer planes as one byte
+ * per count, which the f16 GEMM passes convert in registers -- the same operands, the same bits, half the plane bytes;
+ * 0 = the f16 plane as before.  A change takes effect, like CNMF_GEMM3, at the next call: the planes are rebuilt.      */
 int cnmf_reload_env(cnmf_ctx* ctx);
 const char* cnmf_version(void);
 
@@ -129,7 +132,8 @@ int cnmf_get_shape(const cnmf_ctx* ctx, int64_t* n_cells, int64_t* n_genes);
 /* Which images of the matrix are resident right now (round 5): bit 0 the dense float32 image (a CSR upload forms it only when
  * a path that multiplies the dense matrix asks for it: a Kullback-Leibler run on a sparse matrix never does), bit 1 the
  * compressed rows of X, bit 2 those of X^T, bit 3 the dense X^T copy of the dense multiplicative-update kernels,
- * bits 4 / 5 the non-zero images at padded rank 16 / 32, bit 6 the integer count planes of the coordinate-descent path. */
+ * bits 4 / 5 the non-zero images at padded rank 16 / 32, bit 6 the integer count planes of the coordinate-descent path,
+ * bit 7 those planes held as one byte per count (CNMF_G2_U8). */
 int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags);
 /* the resident matrix back on the host ([n_cells][n_genes] float32) */
 int cnmf_get_matrix(cnmf_ctx* ctx, float* out);

@@ -15,6 +15,8 @@ python - <<PY
 import csv, glob, collections, os, json
 R=os.environ['GRAFT_REPO_ROOT']
 XPLANES=int(os.environ.get('PMC_XPLANES','1'))       # 1: the count path's integer plane; 2: a general matrix as two f16 planes (CNMF_NO_COUNTS=1)
+# bytes per element of an X plane: 1 = the count plane as bytes (the default where no count exceeds 255), 2 = f16 (CNMF_G2_U8=0, general matrices)
+XBYTES=int(os.environ.get('PMC_XBYTES', '1' if XPLANES == 1 else '2'))
 NOTE=os.environ.get('PMC_NOTE','')
 OUTNAME=os.environ.get('PMC_OUT','pmc_traffic.json')
 acc=collections.defaultdict(lambda: collections.defaultdict(list))
@@ -43,11 +45,12 @@ for key, part in (("passA","gemm2h_streamk_kernel"),("passB","gemm2h_kernel"),("
     if e["SQ_VALU_MFMA_BUSY_CYCLES"] and e["GRBM_GUI_ACTIVE"]:
         e["mfma_busy_frac"]=e["SQ_VALU_MFMA_BUSY_CYCLES"]/(1024*e["GRBM_GUI_ACTIVE"]/8)
     out[key]=e
-xplane = N_pad*G_pad*2*XPLANES
+xplane = N_pad*G_pad*XBYTES*XPLANES
 out["algorithmic_bytes_per_launch"]={
   "passA": xplane + KC*G_pad*4 + KC*N_pad*4,
   "passB": xplane + KC*N_pad*4 + NSPLIT*KC*G_pad*4,
-  "note": "count plane of X (or X^T) once (2 B per element, f16) + the factor's two f16 planes once (4 B per element) + the product written once (pass A: one XHt plane of 51 MB -- the stream-K partial planes of cut tiles come on top; pass B: the split-K partial planes)"}
+  "x_plane_bytes_per_element": XBYTES,
+  "note": "count plane of X (or X^T) once (x_plane_bytes_per_element: 1 = bytes, 2 = f16) + the factor's two f16 planes once (4 B per element) + the product written once (pass A: one XHt plane of 51 MB -- the stream-K partial planes of cut tiles come on top; pass B: the split-K partial planes)"}
 import sys; sys.path.insert(0, R)
 from bench import source_hashes
 out['kernel_source_sha256']=source_hashes()
