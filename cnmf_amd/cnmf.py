@@ -26,6 +26,7 @@ What is different by design
   normalised matrix is stored as ``.df.npz`` (the reference's own DataFrame container,
   cnmf.py:31-40) or as a CSR container instead of the reference's h5ad.
 """
+import contextlib
 import errno
 import itertools
 import os
@@ -323,6 +324,10 @@ class cNMF:
     # factors uploaded per restart) or "device" (opt-in: Engine.nndsvd_init_batch(tail="device"); factorize() starts
     # the batch from the engine's init store without a transfer).
     nndsvd = "host"
+    # ranks of the multiplicative-update route (beta_loss != 'frobenius'): None = up to 64 (CNMF_MU_KMAX), "wide" = opt-in
+    # up to 128 (CNMF_MU_KMAX_WIDE) -- get_nmf_iter_params admits them, and factorize / _nmf / the MU tail of consensus
+    # raise the engine's limit (Engine.mu_rank_limit) around their own device calls and put the previous value back.
+    mu_ranks = None
 
     def __init__(self, output_dir=".", name=None, device=0, engine=None, compress_merged=True, detect_counts=True):
         """Same constructor semantics as the reference (cnmf.py:268-296) plus the GPU index.
@@ -454,12 +459,12 @@ class cNMF:
         if type(ks) is int:
             ks = [ks]
         k_list = sorted(set(list(ks)))
-        from ._lib import CNMF_KMAX, CNMF_MU_KMAX
-        kmax = CNMF_KMAX if beta_loss == "frobenius" else CNMF_MU_KMAX
+        from ._lib import CNMF_KMAX
+        kmax = CNMF_KMAX if beta_loss == "frobenius" else self._mu_kmax()
         if k_list and max(k_list) > kmax:
             # fail at prepare time, not after the restarts were paid for (the reference itself has no limit,
             # cnmf.py:1243; the device engine: 128 for the coordinate-descent solver, 64 for the
-            # multiplicative-update solver)
+            # multiplicative-update solver -- 128 with self.mu_ranks = "wide")
             raise NotImplementedError("n_components=%d > %d is not supported by the device engine (beta_loss=%r)"
                                       % (max(k_list), kmax, beta_loss))
         replicate_params = []
@@ -725,6 +730,28 @@ class cNMF:
             raise NotImplementedError("init=%r is not implemented on the device (random / nndsvd / nndsvda / nndsvdar / "
                                       "custom)" % kw.get("init"))
 
+    def _mu_kmax(self):
+        """Largest multiplicative-update rank this object admits (``self.mu_ranks``)."""
+        from ._lib import CNMF_MU_KMAX, CNMF_MU_KMAX_WIDE
+        if self.mu_ranks not in (None, "wide"):
+            raise ValueError("cNMF.mu_ranks must be None or 'wide', not %r" % (self.mu_ranks,))
+        return CNMF_MU_KMAX_WIDE if self.mu_ranks == "wide" else CNMF_MU_KMAX
+
+    @contextlib.contextmanager
+    def _mu_rank_scope(self, eng):
+        """``self.mu_ranks = "wide"``: the engine's multiplicative-update rank limit is raised for the device calls inside
+        the block and put back afterwards (the engine may be shared: ``engine=``)."""
+        kmax = self._mu_kmax()
+        if not hasattr(eng, "mu_rank_limit") or eng.mu_rank_limit >= kmax:
+            yield
+            return
+        prev = eng.mu_rank_limit
+        eng.mu_rank_limit = kmax
+        try:
+            yield
+        finally:
+            eng.mu_rank_limit = prev
+
     def _nndsvd_tail(self, variant, eng):
         """The tail ``factorize`` / ``_nmf`` ask the engine for (``self.nndsvd``)."""
         if self.nndsvd not in ("host", "device"):
@@ -755,9 +782,10 @@ class cNMF:
             elif mu:
                 # float64 on the stored entries, like scikit-learn on the reference's float64 matrices (cnmf.py:534); both
                 # beta losses (Itakura-Saito: a strictly positive matrix -- scikit-learn's rule -- stores every entry)
-                W, _, _ = eng.mu_refit_f64(H, tol=kw.get("tol", 1e-4), max_iter=kw.get("max_iter", 200),
-                                           alpha_W=kw.get("alpha_W", 0.0), l1_ratio=kw.get("l1_ratio", 0.0),
-                                           beta_loss=kw["beta_loss"])
+                with self._mu_rank_scope(eng):
+                    W, _, _ = eng.mu_refit_f64(H, tol=kw.get("tol", 1e-4), max_iter=kw.get("max_iter", 200),
+                                               alpha_W=kw.get("alpha_W", 0.0), l1_ratio=kw.get("l1_ratio", 0.0),
+                                               beta_loss=kw["beta_loss"])
             else:
                 # scikit-learn solves in X's dtype (sklearn _nmf.py:1221-1233): float64 matrices get the float64 refit
                 # (product, Gram matrix and sweeps), float32 ones the float32 matrix-pipe path
@@ -780,10 +808,11 @@ class cNMF:
             common = dict(beta_loss=kw["beta_loss"], tol=kw.get("tol", 1e-4), max_iter=kw.get("max_iter", 200),
                           alpha_W=kw.get("alpha_W", 0.0), alpha_H=kw.get("alpha_H", 0.0),
                           l1_ratio=kw.get("l1_ratio", 0.0), return_W=True)
-            if kw.get("init") == "custom":
-                Hl, Wl, _, _ = eng.nmf_mu_batch([k], W0=[kw["W"]], H0=[kw["H"]], **common)
-            else:
-                Hl, Wl, _, _ = eng.nmf_mu_batch([k], seeds=[int(kw["random_state"])], **common)
+            with self._mu_rank_scope(eng):
+                if kw.get("init") == "custom":
+                    Hl, Wl, _, _ = eng.nmf_mu_batch([k], W0=[kw["W"]], H0=[kw["H"]], **common)
+                else:
+                    Hl, Wl, _, _ = eng.nmf_mu_batch([k], seeds=[int(kw["random_state"])], **common)
             xdt = Xv.dtype if Xv.dtype in (np.float32, np.float64) else np.dtype(np.float64)
             return Hl[0].astype(xdt), Wl[0].astype(xdt)
         if kw.get("init") == "custom":
@@ -843,7 +872,8 @@ class cNMF:
             else:                                              # host tail, or the device refused a block
                 init_kw = dict(W0=[w for w, _ in inits], H0=[h for _, h in inits])
         if _nmf_kwargs.get("solver", "cd") == "mu":
-            H_list, _, n_iter, _ = eng.nmf_mu_batch(ks, beta_loss=_nmf_kwargs["beta_loss"], **init_kw, **common)
+            with self._mu_rank_scope(eng):
+                H_list, _, n_iter, _ = eng.nmf_mu_batch(ks, beta_loss=_nmf_kwargs["beta_loss"], **init_kw, **common)
             self.last_factorize_stats = dict(n_iter=n_iter)
         else:
             # the spectra also stay in the engine's device store: k selection and consensus of THIS process take their
@@ -1153,7 +1183,8 @@ class cNMF:
                 # (Kullback-Leibler: the stored entries; Itakura-Saito, round 6: the matrix is strictly positive by
                 # scikit-learn's rule, every entry is stored)
                 solver_kw["beta_loss"] = kw.get("beta_loss")
-                Wt, _, _ = eng.mu_refit_f64(norm_usages.values.T, transposed=True, **solver_kw)
+                with self._mu_rank_scope(eng):
+                    Wt, _, _ = eng.mu_refit_f64(norm_usages.values.T, transposed=True, **solver_kw)
                 spectra_tpm = Wt.T
             else:
                 spectra_tpm, _ = eng.nnls_spectra(norm_usages.values.astype(tdt), **solver_kw)
@@ -1187,7 +1218,8 @@ class cNMF:
                     H_full = np.zeros((Hrf.shape[0], len(tpm_genes)))
                     H_full[:, hidx] = Hrf
                     w0 = float(np.sqrt((mean[hidx] / std1).mean() / Hrf.shape[0]))
-                    rf, _, _ = eng.mu_refit_f64(H_full, col_divisor=div, w_init=w0, n_features=len(hvgs), **solver_kw)
+                    with self._mu_rank_scope(eng):
+                        rf, _, _ = eng.mu_refit_f64(H_full, col_divisor=div, w_init=w0, n_features=len(hvgs), **solver_kw)
                 elif tdt == np.float64:
                     rf, _ = eng.nnls_f64(H_prod, gram=Hrf @ Hrf.T, n_features=len(hvgs), **solver_kw)
                 else:

@@ -21,7 +21,8 @@
 // (rows 0..15 = hi, 16..31 = lo of the same 16 components): one MFMA per Q plane covers both.
 //
 // Restarts share each X tile: a workgroup is 4 restarts on the SAME block of X (staged once through LDS), further
-// restart groups sit in gridDim.z.  Each wave owns two 32 x 32 tiles along the non-reduced dimension.
+// restart groups sit in gridDim.z.  Each wave owns two 32 x 32 tiles along the non-reduced dimension.  (Ranks 33..64 and
+// 65..128 trade restarts per workgroup for rank: MuShape.)
 // Measured (PMC, 16 restarts of rank 9 at 50000 x 2000): vector ALU 60 % busy (the quotient: clamp, reciprocal, two
 // bf16 planes = about 8 issue slots per element), matrix pipe 24 % -- they do not overlap inside a SIMD here, so the step is
 // bound by their sum.
@@ -128,13 +129,24 @@ __device__ __forceinline__ void mu_planes8(const float (&q)[8], mu_bf16x8& bh, m
 //   KP = 16, 32: 4 restarts x 2 halves of the 128-wide block, two 32-wide tiles per wave, one 32-row M tile of the
 //                second product (for 16 the hi and lo planes are stacked in it);
 //   KP = 64    : 2 restarts x 4 quarters, ONE tile per wave, TWO M tiles (components 0..31 and 32..63) -- the same
-//                register and LDS budget, twice the MFMAs per element, the same quotient work.
+//                register and LDS budget, twice the MFMAs per element, the same quotient work;
+//   KP = 128   : ONE restart x 4 quarters x 2 component halves (its own specialisation below).
 template <int KP> struct MuShape {
     static constexpr int RPW = KP == 64 ? 2 : 4;         // restarts per workgroup
     static constexpr int NJT = KP == 64 ? 1 : 2;         // 32-wide tiles per wave
     static constexpr int NMH = KP == 64 ? 2 : 1;         // M tiles of the second product
     static constexpr int NA2 = KP == 16 ? 1 : 2 * NMH;   // A fragments of the second product per 16-deep chunk
     static constexpr int TPR = 512 / RPW;                // loader threads per restart
+    static constexpr int NCH = 1;                        // component halves: waves that share a tile and split the components
+    static constexpr int KW = KP;                        // components whose numerators one wave accumulates
+};
+// Ranks 65..128.  Held like rank 64 the operands do not fit the 256 registers of a lane in a 512-thread workgroup
+// (b1 64 + a1 64 + accumulators 64 / 128 + s, x 32 + a2c 32), so: one restart per workgroup; the 8 waves are the 4
+// quarters of the 128-wide block x 2 halves of the components.  Every wave forms S over the FULL rank -- the streamed
+// factor's fragments come from LDS one 16-deep chunk at a time instead of being held -- and carries the second product
+// for its own 64 components (two M tiles, as at rank 64).  S and the quotient are therefore computed twice per tile.
+template <> struct MuShape<128> {
+    static constexpr int RPW = 1, NJT = 1, NMH = 2, NA2 = 4, TPR = 512, NCH = 2, KW = 64;
 };
 template <int KP> struct MuAcc { f32x16 v[MuShape<KP>::NMH]; };
 
@@ -243,16 +255,16 @@ __global__ __launch_bounds__(256) void mu_planes_kernel(const float* __restrict_
 template <int KP, bool BETA1>
 __device__ __forceinline__ void mu_w_epilogue(const MuSlotDev& sd, const MuAcc<KP> (&acc)[MuShape<KP>::NJT],
                                               const MuAcc<KP> (&accd)[MuShape<KP>::NJT], int r0,
-                                              int l32, int h, int N, int ldxt, float l1, float l2)
+                                              int l32, int h, int N, int ldxt, float l1, float l2, int cb = 0)
 {
 #pragma unroll
     for (int jt = 0; jt < MuShape<KP>::NJT; ++jt) {
         const int row = r0 + 32 * jt + l32;
         if (row >= N) continue;
-        constexpr int NQ = KP / 8;                     // groups of 4 components held by this lane
+        constexpr int NQ = MuShape<KP>::KW / 8;        // groups of 4 components held by this lane (from component cb on)
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
-            const int c0 = 8 * q + 4 * h;
+            const int c0 = cb + 8 * q + 4 * h;
             float num[4], den[4] = {0.f, 0.f, 0.f, 0.f};
             if constexpr (KP == 16) {
 #pragma unroll
@@ -298,8 +310,8 @@ __device__ __forceinline__ void mu_w_epilogue(const MuSlotDev& sd, const MuAcc<K
     }
 }
 
-// ---- the workgroup: 8 waves = 4 restarts x 2 halves (rank <= 32; 2 restarts x 4 quarters for ranks 33..64, MuShape) of a
-// 128-wide block of the non-reduced dimension.  Per 32-deep
+// ---- the workgroup: 8 waves = 4 restarts x 2 halves (rank <= 32; 2 restarts x 4 quarters for ranks 33..64; 1 restart x
+// 4 quarters x 2 component halves for ranks 65..128, MuShape) of a 128-wide block of the non-reduced dimension.  Per 32-deep
 // step it brings in ONE copy of the X block (32 x 128 floats) and one copy of each restart's factor fragments through
 // LDS (double buffered, one barrier per step); every wave then reads its operands from LDS in the fragment layouts
 // (2 KB of L2 -> CU traffic per tile and restart).
@@ -401,7 +413,8 @@ struct MuCoop {
             for (int p = 0; p < 2; ++p)
                 a1[ks][p] = __builtin_bit_cast(mu_bf16x8, *reinterpret_cast<const u32x4*>(b + ((rs * 2 + p) * 32 + l32) * L::A1ROW + (16 * ks + 8 * h) * 2));
     }
-    __device__ __forceinline__ void read_a2(int buf, int rs, int l32, int h, int c, mu_bf16x8 (&a2c)[MuShape<KP>::NA2]) const
+    // cb: first component of the wave (its component half at rank > 64, else 0)
+    __device__ __forceinline__ void read_a2(int buf, int rs, int l32, int h, int c, mu_bf16x8 (&a2c)[MuShape<KP>::NA2], int cb = 0) const
     {
         const unsigned char* b = lds + buf * L::BUF + L::X_BYTES + L::A1_BYTES;
         if constexpr (KP == 16)
@@ -411,8 +424,26 @@ struct MuCoop {
             for (int mh = 0; mh < MuShape<KP>::NMH; ++mh)
 #pragma unroll
                 for (int p = 0; p < 2; ++p)
-                    a2c[2 * mh + p] = __builtin_bit_cast(mu_bf16x8, *reinterpret_cast<const u32x4*>(b + ((rs * 2 + p) * KP + 32 * mh + l32) * L::A2ROW + (16 * c + 8 * h) * 2));
+                    a2c[2 * mh + p] = __builtin_bit_cast(mu_bf16x8, *reinterpret_cast<const u32x4*>(b + ((rs * 2 + p) * KP + cb + 32 * mh + l32) * L::A2ROW + (16 * c + 8 * h) * 2));
         }
+    }
+    // S of one tile with the streamed factor's fragments read per 16-deep chunk (rank > 64): mu_product's order
+    __device__ __forceinline__ f32x16 product_streamed(int buf, int rs, int l32, int h, const mu_bf16x8 (&b1)[KP / 16][2]) const
+    {
+        const unsigned char* b = lds + buf * L::BUF + L::X_BYTES;
+        f32x16 s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KP / 16; ++ks) {
+            mu_bf16x8 a[2];
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+                a[p] = __builtin_bit_cast(mu_bf16x8, *reinterpret_cast<const u32x4*>(b + ((rs * 2 + p) * 32 + l32) * L::A1ROW + (16 * ks + 8 * h) * 2));
+            s = MU_MFMA(a[1], b1[ks][1], s);         // smallest terms first
+            s = MU_MFMA(a[0], b1[ks][1], s);
+            s = MU_MFMA(a[1], b1[ks][0], s);
+            s = MU_MFMA(a[0], b1[ks][0], s);
+        }
+        return s;
     }
 };
 
@@ -420,7 +451,7 @@ struct MuCoop {
 template <int KP, int MODE, bool BETA1>
 __device__ __forceinline__ void mu_coop_loop(MuCoop<KP, MODE == 0>& co, bool active, int rs, int gs, int l32, int h,
                                              const mu_bf16x8 (&b1)[MuShape<KP>::NJT][KP / 16][2], MuAcc<KP> (&acc)[MuShape<KP>::NJT],
-                                             MuAcc<KP> (&accd)[MuShape<KP>::NJT], double& dv, int t0, int t1)
+                                             MuAcc<KP> (&accd)[MuShape<KP>::NJT], double& dv, int t0, int t1, int cb = 0)
 {
     if (t0 >= t1) return;
     co.gload(t0);
@@ -430,6 +461,31 @@ __device__ __forceinline__ void mu_coop_loop(MuCoop<KP, MODE == 0>& co, bool act
     for (int t = t0; t < t1; ++t, buf ^= 1) {
         const bool more = t + 1 < t1;
         if (more) co.gload(t + 1);
+        if constexpr (KP == 128) {                       // one tile per wave, the streamed factor read chunk by chunk; cb = 64 x component half
+            if (active) {
+                float x[16];
+                co.read_x(buf, gs, 0, l32, h, x);
+                const f32x16 s = co.product_streamed(buf, rs, l32, h, b1[0]);
+                if constexpr (MODE == 0) {
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        mu_bf16x8 a2c[MuShape<KP>::NA2];
+                        co.read_a2(buf, rs, l32, h, c, a2c, cb);
+                        mu_quotient_accumulate_chunk<KP, BETA1>(acc[0], accd[0], s, x, c, a2c);
+                    }
+                } else {
+                    float part = 0.f;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {       // (the same terms as below)
+                        const float dq = x[r] * __builtin_amdgcn_rcpf(mu_clamp_eps(s[r]));
+                        const float lg = __builtin_amdgcn_logf(dq) * 0.69314718056f;
+                        const float t = BETA1 ? (x[r] * lg - x[r]) : (dq - lg);
+                        part += (x[r] > MU_EPS) ? t : 0.f;
+                    }
+                    dv += (double)part;
+                }
+            }
+        } else
         if (active) {
             mu_bf16x8 a1[KP / 16][2];
             co.read_a1(buf, rs, l32, h, a1);
@@ -482,7 +538,9 @@ __global__ __launch_bounds__(512) void mu_h_coop_kernel(const float* __restrict_
     const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     using SH = MuShape<KP>;
-    const int rs = wave % SH::RPW, gs = wave / SH::RPW;
+    const int rs = wave % SH::RPW;
+    int gs = wave / SH::RPW, ch = 0;                                 // part of the 128-wide block, component half
+    if constexpr (SH::NCH == 2) { ch = gs >> 2; gs &= 3; }
     const int slot = blockIdx.z * SH::RPW + rs;
     const bool active = slot < mb.n;
     const MuSlotDev& sd = mb.s[active ? slot : 0];
@@ -518,7 +576,7 @@ __global__ __launch_bounds__(512) void mu_h_coop_kernel(const float* __restrict_
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc[jt].v[mh][r] = 0.f; accd[jt].v[mh][r] = 0.f; }
     double dv = 0.0;
-    mu_coop_loop<KP, 0, BETA1>(co, active, rs, gs, l32, h, b1, acc, accd, dv, rt0, rt1);
+    mu_coop_loop<KP, 0, BETA1>(co, active, rs, gs, l32, h, b1, acc, accd, dv, rt0, rt1, SH::KW * ch);
     if (!active) return;
     // C layout: register r <-> row m = 8 (r / 4) + 4 h + r % 4, column (gene) l32
     auto store = [&](float* base, const MuAcc<KP> (&a)[SH::NJT]) {
@@ -539,7 +597,7 @@ __global__ __launch_bounds__(512) void mu_h_coop_kernel(const float* __restrict_
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         v4f v = {a[jt].v[mh][4 * q], a[jt].v[mh][4 * q + 1], a[jt].v[mh][4 * q + 2], a[jt].v[mh][4 * q + 3]};
-                        *reinterpret_cast<v4f*>(pn + 32 * mh + 8 * q + 4 * h) = v;
+                        *reinterpret_cast<v4f*>(pn + SH::KW * ch + 32 * mh + 8 * q + 4 * h) = v;
                     }
             }
         }
@@ -558,9 +616,11 @@ __global__ __launch_bounds__(512) void mu_w_coop_kernel(const float* __restrict_
     const int tid = threadIdx.x, lane = tid & 63, l32 = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     using SH = MuShape<KP>;
-    const int rs = wave % SH::RPW, gs = wave / SH::RPW;
+    const int rs = wave % SH::RPW;
+    int gs = wave / SH::RPW, ch = 0;                                 // part of the 128-wide block, component half
+    if constexpr (SH::NCH == 2) { ch = gs >> 2; gs &= 3; }
     const int slot = blockIdx.z * SH::RPW + rs;
-    const bool active = slot < mb.n;
+    const bool active = slot < mb.n && (MODE == 0 || ch == 0);       // (the divergence has no second product to split)
     const MuSlotDev& sd = mb.s[active ? slot : 0];
     const int r0 = blockIdx.x * 128 + gs * 32 * SH::NJT;             // (ldxt = N_pad is a multiple of 128)
 
@@ -591,15 +651,15 @@ __global__ __launch_bounds__(512) void mu_w_coop_kernel(const float* __restrict_
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc[jt].v[mh][r] = 0.f; accd[jt].v[mh][r] = 0.f; }
     double dv = 0.0;
-    mu_coop_loop<KP, MODE, BETA1>(co, active, rs, gs, l32, h, b1, acc, accd, dv, 0, Gs / 32);
+    mu_coop_loop<KP, MODE, BETA1>(co, active, rs, gs, l32, h, b1, acc, accd, dv, 0, Gs / 32, SH::KW * ch);
     if (!active) return;
     if constexpr (MODE == 1) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) dv += __shfl_xor(dv, o, 64);
-        if (lane == 0 && r0 < N) sd.divpart[blockIdx.x * (8 / SH::RPW) + gs] = dv;    // one partial per strip of 32 NJT cells
+        if (lane == 0 && r0 < N) sd.divpart[blockIdx.x * (8 / SH::RPW / SH::NCH) + gs] = dv;    // one partial per strip of 32 NJT cells
         return;
     } else {
-        mu_w_epilogue<KP, BETA1>(sd, acc, accd, r0, l32, h, N, ldxt, l1, l2);
+        mu_w_epilogue<KP, BETA1>(sd, acc, accd, r0, l32, h, N, ldxt, l1, l2, SH::KW * ch);
     }
 }
 

@@ -3,7 +3,7 @@
 // 731-893): W then H half-steps, the beta-divergence every 10 iterations, stop when (previous - error) / error_at_init < tol.
 // mu_sched.h (standard library only) decides which restart sits in which slot, when the divergence is due, who stops and
 // who is refilled; this file makes the HIP calls that go with each decision.  The restarts of a call are grouped by padded
-// rank 16 / 32 / 64 and run up to MU_MAXSLOTS at a time: one round of launches advances every live slot by one iteration.
+// rank 16 / 32 / 64 (and 128 where the context's rank limit was raised) and run up to MU_MAXSLOTS at a time: one round of launches advances every live slot by one iteration.
 // Three kernel families behind ONE driver (mu_drive) and one slot path (install_slots, retire_slot, reduce_divergence):
 // MuMfma dense (Kullback-Leibler and Itakura-Saito on the matrix pipe, reading X and X^T), MuMfma sparse (Kullback-Leibler
 // at padded ranks 16 / 32 on the non-zeros, chosen by mu_sparse_prepare) and MuValu (the vector-ALU kernels: the same
@@ -553,7 +553,9 @@ static int mu_run_on(cnmf_ctx* ctx, const MuCall& c, const std::vector<MuJob>& j
 template <int KP, bool BETA1>
 static int mu_run(cnmf_ctx* ctx, const MuCall& c, const std::vector<MuJob>& jobs, MuFamily fam)
 {
-    if (fam == MU_VALU) return mu_run_on<MuValu<KP, BETA1>>(ctx, c, jobs, 1, false);
+    if constexpr (KP <= 64) {              // (their per-lane w[KP], num[KP], den[KP] do not fit above; refused before any launch)
+        if (fam == MU_VALU) return mu_run_on<MuValu<KP, BETA1>>(ctx, c, jobs, 1, false);
+    } else if (fam == MU_VALU) return CNMF_EUNSUPPORTED;
     if constexpr (KP >= 16)
         return mu_run_on<MuMfma<KP, BETA1>>(ctx, c, jobs, (int)std::min<size_t>(MU_MAXSLOTS, jobs.size()), fam == MU_SPARSE);
     return CNMF_EINVAL;
@@ -566,11 +568,25 @@ static int mu_run_kp(cnmf_ctx* ctx, const MuCall& c, const std::vector<MuJob>& j
     case 8:  return b1 ? mu_run<8, true>(ctx, c, jobs, fam) : mu_run<8, false>(ctx, c, jobs, fam);
     case 16: return b1 ? mu_run<16, true>(ctx, c, jobs, fam) : mu_run<16, false>(ctx, c, jobs, fam);
     case 32: return b1 ? mu_run<32, true>(ctx, c, jobs, fam) : mu_run<32, false>(ctx, c, jobs, fam);
+    case 128: return b1 ? mu_run<128, true>(ctx, c, jobs, fam) : mu_run<128, false>(ctx, c, jobs, fam);
     default: return b1 ? mu_run<64, true>(ctx, c, jobs, fam) : mu_run<64, false>(ctx, c, jobs, fam);
     }
 }
 
 }  // namespace cnmf
+
+// the largest rank the multiplicative-update entry points accept on this context: CNMF_MU_KMAX unless the caller opts in
+extern "C" int cnmf_set_mu_rank_limit(cnmf_ctx* ctx, int limit)
+{
+    if (!ctx) { SET_ERR(ctx, "ctx is NULL"); return CNMF_EINVAL; }
+    if (limit != CNMF_MU_KMAX && limit != CNMF_MU_KMAX_WIDE) {
+        SET_ERR(ctx, "the multiplicative-update rank limit is %d or %d, not %d", CNMF_MU_KMAX, CNMF_MU_KMAX_WIDE, limit);
+        return CNMF_EINVAL;
+    }
+    ctx->mu_rank_limit = limit;
+    return CNMF_OK;
+}
+extern "C" int cnmf_get_mu_rank_limit(const cnmf_ctx* ctx) { return ctx ? ctx->mu_rank_limit : CNMF_MU_KMAX; }
 
 extern "C" int cnmf_nmf_mu_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode,
                                  const uint32_t* seeds, const double* avg, const float* W0,
@@ -592,17 +608,33 @@ extern "C" int cnmf_nmf_mu_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int in
     if (update_H && n > 0 && !H_out) { SET_ERR(ctx, "H_out is NULL"); return CNMF_EINVAL; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const MuCall call{init_mode, beta, update_H, seeds, avg, W0, H0, prm, H_out, W_out, n_iter_out, err_out};
-    // jobs by padded rank 16 / 32 / 64, each group batched on the matrix pipe; or one restart at a time on the vector-ALU
+    // jobs by padded rank 16 / 32 / 64 / 128 (the last under cnmf_set_mu_rank_limit(CNMF_MU_KMAX_WIDE) only), each group
+    // batched on the matrix pipe; or one restart at a time on the vector-ALU
     // kernels: CNMF_MU_VALU=1, and matrices beyond 2^24 cells or genes (the matrix-pipe kernels address a 32-row step of
     // X / X^T with 32-bit byte offsets below 2^31, the buffer descriptor's range: 4 * 32 * row length)
     const bool valu = ctx->mu_knobs.valu || ctx->N_pad > (1 << 24) || ctx->G_pad > (1 << 24);
-    std::vector<MuJob> group[3], one(1);
+    std::vector<MuJob> group[4], one(1);
     size_t ho = 0, wo = 0;
     for (int r = 0; r < n; ++r) {
         const int k = kk[r];
         if (k < 1) { SET_ERR(ctx, "n_components must be >= 1"); return CNMF_EINVAL; }
-        if (k > CNMF_MU_KMAX) { SET_ERR(ctx, "n_components=%d > %d is not supported by the multiplicative-update solver on the device", k, CNMF_MU_KMAX); return CNMF_EUNSUPPORTED; }
-        group[valu ? 0 : (k <= 16 ? 0 : (k <= 32 ? 1 : 2))].push_back(MuJob{r, k, ho, wo});
+        if (k > ctx->mu_rank_limit) {
+            if (ctx->mu_rank_limit < CNMF_MU_KMAX_WIDE && k <= CNMF_MU_KMAX_WIDE)
+                SET_ERR(ctx, "n_components=%d > %d is not supported by the multiplicative-update solver on the device under the rank limit in force "
+                             "(%d); cnmf_set_mu_rank_limit(ctx, %d) admits ranks up to %d", k, ctx->mu_rank_limit, ctx->mu_rank_limit,
+                        CNMF_MU_KMAX_WIDE, CNMF_MU_KMAX_WIDE);
+            else
+                SET_ERR(ctx, "n_components=%d > %d is not supported by the multiplicative-update solver on the device (rank limit in force %d, "
+                             "the largest cnmf_set_mu_rank_limit accepts is %d)", k, ctx->mu_rank_limit, ctx->mu_rank_limit, CNMF_MU_KMAX_WIDE);
+            return CNMF_EUNSUPPORTED;
+        }
+        if (valu && k > CNMF_MU_KMAX) {
+            SET_ERR(ctx, "n_components=%d > %d is not supported on the vector-ALU route of the multiplicative-update solver (CNMF_MU_VALU=1, "
+                         "or a matrix beyond 2^24 cells or genes): ranks %d..%d run on the matrix-pipe kernels only", k, CNMF_MU_KMAX,
+                    CNMF_MU_KMAX + 1, CNMF_MU_KMAX_WIDE);
+            return CNMF_EUNSUPPORTED;
+        }
+        group[valu ? 0 : (k <= 16 ? 0 : (k <= 32 ? 1 : (k <= 64 ? 2 : 3)))].push_back(MuJob{r, k, ho, wo});
         ho += (size_t)k * ctx->G; wo += (size_t)k * ctx->N;
     }
     if (valu) {
@@ -613,10 +645,10 @@ extern "C" int cnmf_nmf_mu_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int in
         return CNMF_OK;
     }
     // Kullback-Leibler at padded ranks 16 / 32 on a matrix that is mostly zeros: only the non-zeros are touched
-    bool sparse[3] = {false, false, false};
+    bool sparse[4] = {false, false, false, false};
     for (int g = 0; g < 2; ++g)
         if (beta == 1 && !group[g].empty() && (rc = mu_sparse_prepare(ctx, 16 << g, &sparse[g]))) return rc;
-    for (int g = 0; g < 3; ++g)
+    for (int g = 0; g < 4; ++g)
         if (!group[g].empty() && (rc = mu_run_kp(ctx, call, group[g], 16 << g, sparse[g] ? MU_SPARSE : MU_DENSE))) return rc;
     return CNMF_OK;
 }

@@ -150,6 +150,114 @@ __global__ __launch_bounds__(256) void mu_refit_f64_kernel(const long long* __re
     }
 }
 
+// Ranks 65..128 (padded to 128): the same iteration, but w[128] + acc[128] (+ dacc[128]) doubles per lane are 512 (768)
+// registers.  The row's factor therefore lives in LDS (a 128-double row per wavefront, read by broadcast) with lane l
+// holding components l and l + 64 of the NEXT iterate, and the components are accumulated in passes of PC (64 for
+// Kullback-Leibler, 32 for Itakura-Saito with its second set of sums: 128 accumulator registers either way) -- the
+// row's entries are walked once per pass and s_ij recomputed in each.  Same lane stride over the entries, same butterfly.
+// w . h over 128 components runs as four interleaved chains (c mod 4) closed as (s0 + s1) + (s2 + s3).
+__device__ __forceinline__ double mu_refit_dot128(const double* w, const double* __restrict__ h)
+{
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+#pragma unroll 8
+    for (int c = 0; c < 128; c += 4) {
+        s0 += w[c] * h[c]; s1 += w[c + 1] * h[c + 1]; s2 += w[c + 2] * h[c + 2]; s3 += w[c + 3] * h[c + 3];
+    }
+    return (s0 + s1) + (s2 + s3);
+}
+template <int BETA>
+__global__ __launch_bounds__(256) void mu_refit_f64_wide_kernel(const long long* __restrict__ ptr, const int* __restrict__ idx,
+                                                                const float* __restrict__ val, int nrows,
+                                                                const double* __restrict__ Ht, const double* __restrict__ coldiv,
+                                                                double* __restrict__ W, const double* __restrict__ hsum,
+                                                                double l1, double l2, int n_inner, double* __restrict__ err_part,
+                                                                double ncount)
+{
+    constexpr int KP = 128, PC = BETA == 1 ? 64 : 32;
+    __shared__ double wsh[4][KP];
+    const int wv = threadIdx.x >> 6, row = blockIdx.x * 4 + wv, lane = threadIdx.x & 63;
+    if (row >= nrows) return;                      // (a whole wavefront: the kernel has no workgroup barrier)
+    const long long b = ptr[row], e = ptr[row + 1];
+    double* w = wsh[wv];
+    double wn[2] = {W[(size_t)row * KP + lane], W[(size_t)row * KP + 64 + lane]};
+    w[lane] = wn[0]; w[64 + lane] = wn[1];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int it = 0; it < n_inner; ++it) {
+#pragma unroll 1
+        for (int c0 = 0; c0 < KP; c0 += PC) {
+            double acc[PC], dacc[BETA == 1 ? 1 : PC];
+#pragma unroll
+            for (int c = 0; c < PC; ++c) { acc[c] = 0.0; if constexpr (BETA != 1) dacc[c] = 0.0; }
+            for (long long p = b + lane; p < e; p += 64) {
+                const int j = idx[p];
+                double x = (double)val[p];
+                if (coldiv) { const double d = coldiv[j]; x = d != 0.0 ? x / d : 0.0; }
+                const double* h = Ht + (size_t)j * KP;
+                const double s = fmax(mu_refit_dot128(w, h), MU_EPS32);
+                if constexpr (BETA == 1) {
+                    const double q = x / s;
+#pragma unroll
+                    for (int c = 0; c < PC; ++c) acc[c] += q * h[c0 + c];
+                } else {
+                    const double r = 1.0 / s;
+                    const double q = (r * r) * x;
+#pragma unroll
+                    for (int c = 0; c < PC; ++c) { const double hv = h[c0 + c]; acc[c] += q * hv; dacc[c] += r * hv; }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < PC; ++c) {
+                double a = acc[c], d = 0.0;
+                if constexpr (BETA != 1) d = dacc[c];
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    a += __shfl_xor(a, o, 64);
+                    if constexpr (BETA != 1) d += __shfl_xor(d, o, 64);
+                }
+                const double wc = w[c0 + c];
+                double den = (BETA == 1 ? hsum[c0 + c] : d) + l1 + l2 * wc;
+                if (den == 0.0) den = MU_EPS32;
+                double nw;
+                if constexpr (BETA == 1) nw = wc * (a / den);
+                else {
+                    nw = wc * sqrt(a / den);
+                    if (nw < 2.220446049250313e-16) nw = 0.0;
+                }
+                if (lane == ((c0 + c) & 63)) wn[(c0 + c) >> 6] = nw;       // (every lane holds the same nw)
+            }
+        }
+        __builtin_amdgcn_wave_barrier();           // every read of the old iterate is done
+        w[lane] = wn[0]; w[64 + lane] = wn[1];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (n_inner > 0) { W[(size_t)row * KP + lane] = wn[0]; W[(size_t)row * KP + 64 + lane] = wn[1]; }
+    if (err_part) {
+        double r = 0.0;
+        for (long long p = b + lane; p < e; p += 64) {
+            const int j = idx[p];
+            double x = (double)val[p];
+            if (coldiv) { const double d = coldiv[j]; x = d != 0.0 ? x / d : 0.0; }
+            if (!(x > MU_EPS32)) continue;
+            const double s = fmax(mu_refit_dot128(w, Ht + (size_t)j * KP), MU_EPS32);
+            if constexpr (BETA == 1) r += x * log(x / s) - x;
+            else { const double dv = x / s; r += dv - log(dv); }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
+        if (lane == 0) {
+            if constexpr (BETA == 1) {
+                double swh = 0.0;
+                for (int c = 0; c < KP; ++c) swh += w[c] * hsum[c];
+                err_part[row] = r + swh;
+            } else {
+                err_part[row] = r - ncount;
+            }
+        }
+    }
+}
+
 // fixed-order sum of the per-row shares: 1024 strided partial sums, then one thread
 __global__ __launch_bounds__(1024) void mu_refit_err_kernel(const double* __restrict__ part, int n, double* __restrict__ out)
 {
@@ -183,7 +291,14 @@ extern "C" int cnmf_mu_refit_f64(cnmf_ctx* ctx, int side, int beta, int k, const
     if (!ctx || !H || !prm || !W_out) { SET_ERR(ctx, "null argument"); return CNMF_EINVAL; }
     if (beta != 0 && beta != 1) { SET_ERR(ctx, "beta must be 1 (Kullback-Leibler) or 0 (Itakura-Saito)"); return CNMF_EINVAL; }
     if (!ctx->X && !ctx->csr.ptr) { SET_ERR(ctx, "cnmf_set_matrix has not been called"); return CNMF_ESTATE; }
-    if (k < 1 || k > CNMF_MU_KMAX) { SET_ERR(ctx, "rank %d outside 1..%d (multiplicative updates)", k, CNMF_MU_KMAX); return CNMF_EUNSUPPORTED; }
+    if (k < 1 || k > ctx->mu_rank_limit) {
+        if (k > CNMF_MU_KMAX && k <= CNMF_MU_KMAX_WIDE)
+            SET_ERR(ctx, "rank %d outside 1..%d (multiplicative updates; the rank limit in force: cnmf_set_mu_rank_limit(ctx, %d) admits ranks up to %d)",
+                    k, ctx->mu_rank_limit, CNMF_MU_KMAX_WIDE, CNMF_MU_KMAX_WIDE);
+        else
+            SET_ERR(ctx, "rank %d outside 1..%d (multiplicative updates; the rank limit in force, at most %d)", k, ctx->mu_rank_limit, CNMF_MU_KMAX_WIDE);
+        return CNMF_EUNSUPPORTED;
+    }
     if (side != 0 && side != 1) { SET_ERR(ctx, "side must be 0 (rows = cells) or 1 (rows = genes)"); return CNMF_EINVAL; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = side == 0 ? ensure_csr(ctx) : ensure_csc(ctx);
@@ -193,7 +308,7 @@ extern "C" int cnmf_mu_refit_f64(cnmf_ctx* ctx, int side, int beta, int k, const
     const long long* ptr = side == 0 ? ctx->csr.ptr : ctx->csc.ptr;
     const int* idx = side == 0 ? ctx->csr.idx : ctx->csc.idx;
     const float* val = side == 0 ? ctx->csr.val : ctx->csc.val;
-    const int KP = k <= 8 ? 8 : (k <= 16 ? 16 : (k <= 32 ? 32 : 64));
+    const int KP = k <= 8 ? 8 : (k <= 16 ? 16 : (k <= 32 ? 32 : (k <= 64 ? 64 : 128)));
     if (beta == 0) {
         // scikit-learn's own refusal (_nmf.py:1679-1684): every entry must be positive, i.e. every entry is stored
         long long nnz = 0;
@@ -237,11 +352,14 @@ extern "C" int cnmf_mu_refit_f64(cnmf_ctx* ctx, int side, int beta, int k, const
         const unsigned grid = (unsigned)((nrows + 3) / 4);
 #define CNMF_MU_REFIT_LAUNCH(KPV, BV) mu_refit_f64_kernel<KPV, BV><<<grid, 256, 0, st>>>(ptr, idx, val, nrows, dHt, dDiv, dW, dHs, l1, l2, \
                                                                                      n_inner, err ? dPart : nullptr, ncount)
+#define CNMF_MU_REFIT_WIDE(BV) mu_refit_f64_wide_kernel<BV><<<grid, 256, 0, st>>>(ptr, idx, val, nrows, dHt, dDiv, dW, dHs, l1, l2, \
+                                                                                 n_inner, err ? dPart : nullptr, ncount)
         if (beta == 1) {
             switch (KP) {
                 case 8:  CNMF_MU_REFIT_LAUNCH(8, 1); break;
                 case 16: CNMF_MU_REFIT_LAUNCH(16, 1); break;
                 case 32: CNMF_MU_REFIT_LAUNCH(32, 1); break;
+                case 128: CNMF_MU_REFIT_WIDE(1); break;
                 default: CNMF_MU_REFIT_LAUNCH(64, 1); break;
             }
         } else {
@@ -249,10 +367,12 @@ extern "C" int cnmf_mu_refit_f64(cnmf_ctx* ctx, int side, int beta, int k, const
                 case 8:  CNMF_MU_REFIT_LAUNCH(8, 0); break;
                 case 16: CNMF_MU_REFIT_LAUNCH(16, 0); break;
                 case 32: CNMF_MU_REFIT_LAUNCH(32, 0); break;
+                case 128: CNMF_MU_REFIT_WIDE(0); break;
                 default: CNMF_MU_REFIT_LAUNCH(64, 0); break;
             }
         }
 #undef CNMF_MU_REFIT_LAUNCH
+#undef CNMF_MU_REFIT_WIDE
         HIP_TRY(ctx, hipGetLastError());
         if (err) {
             double res = 0.0;

@@ -287,6 +287,7 @@ struct cnmf_ctx {
     std::map<std::string, std::string> env;
     CdKnobs knobs;                                 // ... and the switches of the coordinate-descent batch path, parsed from it
     MuKnobs mu_knobs;                              // ... and of the multiplicative-update solver
+    int mu_rank_limit = CNMF_MU_KMAX;              // cnmf_set_mu_rank_limit(): CNMF_MU_KMAX, or CNMF_MU_KMAX_WIDE by opt-in (never from the environment)
 
     // data matrix
     int64_t N = 0, G = 0;

@@ -95,9 +95,9 @@ def _nndsvd_fill(W, H, variant, x_mean, random_state):
 
 
 class Engine:
-    def __init__(self, device=0, detect_counts=True):
+    def __init__(self, device=0, detect_counts=True, mu_rank_limit=_lib.CNMF_MU_KMAX):
         """``detect_counts=False``: never take the integer-plane (count-structured) GEMM path -- see
-        :meth:`set_count_detection`."""
+        :meth:`set_count_detection`.  ``mu_rank_limit``: 64 (default) or 128, see :attr:`mu_rank_limit`."""
         self._lib = _lib.load()
         if self._lib.cnmf_device_count() <= 0:
             raise RuntimeError("cnmf_amd: no HIP device visible -- the engine has no CPU fallback")
@@ -117,6 +117,20 @@ class Engine:
         self.last_store_gen = -1
         if not detect_counts:
             self.set_count_detection(False)
+        if mu_rank_limit != _lib.CNMF_MU_KMAX:
+            self.mu_rank_limit = mu_rank_limit
+
+    @property
+    def mu_rank_limit(self):
+        """Largest rank :meth:`nmf_mu_batch`, :meth:`nnls_mu` and :meth:`mu_refit_f64` accept on this engine: 64
+        (``CNMF_MU_KMAX``, the default) or, by opt-in, 128 (``CNMF_MU_KMAX_WIDE``: ranks 65..128 on the matrix-pipe kernels
+        and the float64 refit; the vector-ALU route -- ``CNMF_MU_VALU=1`` or a matrix beyond 2^24 cells or genes -- stays at
+        64).  Any other value raises ValueError."""
+        return int(self._lib.cnmf_get_mu_rank_limit(self._ctx))
+
+    @mu_rank_limit.setter
+    def mu_rank_limit(self, limit):
+        self._check(self._lib.cnmf_set_mu_rank_limit(self._ctx, int(limit)))
 
     def set_count_detection(self, enabled):
         """The engine recognises ``X = counts / std`` (integers x one constant per gene, tolerance 1e-3 count units;
@@ -1135,7 +1149,8 @@ class Engine:
                      max_iter=1000, alpha_W=0.0, alpha_H=0.0, l1_ratio=0.0, return_W=False, warn=True, init_store=False):
         """``solver='mu'`` restarts (the reference's path for beta_loss != 'frobenius',
         cnmf.py:618-631).  Same arguments / returns as :meth:`nmf_batch` (``init_store=True`` included); the last element
-        of the returned tuple is sqrt(2*beta-divergence) at the final evaluation."""
+        of the returned tuple is sqrt(2*beta-divergence) at the final evaluation.  Ranks above :attr:`mu_rank_limit`
+        (64 unless raised to 128) raise NotImplementedError."""
         if self.shape is None:
             raise RuntimeError("set_matrix() has not been called")
         if beta_loss not in self._BETA:
@@ -1186,7 +1201,7 @@ class Engine:
                 warn=True):
         """Refit with fixed H and ``solver='mu'``: W starts from avg everywhere (sklearn _nmf.py:1229-1231).
         Both losses: the float64 refit on the stored entries (:meth:`mu_refit_f64`; result cast to float32 like the
-        other refits of this class)."""
+        other refits of this class).  Ranks above :attr:`mu_rank_limit` (64 unless raised to 128): NotImplementedError."""
         if self.shape is None:
             raise RuntimeError("set_matrix() has not been called")
         N, G = self.shape
@@ -1216,7 +1231,7 @@ class Engine:
         """``non_negative_factorization(X, H=H, update_H=False, solver='mu', beta_loss=...)`` in float64 on
         the stored entries of the resident matrix (cnmf_mu_refit_f64): returns ``(W float64, n_iter, err)``.
         ``beta_loss='itakura-saito'`` (round 6): the matrix must be strictly positive (scikit-learn's rule), so every entry
-        is a stored entry.
+        is a stored entry.  ``H`` has at most :attr:`mu_rank_limit` rows (64 unless raised to 128), else NotImplementedError.
 
         ``transposed=False``: X = the resident cells x genes matrix, ``H`` [k, n_genes], W [n_cells, k] (refit_usage,
         cnmf.py:776-802).  ``transposed=True``: the problem on X^T -- ``H`` [k, n_cells] (usages^T), W [n_genes, k]

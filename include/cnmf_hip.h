@@ -43,7 +43,10 @@ extern "C" {
 #define CNMF_KMAX 128          /* largest rank of the coordinate-descent / NNLS / consensus entry points
                                   (<= 64: register-resident sweep; 65..128: sweep_big_kernel)              */
 
-#define CNMF_MU_KMAX 64        /* largest rank of the multiplicative-update solver (cnmf_nmf_mu_batch)      */
+#define CNMF_MU_KMAX 64        /* largest rank of the multiplicative-update entry points (cnmf_nmf_mu_batch,
+                                  cnmf_mu_refit_f64) on a context as created ...                            */
+#define CNMF_MU_KMAX_WIDE 128  /* ... and after cnmf_set_mu_rank_limit(ctx, CNMF_MU_KMAX_WIDE): ranks 65..128 on the
+                                  matrix-pipe kernels and the float64 refit (the vector-ALU route stays at 64)  */
 
 typedef struct cnmf_ctx cnmf_ctx;
 
@@ -467,7 +470,10 @@ int cnmf_set_iteration_hints(cnmf_ctx* ctx, int n, const int32_t* k, const doubl
  * err_out[r] = sqrt(2 * beta-divergence) of the FINAL factors (sklearn's reconstruction_err_).
  * Restarts run batched on the matrix pipe (padded rank 16 / 32 / 64, both losses), up to 32 per round of
  * launches sharing each pass over X (kernels_mu_mfma.hip.h); a restart's result does not depend on the
- * batch it ran in.  Ranks above CNMF_MU_KMAX (64): CNMF_EUNSUPPORTED.
+ * batch it ran in.  Ranks above the context's limit (cnmf_get_mu_rank_limit: CNMF_MU_KMAX = 64 unless raised):
+ * CNMF_EUNSUPPORTED.  With the limit raised to CNMF_MU_KMAX_WIDE, ranks 65..128 run as a fourth group at padded rank 128
+ * (one restart per workgroup, the same arithmetic); on the vector-ALU route (CNMF_MU_VALU=1, or a matrix beyond 2^24
+ * cells or genes) they are CNMF_EUNSUPPORTED before any launch.
  * The first call builds a resident transposed copy of X (freed with the matrix).
  * Kullback-Leibler on the NON-ZEROS (round 4, kernels_mu_sparse.hip.h) -- scikit-learn's own route for scipy.sparse input
  * (sklearn:_nmf.py:192 `_special_sparse_dot`): taken by itself when beta = 1, every rank of the call is <= 32 and at most a
@@ -478,6 +484,10 @@ int cnmf_set_iteration_hints(cnmf_ctx* ctx, int n, const int32_t* k, const doubl
  * restart in flight the partial numerators [blocks of the other side][own rows][padded rank] float32.  When those
  * allocations do not fit the call falls back to the dense kernels.  The environment variable CNMF_MU_SPARSE (read when the
  * context is created; 0 = never, 1 = always where the rank allows) overrides the density rule.                       */
+/* The largest rank cnmf_nmf_mu_batch and cnmf_mu_refit_f64 accept on this context: CNMF_MU_KMAX (the default) or
+ * CNMF_MU_KMAX_WIDE; any other value is CNMF_EINVAL.  Per context, set through this call only (no environment switch). */
+int cnmf_set_mu_rank_limit(cnmf_ctx* ctx, int limit);
+int cnmf_get_mu_rank_limit(const cnmf_ctx* ctx);
 int cnmf_nmf_mu_batch(cnmf_ctx* ctx, int n_restarts, const int32_t* k, int init_mode,
                       const uint32_t* seeds, const double* avg, const float* W0, const float* H0,
                       int beta, int update_H, const cnmf_cd_params* params,
@@ -498,7 +508,8 @@ int cnmf_nmf_mu_batch(cnmf_ctx* ctx, int n_restarts, const int32_t* k, int init_
  *   usage refit on tpm[:, hvgs] / std (cnmf.py:963-972) against the resident full TPM matrix.
  * w_init: W starts from this value everywhere (sklearn:_nmf.py:1229-1231: sqrt(X.mean() / k) of the matrix meant).
  * params: tol, max_iter, l1_reg_W, l2_reg_W.  n_iter_out as scikit-learn counts (a multiple of 10 or max_iter),
- * err_out = sqrt(2 x divergence) of the final factors.  Ranks above CNMF_MU_KMAX: CNMF_EUNSUPPORTED.             */
+ * err_out = sqrt(2 x divergence) of the final factors.  Ranks above the context's limit (cnmf_get_mu_rank_limit):
+ * CNMF_EUNSUPPORTED; ranks 65..128 (limit raised) keep the row's factor in LDS and accumulate the components in passes.  */
 int cnmf_mu_refit_f64(cnmf_ctx* ctx, int side, int beta, int k, const double* H, const double* coldiv, double w_init,
                       const cnmf_cd_params* params, double* W_out, int32_t* n_iter_out, double* err_out);
 

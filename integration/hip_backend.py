@@ -29,6 +29,7 @@ import yaml
 import cnmf.cnmf as _ref                      # the UNMODIFIED reference module
 from cnmf.cnmf import load_df_from_npz, save_df_to_npz, worker_filter
 
+from cnmf_amd.cnmf import cNMF as _mirror
 from cnmf_amd.engine import NNDSVD_VARIANTS, Engine
 from cnmf_amd.standins import DeviceKMeans, device_euclidean_distances, device_silhouette_score
 
@@ -40,6 +41,9 @@ class cNMF(_ref.cNMF):
     _untransposed = None          # set by refit_spectra around the inherited call
     _resident = None              # STRONG reference to the matrix object that is on the device (identity check)
     nndsvd = "host"               # "device": the tail of init='nndsvd*' on the device too (cnmf_amd.cnmf.cNMF.nndsvd)
+    mu_ranks = None               # "wide": multiplicative-update ranks 65..128 (cnmf_amd.cnmf.cNMF.mu_ranks); None: up to 64
+    _mu_kmax = _mirror._mu_kmax
+    _mu_rank_scope = _mirror._mu_rank_scope       # raises Engine.mu_rank_limit around a device call, puts it back after
 
     # -- engine plumbing ---------------------------------------------------------------------------
     def __getstate__(self):       # multiprocessing pickles the object (cnmf.py:254-262): a ctypes handle cannot travel
@@ -112,7 +116,8 @@ class cNMF(_ref.cNMF):
                 # float64 on the stored entries of the matrix (cnmf_mu_refit_f64), like scikit-learn on float64 input; the
                 # transposed problem walks the column-compressed image (rows = genes).  Both beta losses: an Itakura-Saito
                 # run's matrices are strictly positive (scikit-learn refuses anything else), every entry is stored
-                W, _, _ = eng.mu_refit_f64(H, transposed=transposed, beta_loss=kw["beta_loss"], **common)
+                with self._mu_rank_scope(eng):
+                    W, _, _ = eng.mu_refit_f64(H, transposed=transposed, beta_loss=kw["beta_loss"], **common)
             elif transposed:
                 Hs, _ = eng.nnls_spectra(np.ascontiguousarray(H.T), **common)  # k x genes on the resident matrix
                 W = np.ascontiguousarray(Hs.T)
@@ -126,8 +131,9 @@ class cNMF(_ref.cNMF):
         else:
             init = dict(seeds=[seed])
         if mu:
-            Hl, Wl, _, _ = eng.nmf_mu_batch([k], beta_loss=kw["beta_loss"], alpha_H=kw.get("alpha_H", 0.0), return_W=True,
-                                            **init, **common)
+            with self._mu_rank_scope(eng):
+                Hl, Wl, _, _ = eng.nmf_mu_batch([k], beta_loss=kw["beta_loss"], alpha_H=kw.get("alpha_H", 0.0), return_W=True,
+                                                **init, **common)
         else:
             Hl, Wl, _, _ = eng.nmf_batch([k], alpha_H=kw.get("alpha_H", 0.0), return_W=True, **init, **common)
         return Hl[0].astype(xdt), Wl[0].astype(xdt)
@@ -159,7 +165,8 @@ class cNMF(_ref.cNMF):
             inits = eng.nndsvd_init_batch(ks, seeds, variant=kw["init"], tail=tail, keep=tail == "device")
             init = dict(init_store=True) if inits is None else dict(W0=[w for w, _ in inits], H0=[h for _, h in inits])
         if kw.get("solver", "cd") == "mu":
-            H, _, _, _ = eng.nmf_mu_batch(ks, beta_loss=kw["beta_loss"], **init, **common)
+            with self._mu_rank_scope(eng):
+                H, _, _, _ = eng.nmf_mu_batch(ks, beta_loss=kw["beta_loss"], **init, **common)
         else:
             H, _, _, _ = eng.nmf_batch(ks, **init, **common)              # ONE batched call: X is read per PASS, not per restart
         xdt = norm_counts.X.dtype if norm_counts.X.dtype in (np.float32, np.float64) else np.float64
