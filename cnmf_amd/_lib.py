@@ -47,7 +47,7 @@ SYMBOLS = [
     "cnmf_consensus_store", "cnmf_kselect_stats_store", "cnmf_clustergram", "cnmf_clustergram_step_ms",
     "cnmf_range_finder", "cnmf_format_rows_f64",
     "cnmf_nndsvd_group", "cnmf_init_store_reset", "cnmf_init_store_fetch",
-    "cnmf_set_mu_rank_limit", "cnmf_get_mu_rank_limit",
+    "cnmf_set_mu_rank_limit", "cnmf_get_mu_rank_limit", "cnmf_set_mu_sparse_rank_limit", "cnmf_get_mu_sparse_rank_limit",
 ]
 # test hooks (include/cnmf_hip_debug.h): present only in a library built with -DCNMF_DEBUG_ABI -- the in-tree default,
 # because tests/ call them; CNMF_PRODUCT_BUILD=1 in the environment of build() leaves them out
@@ -59,6 +59,8 @@ COMM_ID_BYTES = 128
 CNMF_KMAX = 128
 CNMF_MU_KMAX = 64
 CNMF_MU_KMAX_WIDE = 128         # (cnmf_set_mu_rank_limit: the opt-in limit of the multiplicative-update entry points)
+CNMF_MU_SPARSE_KMAX = 32
+CNMF_MU_SPARSE_KMAX_WIDE = 64   # (cnmf_set_mu_sparse_rank_limit: the opt-in limit of Kullback-Leibler on the non-zeros)
 CNMF_RIDGE_MAX = 4096
 CNMF_PCA_NMAX = 8192
 CNMF_NOT_ACCEPTED = 1           # (no error: the device's check of its tridiagonal solve failed; the caller falls back)
@@ -306,6 +308,10 @@ def load():
     lib.cnmf_set_mu_rank_limit.argtypes = [vp, i32]
     lib.cnmf_get_mu_rank_limit.restype = i32
     lib.cnmf_get_mu_rank_limit.argtypes = [vp]
+    lib.cnmf_set_mu_sparse_rank_limit.restype = i32
+    lib.cnmf_set_mu_sparse_rank_limit.argtypes = [vp, i32]
+    lib.cnmf_get_mu_sparse_rank_limit.restype = i32
+    lib.cnmf_get_mu_sparse_rank_limit.argtypes = [vp]
     lib.cnmf_mu_refit_f64.restype = i32
     lib.cnmf_mu_refit_f64.argtypes = [vp, i32, i32, i32, dblp, dblp, C.c_double, C.POINTER(CdParams), dblp, i32p, dblp]
     lib.cnmf_get_iteration_means.restype = i32

@@ -328,6 +328,10 @@ class cNMF:
     # up to 128 (CNMF_MU_KMAX_WIDE) -- get_nmf_iter_params admits them, and factorize / _nmf / the MU tail of consensus
     # raise the engine's limit (Engine.mu_rank_limit) around their own device calls and put the previous value back.
     mu_ranks = None
+    # Kullback-Leibler on the non-zeros of the matrix: None = ranks up to 32 (CNMF_MU_SPARSE_KMAX; above, the dense kernels),
+    # "wide" = opt-in up to 64 (CNMF_MU_SPARSE_KMAX_WIDE, two lanes per row).  The same call sites raise
+    # Engine.mu_sparse_rank_limit around their device calls and put the previous value back.
+    mu_sparse_ranks = None
 
     def __init__(self, output_dir=".", name=None, device=0, engine=None, compress_merged=True, detect_counts=True):
         """Same constructor semantics as the reference (cnmf.py:268-296) plus the GPU index.
@@ -461,6 +465,8 @@ class cNMF:
         k_list = sorted(set(list(ks)))
         from ._lib import CNMF_KMAX
         kmax = CNMF_KMAX if beta_loss == "frobenius" else self._mu_kmax()
+        if beta_loss != "frobenius":
+            self._mu_sparse_kmax()                            # (a mistyped mu_sparse_ranks is refused here, before any run)
         if k_list and max(k_list) > kmax:
             # fail at prepare time, not after the restarts were paid for (the reference itself has no limit,
             # cnmf.py:1243; the device engine: 128 for the coordinate-descent solver, 64 for the
@@ -737,20 +743,45 @@ class cNMF:
             raise ValueError("cNMF.mu_ranks must be None or 'wide', not %r" % (self.mu_ranks,))
         return CNMF_MU_KMAX_WIDE if self.mu_ranks == "wide" else CNMF_MU_KMAX
 
+    def _mu_sparse_kmax(self):
+        """Largest rank this object lets a Kullback-Leibler restart run on the non-zeros (``self.mu_sparse_ranks``)."""
+        from ._lib import CNMF_MU_SPARSE_KMAX, CNMF_MU_SPARSE_KMAX_WIDE
+        ranks = getattr(self, "mu_sparse_ranks", None)
+        if ranks not in (None, "wide"):
+            raise ValueError("cNMF.mu_sparse_ranks must be None or 'wide', not %r" % (ranks,))
+        return CNMF_MU_SPARSE_KMAX_WIDE if ranks == "wide" else CNMF_MU_SPARSE_KMAX
+
     @contextlib.contextmanager
-    def _mu_rank_scope(self, eng):
-        """``self.mu_ranks = "wide"``: the engine's multiplicative-update rank limit is raised for the device calls inside
-        the block and put back afterwards (the engine may be shared: ``engine=``)."""
-        kmax = self._mu_kmax()
-        if not hasattr(eng, "mu_rank_limit") or eng.mu_rank_limit >= kmax:
+    def _mu_sparse_rank_scope(self, eng):
+        """``self.mu_sparse_ranks = "wide"``: the engine's rank limit of the non-zero path is raised for the device calls
+        inside the block and put back afterwards (the engine may be shared: ``engine=``)."""
+        kmax = self._mu_sparse_kmax()
+        if not hasattr(eng, "mu_sparse_rank_limit") or eng.mu_sparse_rank_limit >= kmax:
             yield
             return
-        prev = eng.mu_rank_limit
-        eng.mu_rank_limit = kmax
+        prev = eng.mu_sparse_rank_limit
+        eng.mu_sparse_rank_limit = kmax
         try:
             yield
         finally:
-            eng.mu_rank_limit = prev
+            eng.mu_sparse_rank_limit = prev
+
+    @contextlib.contextmanager
+    def _mu_rank_scope(self, eng):
+        """``self.mu_ranks = "wide"``: the engine's multiplicative-update rank limit is raised for the device calls inside
+        the block and put back afterwards (the engine may be shared: ``engine=``).  The same block runs under
+        :meth:`_mu_sparse_rank_scope`: every device call of the multiplicative-update route sits in one of these blocks."""
+        kmax = self._mu_kmax()
+        with self._mu_sparse_rank_scope(eng):
+            if not hasattr(eng, "mu_rank_limit") or eng.mu_rank_limit >= kmax:
+                yield
+                return
+            prev = eng.mu_rank_limit
+            eng.mu_rank_limit = kmax
+            try:
+                yield
+            finally:
+                eng.mu_rank_limit = prev
 
     def _nndsvd_tail(self, variant, eng):
         """The tail ``factorize`` / ``_nmf`` ask the engine for (``self.nndsvd``)."""

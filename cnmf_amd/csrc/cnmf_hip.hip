@@ -113,7 +113,7 @@ static void drop_derived_images(cnmf_ctx* c)
     hipStreamSynchronize(c->stream);
     c->planes.release(); c->counts.release(); c->x2.release();
     c->XtF.release();
-    for (int i = 0; i < 2; ++i) { c->spA[i].release(); c->spB[i].release(); }
+    for (int i = 0; i < cnmf_ctx::SP_IMAGES; ++i) { c->spA[i].release(); c->spB[i].release(); }
     c->x_nnz = -1;
     c->inits.release();                                  // (start factors computed from the old values)
     free_csr(c);
@@ -295,7 +295,7 @@ extern "C" int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags)
     if (!ctx || !flags) return CNMF_EINVAL;
     *flags = (ctx->X ? 1 : 0) | (ctx->csr.ptr ? 2 : 0) | (ctx->csc.ptr ? 4 : 0) | (ctx->XtF.p ? 8 : 0) |
              ((ctx->spA[0].ent && ctx->spB[0].ent) ? 16 : 0) | ((ctx->spA[1].ent && ctx->spB[1].ent) ? 32 : 0) | (ctx->counts.C1 ? 64 : 0) |
-             ((ctx->counts.C1 && ctx->counts.bytes) ? 128 : 0);
+             ((ctx->counts.C1 && ctx->counts.bytes) ? 128 : 0) | ((ctx->spA[2].ent && ctx->spB[2].ent) ? 256 : 0);
     return CNMF_OK;
 }
 

@@ -18,6 +18,10 @@
 // Measured there: 108 us per restart-iteration at ranks up to 13 (dense matrix-pipe kernels: 340), DESIGN.md section 4.
 //
 // Summation order is fixed (entries of a row in storage order, blocks in index order): results are run-to-run identical.
+//
+// Padded ranks 16 and 32 run a lane per row (sp_slices); padded rank 64 (ranks 33..64, admitted by
+// cnmf_set_mu_sparse_rank_limit only) runs two lanes per row on the same image format (sp_slices_pair).  Padded rank 128
+// has no image: the builders divide by 16 / (KP / 4) rows per bank line.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels_mu.hip.h"
@@ -353,6 +357,139 @@ __device__ __forceinline__ void sp_slices(const BSellDev& A, const MuSlotDev& sd
     }
 }
 
+// ---- padded rank 64 (ranks 33..64): TWO lanes per own row.  One lane with w[64], num[64] and a gathered row would need
+// ~200 registers; the workgroup is 1024 threads (128 registers a lane).  So lanes l and l + 32 of a wavefront share a row of
+// the slice and each holds every other live quad of it: half h = lane / 32 owns logical quads h, h + 2, ..., NH of them
+// (NH = ceil(live quads / 2) = 5..8: the register picture of sp_slices at NQ <= 8).  A 64-row slice is walked in two passes
+// of 32 rows; in pass p lane l reads entry 32 p + (l & 31) of a step, the same address in both halves (256 contiguous
+// bytes a step).  The image is the one the builders make for KP = 64: in pass 0 the four ds_read_b128 lane groups read the
+// row sets that sp_reorder_kernel arranged for groups 0 and 1 (groups 2 and 3 of the hardware read the same rows, another
+// quad), in pass 1 those of groups 2 and 3; a group reads ONE logical quad of 16 rows whose residues modulo 16 differ, and
+// the rotation (row r by r mod 16 quads of a 256-byte row) maps them onto the 16 quad slots one to one.
+// The two partial dot products of an entry meet in one v_permlane32_swap: both lanes form (low half) + (high half).
+// (addresses: a wave-uniform base and a 32-bit byte offset per lane -- one register where a pointer per lane takes two; a
+// (slice, block) holds at most BS steps of 512 bytes)
+template <class T> __device__ __forceinline__ const T& sp_at(const T* base, unsigned byte_off)
+{
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+__device__ __forceinline__ long long sp_uniform(long long v)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+template <int MODE, int SIDE, int NH>
+__device__ __forceinline__ void sp_slices_pair(const BSellDev& A, const MuSlotDev& sd, const unsigned char* lds_raw, int grp, int blk,
+                                               int spw, int wv, int lane, int nq, float l1, float l2, int Rs, double& acc)
+{
+    constexpr int KP = 64, KH = NH * 2;
+    constexpr unsigned RM = KP * 4 - 1;                                     // byte mask of one row
+    float* own = SIDE ? sd.Ht : sd.W;
+    const float* osum = SIDE ? sd.Wsum : sd.Hsum;
+    const int half = lane >> 5, l32 = lane & 31;
+    const int nlive = (nq - half + 1) >> 1;                                 // this half's live quads (an odd count: half 1 has one less)
+    const int hq = half * 4;                                                // quad i of this half: floats hq + 8 i of a row
+    for (int j = 0; j < spw; ++j) {
+        const int s = (grp * spw + j) * SP_WAVES + ((j & 1) ? SP_WAVES - 1 - wv : wv);
+        if (s >= A.nslice) continue;
+        const int L = __builtin_amdgcn_readfirstlane(A.len[(size_t)s * A.nblk + blk]);
+        const uint2* eb = A.ent + sp_uniform(A.off[(size_t)s * A.nblk + blk]);
+        for (int p = 0; p < 2; ++p) {
+            const int row = sp_at(A.perm + (size_t)s * 64, (unsigned)(p * 32 + l32) * 4u);
+            if (__ballot(row >= 0) == 0ull) continue;                       // (a short last slice: no row in this pass)
+            sp_f32x2 w[KH], num[KH];
+#pragma unroll
+            for (int c = 0; c < KH; ++c) { w[c] = sp_f32x2{0.f, 0.f}; num[c] = sp_f32x2{0.f, 0.f}; }
+            if (row >= 0) {
+#pragma unroll
+                for (int i = 0; i < NH; ++i) {
+                    if (i < nlive) {                                        // (beyond: padding, zeros)
+                        const v4f v = *reinterpret_cast<const v4f*>(own + ((size_t)row * KP + hq) + i * 8);
+                        w[i * 2] = sp_f32x2{v.x, v.y}; w[i * 2 + 1] = sp_f32x2{v.z, v.w};
+                    }
+                }
+            }
+            const unsigned eo = (unsigned)(p * 32 + l32) * 8u;                 // this lane's entry of step 0
+            constexpr int U = NH <= 5 ? 2 : 1;                              // gathers in flight per lane (registers: no spills)
+            static_assert(SP_UNROLL % U == 0, "the builder rounds every length up to a multiple of SP_UNROLL: L is one of U");
+            uint2 nxt[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) nxt[u] = L > 0 ? sp_at(eb, eo + (unsigned)u * 512u) : uint2{0u, 0u};
+            for (int t = 0; t < L; t += U) {
+                uint2 e[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) e[u] = nxt[u];
+                if (t + U < L) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) nxt[u] = sp_at(eb, eo + (unsigned)(t + U + u) * 512u);
+                }
+                sp_f32x2 h[U][KH];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const unsigned rb = e[u].x & ~RM, a0 = e[u].x + 16u * (unsigned)half;    // quad q: (quad 0 + q) modulo the row
+#pragma unroll
+                    for (int i = 0; i < NH; ++i) {
+                        const v4f v = *reinterpret_cast<const v4f*>(lds_raw + (rb | ((a0 + 32u * i) & RM)));
+                        h[u][i * 2] = sp_f32x2{v.x, v.y}; h[u][i * 2 + 1] = sp_f32x2{v.z, v.w};
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const float x = __uint_as_float(e[u].y);
+                    sp_f32x2 da = w[0] * h[u][0], db = w[1] * h[u][1];
+#pragma unroll
+                    for (int c = 2; c < KH; c += 2) {
+                        da = __builtin_elementwise_fma(w[c], h[u][c], da);
+                        db = __builtin_elementwise_fma(w[c + 1], h[u][c + 1], db);
+                    }
+                    da += db;
+                    const unsigned part = __float_as_uint(da.x + da.y);     // this half's quads; [0] = lanes 0..31's, [1] = lanes 32..63's
+                    const auto both = __builtin_amdgcn_permlane32_swap(part, part, false, false);
+                    const float whs = fmaxf(__uint_as_float(both[0]) + __uint_as_float(both[1]), MU_EPS);
+                    if (MODE == 0) {
+                        const float rr = x * __builtin_amdgcn_rcpf(whs);
+                        const sp_f32x2 r2 = sp_f32x2{rr, rr};
+#pragma unroll
+                        for (int c = 0; c < KH; ++c) num[c] = __builtin_elementwise_fma(r2, h[u][c], num[c]);
+                    } else if (half == 0 && x > MU_EPS) {                   // (one lane of the pair: the term counts once)
+                        acc += (double)(x * logf(x / whs) - x);
+                    }
+                }
+            }
+            if (MODE == 1 || row < 0) continue;
+            if (A.nblk == 1) {
+                // the whole other side was one block: finish the update here, every lane its own quads of the row
+#pragma unroll
+                for (int i = 0; i < NH; ++i) {
+                    if (i >= nlive) continue;                               // padding quads: never written, stay zero
+                    float o[4];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const int cc = i * 4 + c;
+                        const float w0 = (cc & 1) ? w[cc / 2].y : w[cc / 2].x, nm = (cc & 1) ? num[cc / 2].y : num[cc / 2].x;
+                        float dn = sp_at(osum, (unsigned)(hq + i * 8 + c) * 4u);
+                        if (SIDE && dn == 0.f) dn = 1.0f;
+                        if (l1 > 0.f) dn += l1;
+                        if (l2 > 0.f) dn += l2 * w0;
+                        if (dn == 0.f) dn = MU_EPS;
+                        float v = w0 * (nm / dn);
+                        if (SIDE && v < F64_EPS_AS_F32) v = 0.f;
+                        o[c] = v;
+                    }
+                    *reinterpret_cast<v4f*>(own + ((size_t)row * KP + hq) + i * 8) = v4f{o[0], o[1], o[2], o[3]};
+                }
+            } else {
+                float* pp = sd.pnum + (((size_t)blk * Rs + row) * KP + hq);
+#pragma unroll
+                for (int i = 0; i < NH; ++i)
+                    if (i < nlive) *reinterpret_cast<v4f*>(pp + i * 8) = v4f{num[i * 2].x, num[i * 2].y, num[i * 2 + 1].x, num[i * 2 + 1].y};
+            }
+        }
+    }
+}
+
 template <int KP, int MODE, int SIDE>
 __global__ __launch_bounds__(SP_WAVES * 64) void mu_sp_kernel(BSellDev A, MuBatch mb, int ngroups, int spw, float l1, float l2,
                                                               int Rs /* padded own rows: row stride of the partials */)
@@ -380,9 +517,17 @@ __global__ __launch_bounds__(SP_WAVES * 64) void mu_sp_kernel(BSellDev A, MuBatc
     }
     __syncthreads();
     double acc = 0.0;
+    if constexpr (KP == 64) {
+        // by the quads per lane half (9..16 live quads: ranks 33..48 do not pay for 64; fewer than 9 never come here, and
+        // would still be right -- the quads beyond the live ones hold zeros and are not written)
+#define SP_CASE2(NH_) case NH_: sp_slices_pair<MODE, SIDE, NH_>(A, sd, sp_lds_raw, grp, blk, spw, wv, lane, nq, l1, l2, Rs, acc); break;
+        switch (max(5, (nq + 1) >> 1)) { SP_CASE2(5) SP_CASE2(6) SP_CASE2(7) SP_CASE2(8) default: break; }
+#undef SP_CASE2
+    } else {
 #define SP_CASE(NQ_) case NQ_: if constexpr (NQ_ <= QPR) sp_slices<KP, MODE, SIDE, NQ_>(A, sd, sp_lds_raw, grp, blk, spw, wv, lane, l1, l2, Rs, acc); break;
     switch (nq) { SP_CASE(1) SP_CASE(2) SP_CASE(3) SP_CASE(4) SP_CASE(5) SP_CASE(6) SP_CASE(7) SP_CASE(8) default: break; }
 #undef SP_CASE
+    }
     if (MODE == 1) {
         __syncthreads();                                    // (every wave is past the factor block: LDS is free)
         double* red = reinterpret_cast<double*>(sp_lds_raw);

@@ -6,7 +6,7 @@
 // rank 16 / 32 / 64 (and 128 where the context's rank limit was raised) and run up to MU_MAXSLOTS at a time: one round of launches advances every live slot by one iteration.
 // Three kernel families behind ONE driver (mu_drive) and one slot path (install_slots, retire_slot, reduce_divergence):
 // MuMfma dense (Kullback-Leibler and Itakura-Saito on the matrix pipe, reading X and X^T), MuMfma sparse (Kullback-Leibler
-// at padded ranks 16 / 32 on the non-zeros, chosen by mu_sparse_prepare) and MuValu (the vector-ALU kernels: the same
+// at padded ranks 16 / 32 / 64 on the non-zeros, chosen by mu_sparse_prepare) and MuValu (the vector-ALU kernels: the same
 // driver with one slot, for CNMF_MU_VALU=1 and matrices beyond 2^24 cells or genes).
 #pragma once
 #include "kernels_mu.hip.h"
@@ -103,15 +103,16 @@ static int sp_build_image(cnmf_ctx* ctx, const long long* ptr, const int* idx, c
     return CNMF_OK;
 }
 
-// Does this call take the non-zero path?  CNMF_MU_SPARSE=0 never, =1 always, otherwise when at most a quarter of X is
-// non-zero (the dense matrix-pipe kernels cost ~0.9 ns per ELEMENT and restart-iteration at k <= 16, these ~3 ns per NON-ZERO)
+// Does this call take the non-zero path?  CNMF_MU_SPARSE=0 never, =1 always, otherwise when at most a quarter of X (at
+// padded rank 64: 15 %) is non-zero (the dense matrix-pipe kernels cost ~0.9 ns per ELEMENT and restart-iteration at k <= 16, these ~3 ns per NON-ZERO)
 // and its images and partial numerators fit the free device memory (else: the dense kernels).
 static int mu_sparse_prepare(cnmf_ctx* ctx, int KP, bool* use)
 {
     *use = false;
     const int mode = ctx->mu_knobs.sparse;
-    if (mode == 0 || (KP != 16 && KP != 32)) return CNMF_OK;
-    const int N = (int)ctx->N, G = (int)ctx->G, idx = KP == 16 ? 0 : 1, BS = SP_LDS_BYTES / (KP * 4);
+    // padded rank 64 (ranks 33..64, two lanes per row) only under cnmf_set_mu_sparse_rank_limit(ctx, CNMF_MU_SPARSE_KMAX_WIDE)
+    if (mode == 0 || (KP != 16 && KP != 32 && !(KP == 64 && ctx->mu_sparse_rank_limit >= CNMF_MU_SPARSE_KMAX_WIDE))) return CNMF_OK;
+    const int N = (int)ctx->N, G = (int)ctx->G, idx = cnmf_ctx::sp_image_index(KP), BS = SP_LDS_BYTES / (KP * 4);
     // how many entries are stored?  From the compressed rows when the matrix came as CSR; a dense upload is only COUNTED here
     // (N + 1 counters) -- its compressed rows (12 B per entry) are built below, once the density and memory rules have chosen
     // this path, and not at all when they send the call back to the dense kernels
@@ -127,7 +128,10 @@ static int mu_sparse_prepare(cnmf_ctx* ctx, int KP, bool* use)
         if (rc) return rc;
         ctx->x_nnz = nnz;
     }
-    if (mode != 1 && (double)ctx->x_nnz > 0.25 * (double)N * (double)G) return CNMF_OK;
+    // (padded rank 64: measured at 50 000 x 2 000, the two routes meet at 23 / 19 / 16 % non-zero at k = 40 / 48 / 64 --
+    // profiles/mu_sparse_ranks_33_64_50000x2000.json, between its 9 % and 34 % rows -- so that group switches at 15 %)
+    const double max_density = KP == 64 ? 0.15 : 0.25;
+    if (mode != 1 && (double)ctx->x_nnz > max_density * (double)N * (double)G) return CNMF_OK;
     if (!ctx->spA[idx].ent || !ctx->spB[idx].ent) {
         // the partial numerators of a half-step whose other side needs several blocks ([blocks][own rows][KP] per slot), the
         // two images (8 B per entry, padded: x 1.25 allowed for), X^T's compressed rows and the build's scratch
@@ -223,7 +227,7 @@ static int mu_setup(MuRun& r, MuMfma<KP, BETA1>& p, bool sparse)
     cnmf_ctx* ctx = r.ctx;
     p.sparse = sparse;
     if (sparse) {                          // same slots, same schedule, other kernels
-        p.dA = sp_dev(ctx->spA[KP == 16 ? 0 : 1]); p.dB = sp_dev(ctx->spB[KP == 16 ? 0 : 1]);
+        p.dA = sp_dev(ctx->spA[cnmf_ctx::sp_image_index(KP)]); p.dB = sp_dev(ctx->spB[cnmf_ctx::sp_image_index(KP)]);
         // cells: one slice per wave (sorted rows: the slices of a workgroup are equally long); genes: all slices of up to
         // 8192 genes in ONE workgroup per block of cells, long and short slices paired on the waves
         p.spwB = std::max(1, std::min(8, (p.dB.nslice + SP_WAVES - 1) / SP_WAVES));
@@ -257,7 +261,7 @@ static int mu_setup(MuRun& r, MuMfma<KP, BETA1>& p, bool sparse)
     HIP_TRY(ctx, dyn_lds_optin((const void*)mu_h_coop_kernel<KP, BETA1>, p.coop_lds));
     HIP_TRY(ctx, dyn_lds_optin((const void*)mu_w_coop_kernel<KP, 0, BETA1>, p.coop_lds));
     HIP_TRY(ctx, dyn_lds_optin((const void*)mu_w_coop_kernel<KP, 1, BETA1>, p.coop_lds));
-    if constexpr (BETA1 && KP <= 32) if (sparse) {
+    if constexpr (BETA1 && KP <= 64) if (sparse) {
         HIP_TRY(ctx, dyn_lds_optin((const void*)mu_sp_kernel<KP, 0, 0>, SP_LDS_BYTES));
         HIP_TRY(ctx, dyn_lds_optin((const void*)mu_sp_kernel<KP, 0, 1>, SP_LDS_BYTES));
         HIP_TRY(ctx, dyn_lds_optin((const void*)mu_sp_kernel<KP, 1, 0>, SP_LDS_BYTES));
@@ -296,7 +300,7 @@ static int mu_step(const MuRun& r, MuMfma<KP, BETA1>& p, const std::vector<int>&
     const MuBatch mb = mu_batch_of(r, ids);
     const int gz4 = (mb.n + p.RPW - 1) / p.RPW;
     if (p.sparse) {
-        if constexpr (BETA1 && KP <= 32) {
+        if constexpr (BETA1 && KP <= 64) {
             mu_sp_kernel<KP, 0, 0><<<(p.tilesA + 7) / 8 * 8 * mb.n, SP_WAVES * 64, SP_LDS_BYTES, st>>>(p.dA, mb, p.grpA, 1, r.l1W, r.l2W, Np);
             if (p.dA.nblk > 1)
                 mu_sp_finish_kernel<KP><<<dim3((unsigned)(((size_t)N * KP + 255) / 256), mb.n), 256, 0, st>>>(mb, 0, N, Np, p.dA.nblk, r.l1W, r.l2W);
@@ -328,7 +332,7 @@ static int mu_divergence(const MuRun& r, MuMfma<KP, BETA1>& p, const MuSched&, c
     const MuBatch mb = mu_batch_of(r, ids);
     if (!r.c->update_H) mu_colsum_batch<KP>(r, mb, 0);           // refit: the iterations do not need the column sums of W
     if (p.sparse) {
-        if constexpr (BETA1 && KP <= 32)
+        if constexpr (BETA1 && KP <= 64)
             mu_sp_kernel<KP, 1, 0><<<(p.tilesA + 7) / 8 * 8 * mb.n, SP_WAVES * 64, SP_LDS_BYTES, r.st>>>(p.dA, mb, p.grpA, 1, 0.f, 0.f, r.Np);
     } else
         mu_w_coop_kernel<KP, 1, BETA1><<<dim3((r.N + 127) / 128, 1, (mb.n + p.RPW - 1) / p.RPW), 512, p.coop_lds, r.st>>>(r.ctx->XtF.p, r.Np, r.N, r.Gs, mb, 0.f, 0.f);
@@ -588,6 +592,19 @@ extern "C" int cnmf_set_mu_rank_limit(cnmf_ctx* ctx, int limit)
 }
 extern "C" int cnmf_get_mu_rank_limit(const cnmf_ctx* ctx) { return ctx ? ctx->mu_rank_limit : CNMF_MU_KMAX; }
 
+// the largest rank of a Kullback-Leibler restart that may run on the non-zeros: CNMF_MU_SPARSE_KMAX unless the caller opts in
+extern "C" int cnmf_set_mu_sparse_rank_limit(cnmf_ctx* ctx, int limit)
+{
+    if (!ctx) { SET_ERR(ctx, "ctx is NULL"); return CNMF_EINVAL; }
+    if (limit != CNMF_MU_SPARSE_KMAX && limit != CNMF_MU_SPARSE_KMAX_WIDE) {
+        SET_ERR(ctx, "the rank limit of the non-zero path is %d or %d, not %d", CNMF_MU_SPARSE_KMAX, CNMF_MU_SPARSE_KMAX_WIDE, limit);
+        return CNMF_EINVAL;
+    }
+    ctx->mu_sparse_rank_limit = limit;
+    return CNMF_OK;
+}
+extern "C" int cnmf_get_mu_sparse_rank_limit(const cnmf_ctx* ctx) { return ctx ? ctx->mu_sparse_rank_limit : CNMF_MU_SPARSE_KMAX; }
+
 extern "C" int cnmf_nmf_mu_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int init_mode,
                                  const uint32_t* seeds, const double* avg, const float* W0,
                                  const float* H0, int beta, int update_H, const cnmf_cd_params* prm,
@@ -644,9 +661,10 @@ extern "C" int cnmf_nmf_mu_batch(cnmf_ctx* ctx, int n, const int32_t* kk, int in
         }
         return CNMF_OK;
     }
-    // Kullback-Leibler at padded ranks 16 / 32 on a matrix that is mostly zeros: only the non-zeros are touched
+    // Kullback-Leibler at padded ranks 16 / 32 (and 64 under cnmf_set_mu_sparse_rank_limit) on a matrix that is mostly zeros:
+    // only the non-zeros are touched; ranks 65..128 stay on the dense kernels
     bool sparse[4] = {false, false, false, false};
-    for (int g = 0; g < 2; ++g)
+    for (int g = 0; g < 3; ++g)
         if (beta == 1 && !group[g].empty() && (rc = mu_sparse_prepare(ctx, 16 << g, &sparse[g]))) return rc;
     for (int g = 0; g < 4; ++g)
         if (!group[g].empty() && (rc = mu_run_kp(ctx, call, group[g], 16 << g, sparse[g] ? MU_SPARSE : MU_DENSE))) return rc;

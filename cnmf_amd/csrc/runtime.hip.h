@@ -288,6 +288,7 @@ struct cnmf_ctx {
     CdKnobs knobs;                                 // ... and the switches of the coordinate-descent batch path, parsed from it
     MuKnobs mu_knobs;                              // ... and of the multiplicative-update solver
     int mu_rank_limit = CNMF_MU_KMAX;              // cnmf_set_mu_rank_limit(): CNMF_MU_KMAX, or CNMF_MU_KMAX_WIDE by opt-in (never from the environment)
+    int mu_sparse_rank_limit = CNMF_MU_SPARSE_KMAX;  // cnmf_set_mu_sparse_rank_limit(): largest rank on the non-zero path, 32 or (opt-in) 64
 
     // data matrix
     int64_t N = 0, G = 0;
@@ -300,9 +301,11 @@ struct cnmf_ctx {
     Owned<CountPlanesF> counts;                    // ensure_counts; counts.state says whether X has the structure at all
     Owned<GeneralPlanesF> x2;                      // ensure_x2planes
     Owned<DenseTF> XtF;                            // mu_ensure_xt (mu_host.hip.h)
-    // Kullback-Leibler on the non-zeros (kernels_mu_sparse.hip.h): images for padded ranks 16 and 32, cells x genes (A) and
-    // genes x cells (B); x_nnz = -1 until the first Kullback-Leibler call counted the matrix
-    SpImage spA[2], spB[2];
+    // Kullback-Leibler on the non-zeros (kernels_mu_sparse.hip.h): images for padded ranks 16, 32 and 64 (sp_image_index), cells x
+    // genes (A) and genes x cells (B); x_nnz = -1 until the first Kullback-Leibler call counted the matrix
+    static constexpr int SP_IMAGES = 3;
+    static constexpr int sp_image_index(int KP) { return KP <= 16 ? 0 : (KP <= 32 ? 1 : 2); }
+    SpImage spA[SP_IMAGES], spB[SP_IMAGES];
     long long x_nnz = -1;
     // compressed rows of X (cells x genes) and of X^T (genes x cells), csr_host.hip.h: kept from cnmf_set_matrix_csr or
     // built from the dense matrix on first use; 64-bit row pointers, float32 values like the dense image

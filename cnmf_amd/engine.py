@@ -95,9 +95,10 @@ def _nndsvd_fill(W, H, variant, x_mean, random_state):
 
 
 class Engine:
-    def __init__(self, device=0, detect_counts=True, mu_rank_limit=_lib.CNMF_MU_KMAX):
+    def __init__(self, device=0, detect_counts=True, mu_rank_limit=_lib.CNMF_MU_KMAX, mu_sparse_rank_limit=_lib.CNMF_MU_SPARSE_KMAX):
         """``detect_counts=False``: never take the integer-plane (count-structured) GEMM path -- see
-        :meth:`set_count_detection`.  ``mu_rank_limit``: 64 (default) or 128, see :attr:`mu_rank_limit`."""
+        :meth:`set_count_detection`.  ``mu_rank_limit``: 64 (default) or 128, see :attr:`mu_rank_limit`.
+        ``mu_sparse_rank_limit``: 32 (default) or 64, see :attr:`mu_sparse_rank_limit`."""
         self._lib = _lib.load()
         if self._lib.cnmf_device_count() <= 0:
             raise RuntimeError("cnmf_amd: no HIP device visible -- the engine has no CPU fallback")
@@ -119,6 +120,8 @@ class Engine:
             self.set_count_detection(False)
         if mu_rank_limit != _lib.CNMF_MU_KMAX:
             self.mu_rank_limit = mu_rank_limit
+        if mu_sparse_rank_limit != _lib.CNMF_MU_SPARSE_KMAX:
+            self.mu_sparse_rank_limit = mu_sparse_rank_limit
 
     @property
     def mu_rank_limit(self):
@@ -131,6 +134,20 @@ class Engine:
     @mu_rank_limit.setter
     def mu_rank_limit(self, limit):
         self._check(self._lib.cnmf_set_mu_rank_limit(self._ctx, int(limit)))
+
+    @property
+    def mu_sparse_rank_limit(self):
+        """Largest rank at which a Kullback-Leibler restart of :meth:`nmf_mu_batch` / :meth:`nnls_mu` may run on the non-zeros
+        of the matrix: 32 (``CNMF_MU_SPARSE_KMAX``, the default: ranks 33 up on the dense kernels) or, by opt-in, 64
+        (``CNMF_MU_SPARSE_KMAX_WIDE``: ranks 33..64 at padded rank 64, two lanes per row).  ``CNMF_MU_SPARSE`` decides as
+        at ranks up to 32, the density rule at 15 % non-zero instead of a quarter (the measured crossover); ranks 65..128 and
+        Itakura-Saito stay on the dense kernels.
+        Any other value raises ValueError."""
+        return int(self._lib.cnmf_get_mu_sparse_rank_limit(self._ctx))
+
+    @mu_sparse_rank_limit.setter
+    def mu_sparse_rank_limit(self, limit):
+        self._check(self._lib.cnmf_set_mu_sparse_rank_limit(self._ctx, int(limit)))
 
     def set_count_detection(self, enabled):
         """The engine recognises ``X = counts / std`` (integers x one constant per gene, tolerance 1e-3 count units;
@@ -244,7 +261,7 @@ class Engine:
         f = C.c_int32(0)
         self._check(self._lib.cnmf_matrix_images(self._ctx, C.byref(f)))
         names = ("dense", "csr", "csr_of_transpose", "dense_transpose", "non_zero_images_16", "non_zero_images_32", "count_planes",
-                 "count_planes_bytes")
+                 "count_planes_bytes", "non_zero_images_64")
         return {n: bool(f.value >> i & 1) for i, n in enumerate(names)}
 
     def get_matrix(self):
@@ -1150,7 +1167,10 @@ class Engine:
         """``solver='mu'`` restarts (the reference's path for beta_loss != 'frobenius',
         cnmf.py:618-631).  Same arguments / returns as :meth:`nmf_batch` (``init_store=True`` included); the last element
         of the returned tuple is sqrt(2*beta-divergence) at the final evaluation.  Ranks above :attr:`mu_rank_limit`
-        (64 unless raised to 128) raise NotImplementedError."""
+        (64 unless raised to 128) raise NotImplementedError.  Kullback-Leibler restarts on a matrix that is at most a quarter
+        non-zero (or under ``CNMF_MU_SPARSE=1``) run on the stored entries only, at ranks up to
+        :attr:`mu_sparse_rank_limit` (32 unless raised to 64; ranks 33..64 by themselves at up to 15 % non-zero); above it they
+        run on the dense matrix-pipe kernels."""
         if self.shape is None:
             raise RuntimeError("set_matrix() has not been called")
         if beta_loss not in self._BETA:
@@ -1201,7 +1221,8 @@ class Engine:
                 warn=True):
         """Refit with fixed H and ``solver='mu'``: W starts from avg everywhere (sklearn _nmf.py:1229-1231).
         Both losses: the float64 refit on the stored entries (:meth:`mu_refit_f64`; result cast to float32 like the
-        other refits of this class).  Ranks above :attr:`mu_rank_limit` (64 unless raised to 128): NotImplementedError."""
+        other refits of this class).  Ranks above :attr:`mu_rank_limit` (64 unless raised to 128): NotImplementedError.
+        The float64 refit walks the stored entries at every rank: :attr:`mu_sparse_rank_limit` does not bear on it."""
         if self.shape is None:
             raise RuntimeError("set_matrix() has not been called")
         N, G = self.shape

@@ -48,6 +48,10 @@ extern "C" {
 #define CNMF_MU_KMAX_WIDE 128  /* ... and after cnmf_set_mu_rank_limit(ctx, CNMF_MU_KMAX_WIDE): ranks 65..128 on the
                                   matrix-pipe kernels and the float64 refit (the vector-ALU route stays at 64)  */
 
+#define CNMF_MU_SPARSE_KMAX 32       /* largest rank of a Kullback-Leibler restart on the non-zeros of X on a context as created ... */
+#define CNMF_MU_SPARSE_KMAX_WIDE 64  /* ... and after cnmf_set_mu_sparse_rank_limit(ctx, CNMF_MU_SPARSE_KMAX_WIDE): ranks 33..64 at padded
+                                        rank 64, two lanes per row (ranks 65..128 stay on the dense kernels)                        */
+
 typedef struct cnmf_ctx cnmf_ctx;
 
 /* numpy's RandomState state (get_state()): the MT19937 key, pos in [0, 624], the cached Gaussian */
@@ -136,7 +140,7 @@ int cnmf_get_shape(const cnmf_ctx* ctx, int64_t* n_cells, int64_t* n_genes);
  * a path that multiplies the dense matrix asks for it: a Kullback-Leibler run on a sparse matrix never does), bit 1 the
  * compressed rows of X, bit 2 those of X^T, bit 3 the dense X^T copy of the dense multiplicative-update kernels,
  * bits 4 / 5 the non-zero images at padded rank 16 / 32, bit 6 the integer count planes of the coordinate-descent path,
- * bit 7 those planes held as one byte per count (CNMF_G2_U8). */
+ * bit 7 those planes held as one byte per count (CNMF_G2_U8), bit 8 the non-zero images at padded rank 64. */
 int cnmf_matrix_images(const cnmf_ctx* ctx, int32_t* flags);
 /* the resident matrix back on the host ([n_cells][n_genes] float32) */
 int cnmf_get_matrix(cnmf_ctx* ctx, float* out);
@@ -476,10 +480,12 @@ int cnmf_set_iteration_hints(cnmf_ctx* ctx, int n, const int32_t* k, const doubl
  * cells or genes) they are CNMF_EUNSUPPORTED before any launch.
  * The first call builds a resident transposed copy of X (freed with the matrix).
  * Kullback-Leibler on the NON-ZEROS (round 4, kernels_mu_sparse.hip.h) -- scikit-learn's own route for scipy.sparse input
- * (sklearn:_nmf.py:192 `_special_sparse_dot`): taken by itself when beta = 1, every rank of the call is <= 32 and at most a
- * quarter of X is non-zero (counted once per matrix); same mathematics (the quotient vanishes where X does), exact float32
+ * (sklearn:_nmf.py:192 `_special_sparse_dot`): taken by itself, per group of restarts of one padded rank, when beta = 1,
+ * the group's ranks are <= the context's non-zero rank limit (cnmf_get_mu_sparse_rank_limit: CNMF_MU_SPARSE_KMAX = 32
+ * unless raised to CNMF_MU_SPARSE_KMAX_WIDE = 64; the other groups of the call run on the dense kernels) and at most
+ * a quarter of X (15 % for the padded-rank-64 group) is non-zero (counted once per matrix); same mathematics (the quotient vanishes where X does), exact float32
  * products, another summation order than the dense kernels (results agree to float32 round-off, not bit for bit).
- * Extra device memory: per padded rank in use (16, 32) two blocked sliced-ELL images, 8 B x non-zeros x 1.0-1.2 each
+ * Extra device memory: per padded rank in use (16, 32, 64) two blocked sliced-ELL images, 8 B x non-zeros x 1.0-1.2 each
  * (round 5: built from the compressed rows of the matrix, csr_host.hip.h -- no dense transposed copy on this path), and per
  * restart in flight the partial numerators [blocks of the other side][own rows][padded rank] float32.  When those
  * allocations do not fit the call falls back to the dense kernels.  The environment variable CNMF_MU_SPARSE (read when the
@@ -488,6 +494,12 @@ int cnmf_set_iteration_hints(cnmf_ctx* ctx, int n, const int32_t* k, const doubl
  * CNMF_MU_KMAX_WIDE; any other value is CNMF_EINVAL.  Per context, set through this call only (no environment switch). */
 int cnmf_set_mu_rank_limit(cnmf_ctx* ctx, int limit);
 int cnmf_get_mu_rank_limit(const cnmf_ctx* ctx);
+/* The largest rank of a Kullback-Leibler restart that cnmf_nmf_mu_batch may run on the non-zeros: CNMF_MU_SPARSE_KMAX (the
+ * default) or CNMF_MU_SPARSE_KMAX_WIDE; any other value is CNMF_EINVAL.  Per context, set through this call only (no
+ * environment switch); CNMF_MU_SPARSE and the fall-back to the dense kernels apply as at ranks <= 32; the density rule
+ * takes ranks 33..64 to the non-zeros at up to 15 % non-zero (the measured crossover; a quarter at ranks <= 32).         */
+int cnmf_set_mu_sparse_rank_limit(cnmf_ctx* ctx, int limit);
+int cnmf_get_mu_sparse_rank_limit(const cnmf_ctx* ctx);
 int cnmf_nmf_mu_batch(cnmf_ctx* ctx, int n_restarts, const int32_t* k, int init_mode,
                       const uint32_t* seeds, const double* avg, const float* W0, const float* H0,
                       int beta, int update_H, const cnmf_cd_params* params,

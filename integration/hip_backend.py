@@ -42,8 +42,11 @@ class cNMF(_ref.cNMF):
     _resident = None              # STRONG reference to the matrix object that is on the device (identity check)
     nndsvd = "host"               # "device": the tail of init='nndsvd*' on the device too (cnmf_amd.cnmf.cNMF.nndsvd)
     mu_ranks = None               # "wide": multiplicative-update ranks 65..128 (cnmf_amd.cnmf.cNMF.mu_ranks); None: up to 64
+    mu_sparse_ranks = None        # "wide": Kullback-Leibler on the non-zeros at ranks 33..64 too (cnmf_amd.cnmf.cNMF.mu_sparse_ranks)
     _mu_kmax = _mirror._mu_kmax
-    _mu_rank_scope = _mirror._mu_rank_scope       # raises Engine.mu_rank_limit around a device call, puts it back after
+    _mu_sparse_kmax = _mirror._mu_sparse_kmax
+    _mu_sparse_rank_scope = _mirror._mu_sparse_rank_scope
+    _mu_rank_scope = _mirror._mu_rank_scope       # raises Engine.mu_rank_limit (and mu_sparse_rank_limit) around a device call, puts them back after
 
     # -- engine plumbing ---------------------------------------------------------------------------
     def __getstate__(self):       # multiprocessing pickles the object (cnmf.py:254-262): a ctypes handle cannot travel
